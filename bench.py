@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- VB update iterations/sec of the LDS path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]           (N > 1: starts its own N ranks, one per GPU)
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]   (N > 1: starts its own N ranks, one per GPU)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 One "step" = one variational iteration of every replicate resident on the rank's GPU:
@@ -13,6 +13,11 @@ and already resident in HBM when the timed region starts.
 
 Rank 0 prints one JSON line.  `value` counts iterations of a 1024-replicate block per second
 summed over all GPUs, so it equals plain iterations/s at N = 1 and adds up across ranks.
+
+A plain run sets up, warms up, times the K steps and prints the line (`roofline` and `cpu_baseline` are null).
+--full adds what takes time of its own: HIP-event times per kernel and the roofline built on them, the oracle's
+CPU baseline and parity check on the timed batch, and the extra workloads (VB-PCA, the 128-wide class).
+--dump-outputs DIR writes what the last timed step computed on rank 0 as DIR/<name>.npy (see dump_outputs).
 """
 import argparse
 import json
@@ -53,6 +58,31 @@ def make_inputs(T, D, K, N, seed):
             st[k] = big[k]
         st0 = st
     return Y, st0, pri
+
+
+DUMP_REPLICATES, DUMP_TIMES, DUMP_SEED = 32, 256, 12345
+
+
+def dump_outputs(path, b, last_total):
+    """What a caller of the timed path receives after its last step, as float64 .npy files under `path`:
+    elbo_total [6] (the lower-bound parts of the last step, summed over the replicates and ranks), elbo [N, 6] (per
+    replicate), and the posterior state of a fixed sample of replicates (DUMP_REPLICATES of them, drawn with DUMP_SEED):
+    A_mean, A_colvar, C_mean, C_colvar, Q_a, Q_b, R_a, R_b in full, X at DUMP_TIMES time steps drawn with the same
+    generator.  Well under 64 MB for every shape the fused kernels serve."""
+    N, T = b.N, b.T
+    rng = np.random.default_rng(DUMP_SEED)
+    reps = np.sort(rng.choice(N, min(N, DUMP_REPLICATES), replace=False))
+    times = np.sort(rng.choice(T, min(T, DUMP_TIMES), replace=False))
+    st = b.get_state()
+    out = {"elbo_total": last_total, "elbo": b.elbo()}
+    for k, v in st.items():
+        out[k] = v[reps][:, times] if k == "X" else v[reps]
+    del st
+    total = sum(v.size * 8 for v in out.values())
+    assert total <= 64 << 20, "outputs dump of %d bytes is over 64 MB" % total
+    os.makedirs(path, exist_ok=True)
+    for k, v in out.items():
+        np.save(os.path.join(path, k + ".npy"), np.ascontiguousarray(v, dtype=np.float64))
 
 
 def cpu_baseline_and_parity(sample, pri, iters, got_elbo, got_X):
@@ -273,180 +303,9 @@ def d128_workload(steps, warmup, with_cpu):
             "cpu_baseline": cpu}
 
 
-def launch_ranks(n, argv):
-    """`python bench.py --gpus N` without a launcher: this process -- which has not touched the GPU (pyvb_amd is imported
-    only further down, in the ranks) -- starts N fresh child processes of this script, one per GPU, with the environment a
-    launcher would give them (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_ADDR / MASTER_PORT), relays rank 0's JSON line and
-    returns non-zero if any rank fails or the line does not say n_gpus == N.  Children are started with subprocess, never
-    by replacing this process."""
-    import socket
-    import subprocess
-    with socket.socket(socket.AF_INET, socket.SOCK_STREAM) as s:
-        s.bind(("127.0.0.1", 0))
-        port = s.getsockname()[1]
-    procs = []
-    for r in range(n):
-        env = dict(os.environ, RANK=str(r), LOCAL_RANK=str(r), WORLD_SIZE=str(n), LOCAL_WORLD_SIZE=str(n),
-                   MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), PYVB_BENCH_CHILD="1")
-        env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-        procs.append(subprocess.Popen([sys.executable, os.path.abspath(__file__)] + list(argv), env=env,
-                                      stdout=(subprocess.PIPE if r == 0 else subprocess.DEVNULL), text=True))
-    import threading
-    out0 = []
-    reader = threading.Thread(target=lambda: out0.extend(procs[0].stdout.readlines()))
-    reader.start()
-    rc = 0
-    live = set(range(n))
-    kill_at = None              # after one rank has failed: when the others, already asked to terminate, are killed
-    while live:
-        for r in sorted(live):
-            code = procs[r].poll()
-            if code is None:
-                continue
-            live.discard(r)
-            if code != 0 and rc == 0:
-                rc = code if code > 0 else 1
-                sys.stderr.write("bench.py: rank %d exited with status %d; stopping the other ranks\n" % (r, code))
-                for o in live:
-                    procs[o].terminate()        # exactly the children started above
-                kill_at = time.time() + 15.0
-        if kill_at is not None and live and time.time() > kill_at:
-            for o in live:                      # a rank stuck in a GPU call ignores SIGTERM: do not wait for it for ever
-                procs[o].kill()
-            kill_at = time.time() + 15.0
-        time.sleep(0.05)
-    reader.join()
-    lines = [l for l in out0 if l.startswith("{")]
-    for l in out0:
-        if not l.startswith("{"):
-            sys.stderr.write(l)
-    if rc:
-        return rc
-    if len(lines) != 1:
-        sys.stderr.write("bench.py: expected one JSON line from rank 0, got %d\n" % len(lines))
-        return 1
-    d = json.loads(lines[0])
-    if d.get("n_gpus") != n:
-        sys.stderr.write("bench.py: asked for %d GPUs, the line reports n_gpus = %r\n" % (n, d.get("n_gpus")))
-        return 1
-    sys.stdout.write(lines[0])
-    sys.stdout.flush()
-    return 0
-
-
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--replicates", type=int, default=1024, help="replicates per GPU")
-    ap.add_argument("--T", type=int, default=10000)
-    ap.add_argument("--D", type=int, default=64)
-    ap.add_argument("--K", type=int, default=64)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-workloads", action="store_true", help="skip the second workload (VB-PCA, BASELINE configs[4]) after the headline")
-    ap.add_argument("--workloads", default="auto", help="comma list of pca_config5, lds_d128; auto: both after the headline shape on one "
-                                                        "GPU, pca_config5 (rows sharded over the ranks) with several")
-    ap.add_argument("--pca-rows", type=int, default=1000000, help="rows of the VB-PCA workload (BASELINE configs[4]: 10^6)")
-    ap.add_argument("--parity-replicates", type=int, default=4, help="replicates of the timed batch re-run in the oracle")
-    ap.add_argument("--rccl-single", action="store_true",
-                    help="with one process: still create a (one-rank) RCCL communicator and all-reduce the lower bound through it, "
-                         "i.e. run the multi-GPU code path as far as one GPU allows")
-    ap.add_argument("--allow-host-fallback", "--allow-gloo-fallback", dest="allow_host_fallback", action="store_true",
-                    help="if the RCCL communicator cannot be created, reduce the lower bound through host memory over the rendezvous "
-                         "sockets (line marked degraded) instead of failing")
-    args = ap.parse_args()
-
-    if args.gpus < 1:
-        raise SystemExit("--gpus must be at least 1")
-    if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
-        # no launcher: start the N ranks ourselves (nothing has touched the GPU in this process yet)
-        raise SystemExit(launch_ranks(args.gpus, sys.argv[1:]))
-    rank = int(os.environ.get("RANK", "0"))
-    world = int(os.environ.get("WORLD_SIZE", "1"))
-    local_rank = int(os.environ.get("LOCAL_RANK", "0"))
-    if world != args.gpus:
-        # one rank asked to stand for N GPUs (or the reverse) would put a wrong n_gpus beside a real number: refuse
-        raise SystemExit("--gpus %d but WORLD_SIZE=%d: start one rank per GPU (python bench.py --gpus N does so itself)" % (args.gpus, world))
-
-    from pyvb_amd.lds import LDSBatch      # raises if libpyvb_hip.so is missing: no fallback
-    from pyvb_amd import dist as pdist
-
-    comm = pdist.init(world, rank)         # TCP rendezvous (standard library) for barriers / max-reduce; RCCL inside the library
-    T, D, K, N = args.T, args.D, args.K, args.replicates
-    Y, st0, pri = make_inputs(T, D, K, N, seed=20240 + 1000 * rank)
-    from pyvb_amd import _capi
-    ndev = _capi.ctypes.c_int(0)
-    _capi.check(_capi.lib.pyvb_device_count(_capi.ctypes.byref(ndev)))
-    device = local_rank % max(ndev.value, 1)          # a launcher may already have narrowed the visible devices
-    b = LDSBatch.from_problem(Y, st0, pri, device=device)
-    n_par = max(1, min(args.parity_replicates, N))
-    sample = (Y[:n_par].copy(), {k: v[:n_par].copy() for k, v in st0.items()})
-    del Y
-    collective = "none (1 GPU)"
-    degraded = False
-    use_rccl = False
-    if world > 1 or args.rccl_single:
-        # the one collective of the data path: all-reduce of the 6 lower-bound parts, over RCCL inside the library
-        uid, ok, why = None, 0.0, ""
-        # one node: RCCL's bootstrap (sockets, not the data path) over loopback, like the rendezvous above --
-        # the container's hostname / outward interface may not be usable
-        if os.environ.get("MASTER_ADDR", "127.0.0.1") in ("127.0.0.1", "localhost"):
-            os.environ.setdefault("NCCL_SOCKET_IFNAME", "lo")
-        if rank == 0:
-            try:
-                uid = LDSBatch.comm_unique_id()
-            except Exception as e:
-                why = "rank 0: no RCCL unique id (%s)" % (e,)
-        uid = comm.broadcast_bytes(uid)
-        if uid is not None:
-            try:
-                b.comm_init(uid, rank, world)
-                ok = 1.0
-            except Exception as e:
-                why = "rank %d: RCCL communicator failed (%s)" % (rank, e)
-        ok = -comm.max_float(-ok)       # min over ranks
-        use_rccl = ok == 1.0
-        if not use_rccl:
-            # a number taken with the lower bound going through host memory is not this design's data path:
-            # fail unless the caller asked for the fallback, and mark the line if so
-            if why:
-                sys.stderr.write(why + "\n")
-            if not args.allow_host_fallback:
-                b.close()
-                comm.close()
-                raise SystemExit("RCCL communicator could not be created on every rank (see stderr); "
-                                 "re-run with --allow-host-fallback for a degraded measurement (lower bound reduced through host memory)")
-            degraded = True
-            b.comm_init_host(comm, rank, world)     # the library's own collective calls, carried by the rendezvous sockets
-        collective = ("rccl allreduce(6 x f64) per step, %d rank(s)" % world) if use_rccl else "host allreduce(6 x f64) per step over TCP (RCCL init failed: DEGRADED)"
-
-    def step():
-        # one variational iteration of every replicate on this GPU: forward sweep, backward sweep, A, C, Q, R on the handle's
-        # main stream; the lower bound, its reduction over the replicates and the RCCL all-reduce over the ranks on the
-        # side stream (they feed nothing in the next iteration).  Nothing synchronises with the host inside a step; the
-        # per-step lower bounds are read from the library's history ring after the timed region.
-        b.iterate(1)
-
-    for _ in range(args.warmup):
-        step()
-    b.sync()
-    b.reset_elbo_history()
-    b.timing(True)
-    comm.barrier()
-    t0 = time.perf_counter()
-    for _ in range(args.steps):
-        step()
-    b.sync()
-    comm.barrier()
-    dt = time.perf_counter() - t0
-    dt = comm.max_float(dt)
-    hist = b.elbo_history(args.steps)
-    assert hist.shape[0] == min(args.steps, 4096) and np.all(np.isfinite(hist)), "lower-bound history incomplete"
-    elbo = hist[-1]
-    kt = b.kernel_times()
-    b.timing(False)
-
+def roofline_figures(kt, N, T, D, K, dt, steps):
+    """`roofline` of the headline's line (--full): per-kernel figures from the HIP-event times `kt` of the timed steps and
+    the whole iteration over their wall time `dt`."""
     # ---- roofline, per kernel instantiation.  Work per launch (N replicates, T nodes; unit u = 2 D^2 flops per node):
     #   forward sweep   k_sweep<..,1,..>: F mu_{t-1} + B mu_{t+1} + G y_t          executed = algorithmic = T (4 D^2 + 2 D K)
     #   backward sweep  k_sweep<..,2,..>: B mu_{t+1} + c_t (c_t cached by the forward sweep) + the 10 upper tiles of Sxx
@@ -529,17 +388,209 @@ def main():
     # of a step -- independent of which kernel a piece of the work is fused into -- and the flops actually executed
     iter_flops = float(N) * T * (12 * D * D + 6 * D * K + 2 * K)
     iter_exec = sum(w["executed_flops"] for w in work.values())
-    step_s = dt / args.steps
+    step_s = dt / steps
     roofline["iteration"] = {"algorithmic_flops": iter_flops, "achieved": iter_flops / step_s / 1e12,
                              "frac": iter_flops / step_s / 1e12 / FP64_MFMA_PEAK_TFLOPS,
                              "executed_flops_big_kernels": iter_exec, "executed_TFLOPs": iter_exec / step_s / 1e12,
                              "executed_frac": iter_exec / step_s / 1e12 / FP64_MFMA_PEAK_TFLOPS,
                              "algorithmic_bytes": float(N) * 16 * T * (K + 2 * D),
                              "traffic": (sum(traffic.values()) if len(traffic) == len(work) else None)}
+    return roofline
+
+
+def launch_ranks(n, argv):
+    """`python bench.py --gpus N` without a launcher: this process -- which has not touched the GPU (pyvb_amd is imported
+    only further down, in the ranks) -- starts N fresh child processes of this script, one per GPU, with the environment a
+    launcher would give them (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_ADDR / MASTER_PORT), relays rank 0's JSON line and
+    returns non-zero if any rank fails or the line does not say n_gpus == N.  Children are started with subprocess, never
+    by replacing this process."""
+    import socket
+    import subprocess
+    with socket.socket(socket.AF_INET, socket.SOCK_STREAM) as s:
+        s.bind(("127.0.0.1", 0))
+        port = s.getsockname()[1]
+    procs = []
+    for r in range(n):
+        env = dict(os.environ, RANK=str(r), LOCAL_RANK=str(r), WORLD_SIZE=str(n), LOCAL_WORLD_SIZE=str(n),
+                   MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), PYVB_BENCH_CHILD="1")
+        env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
+        procs.append(subprocess.Popen([sys.executable, os.path.abspath(__file__)] + list(argv), env=env,
+                                      stdout=(subprocess.PIPE if r == 0 else subprocess.DEVNULL), text=True))
+    import threading
+    out0 = []
+    reader = threading.Thread(target=lambda: out0.extend(procs[0].stdout.readlines()))
+    reader.start()
+    rc = 0
+    live = set(range(n))
+    kill_at = None              # after one rank has failed: when the others, already asked to terminate, are killed
+    while live:
+        for r in sorted(live):
+            code = procs[r].poll()
+            if code is None:
+                continue
+            live.discard(r)
+            if code != 0 and rc == 0:
+                rc = code if code > 0 else 1
+                sys.stderr.write("bench.py: rank %d exited with status %d; stopping the other ranks\n" % (r, code))
+                for o in live:
+                    procs[o].terminate()        # exactly the children started above
+                kill_at = time.time() + 15.0
+        if kill_at is not None and live and time.time() > kill_at:
+            for o in live:                      # a rank stuck in a GPU call ignores SIGTERM: do not wait for it for ever
+                procs[o].kill()
+            kill_at = time.time() + 15.0
+        time.sleep(0.05)
+    reader.join()
+    lines = [l for l in out0 if l.startswith("{")]
+    for l in out0:
+        if not l.startswith("{"):
+            sys.stderr.write(l)
+    if rc:
+        return rc
+    if len(lines) != 1:
+        sys.stderr.write("bench.py: expected one JSON line from rank 0, got %d\n" % len(lines))
+        return 1
+    d = json.loads(lines[0])
+    if d.get("n_gpus") != n:
+        sys.stderr.write("bench.py: asked for %d GPUs, the line reports n_gpus = %r\n" % (n, d.get("n_gpus")))
+        return 1
+    sys.stdout.write(lines[0])
+    sys.stdout.flush()
+    return 0
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--gpus", type=int, default=1)
+    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--replicates", type=int, default=1024, help="replicates per GPU")
+    ap.add_argument("--T", type=int, default=10000)
+    ap.add_argument("--D", type=int, default=64)
+    ap.add_argument("--K", type=int, default=64)
+    ap.add_argument("--full", action="store_true",
+                    help="also per-kernel times and the roofline, the CPU baseline with the parity check of the timed batch, and "
+                         "the extra workloads after the headline (a plain run measures the headline's steps only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (rank 0) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and parity check")
+    ap.add_argument("--no-workloads", action="store_true", help="with --full: skip the extra workloads after the headline")
+    ap.add_argument("--workloads", default="auto", help="with --full: comma list of pca_config5, lds_d128; auto: both after the headline "
+                                                        "shape on one GPU, pca_config5 (rows sharded over the ranks) with several")
+    ap.add_argument("--pca-rows", type=int, default=1000000, help="rows of the VB-PCA workload (BASELINE configs[4]: 10^6)")
+    ap.add_argument("--parity-replicates", type=int, default=4, help="replicates of the timed batch re-run in the oracle")
+    ap.add_argument("--rccl-single", action="store_true",
+                    help="with one process: still create a (one-rank) RCCL communicator and all-reduce the lower bound through it, "
+                         "i.e. run the multi-GPU code path as far as one GPU allows")
+    ap.add_argument("--allow-host-fallback", "--allow-gloo-fallback", dest="allow_host_fallback", action="store_true",
+                    help="if the RCCL communicator cannot be created, reduce the lower bound through host memory over the rendezvous "
+                         "sockets (line marked degraded) instead of failing")
+    args = ap.parse_args()
+
+    if args.gpus < 1:
+        raise SystemExit("--gpus must be at least 1")
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
+    if args.workloads != "auto" and not args.full:
+        raise SystemExit("--workloads selects among the extra workloads of --full: add --full")
+    if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
+        # no launcher: start the N ranks ourselves (nothing has touched the GPU in this process yet)
+        raise SystemExit(launch_ranks(args.gpus, sys.argv[1:]))
+    rank = int(os.environ.get("RANK", "0"))
+    world = int(os.environ.get("WORLD_SIZE", "1"))
+    local_rank = int(os.environ.get("LOCAL_RANK", "0"))
+    if world != args.gpus:
+        # one rank asked to stand for N GPUs (or the reverse) would put a wrong n_gpus beside a real number: refuse
+        raise SystemExit("--gpus %d but WORLD_SIZE=%d: start one rank per GPU (python bench.py --gpus N does so itself)" % (args.gpus, world))
+
+    from pyvb_amd.lds import LDSBatch      # raises if libpyvb_hip.so is missing: no fallback
+    from pyvb_amd import dist as pdist
+
+    comm = pdist.init(world, rank)         # TCP rendezvous (standard library) for barriers / max-reduce; RCCL inside the library
+    T, D, K, N = args.T, args.D, args.K, args.replicates
+    Y, st0, pri = make_inputs(T, D, K, N, seed=20240 + 1000 * rank)
+    from pyvb_amd import _capi
+    ndev = _capi.ctypes.c_int(0)
+    _capi.check(_capi.lib.pyvb_device_count(_capi.ctypes.byref(ndev)))
+    device = local_rank % max(ndev.value, 1)          # a launcher may already have narrowed the visible devices
+    b = LDSBatch.from_problem(Y, st0, pri, device=device)
+    with_cpu = args.full and not args.no_cpu_baseline
+    n_par = max(1, min(args.parity_replicates, N))
+    sample = (Y[:n_par].copy(), {k: v[:n_par].copy() for k, v in st0.items()}) if with_cpu else None
+    del Y, st0
+    collective = "none (1 GPU)"
+    degraded = False
+    use_rccl = False
+    if world > 1 or args.rccl_single:
+        # the one collective of the data path: all-reduce of the 6 lower-bound parts, over RCCL inside the library
+        uid, ok, why = None, 0.0, ""
+        # one node: RCCL's bootstrap (sockets, not the data path) over loopback, like the rendezvous above --
+        # the container's hostname / outward interface may not be usable
+        if os.environ.get("MASTER_ADDR", "127.0.0.1") in ("127.0.0.1", "localhost"):
+            os.environ.setdefault("NCCL_SOCKET_IFNAME", "lo")
+        if rank == 0:
+            try:
+                uid = LDSBatch.comm_unique_id()
+            except Exception as e:
+                why = "rank 0: no RCCL unique id (%s)" % (e,)
+        uid = comm.broadcast_bytes(uid)
+        if uid is not None:
+            try:
+                b.comm_init(uid, rank, world)
+                ok = 1.0
+            except Exception as e:
+                why = "rank %d: RCCL communicator failed (%s)" % (rank, e)
+        ok = -comm.max_float(-ok)       # min over ranks
+        use_rccl = ok == 1.0
+        if not use_rccl:
+            # a number taken with the lower bound going through host memory is not this design's data path:
+            # fail unless the caller asked for the fallback, and mark the line if so
+            if why:
+                sys.stderr.write(why + "\n")
+            if not args.allow_host_fallback:
+                b.close()
+                comm.close()
+                raise SystemExit("RCCL communicator could not be created on every rank (see stderr); "
+                                 "re-run with --allow-host-fallback for a degraded measurement (lower bound reduced through host memory)")
+            degraded = True
+            b.comm_init_host(comm, rank, world)     # the library's own collective calls, carried by the rendezvous sockets
+        collective = ("rccl allreduce(6 x f64) per step, %d rank(s)" % world) if use_rccl else "host allreduce(6 x f64) per step over TCP (RCCL init failed: DEGRADED)"
+
+    def step():
+        # one variational iteration of every replicate on this GPU: forward sweep, backward sweep, A, C, Q, R on the handle's
+        # main stream; the lower bound, its reduction over the replicates and the RCCL all-reduce over the ranks on the
+        # side stream (they feed nothing in the next iteration).  Nothing synchronises with the host inside a step; the
+        # per-step lower bounds are read from the library's history ring after the timed region.
+        b.iterate(1)
+
+    for _ in range(args.warmup):
+        step()
+    b.sync()
+    b.reset_elbo_history()
+    if args.full:
+        b.timing(True)
+    comm.barrier()
+    t0 = time.perf_counter()
+    for _ in range(args.steps):
+        step()
+    b.sync()
+    comm.barrier()
+    dt = time.perf_counter() - t0
+    dt = comm.max_float(dt)
+    hist = b.elbo_history(args.steps)
+    assert hist.shape[0] == min(args.steps, 4096) and np.all(np.isfinite(hist)), "lower-bound history incomplete"
+    elbo = hist[-1]
+    kt, roofline = {}, None
+    if args.full:
+        kt = b.kernel_times()
+        b.timing(False)
+        roofline = roofline_figures(kt, N, T, D, K, dt, args.steps)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, b, elbo)
 
     if rank == 0:
         cpu, rel, rel_x = (None, None, None)
-        if not args.no_cpu_baseline:
+        if with_cpu:
             got = b.elbo()
             gx = b.get_state(("X",))["X"][:n_par].copy()
             cpu, rel, rel_x = cpu_baseline_and_parity(sample, pri, args.warmup + args.steps, got, gx)
@@ -556,7 +607,8 @@ def main():
                                    if (T, D, K, N) == (10000, 64, 64, 1024) else "LDS T=%d D=%d K=%d, %d replicates per GPU (not a BASELINE configuration)" % (T, D, K, N),
                        "replicates_total": total_rep, "parallelism": "replicates sharded over %d GPU(s)" % world, "collective": collective,
                        "elbo_rel_err_vs_numpy": rel, "state_rel_err_vs_numpy": rel_x,
-                       "parity_checked_on": "replicates 0..%d of the timed batch after %d iterations" % (n_par - 1, args.warmup + args.steps),
+                       "parity_checked_on": ("replicates 0..%d of the timed batch after %d iterations" % (n_par - 1, args.warmup + args.steps))
+                                            if with_cpu else None,
                        "degraded": degraded, "elbo_total": float(np.sum(elbo)),
                        "elbo_total_first_timed_step": float(hist[0].sum()),
                        "kernel_ms_per_step": {k: v[0] / args.steps for k, v in kt.items() if v[1]}},
@@ -568,7 +620,9 @@ def main():
     b.close()
     # the other GPU-sized configurations of BASELINE.json, after the headline's timed region and with its memory released.
     # VB-PCA (configs[4]) is a job of ALL ranks -- its rows are sharded over them; the 128-wide LDS class runs on one GPU only
-    if args.workloads == "auto":
+    if not args.full:
+        want = []
+    elif args.workloads == "auto":
         want = [] if args.no_workloads or (N, T, D, K) != (1024, 10000, 64, 64) else (["pca_config5", "lds_d128"] if world == 1 else ["pca_config5"])
     else:
         want = [w for w in args.workloads.split(",") if w]

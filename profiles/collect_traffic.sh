@@ -9,7 +9,7 @@ OUT=$ROOT/gpurun_out/traffic_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 for C in FETCH_SIZE WRITE_SIZE; do
-  rocprofv3 --kernel-trace --pmc $C -d $OUT/$C -o t --output-format csv -- python3 $ROOT/bench.py --steps 3 --warmup 1 --no-cpu-baseline > $OUT/$C.log 2>&1
+  rocprofv3 --kernel-trace --pmc $C -d $OUT/$C -o t --output-format csv -- python3 $ROOT/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline > $OUT/$C.log 2>&1
 done
 python3 - "$OUT" <<'PY'
 import csv, sys, json, collections

@@ -11,7 +11,7 @@ cd $ROOT
 bash profiles/profile_wishart.sh $TAG > $OUT/wishart.log 2>&1
 cp $ROOT/gpurun_out/wishart_$TAG/wishart_probe.txt $ROOT/gpurun_out/wishart_$TAG/wishart_kernel_stats.csv $ROOT/gpurun_out/wishart_$TAG/wishart_traffic_pmc.json $OUT/
 cd /tmp && export TMPDIR=/tmp
-python3 $ROOT/bench.py --D 128 --K 128 --steps 10 --warmup 2 --parity-replicates 1 > $OUT/bench_d128.json 2> $OUT/bench_d128.err
+python3 $ROOT/bench.py --full --D 128 --K 128 --steps 10 --warmup 2 --parity-replicates 1 > $OUT/bench_d128.json 2> $OUT/bench_d128.err
 rocprofv3 --kernel-trace --stats -d $OUT/d128_stats -o b --output-format csv -- python3 $ROOT/bench.py --D 128 --K 128 --steps 5 --warmup 1 --no-cpu-baseline > $OUT/d128_stats.log 2>&1
 cp $OUT/d128_stats/b_kernel_stats.csv $OUT/d128_kernel_stats.csv
 rocprofv3 --kernel-trace --stats -d $OUT/pca_stats -o p --output-format csv -- python3 $ROOT/profiles/pca_probe.py > $OUT/pca_stats.log 2>&1

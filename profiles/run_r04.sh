@@ -9,11 +9,11 @@ OUT=$ROOT/gpurun_out/r04
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 if [ "$PART" = A ]; then
-  python3 $ROOT/bench.py > $OUT/bench_final.json 2> $OUT/bench.err
-  rocprofv3 --kernel-trace --stats -d $OUT/stats -o k --output-format csv -- python3 $ROOT/bench.py --steps 10 --warmup 2 --no-cpu-baseline > $OUT/stats.log 2>&1
+  python3 $ROOT/bench.py --full > $OUT/bench_final.json 2> $OUT/bench.err
+  rocprofv3 --kernel-trace --stats -d $OUT/stats -o k --output-format csv -- python3 $ROOT/bench.py --full --steps 10 --warmup 2 --no-cpu-baseline > $OUT/stats.log 2>&1
   cp $OUT/stats/k_kernel_stats.csv $OUT/bench_kernel_stats.csv
   for C in FETCH_SIZE WRITE_SIZE; do
-    rocprofv3 --kernel-trace --pmc $C -d $OUT/tr/$C -o t --output-format csv -- python3 $ROOT/bench.py --steps 3 --warmup 1 --no-cpu-baseline > $OUT/tr_$C.log 2>&1
+    rocprofv3 --kernel-trace --pmc $C -d $OUT/tr/$C -o t --output-format csv -- python3 $ROOT/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline > $OUT/tr_$C.log 2>&1
   done
   python3 $ROOT/profiles/traffic_summary.py $OUT/tr k_sweep k_stats k_prep k_cols k_gy_big k_pca_pass12 k_pca_pairs k_pca_small k_pca_reduce k_pca_rowvar > $OUT/traffic_pmc.json
   python3 - $OUT <<'PY'

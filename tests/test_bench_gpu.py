@@ -6,6 +6,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -26,7 +27,7 @@ def _line(out):
 
 
 def test_single_gpu_line_and_parity_of_the_timed_batch():
-    r = _run([sys.executable, "bench.py"] + SMALL)
+    r = _run([sys.executable, "bench.py", "--full"] + SMALL)
     assert r.returncode == 0, r.stderr[-2000:]
     d = _line(r.stdout)
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
@@ -38,6 +39,34 @@ def test_single_gpu_line_and_parity_of_the_timed_batch():
     rf = d["roofline"]
     assert rf["frac"] <= 1.0 and all(v["frac"] <= 1.0 for v in rf["secondary"].values())
     assert d["cpu_baseline"]["kind"] == "port" and d["cpu_baseline"]["value"] > 0
+
+
+def test_plain_line_and_output_dump(tmp_path):
+    """A plain run (no --full) times the steps and prints the headline fields without the figures that --full adds; its
+    --dump-outputs files are what the last timed step computed, and a --full run of the same arguments dumps the same."""
+    plain, full = tmp_path / "plain", tmp_path / "full"
+    r = _run([sys.executable, "bench.py", "--dump-outputs", str(plain)] + SMALL)
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = _line(r.stdout)
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "n_gpus", "steps", "warmup"):
+        assert k in d, k
+    assert d["steps"] == 3 and d["ms_per_step"] > 0 and abs(d["value"] * d["ms_per_step"] - 1e3 * 6 / 1024) < 1e-6 * d["value"] * d["ms_per_step"]
+    assert d["roofline"] is None and d["cpu_baseline"] is None and "workloads" not in d
+    assert d["config"]["elbo_rel_err_vs_numpy"] is None and d["config"]["parity_checked_on"] is None
+    names = sorted(p.name for p in plain.iterdir())
+    assert names == sorted(n + ".npy" for n in ("elbo_total", "elbo", "X", "A_mean", "A_colvar", "C_mean", "C_colvar",
+                                                "Q_a", "Q_b", "R_a", "R_b"))
+    got = {p.stem: np.load(p) for p in plain.iterdir()}
+    assert all(v.dtype == np.float64 and np.all(np.isfinite(v)) for v in got.values())
+    assert got["elbo"].shape == (6, 6) and got["X"].shape == (6, 256, 16) and got["A_mean"].shape == (6, 16, 16)
+    assert abs(got["elbo_total"].sum() - d["config"]["elbo_total"]) <= 1e-12 * abs(d["config"]["elbo_total"])
+    np.testing.assert_allclose(got["elbo"].sum(0), got["elbo_total"], rtol=1e-10, atol=1e-10 * np.abs(got["elbo_total"]).max())
+    r = _run([sys.executable, "bench.py", "--full", "--dump-outputs", str(full)] + SMALL)
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert _line(r.stdout)["config"]["elbo_rel_err_vs_numpy"] < 1e-8
+    for k, v in got.items():
+        w = np.load(full / (k + ".npy"))
+        np.testing.assert_allclose(w, v, rtol=1e-12, atol=1e-12 * np.abs(v).max(), err_msg=k)
 
 
 def test_one_rank_rccl_communicator_through_the_multi_gpu_branch():
@@ -89,7 +118,7 @@ def test_gpus_flag_starts_its_own_ranks():
     both = r.stderr + r.stdout
     assert "Duplicate GPU" in both, both[-3000:]
     assert not [l for l in r.stdout.splitlines() if l.startswith("{")]          # no line from a failed run
-    r2 = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--allow-host-fallback"] + SMALL, cwd=REPO, env=env_clean,
+    r2 = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--allow-host-fallback", "--full"] + SMALL, cwd=REPO, env=env_clean,
                         capture_output=True, text=True, timeout=600)
     assert r2.returncode == 0, r2.stderr[-2000:]
     d = _line(r2.stdout)
@@ -111,7 +140,7 @@ def test_pca_workload_with_its_rows_sharded_over_two_ranks():
     env = {"HSA_ENABLE_IPC_MODE_LEGACY": "0"}
     env_clean = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env_clean.update(env)
-    extra = ["--workloads", "pca_config5", "--pca-rows", "60000"]
+    extra = ["--full", "--workloads", "pca_config5", "--pca-rows", "60000"]
     r1 = subprocess.run([sys.executable, "bench.py", "--gpus", "1"] + extra + SMALL, cwd=REPO, env=env_clean, capture_output=True, text=True, timeout=600)
     assert r1.returncode == 0, r1.stderr[-2000:]
     one = _line(r1.stdout)["workloads"]["pca_config5"]

@@ -27,6 +27,16 @@ def test_world_size_mismatch_is_refused_before_any_gpu_call():
     assert r.returncode != 0 and "--gpus 1 but WORLD_SIZE=2" in r.stderr
 
 
+def test_extra_workloads_need_full_and_steps_are_counted():
+    """--workloads picks among what --full runs: without --full it is refused, as are zero timed steps, before any GPU call."""
+    r = subprocess.run([sys.executable, "bench.py", "--workloads", "pca_config5"] + SMALL, cwd=REPO, env=_env(),
+                       capture_output=True, text=True, timeout=120)
+    assert r.returncode != 0 and "--full" in r.stderr
+    r = subprocess.run([sys.executable, "bench.py"] + SMALL + ["--steps", "0"], cwd=REPO, env=_env(),
+                       capture_output=True, text=True, timeout=120)
+    assert r.returncode != 0 and "--steps must be at least 1" in r.stderr
+
+
 def test_self_launch_spawns_ranks_and_propagates_failure():
     if _has_gpu():
         import pytest
