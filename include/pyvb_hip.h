@@ -53,6 +53,13 @@ enum { PYVB_NOISE_DIAGONAL_GAMMA = 0,   /* nodes_todo.py:159-204 DiagonalGamma *
        PYVB_NOISE_WISHART = 2 };        /* nodes_todo.py:205-234 Wishart (dense precisions; see pyvb_lds_set_wishart_priors) */
 enum { PYVB_FORWARD = 0, PYVB_BACKWARD = 1 };
 
+/* Which lower bound the ELBO entry points form (pyvb_lds_set_bound_mode, pyvb_pca_set_bound_mode):
+ *   REFERENCE  the reference's log_lower_bound, quirks Q1 / Q2 of SURVEY.md included (the default)
+ *   EXACT      E_q[ln p] - E_q[ln q]: the entropies of latent Gaussians from ln det qcov, those of partially observed ones with
+ *              the sign of a true entropy, E[ln det Lambda] in place of ln det E[Lambda] in the Gaussians' own terms */
+#define PYVB_BOUND_REFERENCE 0
+#define PYVB_BOUND_EXACT 1
+
 /* which kernels pyvb_lds_timing_get() reports on */
 enum { PYVB_K_PREP = 0, PYVB_K_SWEEP_FWD = 1, PYVB_K_STATS = 2, PYVB_K_PARAMS = 3, PYVB_K_STEP = 4,
        PYVB_K_SWEEP_BWD = 5, PYVB_K_ELBO = 6, PYVB_K_GY = 7 /* 128-wide class: G y_t ahead of a sweep */, PYVB_K_COUNT = 8 };
@@ -143,7 +150,8 @@ int pyvb_lds_update_columns(pyvb_lds* h, int which, int col_begin, int col_end);
 int pyvb_lds_update_Q(pyvb_lds* h);
 int pyvb_lds_update_R(pyvb_lds* h);
 /* sum of log_lower_bound() per node class (network.py:49; gaussian.py:136-151; nodes_todo.py:149-157,:199-204),
- * reference mode (quirks Q1, Q2 of SURVEY.md reproduced). Leaves the parts on the device. */
+ * in the mode pyvb_lds_set_bound_mode chose (default: reference mode, quirks Q1, Q2 of SURVEY.md reproduced). Leaves the parts
+ * on the device. */
 int pyvb_lds_elbo(pyvb_lds* h);
 int pyvb_lds_get_elbo(pyvb_lds* h, double* parts);
 /* parts summed over this handle's replicates, then over all ranks if a communicator is attached
@@ -156,6 +164,13 @@ int pyvb_lds_iterate(pyvb_lds* h, int niters);
  * last 4096 iterations.  out[count][6], oldest first; synchronises. */
 int pyvb_lds_get_elbo_history(pyvb_lds* h, double* out, int max_count, int* count);
 int pyvb_lds_reset_elbo_history(pyvb_lds* h);
+/* The lower bound that pyvb_lds_elbo and pyvb_lds_iterate form from now on (PYVB_BOUND_*; anything else: PYVB_E_ARG).  The state
+ * updates are the same in both modes.  A change of mode empties the ELBO history. */
+int pyvb_lds_set_bound_mode(pyvb_lds* h, int mode);
+/* ln det qcov of the X_t classes lnd_x[N][3], of the columns of A and C lnd_A[N][D], lnd_C[N][D], and of the outputs with missing
+ * entries Ylnd[N][T] (of inv <R>, before the known entries are conditioned on), as their last updates left them; NaN where the
+ * q_ln_det getters give NaN.  Kept in both modes; NULL = skip. */
+int pyvb_lds_get_logdets(pyvb_lds* h, double* lnd_x, double* lnd_A, double* lnd_C, double* Ylnd);
 int pyvb_lds_sync(pyvb_lds* h);
 
 /* HIP-event timing of the kernels on the handle's stream (for bench.py's roofline figures). */
@@ -217,6 +232,11 @@ int pyvb_pca_get_state(pyvb_pca* h, double* X, double* X_rowvar, double* W_mean,
  * update()).  qld_W [q]; qld_Z, qld_Mu one double each (all Z_n share one); qld_X [N]: rows without any observed entry,
  * NaN for the others.  Any pointer may be NULL. */
 int pyvb_pca_get_qld(pyvb_pca* h, double* qld_W, double* qld_Z, double* qld_Mu, double* qld_X);
+/* The lower bound pyvb_pca_elbo and pyvb_pca_iterate form from now on (PYVB_BOUND_*; anything else: PYVB_E_ARG); the updates do not
+ * depend on it.  pyvb_pca_get_logdets: ln det qcov where pyvb_pca_get_qld gives q_ln_det, same shapes, same NaN, kept in both
+ * modes; any pointer may be NULL. */
+int pyvb_pca_set_bound_mode(pyvb_pca* h, int mode);
+int pyvb_pca_get_logdets(pyvb_pca* h, double* lnd_W, double* lnd_Z, double* lnd_Mu, double* lnd_X);
 /* [w.update() for w in Ws]; [z.update() for z in Zs]; Xs[lo:hi] updates; Mu.update(); Beta.update()
  * (gaussian.py:102-134, nodes_todo.py:130-138).  Results are what the reference's order of node updates gives, call by call; the work
  * behind pyvb_pca_update_Z is scheduled lazily: the call forms the shared posterior covariance of the Z_n, the gains and the sum of

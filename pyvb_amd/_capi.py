@@ -15,6 +15,8 @@ LIB_PATH = os.environ.get("PYVB_HIP_LIB") or os.path.join(_HERE, "libpyvb_hip.so
 OK, E_ARG, E_HIP, E_LINALG, E_STALE, E_RCCL, E_UNSUPPORTED = range(7)
 NOISE_DIAGONAL_GAMMA, NOISE_GAMMA, NOISE_WISHART = 0, 1, 2
 FORWARD, BACKWARD = 0, 1
+BOUND_REFERENCE, BOUND_EXACT = 0, 1
+BOUND_MODES = {"reference": BOUND_REFERENCE, "exact": BOUND_EXACT}
 K_PREP, K_SWEEP_FWD, K_STATS, K_PARAMS, K_STEP, K_SWEEP_BWD, K_ELBO, K_GY = range(8)
 
 _dp = ctypes.POINTER(ctypes.c_double)
@@ -60,6 +62,8 @@ SIGNATURES = {
     "pyvb_lds_iterate": (ctypes.c_int, [_h, ctypes.c_int]),
     "pyvb_lds_get_elbo_history": (ctypes.c_int, [_h, _dp, ctypes.c_int, _ip]),
     "pyvb_lds_reset_elbo_history": (ctypes.c_int, [_h]),
+    "pyvb_lds_set_bound_mode": (ctypes.c_int, [_h, ctypes.c_int]),
+    "pyvb_lds_get_logdets": (ctypes.c_int, [_h, _dp, _dp, _dp, _dp]),
     "pyvb_lds_sync": (ctypes.c_int, [_h]),
     "pyvb_lds_timing_enable": (ctypes.c_int, [_h, ctypes.c_int]),
     "pyvb_lds_timing_reset": (ctypes.c_int, [_h]),
@@ -89,6 +93,8 @@ SIGNATURES = {
     "pyvb_pca_set_initial_variances": (ctypes.c_int, [_h, _dp, _dp]),
     "pyvb_pca_get_state": (ctypes.c_int, [_h] + [_dp] * 9),
     "pyvb_pca_get_qld": (ctypes.c_int, [_h, _dp, _dp, _dp, _dp]),
+    "pyvb_pca_set_bound_mode": (ctypes.c_int, [_h, ctypes.c_int]),
+    "pyvb_pca_get_logdets": (ctypes.c_int, [_h, _dp, _dp, _dp, _dp]),
     "pyvb_pca_update_W": (ctypes.c_int, [_h]),
     "pyvb_pca_update_Z": (ctypes.c_int, [_h]),
     "pyvb_pca_update_X": (ctypes.c_int, [_h, ctypes.c_long, ctypes.c_long]),

@@ -30,6 +30,16 @@ _BATCH_OPS = ("F", "B", "Y", "A", "C", "Q", "R")
 _pool = {}          # signature -> weak references to LDSPlans that are bound but not yet on the device, in binding order
 
 
+
+def exact_elbo(batch):
+    """The parts of the exact lower bound of a fused handle (LDSBatch / PCABatch); the handle is left in the reference mode the
+    node API keeps it in."""
+    batch.set_bound_mode("exact")
+    try:
+        return batch.elbo()
+    finally:
+        batch.set_bound_mode("reference")
+
 class LDSGroup(object):
     """ONE LDSBatch for M graphs of the same structure: replicate r is the graph of members[r].
 
@@ -72,6 +82,7 @@ class LDSGroup(object):
         self.ran = False                # anything at all has run on the device (the outputs can update before any sweep)
         self.cache = None
         self._elbo = None
+        self._elbo_x = None             # the same parts of the exact lower bound
         self.epoch = 0                  # counts the members that have left (Network.learn's schedule looks at it)
         for r, m in enumerate(members):
             m.group, m.r = self, r
@@ -82,6 +93,7 @@ class LDSGroup(object):
     def invalidate(self):
         self.cache = None
         self._elbo = None
+        self._elbo_x = None
 
     def drop(self, member):
         """`member` has left (its replicate keeps being computed with the others; nobody reads it)."""
@@ -176,7 +188,11 @@ class LDSGroup(object):
             self.cache = c
         return self.cache
 
-    def elbo(self):
+    def elbo(self, bound="reference"):
+        if bound == "exact":
+            if self._elbo_x is None:
+                self._elbo_x = exact_elbo(self.batch)
+            return self._elbo_x
         if self._elbo is None:
             self._elbo = self.batch.elbo()
         return self._elbo
@@ -521,30 +537,30 @@ class LDSPlan(object):
         return True
 
     # -- lower bound -----------------------------------------------------------------------------
-    def elbo_parts(self):
+    def elbo_parts(self, bound="reference"):
         self.flush()
         if self.Xs[0]._plan is not self:        # the graph has moved: to a handle of its own, or to the node-by-node plan
             plan = N._plan_of(self.Xs[0])
             if isinstance(plan, LDSPlan):
-                return plan.elbo_parts()
+                return plan.elbo_parts(bound)
             raise NotImplementedError("the graph runs node by node now: use Network.learn or the nodes' log_lower_bound()")
-        return self._materialize().elbo()[self.r]
+        return self._materialize().elbo(bound)[self.r]
 
-    def node_llb(self, node):
+    def node_llb(self, node, bound="reference"):
         self.flush()
         if node._plan is not self:
-            return N._plan_of(node).node_llb(node)
+            return N._plan_of(node).node_llb(node, bound)
         if not self.x_updated:                  # single terms before any sweep: only the generic plan knows the initial covariances
             self._demote(self._rest())
-            return N._plan_of(node).node_llb(node)
+            return N._plan_of(node).node_llb(node, bound)
         kind, _ = self.index[id(node)]
-        if kind == "q":
-            return float(self.elbo_parts()[4])
+        if kind == "q":                         # (the noise nodes' own terms are the same in both modes)
+            return float(self.elbo_parts(bound)[4])
         if kind == "r":
-            return float(self.elbo_parts()[5])
+            return float(self.elbo_parts(bound)[5])
         # a single state / output / column node: the fused kernels only form class sums, so the term is evaluated by the
         # generic tape path on a mirror of the current state (gaussian.py:136-151)
-        return self.mirror().node_llb(node)
+        return self.mirror().node_llb(node, bound)
 
     def mirror(self):
         """A generic (node-by-node) plan holding a copy of this plan's current posteriors: serves single messages
@@ -918,22 +934,22 @@ class PCAPlan(object):
             return node._plan.write(node, name, value)
         return name not in ("qmu", "qcov", "qb", "qw")
 
-    def elbo_parts(self):
+    def elbo_parts(self, bound="reference"):
         self.flush()
         if self.W._plan is not self:
             raise NotImplementedError("the graph runs node by node now: use Network.learn or the nodes' log_lower_bound()")
-        return self.batch.elbo()
+        return exact_elbo(self.batch) if bound == "exact" else self.batch.elbo()
 
-    def node_llb(self, node):
+    def node_llb(self, node, bound="reference"):
         self.flush()
         if node._plan is not self:
-            return node._plan.node_llb(node)
+            return node._plan.node_llb(node, bound)
         kind, _ = self.index[id(node)]
         if kind == "beta":
-            return float(self.elbo_parts()[4])
+            return float(self.elbo_parts(bound)[4])
         # single Gaussian nodes: the fused kernels form class sums (and keep Mu's q_ln_det only from its last update on THIS
         # handle: a graph bound anew has it on the host), so the term comes from the generic tape path on a mirror of the state
-        return self.mirror().node_llb(node)
+        return self.mirror().node_llb(node, bound)
 
     def _sync_host(self):
         st = self._pull()

@@ -108,6 +108,8 @@ int pyvb_lds_create(pyvb_lds** out, int device, int N, int T, int D, int K, int 
     TRY(dev_alloc(&h->qld_A, n * D)); TRY(dev_alloc(&h->qld_C, n * D));
     TRY(dev_alloc(&h->Sigma, n * 3 * D * D)); TRY(dev_alloc(&h->Sigma_new, n * 3 * D * D));
     TRY(dev_alloc(&h->qld_x, n * 3)); TRY(dev_alloc(&h->qld_x_new, n * 3));
+    TRY(dev_alloc(&h->lnd_A, n * D)); TRY(dev_alloc(&h->lnd_C, n * D));
+    TRY(dev_alloc(&h->lnd_x, n * 3)); TRY(dev_alloc(&h->lnd_x_new, n * 3));
     TRY(dev_alloc(&h->gains, n * L.gains_total));
     TRY(dev_alloc(&h->scratch, h->big ? n * 2 * L.DP * L.DP : n * 2 * D * D));
     TRY(dev_alloc(&h->zeros, 128));
@@ -180,6 +182,9 @@ int pyvb_lds_create(pyvb_lds** out, int device, int N, int T, int D, int K, int 
         TRYHIP(hipMemcpy(h->qld_x, nanv.data(), n * 3 * sizeof(double), hipMemcpyHostToDevice));
         TRYHIP(hipMemcpy(h->qld_A, nanv.data(), n * D * sizeof(double), hipMemcpyHostToDevice));
         TRYHIP(hipMemcpy(h->qld_C, nanv.data(), n * D * sizeof(double), hipMemcpyHostToDevice));
+        TRYHIP(hipMemcpy(h->lnd_x, nanv.data(), n * 3 * sizeof(double), hipMemcpyHostToDevice));
+        TRYHIP(hipMemcpy(h->lnd_A, nanv.data(), n * D * sizeof(double), hipMemcpyHostToDevice));
+        TRYHIP(hipMemcpy(h->lnd_C, nanv.data(), n * D * sizeof(double), hipMemcpyHostToDevice));
     }
 #undef TRY
 #undef TRYHIP
@@ -201,7 +206,8 @@ int pyvb_lds_destroy(pyvb_lds* h) {
                       h->qld_A, h->qld_C, h->Sigma, h->Sigma_new, h->qld_x, h->qld_x_new, h->gains, h->scratch, h->stats,
                       h->resQ, h->resR, h->elbo, h->elbo_sum, h->pri_block, h->trash, h->zeros, h->mom, h->sxx, h->U,
                       h->Q_w, h->R_w, h->Qbar, h->Rbar, h->lnd, h->QA, h->RC, h->trA, h->trC, h->A_cov, h->C_cov, h->SyyF, h->RQ, h->RR, h->SG, h->ldm,
-                      h->Yobs, h->Yvar, h->Yqld, h->Yent, h->Yld, h->YcovS, h->U2};
+                      h->Yobs, h->Yvar, h->Yqld, h->Yent, h->Yld, h->YcovS, h->U2,
+                      h->lnd_A, h->lnd_C, h->lnd_x, h->lnd_x_new, h->Ylnd, h->YentX};
     for (double* b : bufs) if (b) (void)hipFree(b);
     if (h->warm) (void)hipFree(h->warm);
     if (h->status) (void)hipFree(h->status);
@@ -462,6 +468,8 @@ int pyvb_lds_set_observations(pyvb_lds* h, const double* Y) {
             if ((rc = dev_alloc(&h->Yvar, n))) return rc;
             if ((rc = dev_alloc(&h->Yqld, (size_t)h->N * h->T))) return rc;
             if ((rc = dev_alloc(&h->Yent, h->N))) return rc;
+            if ((rc = dev_alloc(&h->Ylnd, (size_t)h->N * h->T))) return rc;
+            if ((rc = dev_alloc(&h->YentX, h->N))) return rc;
             if (h->dense) {
                 if ((rc = dev_alloc(&h->Yld, (size_t)h->N * h->T))) return rc;
                 if ((rc = dev_alloc(&h->YcovS, (size_t)h->N * h->K * h->K))) return rc;
@@ -602,6 +610,7 @@ int pyvb_lds_set_posterior_classes(pyvb_lds* h, const double* Sigma, const doubl
     int rc;
     if ((rc = h2d(h, h->Sigma, Sigma, N * 3 * D * D))) return rc;
     if ((rc = h2d(h, h->qld_x, qld_x, N * 3))) return rc;
+    h->lnd_x_pending = true;        // ln det of these covariances: formed when the exact bound first asks for it (ensure_lnd_x)
     HIPCHK(hipStreamSynchronize(h->stream));
     h->classes_valid = true;
     states_changed(h);
@@ -666,6 +675,36 @@ static int ensure_expect(pyvb_lds* h) {        // E[Q], E[R] of the current Wish
     return PYVB_OK;
 }
 
+// Covariances of the X_t given by pyvb_lds_set_posterior_classes: ln det of each (Cholesky on the host, NaN where one is not
+// positive definite), formed once, when the exact bound or pyvb_lds_get_logdets first needs it -- not on the default path.
+static int ensure_lnd_x(pyvb_lds* h) {
+    if (!h->lnd_x_pending) return PYVB_OK;
+    const size_t N = h->N, D = h->D;
+    std::vector<double> S(N * 3 * D * D), lnd(N * 3), L(D * D);
+    HIPCHK(hipMemcpyAsync(S.data(), h->Sigma, S.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    for (size_t m = 0; m < N * 3; ++m) {
+        const double* Sm = S.data() + m * D * D;
+        double s = 0.0;
+        for (size_t j = 0; j < D && s == s; ++j) {
+            for (size_t i = j; i < D; ++i) {
+                double v = Sm[i * D + j];
+                for (size_t k = 0; k < j; ++k) v -= L[i * D + k] * L[j * D + k];
+                if (i == j) {
+                    if (!(v > 0.0)) { s = NAN; break; }
+                    L[j * D + j] = sqrt(v);
+                    s += log(v);
+                } else L[i * D + j] = v / L[j * D + j];
+            }
+        }
+        lnd[m] = s;
+    }
+    HIPCHK(hipMemcpyAsync(h->lnd_x, lnd.data(), lnd.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    h->lnd_x_pending = false;
+    return PYVB_OK;
+}
+
 static int ensure_gains(pyvb_lds* h) {
     if (h->gains_valid) return PYVB_OK;
     int rc;
@@ -683,6 +722,8 @@ static int ensure_gains(pyvb_lds* h) {
 static void adopt_classes(pyvb_lds* h) {
     double* t = h->Sigma; h->Sigma = h->Sigma_new; h->Sigma_new = t;
     t = h->qld_x; h->qld_x = h->qld_x_new; h->qld_x_new = t;
+    t = h->lnd_x; h->lnd_x = h->lnd_x_new; h->lnd_x_new = t;
+    h->lnd_x_pending = false;
     h->classes_valid = true;
 }
 
@@ -799,6 +840,7 @@ int pyvb_lds_elbo(pyvb_lds* h) {
     int rc;
     if ((rc = ensure_resid(h, 0))) return rc;
     if ((rc = ensure_resid(h, 1))) return rc;
+    if (h->bound == PYVB_BOUND_EXACT && (rc = ensure_lnd_x(h))) return rc;
     if (h->dense) {
         if ((rc = ensure_expect(h))) return rc;
         return launch_elbo_dense(h);
@@ -849,6 +891,7 @@ int pyvb_lds_iterate(pyvb_lds* h, int niters) {
             params_changed(h);
         }
         h->resQ_valid = h->resR_valid = true;
+        if (h->bound == PYVB_BOUND_EXACT && (rc = ensure_lnd_x(h))) return rc;       // (only before the first complete sweep)
         // The lower bound (network.py:49) feeds nothing in the next iteration: it is evaluated on the side stream while
         // the main one goes on with k_prep and the forward sweep.  Its per-iteration totals (summed over the replicates,
         // and over the ranks when a communicator is attached) go into a history ring (pyvb_lds_get_elbo_history).
@@ -885,6 +928,29 @@ int pyvb_lds_get_elbo_history(pyvb_lds* h, double* out, int max_count, int* coun
 }
 
 int pyvb_lds_reset_elbo_history(pyvb_lds* h) { ENTER(h); HIPCHK(hipStreamSynchronize(h->side)); h->hist_count = 0; return PYVB_OK; }
+
+int pyvb_lds_set_bound_mode(pyvb_lds* h, int mode) {
+    ENTER(h);
+    ARGCHK(mode == PYVB_BOUND_REFERENCE || mode == PYVB_BOUND_EXACT, "mode must be PYVB_BOUND_REFERENCE or PYVB_BOUND_EXACT");
+    HIPCHK(hipStreamSynchronize(h->side));
+    h->bound = mode;
+    h->hist_count = 0;              // the history holds bounds of one mode only
+    return PYVB_OK;
+}
+
+int pyvb_lds_get_logdets(pyvb_lds* h, double* lnd_x, double* lnd_A, double* lnd_C, double* Ylnd) {
+    ENTER(h);
+    int rc;
+    if (lnd_x && (rc = ensure_lnd_x(h))) return rc;
+    if ((rc = d2h(h, lnd_x, h->lnd_x, (size_t)h->N * 3))) return rc;
+    if ((rc = d2h(h, lnd_A, h->lnd_A, (size_t)h->N * h->D))) return rc;
+    if ((rc = d2h(h, lnd_C, h->lnd_C, (size_t)h->N * h->D))) return rc;
+    if (Ylnd) {
+        if (h->has_missing) { if ((rc = d2h(h, Ylnd, h->Ylnd, (size_t)h->N * h->T))) return rc; }
+        else for (size_t i = 0; i < (size_t)h->N * h->T; ++i) Ylnd[i] = NAN;
+    }
+    return pyvb_lds_sync(h);
+}
 
 int pyvb_lds_sync(pyvb_lds* h) {
     ENTER(h);

@@ -33,7 +33,7 @@ int pyvb_pca_destroy(pyvb_pca* h) {
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     if (h->comm) pyvb_comm_free(h->comm);
-    void* bufs[] = {h->X, h->M, h->xvar, h->nmiss, h->Z, h->W_mean, h->W_var, h->Mu_mean, h->Mu_var, h->Z_cov, h->qld_W, h->W_pm, h->W_pp,
+    void* bufs[] = {h->X, h->M, h->xvar, h->nmiss, h->Z, h->W_mean, h->W_var, h->Mu_mean, h->Mu_var, h->Z_cov, h->qld_W, h->lnd_W, h->W_pm, h->W_pp,
                     h->Mu_pm, h->Mu_pp, h->scal, h->Gz, h->g0, h->part, h->stats, h->aux, h->elbo, h->status, h->red2, h->Xdata, h->pinned, h->sx_local,
                     h->W_x, h->Mu_x};
     for (void* b : bufs) if (b) (void)hipFree(b);
@@ -84,7 +84,7 @@ int pyvb_pca_create(pyvb_pca** out, int device, long N, int d, int q, long N_tot
     TRYHIP(hipMalloc((void**)&h->nmiss, n * sizeof(int))); TRYHIP(hipMemset(h->nmiss, 0, n * sizeof(int)));
     TRY(alloc_d(&h->Z, n * QP));
     TRY(alloc_d(&h->W_mean, (size_t)d * q)); TRY(alloc_d(&h->W_var, (size_t)q * d));
-    TRY(alloc_d(&h->Mu_mean, d)); TRY(alloc_d(&h->Mu_var, d)); TRY(alloc_d(&h->Z_cov, (size_t)q * q)); TRY(alloc_d(&h->qld_W, q));
+    TRY(alloc_d(&h->Mu_mean, d)); TRY(alloc_d(&h->Mu_var, d)); TRY(alloc_d(&h->Z_cov, (size_t)q * q)); TRY(alloc_d(&h->qld_W, q)); TRY(alloc_d(&h->lnd_W, q));
     TRY(alloc_d(&h->W_pm, (size_t)d * q)); TRY(alloc_d(&h->W_pp, (size_t)q * d)); TRY(alloc_d(&h->Mu_pm, d)); TRY(alloc_d(&h->Mu_pp, d));
     TRY(alloc_d(&h->W_x, (size_t)d * q)); TRY(alloc_d(&h->Mu_x, d));
     { const char* e = getenv("PYVB_PCA_WRITEBACK"); h->lazy_ok = !(e && e[0] == '1'); }
@@ -160,9 +160,11 @@ int pyvb_pca_set_priors(pyvb_pca* h, const double* W_pm, const double* W_pp, con
     sc[PS_BETA_A] = beta_a0 + 0.5 * (double)h->d * (double)h->N_total;      // Gamma.update_a, nodes_todo.py:125-128
     sc[PS_LGAMMA_A0] = std::lgamma(beta_a0); sc[PS_LGAMMA_A] = std::lgamma(sc[PS_BETA_A]); sc[PS_DIGAMMA_A] = digamma_host(sc[PS_BETA_A]);
     sc[PS_QLD_Z] = sc[PS_QLD_X] = sc[PS_QLD_MU] = NAN;
+    sc[PS_LND_Z] = sc[PS_LND_MU] = NAN;
     HIPCHK(hipMemcpy(h->scal, sc, sizeof(sc), hipMemcpyHostToDevice));
     std::vector<double> nanq((size_t)h->q, (double)NAN);        // no column has been updated on this handle yet
     HIPCHK(hipMemcpy(h->qld_W, nanq.data(), nanq.size() * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(h->lnd_W, nanq.data(), nanq.size() * sizeof(double), hipMemcpyHostToDevice));
     HIPCHK(hipStreamSynchronize(h->stream));
     return PYVB_OK;
 }
@@ -338,6 +340,37 @@ int pyvb_pca_get_qld(pyvb_pca* h, double* qld_W, double* qld_Z, double* qld_Mu, 
     HIPCHK(se);
     if (qld_Z) *qld_Z = sc[PS_QLD_Z];
     if (qld_Mu) *qld_Mu = sc[PS_QLD_MU];
+    return PYVB_OK;
+}
+
+int pyvb_pca_set_bound_mode(pyvb_pca* h, int mode) {
+    ENTER(h);
+    ARGCHK(mode == PYVB_BOUND_REFERENCE || mode == PYVB_BOUND_EXACT, "mode must be PYVB_BOUND_REFERENCE or PYVB_BOUND_EXACT");
+    HIPCHK(hipStreamSynchronize(h->stream));
+    h->bound = mode;
+    return PYVB_OK;
+}
+
+int pyvb_pca_get_logdets(pyvb_pca* h, double* lnd_W, double* lnd_Z, double* lnd_Mu, double* lnd_X) {
+    ENTER(h);
+    int rc;
+    double sc[PS_COUNT];
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if ((rc = down(h, lnd_W, h->lnd_W, (size_t)h->q))) return rc;
+    HIPCHK(hipMemcpyAsync(sc, h->scal, sizeof(sc), hipMemcpyDeviceToHost, h->stream));
+    double* tmp = nullptr;
+    if (lnd_X) {
+        HIPCHK(hipMalloc((void**)&tmp, (size_t)h->N * sizeof(double)));
+        if ((rc = pca_launch_rowqld(h, tmp, 1)) || (rc = down(h, lnd_X, tmp, (size_t)h->N))) {
+            (void)hipStreamSynchronize(h->stream); (void)hipFree(tmp);
+            return rc;
+        }
+    }
+    const hipError_t se = hipStreamSynchronize(h->stream);
+    if (tmp) (void)hipFree(tmp);
+    HIPCHK(se);
+    if (lnd_Z) *lnd_Z = sc[PS_LND_Z];
+    if (lnd_Mu) *lnd_Mu = sc[PS_LND_MU];
     return PYVB_OK;
 }
 

@@ -98,11 +98,15 @@ struct pyvb_lds {
     double *A_mean, *A_var, *C_mean, *C_var;
     double *Q_a, *Q_b, *R_a, *R_b;
     double *qld_A, *qld_C;          // [N][D]
+    double *lnd_A, *lnd_C;          // [N][D] ln det qcov of the columns, written where qld_A / qld_C are (NaN before the first update)
+    int bound;                      // PYVB_BOUND_REFERENCE / PYVB_BOUND_EXACT: which lower bound k_elbo / k_elbo_dense form
     Priors pri;
     double *pri_block;
     // derived
     double *Sigma, *qld_x;          // as of the last X update: [N][3][D][D], [N][3]
     double *Sigma_new, *qld_x_new;  // written by k_prep for the current parameters
+    double *lnd_x, *lnd_x_new;      // [N][3] ln det Sigma beside qld_x / qld_x_new (swapped with them)
+    bool lnd_x_pending;             // Sigma was set by the caller: lnd_x is formed from it when first needed (api.hip: ensure_lnd_x)
     double *gains;                  // [N][L.gains_total]
     double *scratch;                // [N][2][DP][DP] (M_C, M_A + M_C)
     int *warm;                      // [N][2]
@@ -140,6 +144,7 @@ struct pyvb_lds {
     // ---- outputs with missing entries (k_missing.hip); allocated when set_observations sees NaN
     bool has_missing;
     double *Yobs, *Yvar, *Yqld, *Yent;      // [N][T][K] observations (NaN = missing), [N][T][K] variances, [N][T], [N]
+    double *Ylnd, *YentX;                   // [N][T] ln det qcov beside Yqld; [N] the exact entropy of those rows (added, not subtracted)
     double *Yld, *YcovS;                    // Wishart noise: [N][T] ln det of each row's covariance of missing entries, [N][K][K] sum_t qcov_t
     // ---- the lower bound does not feed the next iteration: inside pyvb_lds_iterate it runs on a side stream
     hipStream_t side;

@@ -641,7 +641,7 @@ int launch_stats_big(pyvb_lds* h) {
 // ======================================================================================================================
 struct BigPrepArgs {
     const double *A_mean, *A_var, *C_mean, *C_var, *Q_a, *Q_b, *R_a, *R_b, *x0_mean, *x0_prec;
-    double *Sigma, *qld, *gains, *scratch;      // scratch: [N][2][128][128]
+    double *Sigma, *qld, *lnd, *gains, *scratch;        // scratch: [N][2][128][128]; lnd: ln det Sigma beside qld
     // Wishart noise (dense): E[Q] [D][D], E[Q]<A> [D][D], E[R]<C> [K][D], tr(S_i E[Q]) [D], tr(S'_i E[R]) [D] per replicate
     const double *Qbar, *QA, *RC, *trA, *trC;
     int *warm, *status;
@@ -923,7 +923,7 @@ __global__ void __launch_bounds__(256) k_prep_big(BigPrepArgs a) {
                 lp += log(piv);
             }
             lp = wave_sum(lp);
-            if (tid == 0) a.qld[(size_t)n * 3 + c] = 0.5 / (0.5 * lp);
+            if (tid == 0) { a.qld[(size_t)n * 3 + c] = 0.5 / (0.5 * lp); a.lnd[(size_t)n * 3 + c] = -lp; }
         }
         // a thread's eight entries of a row are 64 contiguous bytes: with D a multiple of four they are stored as two 32-byte pieces
         // (element by element a wavefront's store touched 64 separate sectors and wrote a quarter of each)
@@ -1011,7 +1011,7 @@ int launch_prep_big(pyvb_lds* h) {
     a.A_mean = h->A_mean; a.A_var = h->A_var; a.C_mean = h->C_mean; a.C_var = h->C_var;
     a.Q_a = h->Q_a; a.Q_b = h->Q_b; a.R_a = h->R_a; a.R_b = h->R_b;
     a.x0_mean = h->pri.x0_mean; a.x0_prec = h->pri.x0_prec;
-    a.Sigma = h->Sigma_new; a.qld = h->qld_x_new; a.gains = h->gains; a.scratch = h->scratch;
+    a.Sigma = h->Sigma_new; a.qld = h->qld_x_new; a.lnd = h->lnd_x_new; a.gains = h->gains; a.scratch = h->scratch;
     a.warm = h->warm; a.status = h->status;
     a.N = h->N; a.T = h->T; a.D = h->D; a.K = h->K; a.noise = h->noise; a.L = h->L;
     a.dense = h->dense ? 1 : 0; a.Qbar = h->Qbar; a.QA = h->QA; a.RC = h->RC; a.trA = h->trA; a.trC = h->trC;
@@ -1054,6 +1054,7 @@ __global__ void __launch_bounds__(256) k_cols_big_rows(ParamArgs a) {
     double* M = (WHICH == 0 ? a.A_mean : a.C_mean) + (size_t)n * rows * D;
     double* V = (WHICH == 0 ? a.A_var : a.C_var) + (size_t)n * D * rows;
     double* qld = (WHICH == 0 ? a.qld_A : a.qld_C) + (size_t)n * D;
+    double* lnd = (WHICH == 0 ? a.lnd_A : a.lnd_C) + (size_t)n * D;
     const double* pm = WHICH == 0 ? a.pri.A_pm : a.pri.C_pm;    // [row][col]
     const double* pp = WHICH == 0 ? a.pri.A_pp : a.pri.C_pp;    // [col][row]
     const double* obs = WHICH == 0 ? a.pri.A_obs : a.pri.C_obs; // [row][col], NaN = not known
@@ -1122,7 +1123,7 @@ __global__ void __launch_bounds__(256) k_cols_big_rows(ParamArgs a) {
     if (tid >= a.c0 && tid < a.c1 && tid < BDP) {
         const double lp = ((plp[tid] + plp[BDP + tid]) + plp[2 * BDP + tid]) + plp[3 * BDP + tid];
         const double nk = ((pkn[tid] + pkn[BDP + tid]) + pkn[2 * BDP + tid]) + pkn[3 * BDP + tid];
-        if ((int)nk < rows) qld[tid] = 0.5 / (0.5 * lp);                                // quirk Q1, gaussian.py:120: of the whole precision
+        if ((int)nk < rows) { qld[tid] = 0.5 / (0.5 * lp); lnd[tid] = -lp; }          // quirk Q1, gaussian.py:120: of the whole precision
     }
     if (a.c0 < a.c1 && live) {
 #pragma unroll
@@ -1203,6 +1204,7 @@ __global__ void __launch_bounds__(256) k_cols_big(ParamArgs a) {
     double* M = (WHICH == 0 ? a.A_mean : a.C_mean) + (size_t)n * rows * D;
     double* V = (WHICH == 0 ? a.A_var : a.C_var) + (size_t)n * D * rows;
     double* qld = (WHICH == 0 ? a.qld_A : a.qld_C) + (size_t)n * D;
+    double* lnd = (WHICH == 0 ? a.lnd_A : a.lnd_C) + (size_t)n * D;
     const double* pm = WHICH == 0 ? a.pri.A_pm : a.pri.C_pm;    // [row][col]
     const double* pp = WHICH == 0 ? a.pri.A_pp : a.pri.C_pp;    // [col][row]
     const double* obs = WHICH == 0 ? a.pri.A_obs : a.pri.C_obs; // [row][col], NaN = not known
@@ -1452,7 +1454,7 @@ __global__ void __launch_bounds__(256) k_cols_big(ParamArgs a) {
     if (tid >= a.c0 && tid < a.c1 && tid < BDP) {
         const double lp = ((plp[tid] + plp[BDP + tid]) + plp[2 * BDP + tid]) + plp[3 * BDP + tid];
         const double nk = ((pkn[tid] + pkn[BDP + tid]) + pkn[2 * BDP + tid]) + pkn[3 * BDP + tid];
-        if ((int)nk < rows) qld[tid] = 0.5 / (0.5 * lp);                                // quirk Q1, gaussian.py:120: of the whole precision
+        if ((int)nk < rows) { qld[tid] = 0.5 / (0.5 * lp); lnd[tid] = -lp; }          // quirk Q1, gaussian.py:120: of the whole precision
     }
     if (fuse1) {
         // res[k] = 1/2 own[k] + 1/2 (sum_ij M[k,i] G[i,j] M[k,j] + sum_i var_i[k] G[i,i]) - sum_i H[k,i] M[k,i]   (node.py:260-271)

@@ -53,6 +53,7 @@ __global__ void __launch_bounds__(64) k_cols(ParamArgs a) {
     double* M = (WHICH == 0 ? a.A_mean : a.C_mean) + (size_t)n * rows * D;
     double* V = (WHICH == 0 ? a.A_var : a.C_var) + (size_t)n * D * rows;
     double* qld = (WHICH == 0 ? a.qld_A : a.qld_C) + (size_t)n * D;
+    double* lnd = (WHICH == 0 ? a.lnd_A : a.lnd_C) + (size_t)n * D;
     const double* pm = WHICH == 0 ? a.pri.A_pm : a.pri.C_pm;    // [row][col]
     const double* pp = WHICH == 0 ? a.pri.A_pp : a.pri.C_pp;    // [col][row]
     const double* obs = WHICH == 0 ? a.pri.A_obs : a.pri.C_obs; // [row][col], NaN = not observed
@@ -179,8 +180,11 @@ __global__ void __launch_bounds__(64) k_cols(ParamArgs a) {
                     ex += __shfl_xor(ex, o, 64);
                 }
                 const int i = 16 * b + c;
-                if (q == 0 && i >= a.c0 && i < a.c1 && mynk < rows)
-                    qld[i] = 0.5 / (0.5 * (log(mant) + (double)ex * 0.6931471805599453));
+                if (q == 0 && i >= a.c0 && i < a.c1 && mynk < rows) {
+                    const double lp = log(mant) + (double)ex * 0.6931471805599453;
+                    qld[i] = 0.5 / (0.5 * lp);
+                    lnd[i] = -lp;
+                }
             }
         }
         __syncthreads();

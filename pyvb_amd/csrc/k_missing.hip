@@ -6,7 +6,8 @@
 //                  qprec = <R> (diagonal), qmu = <C> mu_t, then the known entries are conditioned on (:125-134), which for
 //                  a diagonal covariance pins them (variance 0) and leaves the others at <C> mu_t with variance 1 / <R>_k
 //   k_syy_missing  sum_t <y y^T> diagonal = sum_t (qmu^2 + variance), and what Gaussian.log_lower_bound subtracts for the
-//                  rows that are not fully observed (:145-150)
+//                  rows that are not fully observed (:145-150); beside it the true entropy of those rows, which the exact
+//                  lower bound adds (both are formed every time, so that the bound mode may change between calls)
 // Until its first update() a partially observed row keeps the constructor's posterior in ALL entries (observe() only
 // records the known values): k_missing_init writes that state.
 #include "params.h"
@@ -14,12 +15,13 @@
 
 struct MissArgs {
     double* Y; const double* Yobs; double* Yvar; double* Yqld;
+    double* Ylnd;       // [N][T] ln det qcov beside Yqld (of inv <R>, before the conditioning on the known entries)
     // Wishart noise (dense <R>): E[R] [N][K][K], [N][4] log-determinants (k_wexpect), the symmetrised qw and qv; per row the
     // ln det of the covariance of its missing entries (NaN: not updated yet, the diagonal initial state), and sum_t qcov_t
     const double *Rbar, *lnd, *R_w; double* Yld; double* YcovS;
     int diag_cov;       // k_missing_ent_dense: 1 = the rows still carry their diagonal initial covariances: form YcovS from Yvar
     const double* X; const double* C_mean; const double *R_a, *R_b;
-    double* Syy; double* Yent;
+    double* Syy; double* Yent; double* YentX;
     const double* Yq0; const double* Yrowvar0;
     int N, T, K, D, DP;
 };
@@ -45,7 +47,10 @@ __global__ void __launch_bounds__(256) k_missing_init(MissArgs a) {
         a.Y[row + k] = any ? (a.Yq0 ? a.Yq0[row + k] : 0.0) : ob[h];
         a.Yvar[row + k] = any ? (a.Yrowvar0 ? a.Yrowvar0[(size_t)n * a.T + t] : 1.0) : 0.0;
     }
-    if (lane == 0) { a.Yqld[(size_t)n * a.T + t] = nan(""); if (a.Yld) a.Yld[(size_t)n * a.T + t] = nan(""); }
+    if (lane == 0) {
+        a.Yqld[(size_t)n * a.T + t] = nan(""); a.Ylnd[(size_t)n * a.T + t] = nan("");
+        if (a.Yld) a.Yld[(size_t)n * a.T + t] = nan("");
+    }
 }
 
 __global__ void __launch_bounds__(256) k_impute(MissArgs a) {
@@ -65,7 +70,7 @@ __global__ void __launch_bounds__(256) k_impute(MissArgs a) {
     }
     if (__ballot(miss[0] || miss[1]) == 0) return;      // fully observed: never updates (gaussian.py:109-110)
     lr = wave_sum(lr);
-    if (lane == 0) a.Yqld[(size_t)n * a.T + t] = 0.5 / lr;    // gaussian.py:120 (quirk Q1)
+    if (lane == 0) { a.Yqld[(size_t)n * a.T + t] = 0.5 / lr; a.Ylnd[(size_t)n * a.T + t] = -2.0 * lr; }    // gaussian.py:120 (quirk Q1); ln det qcov
     const double* x = a.X + ((size_t)n * a.T + t) * a.DP;
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
@@ -85,12 +90,12 @@ __global__ void __launch_bounds__(256) k_impute(MissArgs a) {
 }
 
 __global__ void __launch_bounds__(256) k_syy_missing(MissArgs a) {
-    __shared__ double red[4][130];
+    __shared__ double red[4][131];
     const int n = blockIdx.x, w = threadIdx.x >> 6, lane = threadIdx.x & 63, K = a.K, T = a.T;
     const double* Y = a.Y + (size_t)n * T * K;
     const double* Yo = a.Yobs + (size_t)n * T * K;
     const double* Yv = a.Yvar + (size_t)n * T * K;
-    double s[2] = {0.0, 0.0}, ent = 0.0;
+    double s[2] = {0.0, 0.0}, ent = 0.0, entx = 0.0;
     for (int t = w; t < T; t += 4) {
         bool miss[2];
         double lv = 0.0;
@@ -108,9 +113,11 @@ __global__ void __launch_bounds__(256) k_syy_missing(MissArgs a) {
         lv = wave_sum(lv);
         if (nm == K) ent += -0.5 * K * LN2PI - 0.5 * a.Yqld[(size_t)n * T + t] - 0.5 * K;        // gaussian.py:145-147
         else ent += 0.5 * nm * LN2PI - 0.5 * lv - 0.5 * nm;                                        // gaussian.py:148-150
+        // the entropy of the row's missing entries (exact bound)
+        entx += 0.5 * nm * LN2PI + 0.5 * (nm == K ? a.Ylnd[(size_t)n * T + t] : lv) + 0.5 * nm;
     }
     red[w][lane] = s[0]; red[w][64 + lane] = s[1];
-    if (lane == 0) red[w][128] = ent;
+    if (lane == 0) { red[w][128] = ent; red[w][129] = entx; }
     __syncthreads();
     if (w == 0) {
 #pragma unroll
@@ -118,7 +125,10 @@ __global__ void __launch_bounds__(256) k_syy_missing(MissArgs a) {
             const int k = lane + 64 * h;
             if (k < K) a.Syy[(size_t)n * K + k] = red[0][k] + red[1][k] + red[2][k] + red[3][k];
         }
-        if (lane == 0) a.Yent[n] = red[0][128] + red[1][128] + red[2][128] + red[3][128];
+        if (lane == 0) {
+            a.Yent[n] = red[0][128] + red[1][128] + red[2][128] + red[3][128];
+            a.YentX[n] = red[0][129] + red[1][129] + red[2][129] + red[3][129];
+        }
     }
 }
 
@@ -218,7 +228,7 @@ __global__ void __launch_bounds__(256) k_impute_dense(MissArgs a) {
                 }
         }
         if (lane < K) { a.Y[row + lane] = mean; a.Yvar[row + lane] = var; }
-        if (lane == 0) a.Yqld[(size_t)n * T + t] = qld_full;
+        if (lane == 0) { a.Yqld[(size_t)n * T + t] = qld_full; a.Ylnd[(size_t)n * T + t] = -a.lnd[(size_t)n * 4 + 1]; }
 #pragma unroll
         for (int ra = 0; ra < 8; ++ra)
 #pragma unroll
@@ -244,11 +254,11 @@ __global__ void __launch_bounds__(256) k_impute_dense(MissArgs a) {
 // what Gaussian.log_lower_bound subtracts for the rows that are not fully observed (gaussian.py:145-150), and -- while the rows
 // still carry their diagonal initial covariances (diag_cov) -- the sum of those
 __global__ void __launch_bounds__(256) k_missing_ent_dense(MissArgs a) {
-    __shared__ double red[4][65];
+    __shared__ double red[4][66];
     const int n = blockIdx.x, w = threadIdx.x >> 6, k = threadIdx.x & 63, K = a.K, T = a.T;
     const double* Yo = a.Yobs + (size_t)n * T * K;
     const double* Yv = a.Yvar + (size_t)n * T * K;
-    double s = 0.0, ent = 0.0;
+    double s = 0.0, ent = 0.0, entx = 0.0;
     for (int t = w; t < T; t += 4) {
         const bool live = k < K;
         const double v = live ? Yv[(size_t)t * K + k] : 0.0, ob = live ? Yo[(size_t)t * K + k] : 0.0;
@@ -260,12 +270,16 @@ __global__ void __launch_bounds__(256) k_missing_ent_dense(MissArgs a) {
         const double lv = (ld == ld) ? ld : wave_sum(miss ? log(v) : 0.0);     // not updated yet: the diagonal initial state
         if (nm == K) ent += -0.5 * K * LN2PI - 0.5 * a.Yqld[(size_t)n * T + t] - 0.5 * K;        // gaussian.py:145-147
         else ent += 0.5 * nm * LN2PI - 0.5 * lv - 0.5 * nm;                                        // gaussian.py:148-150
+        entx += 0.5 * nm * LN2PI + 0.5 * (nm == K ? a.Ylnd[(size_t)n * T + t] : lv) + 0.5 * nm;      // exact bound
     }
     red[w][k] = s;
-    if (k == 0) red[w][64] = ent;
+    if (k == 0) { red[w][64] = ent; red[w][65] = entx; }
     __syncthreads();
     if (w == 0) {
-        if (k == 0) a.Yent[n] = red[0][64] + red[1][64] + red[2][64] + red[3][64];
+        if (k == 0) {
+            a.Yent[n] = red[0][64] + red[1][64] + red[2][64] + red[3][64];
+            a.YentX[n] = red[0][65] + red[1][65] + red[2][65] + red[3][65];
+        }
         if (a.diag_cov) {
             const double d = red[0][k] + red[1][k] + red[2][k] + red[3][k];
             for (int l = 0; l < K; ++l) if (k < K) a.YcovS[(size_t)n * K * K + (size_t)k * K + l] = (k == l) ? d : 0.0;
@@ -277,6 +291,7 @@ static MissArgs make_margs(pyvb_lds* h) {
     MissArgs a;
     a.Y = h->Y; a.Yobs = h->Yobs; a.Yvar = h->Yvar; a.Yqld = h->Yqld; a.X = h->X[h->cur]; a.C_mean = h->C_mean;
     a.R_a = h->R_a; a.R_b = h->R_b; a.Syy = h->Syy; a.Yent = h->Yent; a.Yq0 = nullptr; a.Yrowvar0 = nullptr;
+    a.Ylnd = h->Ylnd; a.YentX = h->YentX;
     a.N = h->N; a.T = h->T; a.K = h->K; a.D = h->D; a.DP = h->L.DP;
     a.Rbar = h->Rbar; a.lnd = h->lnd; a.R_w = h->R_w; a.Yld = h->dense ? h->Yld : nullptr; a.YcovS = h->YcovS; a.diag_cov = 0;
     return a;

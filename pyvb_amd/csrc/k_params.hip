@@ -94,22 +94,25 @@ __global__ void __launch_bounds__(64 * NW) k_elbo(ParamArgs a) {
     const int n = blockIdx.x, lane = threadIdx.x, D = a.D, K = a.K, T = a.T;
     const double* S0 = a.Sigma + (size_t)n * 3 * D * D;
     const double* x0 = a.X + (size_t)n * T * a.L.DP;
-    const double* qx = a.qld_x + (size_t)n * 3;
+    const bool exact = a.bound == PYVB_BOUND_EXACT;
+    // the entropy of the X_t: quirk Q1's q_ln_det (reference) or ln det Sigma (exact)
+    const double* qx = (exact ? a.lnd_x : a.qld_x) + (size_t)n * 3;
     // --- noise expectations
     double qbar = 0.0, rbar = 0.0, lnq = 0.0, lnr = 0.0, rq = 0.0, rr = 0.0, lq = 0.0, lr = 0.0;
     if (lane < D) {
         const double qa = a.Q_a[(size_t)n * D + lane], qb = a.Q_b[(size_t)n * D + lane];
-        qbar = qa / qb; lnq = log(qbar); rq = qbar * a.resQ[(size_t)n * D + lane];
+        qbar = qa / qb; lnq = exact ? digamma_pos(qa) - log(qb) : log(qbar); rq = qbar * a.resQ[(size_t)n * D + lane];
         if (a.noise == PYVB_NOISE_DIAGONAL_GAMMA) lq = gamma_llb(a.pri.Q_a0[lane], a.pri.Q_b0[lane], qa, qb);
         else if (lane == 0) lq = gamma_llb(a.pri.Q_a0[0], a.pri.Q_b0[0], qa, qb);
     }
     if (lane < K) {
         const double ra = a.R_a[(size_t)n * K + lane], rb = a.R_b[(size_t)n * K + lane];
-        rbar = ra / rb; lnr = log(rbar); rr = rbar * a.resR[(size_t)n * K + lane];
+        rbar = ra / rb; lnr = exact ? digamma_pos(ra) - log(rb) : log(rbar); rr = rbar * a.resR[(size_t)n * K + lane];
         if (a.noise == PYVB_NOISE_DIAGONAL_GAMMA) lr = gamma_llb(a.pri.R_a0[lane], a.pri.R_b0[lane], ra, rb);
         else if (lane == 0) lr = gamma_llb(a.pri.R_a0[0], a.pri.R_b0[0], ra, rb);
     }
-    const double lndQ = blk_sum<NW>(lnq, red), lndR = blk_sum<NW>(lnr, red);       // pass_down_lndet (quirk Q2)
+    // pass_down_lndet: ln det E[Lambda] (quirk Q2) or E[ln det Lambda] (exact)
+    const double lndQ = blk_sum<NW>(lnq, red), lndR = blk_sum<NW>(lnr, red);
     const double trQ = blk_sum<NW>(rq, red), trR = blk_sum<NW>(rr, red);
     const double LQ = blk_sum<NW>(lq, red), LR = blk_sum<NW>(lr, red);
     // --- X_0 against its Constant parents
@@ -129,10 +132,12 @@ __global__ void __launch_bounds__(64 * NW) k_elbo(ParamArgs a) {
     LX += (double)(T - 1) * (-0.5 * D * LN2PI + 0.5 * lndQ) - trQ;
     LX += (double)T * (0.5 * D * LN2PI + 0.5 * D) + 0.5 * (qx[0] + nint * qx[1] + qx[2]);
     double LY = (double)T * (-0.5 * K * LN2PI + 0.5 * lndR) - trR;
-    if (a.Yent) LY -= a.Yent[n];
+    if (exact) { if (a.YentX) LY += a.YentX[n]; }
+    else if (a.Yent) LY -= a.Yent[n];
     // --- columns of A and C against their Constant parents (gaussian.py:141-150).  The last term depends
     // on how much of the column was observed: nothing -> the q_ln_det form (:147), some entries -> the
     // covariance of the missing part (:150, with the reference's sign of the 2 pi term), all -> no term.
+    // The exact bound takes ln det qcov for the first and the entropy of the missing part for the second.
     double la = 0.0, lc = 0.0;
     if (lane < D) {
         const int i = lane;   // column i
@@ -167,14 +172,15 @@ __global__ void __launch_bounds__(64 * NW) k_elbo(ParamArgs a) {
                     const double ob = obs[(size_t)k * D + i];
                     if (!(ob == ob)) lvar += log(Vi[k]);
                 }
-                r -= 0.5 * missing * LN2PI - 0.5 * lvar - 0.5 * missing;
+                if (exact) r += 0.5 * missing * LN2PI + 0.5 * lvar + 0.5 * missing;
+                else r -= 0.5 * missing * LN2PI - 0.5 * lvar - 0.5 * missing;
             }
             return r;
         };
         la = column(D, a.pri.A_pp, a.pri.A_pm, a.A_mean + (size_t)n * D * D, a.A_var + (size_t)n * D * D, a.pri.A_obs,
-                    a.qld_A[(size_t)n * D + i], a.pri.A_pld[i]);
+                    (exact ? a.lnd_A : a.qld_A)[(size_t)n * D + i], a.pri.A_pld[i]);
         lc = column(K, a.pri.C_pp, a.pri.C_pm, a.C_mean + (size_t)n * K * D, a.C_var + (size_t)n * D * K, a.pri.C_obs,
-                    a.qld_C[(size_t)n * D + i], a.pri.C_pld[i]);
+                    (exact ? a.lnd_C : a.qld_C)[(size_t)n * D + i], a.pri.C_pld[i]);
     }
     const double LA = blk_sum<NW>(la, red), LC = blk_sum<NW>(lc, red);
     if (lane == 0) {
@@ -221,6 +227,7 @@ ParamArgs make_args(pyvb_lds* h) {
     a.A_mean = h->A_mean; a.A_var = h->A_var; a.C_mean = h->C_mean; a.C_var = h->C_var;
     a.Q_a = h->Q_a; a.Q_b = h->Q_b; a.R_a = h->R_a; a.R_b = h->R_b; a.qld_A = h->qld_A; a.qld_C = h->qld_C;
     a.resQ = h->resQ; a.resR = h->resR; a.elbo = h->elbo; a.pri = h->pri; a.Yent = h->has_missing ? h->Yent : nullptr;
+    a.lnd_A = h->lnd_A; a.lnd_C = h->lnd_C; a.lnd_x = h->lnd_x; a.YentX = h->has_missing ? h->YentX : nullptr; a.bound = h->bound;
     a.N = h->N; a.T = h->T; a.D = h->D; a.K = h->K; a.noise = h->noise; a.L = h->L; a.c0 = 0; a.c1 = h->D; a.which0 = 0; a.fuse = 0; a.sxx = nullptr; a.W = 1;
     return a;
 }

@@ -21,12 +21,13 @@
 struct PcaArgs {
     double* X; const unsigned char* M; double* xvar; const int* nmiss; double* Z;
     const double* Xdata; unsigned char* pinned;     // null unless some rows have not been conditioned on their observations yet
-    double *W_mean, *W_var, *Mu_mean, *Mu_var, *Z_cov, *qld_W;
+    double *W_mean, *W_var, *Mu_mean, *Mu_var, *Z_cov, *qld_W, *lnd_W;
     const double *W_pm, *W_pp, *Mu_pm, *Mu_pp;
     double* scal; double* Gz; double* g0; double* sx_local;
     double* part; double* stats; double* aux; double* aux_tail; double* elbo; int* status;     // aux_tail: the [sum z | delta of sum x] vector
     long N, N_total, chunk_rows, lo_upd, hi_upd, n_part_missing, n_none_rows, row_offset;
     int d, q, DP, QP, DT, QT, nchunk, mode;
+    int bound;          // PCA_ELBO: PYVB_BOUND_REFERENCE or PYVB_BOUND_EXACT
     int res_cached;     // PCA_ELBO: scal[PS_RES] holds the residual already
     int keep_z0;        // Z of global row 0 is final already (k_pca_pass12, k_pca_pass1)
     int z_deferred;     // PCA_PREPZ: also form sum z analytically;  PCA_X0: Z of row 0 is formed here
@@ -1274,7 +1275,7 @@ __global__ void __launch_bounds__(512) k_pca_materialize(PcaArgs a) {
 // sum_n #missing_n var_n, and sum over partially observed rows of #missing_n log var_n.  One workgroup per chunk.
 // (256 or 1024 threads: with a chunk per CU a thread of 256 walked 15 rows one dependent trip to memory after the other, 24 us)
 __global__ void __launch_bounds__(1024) k_pca_rowvar(PcaArgs a) {
-    __shared__ double red[3][16];
+    __shared__ double red[4][16];
     const int nt = blockDim.x;
     if (a.save_wx && blockIdx.x == 0) {         // the parameters the sweep before this launch imputed with (k_pca_pass12<.., LAZY>)
         for (int i = threadIdx.x; i < a.d * a.q; i += nt) a.W_x[i] = a.W_mean[i];
@@ -1284,7 +1285,7 @@ __global__ void __launch_bounds__(1024) k_pca_rowvar(PcaArgs a) {
     const long r1 = (r0 + a.chunk_rows < a.N) ? r0 + a.chunk_rows : a.N;
     const double var_new = a.scal[PS_BETA_B] / a.scal[PS_BETA_A];
     const double log_new = log(var_new), qld_new = 0.5 / (0.5 * a.d * log(1.0 / var_new));
-    double sxv = 0.0, slv = 0.0, sql = 0.0;
+    double sxv = 0.0, slv = 0.0, sql = 0.0, sld = 0.0;
     for (long row = r0 + threadIdx.x; row < r1; row += nt) {
         const int nm = a.nmiss[row];
         int cnt = nm;                       // entries of the row that carry this variance
@@ -1299,16 +1300,22 @@ __global__ void __launch_bounds__(1024) k_pca_rowvar(PcaArgs a) {
         }
         sxv += cnt * v;
         if (nm > 0 && nm < a.d) slv += nm * (upd ? log_new : log(v));
-        if (nm == a.d) sql += upd ? qld_new : 0.5 / (0.5 * a.d * log(1.0 / v));     // a latent row: qprec = I / v (gaussian.py:120, quirk Q1)
+        if (nm == a.d) {
+            sql += upd ? qld_new : 0.5 / (0.5 * a.d * log(1.0 / v));     // a latent row: qprec = I / v (gaussian.py:120, quirk Q1)
+            sld += a.d * (upd ? log_new : log(v));                        // its ln det qcov (exact bound)
+        }
     }
     double* P = a.part + (size_t)blockIdx.x * (a.SL.total + a.DT);
-    sxv = wsum(sxv); slv = wsum(slv); sql = wsum(sql);
-    if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = sxv; red[1][threadIdx.x >> 6] = slv; red[2][threadIdx.x >> 6] = sql; }
+    sxv = wsum(sxv); slv = wsum(slv); sql = wsum(sql); sld = wsum(sld);
+    if ((threadIdx.x & 63) == 0) {
+        red[0][threadIdx.x >> 6] = sxv; red[1][threadIdx.x >> 6] = slv; red[2][threadIdx.x >> 6] = sql; red[3][threadIdx.x >> 6] = sld;
+    }
     __syncthreads();
-    if (threadIdx.x < 3) {
+    if (threadIdx.x < 4) {
         double t = 0.0;
         for (int w = 0; w < nt / 64; ++w) t += red[threadIdx.x][w];
-        P[threadIdx.x == 0 ? a.SL.osxv : (threadIdx.x == 1 ? a.SL.oslv : a.SL.osql)] = t;
+        const size_t slot[4] = {a.SL.osxv, a.SL.oslv, a.SL.osql, a.SL.osld};
+        P[slot[threadIdx.x]] = t;
     }
 }
 
@@ -1469,7 +1476,11 @@ __device__ __forceinline__ void pca_small_body(const PcaArgs& a, double* sm, dou
             }
         }
         __syncthreads();
-        if (tid < q) a.qld_W[tid] = 0.5 / (((lred[tid] + lred[32 + tid]) + lred[64 + tid]) + lred[96 + tid]);      // gaussian.py:120 (quirk Q1)
+        if (tid < q) {
+            const double hl = ((lred[tid] + lred[32 + tid]) + lred[64 + tid]) + lred[96 + tid];     // 1/2 ln det qprec
+            a.qld_W[tid] = 0.5 / hl;                // gaussian.py:120 (quirk Q1)
+            a.lnd_W[tid] = -2.0 * hl;               // ln det qcov (exact bound)
+        }
     } else if constexpr (MODE == PCA_PREPZ) {
         // posterior of the Z_n: precision I + beta <W^T W>, shared by all n; Gz = beta Sigma_z <W>^T
         double* P = sm; double* Sg = sm + 64 * 64;
@@ -1493,7 +1504,7 @@ __device__ __forceinline__ void pca_small_body(const PcaArgs& a, double* sm, dou
             double* tsw = P; P = Pn; Pn = tsw;
         }
         for (int idx = tid; idx < q * q; idx += 256) a.Z_cov[idx] = P[idx];
-        if (tid == 0) a.scal[PS_QLD_Z] = 0.5 / (0.5 * logdet);
+        if (tid == 0) { a.scal[PS_QLD_Z] = 0.5 / (0.5 * logdet); a.scal[PS_LND_Z] = -logdet; }
         // Gz[i][k] = beta sum_j Sigma_z[i][j] W[k][j], stored as pass 1's B operands (thread = position in the block: padded
         // positions get their zero in the same pass; Sigma_z is read through its transpose -- it is symmetric -- so that the lanes of a
         // wavefront, which differ in i, read consecutive words, and share the row of <W>);  g0 = Gz <Mu>
@@ -1580,7 +1591,7 @@ __device__ __forceinline__ void pca_small_body(const PcaArgs& a, double* sm, dou
             lp = 0.5 * log(prec);
         }
         lp = bsum(lp, red);
-        if (tid == 0) a.scal[PS_QLD_MU] = 0.5 / lp;
+        if (tid == 0) { a.scal[PS_QLD_MU] = 0.5 / lp; a.scal[PS_LND_MU] = -2.0 * lp; }
     } else if constexpr (MODE == PCA_BETA) {
         // Beta.update(): Gamma, traces (nodes_todo.py:130-138)
         wtw_lds(a, sm, wst);
@@ -1595,16 +1606,21 @@ __device__ __forceinline__ void pca_small_body(const PcaArgs& a, double* sm, dou
             res = residual(a, sm, wst, red);
         }
         const double qa = a.scal[PS_BETA_A], qb = a.scal[PS_BETA_B];
-        const double lnd_beta = d * (log(qa) - log(qb));                  // Gamma.pass_down_lndet (quirk Q2)
+        // the exact bound: E[ln det] in the X_n's own terms, the true entropies of the partially observed and latent X_n, ln det qcov of
+        // the Z_n, W columns and Mu instead of their q_ln_det
+        const bool exact = a.bound == PYVB_BOUND_EXACT;
+        const double lnd_beta = exact ? d * (a.scal[PS_DIGAMMA_A] - log(qb))     // E ln det (beta I)
+                                      : d * (log(qa) - log(qb));                  // Gamma.pass_down_lndet (quirk Q2)
         // X_n (gaussian.py:136-151)
         double LX = N * (-0.5 * d * LN2PI + 0.5 * lnd_beta) - 0.5 * beta * res;
-        LX -= 0.5 * (double)a.n_part_missing * LN2PI - 0.5 * S[a.SL.oslv] - 0.5 * (double)a.n_part_missing;
-        if (a.n_none_rows > 0) LX += (double)a.n_none_rows * (0.5 * d * LN2PI + 0.5 * d) + 0.5 * S[a.SL.osql];
+        if (exact) LX += 0.5 * (double)a.n_part_missing * LN2PI + 0.5 * S[a.SL.oslv] + 0.5 * (double)a.n_part_missing;
+        else LX -= 0.5 * (double)a.n_part_missing * LN2PI - 0.5 * S[a.SL.oslv] - 0.5 * (double)a.n_part_missing;
+        if (a.n_none_rows > 0) LX += (double)a.n_none_rows * (0.5 * d * LN2PI + 0.5 * d) + 0.5 * S[exact ? a.SL.osld : a.SL.osql];
         // Z_n against Constant(0), Constant(I)
         double tr = 0.0;
         if (tid < q) tr = S[a.SL.oSzz + (size_t)tid * QP + tid] + N * a.Z_cov[tid * q + tid];
         tr = bsum(tr, red);
-        const double LZ = N * (-0.5 * q * LN2PI) - 0.5 * tr + N * (0.5 * q * LN2PI + 0.5 * a.scal[PS_QLD_Z] + 0.5 * q);
+        const double LZ = N * (-0.5 * q * LN2PI) - 0.5 * tr + N * (0.5 * q * LN2PI + 0.5 * a.scal[exact ? PS_LND_Z : PS_QLD_Z] + 0.5 * q);
         // W columns and Mu against their Constant parents: thread = row (d <= 256) adds its terms of all columns, one block sum
         double lw = 0.0;
         if (tid < d) {
@@ -1614,14 +1630,14 @@ __device__ __forceinline__ void pca_small_body(const PcaArgs& a, double* sm, dou
                 lw += 0.5 * log(pp) - 0.5 * pp * (w * w + a.W_var[(size_t)i * d + k] + pm * pm - 2.0 * w * pm);
             }
         }
-        if (tid < q) lw += 0.5 * a.qld_W[tid] + 0.5 * d;        // (- d/2 ln 2 pi of the prior term + d/2 ln 2 pi of the entropy cancel)
+        if (tid < q) lw += 0.5 * (exact ? a.lnd_W : a.qld_W)[tid] + 0.5 * d;        // (- d/2 ln 2 pi of the prior term + d/2 ln 2 pi of the entropy cancel)
         const double LW = bsum(lw, red);
         double lm = 0.0;
         if (tid < d) {
             const double pp = a.Mu_pp[tid], mu = a.Mu_mean[tid], pm = a.Mu_pm[tid];
             lm = 0.5 * log(pp) - 0.5 * pp * (mu * mu + a.Mu_var[tid] + pm * pm - 2.0 * mu * pm);
         }
-        const double LM = bsum(lm, red) - 0.5 * d * LN2PI + 0.5 * d * LN2PI + 0.5 * a.scal[PS_QLD_MU] + 0.5 * d;
+        const double LM = bsum(lm, red) - 0.5 * d * LN2PI + 0.5 * d * LN2PI + 0.5 * a.scal[exact ? PS_LND_MU : PS_QLD_MU] + 0.5 * d;
         if (tid == 0) {
             const double a0 = a.scal[PS_BETA_A0], b0 = a.scal[PS_BETA_B0];
             const double Elnx = a.scal[PS_DIGAMMA_A] - log(qb);
@@ -1650,10 +1666,12 @@ __global__ void __launch_bounds__(256) k_pca_small(PcaArgs a) {
 
 // q_ln_det (gaussian.py:120, quirk Q1) of every X_n that has no observed entry -- a latent node with qprec = I / var_n --
 // and NaN for the rows that have one (observed and partially observed nodes never set it)
-__global__ void __launch_bounds__(256) k_pca_rowqld(PcaArgs a, double* out) {
+// (logdet: their ln det qcov = d ln var_n instead)
+__global__ void __launch_bounds__(256) k_pca_rowqld(PcaArgs a, double* out, int logdet) {
     const long row = (long)blockIdx.x * 256 + threadIdx.x;
     if (row >= a.N) return;
-    out[row] = (a.nmiss[row] == a.d) ? 0.5 / (0.5 * a.d * log(1.0 / a.xvar[row])) : __builtin_nan("");
+    if (logdet) out[row] = (a.nmiss[row] == a.d) ? a.d * log(a.xvar[row]) : __builtin_nan("");
+    else out[row] = (a.nmiss[row] == a.d) ? 0.5 / (0.5 * a.d * log(1.0 / a.xvar[row])) : __builtin_nan("");
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -1661,6 +1679,7 @@ static PcaArgs pca_args(pyvb_pca* h) {
     PcaArgs a;
     a.X = h->X; a.M = h->M; a.xvar = h->xvar; a.nmiss = h->nmiss; a.Z = h->Z; a.Xdata = h->Xdata; a.pinned = h->pinned;
     a.W_mean = h->W_mean; a.W_var = h->W_var; a.Mu_mean = h->Mu_mean; a.Mu_var = h->Mu_var; a.Z_cov = h->Z_cov; a.qld_W = h->qld_W;
+    a.lnd_W = h->lnd_W; a.bound = h->bound;
     a.W_pm = h->W_pm; a.W_pp = h->W_pp; a.Mu_pm = h->Mu_pm; a.Mu_pp = h->Mu_pp;
     a.scal = h->scal; a.Gz = h->Gz; a.g0 = h->g0; a.sx_local = h->sx_local; a.part = h->part; a.stats = h->stats; a.aux = h->aux; a.aux_tail = h->aux + (size_t)4 * h->nchunk * h->QP; a.elbo = h->elbo; a.status = h->status;
     a.N = h->N; a.N_total = h->N_total; a.chunk_rows = h->chunk_rows; a.lo_upd = 0; a.hi_upd = 0;
@@ -1792,9 +1811,9 @@ extern "C" int pyvb_pca_debug_stamps(unsigned long long* out, int nblocks) {
 }
 #endif
 
-int pca_launch_rowqld(pyvb_pca* h, double* out) {
+int pca_launch_rowqld(pyvb_pca* h, double* out, int logdet) {
     PcaArgs a = pca_args(h);
-    hipLaunchKernelGGL(k_pca_rowqld, dim3((unsigned)((h->N + 255) / 256)), dim3(256), 0, h->stream, a, out);
+    hipLaunchKernelGGL(k_pca_rowqld, dim3((unsigned)((h->N + 255) / 256)), dim3(256), 0, h->stream, a, out, logdet);
     HIPCHK(hipGetLastError());
     return PYVB_OK;
 }

@@ -17,7 +17,7 @@
 
 struct PrepArgs {
     const double *A_mean, *A_var, *C_mean, *C_var, *Q_a, *Q_b, *R_a, *R_b, *x0_mean, *x0_prec;
-    double *Sigma, *qld, *gains, *scratch;
+    double *Sigma, *qld, *lnd, *gains, *scratch;     // lnd: ln det Sigma of the three classes beside qld
     // Wishart noise (DENSE): E[Q] [D][D], E[Q] <A> [D][D], E[R] <C> [K][D], tr(S_i E[Q]) [D], tr(S'_i E[R]) [D] per replicate
     const double *Qbar, *QA, *RC, *trA, *trC;
     int *warm, *status;
@@ -267,7 +267,7 @@ __global__ void __launch_bounds__(PREP_THREADS) k_prep(PrepArgs a) {
             }
 #pragma unroll
             for (int o = 32; o > 0; o >>= 1) lp += __shfl_xor(lp, o, 64);
-            if (tid == 0) a.qld[(size_t)n * 3 + c] = 0.5 / (0.5 * lp);
+            if (tid == 0) { a.qld[(size_t)n * 3 + c] = 0.5 / (0.5 * lp); a.lnd[(size_t)n * 3 + c] = -lp; }
         }
     }
     if ((D & 3) == 0) {         // a thread's four entries of a row are 32 contiguous bytes: one store (element by element they were 48 scattered ones)
@@ -405,7 +405,7 @@ int launch_prep(pyvb_lds* h) {
     a.A_mean = h->A_mean; a.A_var = h->A_var; a.C_mean = h->C_mean; a.C_var = h->C_var;
     a.Q_a = h->Q_a; a.Q_b = h->Q_b; a.R_a = h->R_a; a.R_b = h->R_b;
     a.x0_mean = h->pri.x0_mean; a.x0_prec = h->pri.x0_prec;
-    a.Sigma = h->Sigma_new; a.qld = h->qld_x_new; a.gains = h->gains; a.scratch = h->scratch;
+    a.Sigma = h->Sigma_new; a.qld = h->qld_x_new; a.lnd = h->lnd_x_new; a.gains = h->gains; a.scratch = h->scratch;
     a.warm = h->warm; a.status = h->status;
     a.Qbar = h->Qbar; a.QA = h->QA; a.RC = h->RC; a.trA = h->trA; a.trC = h->trC;
     a.N = h->N; a.T = h->T; a.D = h->D; a.K = h->K; a.L = h->L;

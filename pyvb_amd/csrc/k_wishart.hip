@@ -40,16 +40,18 @@ __device__ __forceinline__ void cov_tile_ab(int rows, int t, int& A, int& B) {
 struct WArgs {
     double *Q_w, *R_w, *Qbar, *Rbar, *lnd, *QA, *RC, *trA, *trC, *A_cov, *C_cov, *RQ, *RR, *SyyF;
     const double* YcovS; const double* Yent;   // outputs with missing entries (k_missing.hip): sum_t qcov_t [N][K][K], entropy terms [N]; or null
+    const double* YentX;                        // the same rows' exact entropy [N] (k_missing.hip), or null
     double* ldm;        // [N][2][D]: ln det of the covariance of the UNKNOWN entries of a column that has known ones (gaussian.py:150)
     double* SG;         // [N][2][64][64]-slots holding [rows][rows]: sum_i G[i,i] S_i of A's / C's columns (k_cols_wishart), or null: k_wresid sums the covariances itself
     const double *Q_a, *R_a;
-    double *A_mean, *A_var, *C_mean, *C_var, *qld_A, *qld_C;
-    const double *mom, *X, *Sigma, *Y, *qld_x;
+    double *A_mean, *A_var, *C_mean, *C_var, *qld_A, *qld_C, *lnd_A, *lnd_C;     // lnd: ln det qcov beside qld
+    const double *mom, *X, *Sigma, *Y, *qld_x, *lnd_x;
     double* elbo;
     Priors pri;
     int* status;
     int N, T, D, K, DP;
     int which0, c0, c1, update;
+    int bound;          // k_elbo_dense: PYVB_BOUND_REFERENCE or PYVB_BOUND_EXACT
 };
 
 static WArgs make_wargs(pyvb_lds* h) {
@@ -63,6 +65,8 @@ static WArgs make_wargs(pyvb_lds* h) {
     a.N = h->N; a.T = h->T; a.D = h->D; a.K = h->K; a.DP = h->L.DP;
     a.which0 = 0; a.c0 = 0; a.c1 = h->D; a.update = 0; a.SG = nullptr; a.ldm = h->ldm;
     a.YcovS = h->has_missing ? h->YcovS : nullptr; a.Yent = h->has_missing ? h->Yent : nullptr;
+    a.YentX = h->has_missing ? h->YentX : nullptr;
+    a.lnd_A = h->lnd_A; a.lnd_C = h->lnd_C; a.lnd_x = h->lnd_x; a.bound = h->bound;
     return a;
 }
 
@@ -196,6 +200,7 @@ __global__ void __launch_bounds__(64 * CW_WAVES) k_cols_wishart(WArgs a) {
     double* cov = (WHICH == 0 ? a.A_cov : a.C_cov) + (size_t)n * D * cov_stride(rows);
     double* var = (WHICH == 0 ? a.A_var : a.C_var) + (size_t)n * D * rows;
     double* qld = (WHICH == 0 ? a.qld_A : a.qld_C) + (size_t)n * D;
+    double* lnd = (WHICH == 0 ? a.lnd_A : a.lnd_C) + (size_t)n * D;
     double* ldm = a.ldm + ((size_t)n * 2 + WHICH) * D;
     const int RT = (rows + 7) >> 3;
     for (int idx = tid; idx < 64 * 64; idx += 64 * CW_WAVES) {
@@ -245,7 +250,7 @@ __global__ void __launch_bounds__(64 * CW_WAVES) k_cols_wishart(WArgs a) {
             }
             lp = wave_sum(lp);
             const unsigned long long allrows = rows == 64 ? ~0ull : ((1ull << rows) - 1ull);
-            if (lane == 0 && kmask != allrows) qld[i] = 0.5 / (0.5 * lp);      // q_ln_det, gaussian.py:120 (quirk Q1): of the whole precision
+            if (lane == 0 && kmask != allrows) { qld[i] = 0.5 / (0.5 * lp); lnd[i] = -lp; }     // q_ln_det, gaussian.py:120 (quirk Q1): of the whole precision
             bool rk[8], ck[8];              // this lane's rows / columns that are known entries
 #pragma unroll
             for (int u = 0; u < 8; ++u) { rk[u] = (kmask >> (8 * ta + u)) & 1ull; ck[u] = (kmask >> (8 * tb + u)) & 1ull; }
@@ -541,7 +546,8 @@ __global__ void __launch_bounds__(64) k_elbo_dense(WArgs a) {
     const int n = blockIdx.x, lane = threadIdx.x, D = a.D, K = a.K, T = a.T;
     const double* S0 = a.Sigma + (size_t)n * 3 * D * D;
     const double* x0 = a.X + (size_t)n * T * a.DP;
-    const double* qx = a.qld_x + (size_t)n * 3;
+    const bool exact = a.bound == PYVB_BOUND_EXACT;
+    const double* qx = (exact ? a.lnd_x : a.qld_x) + (size_t)n * 3;       // entropy of the X_t: quirk Q1 or ln det Sigma
     const double* Qb = a.Qbar + (size_t)n * D * D;
     const double* Rb = a.Rbar + (size_t)n * K * K;
     const double* RQ = a.RQ + (size_t)n * D * D;
@@ -562,11 +568,15 @@ __global__ void __launch_bounds__(64) k_elbo_dense(WArgs a) {
     }
     e0 = wave_sum(e0);
     const double nint = (double)(T - 2);
+    // ln det E[Lambda] (quirk Q2's form) or E[ln det Lambda] = psi_dim(qv) - ln det sym(qw) (exact)
+    const double lnQ = exact ? psi_multi(a.Q_a[(size_t)n * D], D) - ln[2] : ln[0];
+    const double lnR = exact ? psi_multi(a.R_a[(size_t)n * K], K) - ln[3] : ln[1];
     double LX = -0.5 * D * LN2PI + 0.5 * a.pri.x0_lndet - 0.5 * e0;
-    LX += (double)(T - 1) * (-0.5 * D * LN2PI + 0.5 * ln[0]) - trQ;
+    LX += (double)(T - 1) * (-0.5 * D * LN2PI + 0.5 * lnQ) - trQ;
     LX += (double)T * (0.5 * D * LN2PI + 0.5 * D) + 0.5 * (qx[0] + nint * qx[1] + qx[2]);
-    double LY = (double)T * (-0.5 * K * LN2PI + 0.5 * ln[1]) - trR;
-    if (a.Yent) LY -= a.Yent[n];
+    double LY = (double)T * (-0.5 * K * LN2PI + 0.5 * lnR) - trR;
+    if (exact) { if (a.YentX) LY += a.YentX[n]; }
+    else if (a.Yent) LY -= a.Yent[n];
     double la = 0.0, lc = 0.0;
     for (int i = lane; i < D; i += 64) {
         // the last term depends on how much of the column is known (gaussian.py:145-150, as k_elbo in k_params.hip): nothing ->
@@ -582,13 +592,16 @@ __global__ void __launch_bounds__(64) k_elbo_dense(WArgs a) {
             }
             double r = -0.5 * rows * LN2PI + 0.5 * lndet - 0.5 * trc;
             if (missing == rows) r += 0.5 * rows * LN2PI + 0.5 * qld + 0.5 * rows;
-            else if (missing > 0) r -= 0.5 * missing * LN2PI - 0.5 * ldmv - 0.5 * missing;
+            else if (missing > 0) {
+                if (exact) r += 0.5 * missing * LN2PI + 0.5 * ldmv + 0.5 * missing;      // the entropy of the unknown entries
+                else r -= 0.5 * missing * LN2PI - 0.5 * ldmv - 0.5 * missing;
+            }
             return r;
         };
-        la += column(D, a.pri.A_pp, a.pri.A_pm, a.A_mean + (size_t)n * D * D, a.A_var + (size_t)n * D * D, a.qld_A[(size_t)n * D + i], a.pri.A_pld[i],
-                     a.pri.A_obs, a.ldm[((size_t)n * 2 + 0) * D + i]);
-        lc += column(K, a.pri.C_pp, a.pri.C_pm, a.C_mean + (size_t)n * K * D, a.C_var + (size_t)n * D * K, a.qld_C[(size_t)n * D + i], a.pri.C_pld[i],
-                     a.pri.C_obs, a.ldm[((size_t)n * 2 + 1) * D + i]);
+        la += column(D, a.pri.A_pp, a.pri.A_pm, a.A_mean + (size_t)n * D * D, a.A_var + (size_t)n * D * D,
+                     (exact ? a.lnd_A : a.qld_A)[(size_t)n * D + i], a.pri.A_pld[i], a.pri.A_obs, a.ldm[((size_t)n * 2 + 0) * D + i]);
+        lc += column(K, a.pri.C_pp, a.pri.C_pm, a.C_mean + (size_t)n * K * D, a.C_var + (size_t)n * D * K,
+                     (exact ? a.lnd_C : a.qld_C)[(size_t)n * D + i], a.pri.C_pld[i], a.pri.C_obs, a.ldm[((size_t)n * 2 + 1) * D + i]);
     }
     const double LA = wave_sum(la), LC = wave_sum(lc);
     if (lane == 0) {

@@ -22,7 +22,7 @@
 struct WBArgs {
     double *Q_w, *R_w, *Qbar, *Rbar, *lnd, *QA, *RC, *trA, *trC, *A_cov, *C_cov, *RQ, *RR, *SyyF, *SG, *scratch;
     const double *Q_a, *R_a;
-    double *A_mean, *A_var, *C_mean, *C_var, *qld_A, *qld_C;
+    double *A_mean, *A_var, *C_mean, *C_var, *qld_A, *qld_C, *lnd_A, *lnd_C;
     const double *mom, *X, *Sigma, *Y;
     Priors pri;
     int* status;
@@ -37,6 +37,7 @@ static WBArgs make_wbargs(pyvb_lds* h) {
     a.SG = h->SG; a.scratch = h->scratch;
     a.Q_a = h->Q_a; a.R_a = h->R_a;
     a.A_mean = h->A_mean; a.A_var = h->A_var; a.C_mean = h->C_mean; a.C_var = h->C_var; a.qld_A = h->qld_A; a.qld_C = h->qld_C;
+    a.lnd_A = h->lnd_A; a.lnd_C = h->lnd_C;
     a.mom = h->mom; a.X = h->X[h->cur]; a.Sigma = h->Sigma; a.Y = h->Y;
     a.pri = h->pri; a.status = h->status;
     a.N = h->N; a.T = h->T; a.D = h->D; a.K = h->K; a.DP = h->L.DP;
@@ -146,6 +147,7 @@ __global__ void __launch_bounds__(256) k_cols_wishart_big(WBArgs a) {
     double* cov = (WHICH == 0 ? a.A_cov : a.C_cov) + (size_t)n * D * cov_stride(rows);
     double* var = (WHICH == 0 ? a.A_var : a.C_var) + (size_t)n * D * rows;
     double* qld = (WHICH == 0 ? a.qld_A : a.qld_C) + (size_t)n * D;
+    double* lnd = (WHICH == 0 ? a.lnd_A : a.lnd_C) + (size_t)n * D;
     double* SG = a.SG + ((size_t)n * 2 + WHICH) * 128 * 128;
     const int RT = (rows + 7) >> 3;
     const bool whole = a.c0 == 0 && a.c1 == D;      // the sum is complete (and used) only when every column goes through
@@ -174,7 +176,7 @@ __global__ void __launch_bounds__(256) k_cols_wishart_big(WBArgs a) {
                 lp += log(piv);
             }
             lp = wave_sum(lp);
-            if (tid == 0) qld[i] = 0.5 / (0.5 * lp);            // q_ln_det, gaussian.py:120 (quirk Q1)
+            if (tid == 0) { qld[i] = 0.5 / (0.5 * lp); lnd[i] = -lp; }      // q_ln_det, gaussian.py:120 (quirk Q1); ln det qcov
         }
         // the covariance: upper tiles (cov_pos), the diagonal for the lower bound, and its share of sum_i G_ii S_i
         if (ta <= tb && tb < RT) {

@@ -12,8 +12,12 @@ struct ParamArgs {
     int W;
     // parameters
     double *A_mean, *A_var, *C_mean, *C_var, *Q_a, *Q_b, *R_a, *R_b, *qld_A, *qld_C;
+    double *lnd_A, *lnd_C;  // ln det qcov of the columns, stored beside qld_A / qld_C by the column kernels
+    const double* lnd_x;    // [N][3] ln det Sigma beside qld_x
     double *resQ, *resR, *elbo;
     const double* Yent;     // k_elbo: per replicate, what the outputs that are not fully observed subtract (k_missing.hip), or null
+    const double* YentX;    // k_elbo, exact bound: per replicate, the entropy of those outputs (k_missing.hip), or null
+    int bound;              // k_elbo: PYVB_BOUND_REFERENCE or PYVB_BOUND_EXACT
     Priors pri;
     int N, T, D, K, noise;
     int c0, c1;             // k_cols: columns [c0, c1) are updated

@@ -9,15 +9,16 @@
 //   slv           sum over partially observed rows of #missing_n * log(var_n)
 //   sql           sum over rows without any observation of their q_ln_det = 0.5 / (d/2 log(1 / var_n))   (quirk Q1; each row
 //                 keeps the <beta> of ITS last update)
+//   sld           the same rows' ln det qcov = d log var_n (the exact lower bound)
 struct PcaStatsLayout {
     int DP, QP;
-    size_t oSzz, oSxz, osx, osz, osxx, osxv, oslv, osql, total;
+    size_t oSzz, oSxz, osx, osz, osxx, osxv, oslv, osql, osld, total;
 };
 static inline PcaStatsLayout pca_stats_layout(int DP, int QP) {
     PcaStatsLayout L; L.DP = DP; L.QP = QP;
     size_t o = 0;
     L.oSzz = o; o += (size_t)QP * QP; L.oSxz = o; o += (size_t)DP * QP; L.osx = o; o += DP; L.osz = o; o += QP;
-    L.osxx = o++; L.osxv = o++; L.oslv = o++; L.osql = o++;
+    L.osxx = o++; L.osxv = o++; L.oslv = o++; L.osql = o++; L.osld = o++;
     L.total = (o + 7) & ~(size_t)7;
     return L;
 }
@@ -26,7 +27,8 @@ static inline PcaStatsLayout pca_stats_layout(int DP, int QP) {
 
 // device scalars
 enum { PS_BETA_A = 0, PS_BETA_B, PS_QLD_Z, PS_QLD_X /* unused: latent rows keep their own, statistics slot sql */, PS_QLD_MU, PS_BETA_A0, PS_BETA_B0, PS_RES,
-       PS_LGAMMA_A0, PS_LGAMMA_A, PS_DIGAMMA_A /* of the two shape parameters, which never change after set_priors: formed on the host */, PS_COUNT = 16 };   // PS_RES: the residual of the last Beta update (see res_valid)
+       PS_LGAMMA_A0, PS_LGAMMA_A, PS_DIGAMMA_A /* of the two shape parameters, which never change after set_priors: formed on the host */,
+       PS_LND_Z, PS_LND_MU /* ln det qcov of the Z_n and of Mu, stored beside PS_QLD_Z, PS_QLD_MU */, PS_COUNT = 16 };   // PS_RES: the residual of the last Beta update (see res_valid)
 
 struct pyvb_pca {
     int device; long N, N_total, row_offset; int d, q, DP, QP, DT, QT;
@@ -38,6 +40,8 @@ struct pyvb_pca {
     int *nmiss;                          // [N]
     double *Z;                           // [N][QP]
     double *W_mean, *W_var, *Mu_mean, *Mu_var, *Z_cov, *qld_W;   // [d][q], [q][d], [d], [d], [q][q], [q]
+    double *lnd_W;                       // [q] ln det qcov of the W columns beside qld_W
+    int bound;                           // PYVB_BOUND_REFERENCE / PYVB_BOUND_EXACT: which lower bound PCA_ELBO forms
     double *W_pm, *W_pp, *Mu_pm, *Mu_pp; // priors: [d][q], [q][d], [d], [d]
     double *scal;                        // [PS_COUNT]
     double *Gz, *g0;                     // Z-pass operands: Gz^T as MFMA B operands [QT][DP/4][64], g0 [QP]
@@ -73,6 +77,6 @@ int pca_launch_pass2(pyvb_pca* h, long lo_upd, long hi_upd);
 int pca_launch_pass12(pyvb_pca* h, long lo_upd, long hi_upd);
 int pca_materialize_x(pyvb_pca* h);
 int pca_launch_reduce(pyvb_pca* h, int what);
-int pca_launch_rowqld(pyvb_pca* h, double* out);      // out: device [N]
+int pca_launch_rowqld(pyvb_pca* h, double* out, int logdet = 0);      // out: device [N]; logdet: ln det qcov instead of q_ln_det
 enum { PCA_W = 0, PCA_PREPZ = 1, PCA_MU = 2, PCA_BETA = 3, PCA_ELBO = 4, PCA_X0 = 5, PCA_APPLY = 6,
        PCA_RUN_HEAD = 16, PCA_RUN_MID = 17, PCA_RUN_TAIL = 18 };     // runs of steps in one launch (k_pca.hip: pca_launch_small)

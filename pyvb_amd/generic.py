@@ -678,21 +678,23 @@ class GenericPlan(object):
             self.ex = None
         self.released = True
 
-    def node_llb(self, node):
+    def node_llb(self, node, bound="reference"):
         self._flush_buf()
-        res = self._run(("llb", id(node)), lambda t: self._emit_llb(t, node))
+        exact = bound == "exact"
+        res = self._run(("llb", exact, id(node)), lambda t: self._emit_llb(t, node, exact))     # a tape per mode, built when first asked for
         return float(self._read(res)[0, 0])
 
-    def llb_sum(self, node_list):
+    def llb_sum(self, node_list, bound="reference"):
         """sum of log_lower_bound() over the nodes (network.py:49), one launch."""
         self._flush_buf()
-        key = ("llbsum",) + tuple(id(n) for n in node_list)
+        exact = bound == "exact"
+        key = ("llbsum", exact) + tuple(id(n) for n in node_list)
 
         def build(t):
             parts = t.zeros(len(node_list), 1)
             for i, n in enumerate(node_list):
                 t.mark()
-                t.copy(self._emit_llb(t, n), dst=parts.elem(i))
+                t.copy(self._emit_llb(t, n, exact), dst=parts.elem(i))
             return parts
         return self._read(self._run(key, build)).reshape(-1)
 
@@ -823,6 +825,25 @@ class GenericPlan(object):
             _, o2 = t.cholinv(sym)
             return t.axpby(float(nd.shape[0]), t.unary(s["qv"], U_LOG), -2.0, o2.elem(1))
         raise NotImplementedError("pass_down_lndet of %s" % type(nd).__name__)
+
+    def _lndet_exact(self, t, nd):
+        """E[ln det] of a precision parent (the exact bound's counterpart of _lndet): Gamma dim (psi(qa) - ln qb), DiagonalGamma
+        sum (psi(qa) - ln qb), Wishart psi_dim(qv) - ln det sym(qw); a Constant's log det as it is."""
+        s = self.slot[id(nd)]
+        if isinstance(nd, N.Constant):
+            return s["lndet"]
+        if isinstance(nd, N.Gamma):
+            return t.scale(t.sub(t.unary(s["qa"], U_DIGAMMA), t.unary(s["qb"], U_LOG)), float(nd.shape[0]))
+        if isinstance(nd, N.DiagonalGamma):
+            return t.total(t.sub(t.unary(s["qa"], U_DIGAMMA), t.unary(s["qb"], U_LOG)))
+        if isinstance(nd, N.Wishart):
+            sym = t.axpby(0.5, s["qw"], 0.5, t.transpose(s["qw"]))
+            _, o2 = t.cholinv(sym)
+            acc = t.copy(t.const(0.0))
+            for i in range(nd.shape[0]):
+                t.axpby(1.0, acc, 1.0, t.unary(t.lin(-0.5 * i, [(1.0, s["qv"])]), U_DIGAMMA), dst=acc)
+            return t.axpby(1.0, acc, -2.0, o2.elem(1))
+        raise NotImplementedError("E[ln det] of %s" % type(nd).__name__)
 
     def _ordered_sums(self, t, inits, count, item):
         """K sums at once: inits[k] + the terms item(0)[k], item(1)[k], ... (lists of Refs shaped like inits[k], or (factor, Ref)
@@ -1007,15 +1028,17 @@ class GenericPlan(object):
             raise NotImplementedError("update of %s" % type(nd).__name__)
 
     # -- lower bound ------------------------------------------------------------------------------
-    def _emit_llb(self, t, nd):
+    def _emit_llb(self, t, nd, exact=False):
         if isinstance(nd, N.Gaussian):
-            return self._emit_llb_gaussian(t, nd)
+            return self._emit_llb_gaussian(t, nd, exact)
         if isinstance(nd, (N.Gamma, N.DiagonalGamma, N.Wishart)):
             return self._emit_llb_noise(t, nd)
         return t.copy(t.const(0.0))                              # Node.log_lower_bound, node.py:42-43
 
-    def _emit_llb_gaussian(self, t, nd):
-        """Gaussian.log_lower_bound, gaussian.py:136-151"""
+    def _emit_llb_gaussian(self, t, nd, exact=False):
+        """Gaussian.log_lower_bound, gaussian.py:136-151.  exact: the node's term of the exact lower bound -- E[ln det] of the
+        precision parent (_lndet_exact), the entropy from ln det qcov (from the Cholesky of qcov: out2[1] = 1/2 ln det), and the
+        true entropy of the missing entries of a partially observed node."""
         s = self.slot[id(nd)]
         d = s["qmu"].m
         pp = self._ex(t, nd.precision_parent)
@@ -1023,14 +1046,22 @@ class GenericPlan(object):
         t.gemm(s["qmu"], self._ex(t, nd.mean_parent), tb=True, dst=inner, acc=True, neg=True)
         t.gemm(s["qmu"], self._ex(t, nd.mean_parent), tb=True, dst=inner, acc=True, neg=True)      # -2 qmu <mu>^T
         tr = t.trace(t.gemm(pp, inner))
-        ret = t.lin(-0.5 * d * LN2PI, [(0.5, self._lndet(t, nd.precision_parent)), (-0.5, tr)])
+        lndet = self._lndet_exact(t, nd.precision_parent) if exact else self._lndet(t, nd.precision_parent)
+        ret = t.lin(-0.5 * d * LN2PI, [(0.5, lndet), (-0.5, tr)])
         if not (nd.observed or nd.partially_observed):           # (:145-147)
-            ret = t.lin(0.5 * d * LN2PI + 0.5 * d, [(1.0, ret), (0.5, s["qld"].elem(0))])
+            if exact:
+                _, oq = t.cholinv(s["qcov"])
+                ret = t.lin(0.5 * d * LN2PI + 0.5 * d, [(1.0, ret), (1.0, oq.elem(1))])
+            else:
+                ret = t.lin(0.5 * d * LN2PI + 0.5 * d, [(1.0, ret), (0.5, s["qld"].elem(0))])
         elif nd.partially_observed:                              # (:148-150)
             mi = s["missing_index"]
             nm = mi.size
             _, o2 = t.cholinv(t.gather(s["qcov"], mi, mi))       # ln det = 2 sum log diag chol
-            ret = t.lin(-0.5 * nm * LN2PI + 0.5 * nm, [(1.0, ret), (1.0, o2.elem(1))])
+            if exact:
+                ret = t.lin(0.5 * nm * LN2PI + 0.5 * nm, [(1.0, ret), (1.0, o2.elem(1))])
+            else:
+                ret = t.lin(-0.5 * nm * LN2PI + 0.5 * nm, [(1.0, ret), (1.0, o2.elem(1))])
         return ret
 
     def _emit_llb_noise(self, t, nd):

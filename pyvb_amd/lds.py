@@ -28,6 +28,7 @@ class LDSBatch(object):
         if noise not in _NOISE:
             raise NotImplementedError("noise precision %r has no HIP path (DiagonalGamma, Gamma and Wishart do)" % (noise,))
         self.N, self.T, self.D, self.K, self.noise, self.device = int(N), int(T), int(D), int(K), noise, int(device)
+        self.bound = "reference"
         h = C.ctypes.c_void_p()
         C.check(C.lib.pyvb_lds_create(C.ctypes.byref(h), self.device, self.N, self.T, self.D, self.K, _NOISE[noise]))
         self._h = h
@@ -150,6 +151,22 @@ class LDSBatch(object):
         C.check(C.lib.pyvb_lds_get_column_qld(self._h, C.dptr(qa), C.dptr(qc)))
         return qa, qc
 
+    def get_logdets(self):
+        """ln det qcov as the last updates left it: of the X_t classes [N,3], of the columns of A and C [N,D] each, and of
+        the outputs with missing entries [N,T] (NaN where the q_ln_det getters give NaN).  Stored in both bound modes."""
+        lx, la, lc = np.empty((self.N, 3)), np.empty((self.N, self.D)), np.empty((self.N, self.D))
+        ly = np.empty((self.N, self.T))
+        C.check(C.lib.pyvb_lds_get_logdets(self._h, C.dptr(lx), C.dptr(la), C.dptr(lc), C.dptr(ly)))
+        return {"X": lx, "A": la, "C": lc, "Y": ly}
+
+    def set_bound_mode(self, mode):
+        """Which lower bound elbo(), elbo_total() and iterate() form: "reference" (the reference's, quirks included; the
+        default) or "exact" (E_q[ln p] - E_q[ln q]).  The updates do not depend on it.  Changing it empties the history."""
+        if mode not in C.BOUND_MODES:
+            raise ValueError("bound mode must be 'reference' or 'exact', not %r" % (mode,))
+        C.check(C.lib.pyvb_lds_set_bound_mode(self._h, C.BOUND_MODES[mode]))
+        self.bound = mode
+
     def get_warmup(self):
         w = np.empty((self.N, 2), dtype=np.int32)
         C.check(C.lib.pyvb_lds_get_warmup(self._h, w.ctypes.data_as(C._ip)))
@@ -188,7 +205,7 @@ class LDSBatch(object):
         C.check(C.lib.pyvb_lds_update_R(self._h))
 
     def elbo(self):
-        """Per-replicate lower-bound parts [N,6] (X, Y, A, C, Q, R), reference mode."""
+        """Per-replicate lower-bound parts [N,6] (X, Y, A, C, Q, R) of the current bound mode (set_bound_mode)."""
         C.check(C.lib.pyvb_lds_elbo(self._h))
         out = np.empty((self.N, 6))
         C.check(C.lib.pyvb_lds_get_elbo(self._h, C.dptr(out)))

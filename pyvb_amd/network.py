@@ -88,29 +88,29 @@ class _Schedule(object):
             for m in members:
                 m.flush()
 
-    def llb(self):
+    def llb(self, bound="reference"):
         """sum of log_lower_bound() over the list (network.py:49), accumulated plan by plan in list order."""
         g = self.groups
         vals = np.zeros(len(g))
         for k in self.other:
             p, nodes, whole = g[k]
             if getattr(p, "generic", False):
-                vals[k] = float(p.llb_sum(nodes).sum())
+                vals[k] = float(p.llb_sum(nodes, bound).sum())
             elif whole:
-                vals[k] = float(np.sum(p.elbo_parts()))         # every random node of the graph is listed, once: the class sums
+                vals[k] = float(np.sum(p.elbo_parts(bound)))    # every random node of the graph is listed, once: the class sums
             else:
-                vals[k] = float(sum(n.log_lower_bound() for n in nodes))    # a part of a fused graph: its terms one by one
+                vals[k] = float(sum(n.log_lower_bound(bound) for n in nodes))   # a part of a fused graph: its terms one by one
         rest = self.lds
         if self.handles is not None:
             rest = []
             for grp, ks, rows, sc, epoch, whole, members, where in self.handles:
                 if whole and grp.epoch == epoch:
-                    vals[where] = grp.elbo()[rows].sum(1)       # one launch and one copy for all graphs of the handle
+                    vals[where] = grp.elbo(bound)[rows].sum(1)  # one launch and one copy for all graphs of the handle
                 else:
                     rest += ks
         for k in rest:
             p, nodes, whole = g[k]
-            vals[k] = float(np.sum(p.elbo_parts())) if whole else float(sum(n.log_lower_bound() for n in nodes))
+            vals[k] = float(np.sum(p.elbo_parts(bound))) if whole else float(sum(n.log_lower_bound(bound) for n in nodes))
         llb = 0.0
         for v in vals.tolist():
             llb += v
@@ -153,7 +153,7 @@ class Network(object):
             groups[id(p)].append(n)
         return [[p, groups[id(p)], len(groups[id(p)]) == len(set(id(n) for n in groups[id(p)])) == p.n_random_nodes] for p in plans]
 
-    def learn(self, niters, tol=1e-3, verbose=True):
+    def learn(self, niters, tol=1e-3, verbose=True, bound="reference"):
         """network.py:40-56.  The node list may span any number of unconnected graphs, each on its own plan: a fused LDS
         or VB-PCA plan takes its group's update() calls as queued requests (whole sweeps become single launches) and gives
         the lower bound as the sum of its class parts; a graph that runs node by node gets one launch for all its updates
@@ -161,7 +161,10 @@ class Network(object):
         replicate each (_recognise.LDSGroup): their requests are queued first and carried out together, one launch per
         operation for all of them, and from the second iteration on what the first one's requests spelt for the handle is
         replayed without walking the node list again (_Schedule).  The grouping is redone whenever an update order the
-        fused kernels do not serve has moved a graph to the node-by-node plan (or sweeps have brought it back)."""
+        fused kernels do not serve has moved a graph to the node-by-node plan (or sweeps have brought it back).
+        bound="exact": the lower bound and the stopping test use the exact ELBO (E_q[ln p] - E_q[ln q]) on every plan; the
+        updates are the same, and the predicate stays network.py:53's (with this bound it is a real convergence test)."""
+        N._bound_arg(bound)
         # a second call over the same list starts where the first one stopped: the list is not walked again
         kept = getattr(self, "_kept", None)
         sched = kept[1] if kept is not None and kept[0] == self.nodes and kept[1].valid() else None
@@ -186,7 +189,7 @@ class Network(object):
                     sched.settle()
                 else:
                     raise RuntimeError("the graphs kept changing plans")
-                self.llb = sched.llb()                          # network.py:49
+                self.llb = sched.llb(bound)                     # network.py:49
                 if verbose:
                     print(niters - i, self.llb)
                 if self.llb - old_llb < tol:                    # also fires when the bound decreases

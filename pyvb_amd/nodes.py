@@ -27,6 +27,12 @@ __all__ = ["Node", "Addition", "Multiplication", "Constant", "hstack", "Transpos
            "DiagonalGaussian", "Gamma", "DiagonalGamma", "Wishart", "ConjugacyError"]
 
 
+
+def _bound_arg(bound):
+    if bound not in ("reference", "exact"):
+        raise ValueError("bound must be 'reference' or 'exact', not %r" % (bound,))
+    return bound
+
 class ConjugacyError(ValueError):            # nodes_todo.py:8-10
     def __init__(self, message):
         ValueError.__init__(self, message)
@@ -51,7 +57,7 @@ class Node(object):
     def update(self):
         pass
 
-    def log_lower_bound(self):
+    def log_lower_bound(self, bound="reference"):
         return 0.
 
     def pass_up_m1_m2(self, requester):
@@ -309,8 +315,10 @@ class Gaussian(Node):
             return
         _plan_of(self).enqueue(self)
 
-    def log_lower_bound(self):
-        return _plan_of(self).node_llb(self)
+    def log_lower_bound(self, bound="reference"):
+        """gaussian.py:136-151 / nodes_todo.py:149-157, :199-204; bound="exact": this node's term of the exact lower bound
+        (E_q[ln p] - E_q[ln q], without quirks Q1, Q2 of SURVEY.md)."""
+        return _plan_of(self).node_llb(self, _bound_arg(bound))
 
     def pass_up_m1_m2(self, requester):         # gaussian.py:179-183
         return _messages_of(self, requester)
@@ -352,8 +360,10 @@ class _NoiseNode(object):
     def update(self):
         _plan_of(self).enqueue(self)
 
-    def log_lower_bound(self):
-        return _plan_of(self).node_llb(self)
+    def log_lower_bound(self, bound="reference"):
+        """gaussian.py:136-151 / nodes_todo.py:149-157, :199-204; bound="exact": this node's term of the exact lower bound
+        (E_q[ln p] - E_q[ln q], without quirks Q1, Q2 of SURVEY.md)."""
+        return _plan_of(self).node_llb(self, _bound_arg(bound))
 
 
 class Gamma(_NoiseNode):                        # nodes_todo.py:88-157

@@ -19,6 +19,7 @@ class PCABatch(object):
 
     def __init__(self, N, d, q, device=0, N_total=None, row_offset=0):
         self.N, self.d, self.q = int(N), int(d), int(q)
+        self.bound = "reference"
         h = C.ctypes.c_void_p()
         C.check(C.lib.pyvb_pca_create(C.ctypes.byref(h), int(device), self.N, self.d, self.q,
                                       int(self.N if N_total is None else N_total), int(row_offset)))
@@ -94,6 +95,20 @@ class PCABatch(object):
         x = np.empty(self.N) if rows else None
         C.check(C.lib.pyvb_pca_get_qld(self._h, C.dptr(w), C.dptr(z), C.dptr(m), C.dptr(x)))
         return {"W": w, "Z": float(z[0]), "Mu": float(m[0]), "X": x}
+
+    def get_logdets(self, rows=True):
+        """ln det qcov where get_qld() gives q_ln_det (same keys, same NaN); stored in both bound modes."""
+        w, z, m = np.empty(self.q), np.empty(1), np.empty(1)
+        x = np.empty(self.N) if rows else None
+        C.check(C.lib.pyvb_pca_get_logdets(self._h, C.dptr(w), C.dptr(z), C.dptr(m), C.dptr(x)))
+        return {"W": w, "Z": float(z[0]), "Mu": float(m[0]), "X": x}
+
+    def set_bound_mode(self, mode):
+        """Which lower bound elbo() and iterate() form: "reference" (the default) or "exact" (E_q[ln p] - E_q[ln q])."""
+        if mode not in C.BOUND_MODES:
+            raise ValueError("bound mode must be 'reference' or 'exact', not %r" % (mode,))
+        C.check(C.lib.pyvb_pca_set_bound_mode(self._h, C.BOUND_MODES[mode]))
+        self.bound = mode
 
     def update_W(self):
         C.check(C.lib.pyvb_pca_update_W(self._h))
