@@ -53,6 +53,12 @@ enum { PYVB_NOISE_DIAGONAL_GAMMA = 0,   /* nodes_todo.py:159-204 DiagonalGamma *
        PYVB_NOISE_WISHART = 2 };        /* nodes_todo.py:205-234 Wishart (dense precisions; see pyvb_lds_set_wishart_priors) */
 enum { PYVB_FORWARD = 0, PYVB_BACKWARD = 1 };
 
+/* Why a replicate failed (pyvb_lds_get_status): which family of nodes had a posterior precision that was not positive definite
+ * (gaussian.py:117-119 raises numpy's LinAlgError from that node's update) */
+#define PYVB_FAIL_STATES 1      /* an X_t (k_prep: the three posterior precisions of the states) */
+#define PYVB_FAIL_COLUMNS 2     /* a column of A or C with dense covariance (Wishart noise) */
+#define PYVB_FAIL_NOISE 4       /* the qw of a Wishart precision (nodes_todo.py:233-234 inverts it) */
+
 /* Which lower bound the ELBO entry points form (pyvb_lds_set_bound_mode, pyvb_pca_set_bound_mode):
  *   REFERENCE  the reference's log_lower_bound, quirks Q1 / Q2 of SURVEY.md included (the default)
  *   EXACT      E_q[ln p] - E_q[ln q]: the entropies of latent Gaussians from ln det qcov, those of partially observed ones with
@@ -171,7 +177,29 @@ int pyvb_lds_set_bound_mode(pyvb_lds* h, int mode);
  * entries Ylnd[N][T] (of inv <R>, before the known entries are conditioned on), as their last updates left them; NaN where the
  * q_ln_det getters give NaN.  Kept in both modes; NULL = skip. */
 int pyvb_lds_get_logdets(pyvb_lds* h, double* lnd_x, double* lnd_A, double* lnd_C, double* Ylnd);
+/* Waits for both streams.  PYVB_E_LINALG, once, if a factorisation of an ACTIVE replicate met a non-positive pivot since the last
+ * call (the flags are cleared; the message ends with the index of the first such replicate and their number): cho_factor raising
+ * numpy.linalg.LinAlgError in Gaussian.update, gaussian.py:117-119. */
 int pyvb_lds_sync(pyvb_lds* h);
+
+/* Per-replicate bookkeeping.  A handle's replicates are independent graphs (Linear_Dynamic_System.py:46-66, once each); in the
+ * reference each would raise, converge and be abandoned on its own.
+ *   pyvb_lds_get_status  status[N]: PYVB_FAIL_* bits, the node family whose update would have raised LinAlgError
+ *                        (gaussian.py:117-119; nodes_todo.py:233-234).  Waits for both streams and never fails because of a flag:
+ *                        the OR of the flags pending on the device and of those the most recent failed pyvb_lds_sync reported and
+ *                        cleared; the next successful pyvb_lds_sync forgets the latter.
+ *   pyvb_lds_set_active  active[N], 0 = switch the replicate off: as if its nodes left every update list of the script
+ *                        (Linear_Dynamic_System.py:70-79) and the node list of network.py:46-49.  No update kernel loads or stores a
+ *                        row of it from then on; its state, outputs and elbo parts read back as they were; the totals
+ *                        (pyvb_lds_elbo_total, the history of pyvb_lds_iterate, the all-reduce) leave it out and pyvb_lds_sync does
+ *                        not fail for its flags.  Setters still copy what the caller passes into every row (what they derive from
+ *                        it is update work and skips the row); getters return every row.  Stream ordered after everything queued.
+ *                        The mask can only shrink: turning a replicate back on returns PYVB_E_ARG (the host-side validity tracking
+ *                        is per handle).  With every replicate off the update entries return PYVB_OK without a launch.
+ *   pyvb_lds_get_active  the mask as last set (all ones after pyvb_lds_create). */
+int pyvb_lds_get_status(pyvb_lds* h, int* status);
+int pyvb_lds_set_active(pyvb_lds* h, const unsigned char* active);
+int pyvb_lds_get_active(pyvb_lds* h, unsigned char* active);
 
 /* HIP-event timing of the kernels on the handle's stream (for bench.py's roofline figures). */
 int pyvb_lds_timing_enable(pyvb_lds* h, int on);

@@ -17,10 +17,12 @@ NOISE_DIAGONAL_GAMMA, NOISE_GAMMA, NOISE_WISHART = 0, 1, 2
 FORWARD, BACKWARD = 0, 1
 BOUND_REFERENCE, BOUND_EXACT = 0, 1
 BOUND_MODES = {"reference": BOUND_REFERENCE, "exact": BOUND_EXACT}
+FAIL_STATES, FAIL_COLUMNS, FAIL_NOISE = 1, 2, 4      # PYVB_FAIL_*: bits of pyvb_lds_get_status
 K_PREP, K_SWEEP_FWD, K_STATS, K_PARAMS, K_STEP, K_SWEEP_BWD, K_ELBO, K_GY = range(8)
 
 _dp = ctypes.POINTER(ctypes.c_double)
 _ip = ctypes.POINTER(ctypes.c_int)
+_ucp = ctypes.POINTER(ctypes.c_ubyte)
 _h = ctypes.c_void_p
 # include/pyvb_hip.h: pyvb_host_allreduce_fn -- int (*)(double* buf, size_t count, void* user)
 HOST_ALLREDUCE = ctypes.CFUNCTYPE(ctypes.c_int, _dp, ctypes.c_size_t, ctypes.c_void_p)
@@ -65,6 +67,9 @@ SIGNATURES = {
     "pyvb_lds_set_bound_mode": (ctypes.c_int, [_h, ctypes.c_int]),
     "pyvb_lds_get_logdets": (ctypes.c_int, [_h, _dp, _dp, _dp, _dp]),
     "pyvb_lds_sync": (ctypes.c_int, [_h]),
+    "pyvb_lds_get_status": (ctypes.c_int, [_h, _ip]),
+    "pyvb_lds_set_active": (ctypes.c_int, [_h, _ucp]),
+    "pyvb_lds_get_active": (ctypes.c_int, [_h, _ucp]),
     "pyvb_lds_timing_enable": (ctypes.c_int, [_h, ctypes.c_int]),
     "pyvb_lds_timing_reset": (ctypes.c_int, [_h]),
     "pyvb_lds_timing_get": (ctypes.c_int, [_h, ctypes.c_int, _dp, _ip]),

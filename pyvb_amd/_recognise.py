@@ -40,6 +40,10 @@ def exact_elbo(batch):
     finally:
         batch.set_bound_mode("reference")
 
+# the node families the status bits of a replicate name (include/pyvb_hip.h: PYVB_FAIL_*)
+_FAIL_NAMES = ((1, "a state X_t"), (2, "a column of A / C"), (4, "a Wishart noise precision Q / R"))
+
+
 class LDSGroup(object):
     """ONE LDSBatch for M graphs of the same structure: replicate r is the graph of members[r].
 
@@ -50,9 +54,14 @@ class LDSGroup(object):
     carried out in lock step: when a member needs its queue run (something of it is read), every operation of that queue
     is one launch for all members that ask for the same thing at that point (a forward sweep, the columns 0..D-1 of A ...);
     what the others have queued beyond it waits for their own reads.  Where the member and the others part ways the
-    smaller side leaves the handle with its state (the replicates stay behind as dead rows that nobody reads) and is bound
+    smaller side leaves the handle with its state (its replicates are switched off: LDSBatch.set_active) and is bound
     anew -- on its own, or together with the others that left the same way.  A request no fused kernel serves sends only
-    the graph that made it to the node-by-node plan."""
+    the graph that made it to the node-by-node plan.
+
+    A graph whose data are ill posed fails alone: when a call that synchronises the handle ends in LinAlgError the group
+    reads the per-replicate status, evicts the members whose rows failed (`_evict`) and carries on for the others
+    (`_sync_call`).  A batch object without `status` / `set_active` (the host-only stand-in of the tests) is served as
+    before: the error propagates, dead rows keep being computed."""
 
     def __init__(self, members):
         from .lds import LDSBatch
@@ -84,6 +93,7 @@ class LDSGroup(object):
         self._elbo = None
         self._elbo_x = None             # the same parts of the exact lower bound
         self.epoch = 0                  # counts the members that have left (Network.learn's schedule looks at it)
+        self._mask = np.ones(M, dtype=bool)     # the rows still computed
         for r, m in enumerate(members):
             m.group, m.r = self, r
 
@@ -96,11 +106,64 @@ class LDSGroup(object):
         self._elbo_x = None
 
     def drop(self, member):
-        """`member` has left (its replicate keeps being computed with the others; nobody reads it)."""
+        """`member` has left: its replicate is switched off, so the handle stops paying for it."""
         self.members[member.r] = None
         member.group = None
         self.epoch += 1
         if not any(m is not None for m in self.members):
+            self.batch.close()
+            return
+        self._deactivate(member.r)
+
+    def _deactivate(self, r):
+        set_active = getattr(self.batch, "set_active", None)
+        if set_active is None or not self._mask[r]:
+            return                      # (a batch without a mask: the row is left computing)
+        self._mask[r] = False
+        set_active(self._mask)
+
+    # -- failures --------------------------------------------------------------------------------
+    def _sync_call(self, who, fn, *args, **kw):
+        """Every call of the group and of its plans that synchronises the handle -- and can therefore surface a posterior
+        precision that was not positive definite -- goes through here.  The error belongs to the graphs whose rows carry a
+        status flag: they are evicted, and the call is repeated for the others, so that a healthy graph's read, assignment
+        or bound never raises for a neighbour's failure.  `who`: the plan on whose behalf the handle is read (None: the
+        whole handle); if it is among the failed, the error is raised from it at once."""
+        while True:
+            try:
+                return fn(*args, **kw)
+            except np.linalg.LinAlgError as e:
+                status = getattr(self.batch, "status", None)
+                if status is None:
+                    raise
+                st = np.asarray(status())
+                bad = [m for m in self.members if m is not None and st[m.r]]
+                if not bad:
+                    raise
+                for m in bad:
+                    self._evict(m, int(st[m.r]), e)
+                if who is not None and any(m is who for m in bad):
+                    who._raise_failed()
+                if not self.live():
+                    raise
+
+    def _evict(self, member, bits, cause):
+        """A member whose row failed: row switched off, plan unbound WITHOUT copying the device state (garbage) back -- the
+        nodes keep the host attributes of their last synchronisation -- and the error kept on the plan, which raises it at
+        the graph's next read, update() or learn, once."""
+        family = ", ".join(nm for b, nm in _FAIL_NAMES if bits & b) or "status %d" % bits
+        err = np.linalg.LinAlgError("a posterior precision was not positive definite (numpy.linalg.LinAlgError in the "
+                                    "reference): %s of this graph (replicate %d of a shared handle)" % (family, member.r))
+        err.replicates, err.status_bits, err.__cause__ = [member.r], bits, cause
+        r = member.r
+        member._evicted(err)
+        self.invalidate()
+        self.members[r] = None
+        member.group = None
+        self.epoch += 1
+        if self.live():
+            self._deactivate(r)
+        else:
             self.batch.close()
 
     # -- the queue -------------------------------------------------------------------------------
@@ -173,28 +236,28 @@ class LDSGroup(object):
         return True
 
     # -- results ---------------------------------------------------------------------------------
-    def pull(self):
+    def pull(self, who=None):
         if self.cache is None:
-            b = self.batch
-            st = b.get_state()
-            Sig, qld = b.get_posterior_classes()
-            qa, qc = b.get_column_qld()
+            b, call = self.batch, lambda fn, *a, **kw: self._sync_call(who, fn, *a, **kw)
+            st = call(b.get_state)
+            Sig, qld = call(b.get_posterior_classes)
+            qa, qc = call(b.get_column_qld)
             c = {"st": st, "Sigma": Sig, "qld_x": qld, "qld_A": qa, "qld_C": qc}
             if self.kind == "wishart":
-                c["w"] = b.get_wishart_state()
-                c["A_cov"], c["C_cov"] = b.get_column_cov()
+                c["w"] = call(b.get_wishart_state)
+                c["A_cov"], c["C_cov"] = call(b.get_column_cov)
             if self.members and any(m is not None and m.free_ys for m in self.members):
-                c["Yq"], c["Yvar"], c["Yqld"] = b.get_outputs(with_qld=True)
+                c["Yq"], c["Yvar"], c["Yqld"] = call(b.get_outputs, with_qld=True)
             self.cache = c
         return self.cache
 
-    def elbo(self, bound="reference"):
+    def elbo(self, bound="reference", who=None):
         if bound == "exact":
             if self._elbo_x is None:
-                self._elbo_x = exact_elbo(self.batch)
+                self._elbo_x = self._sync_call(who, exact_elbo, self.batch)
             return self._elbo_x
         if self._elbo is None:
-            self._elbo = self.batch.elbo()
+            self._elbo = self._sync_call(who, self.batch.elbo)
         return self._elbo
 
 
@@ -229,6 +292,7 @@ class LDSPlan(object):
         self.group, self.r = None, -1
         self.stale = False              # set when a node of the graph gains a child or an observation after binding
         self.closed = False
+        self.failed = None              # the LinAlgError of a graph evicted from its handle, until it has been raised (LDSGroup._evict)
         self.n_random_nodes = 2 * self.T + 2 * self.D + 2
         self.sig = _signature(self)
         LDSPlan._count += 1
@@ -296,8 +360,27 @@ class LDSPlan(object):
     def cache(self):
         return self.group.cache if self.group is not None else None
 
+    # -- failure ---------------------------------------------------------------------------------
+    def _evicted(self, err):
+        """The graph's row failed on the device (LDSGroup._evict): nothing is copied back, the queue is dropped, the nodes
+        stay pointed at this plan until the error has been raised."""
+        self.failed = err
+        self.closed = True
+        self.pending, self._pos = [], 0
+
+    def _raise_failed(self):
+        """First thing in every entry of the plan: raise the error of an evicted graph, once, and let go of the nodes (the graph
+        is bound anew, from the host attributes it kept, at its next use)."""
+        err, self.failed = self.failed, None
+        if err is not None:
+            for n in _component(self.Xs[0]):
+                if n._plan is self:
+                    n._plan = None
+            raise err
+
     # -- queue -----------------------------------------------------------------------------------
     def enqueue(self, node):
+        self._raise_failed()
         self.pending.append(self.index[id(node)])
 
     def _peek(self, gate=True):
@@ -371,6 +454,7 @@ class LDSPlan(object):
 
     def flush(self):
         """Run the queued update() requests (LDSGroup.flush: in lock step with the other graphs on this handle)."""
+        self._raise_failed()
         if self._pos >= len(self.pending):
             return
         self._materialize().flush(self)
@@ -386,6 +470,8 @@ class LDSPlan(object):
             return self._demote(self._rest())
         rest, left = self._rest(), self.resume_left
         self._leave()
+        if self.failed is not None:     # the departure's read found this graph's row failed: it stays evicted, the error waits
+            return self
         plan = bind(self.Xs[0])
         plan.resume_left = left
         for entry in rest:
@@ -396,11 +482,15 @@ class LDSPlan(object):
                     nd._plan.enqueue(nd)
         return plan
 
-    def _sync_host(self):
-        """Current device posteriors into the nodes' host attributes."""
+    def _sync_host(self, reader=True):
+        """Current device posteriors into the nodes' host attributes.  reader=False: on behalf of a departure that another
+        graph's request may have caused -- if the read finds this graph's own row failed, the graph is evicted, its error is
+        kept for its own next use and nothing is copied."""
         if not self.ran:
             return              # nothing has run: the host attributes are the state
-        self._pull()
+        self._pull(reader)
+        if self.failed is not None:
+            return
         for nd in self.Xs + self.As + self.Cs + [self.Ys[t] for t in self.free_ys]:
             for name in ("qmu", "qcov"):
                 nd.__dict__["_h_" + name] = self.read(nd, name)
@@ -417,7 +507,9 @@ class LDSPlan(object):
 
     def _leave(self):
         """Device state back into the nodes, the graph unbound, the replicate given up."""
-        self._sync_host()
+        self._sync_host(reader=False)
+        if self.failed is not None:
+            return
         for n in _component(self.Xs[0]):
             if n._plan is self:
                 n._plan = None
@@ -427,6 +519,7 @@ class LDSPlan(object):
 
     def release(self):
         """Device state back into the nodes and the graph unbound (it is bound anew, as it is now, at the next use)."""
+        self._raise_failed()
         self.flush()
         if self.Xs[0]._plan is not self:
             return
@@ -435,7 +528,8 @@ class LDSPlan(object):
     def _demote(self, rest):
         """Hand the graph to the generic node-by-node plan and replay the remaining update() requests there."""
         from .generic import GenericPlan
-        self._sync_host()
+        self._sync_host(reader=False)
+        self._raise_failed()            # (the request that brought the graph here was its own)
         for n in _component(self.Xs[0]):
             n._plan = None
         self.closed = True
@@ -451,11 +545,12 @@ class LDSPlan(object):
         return gp
 
     # -- attribute traffic -----------------------------------------------------------------------
-    def _pull(self):
+    def _pull(self, reader=True):
         self.flush()
-        return self._materialize().pull()
+        return self._materialize().pull(self if reader else None)
 
     def read(self, node, name):
+        self._raise_failed()
         kind, i = self.index[id(node)]
         if kind == "y" and (node.observed or name not in ("qmu", "qcov", "q_ln_det")):
             return node.__dict__.get("_h_" + name)          # observations: host copy
@@ -494,6 +589,7 @@ class LDSPlan(object):
     def write(self, node, name, value):
         """A user assignment to a posterior attribute after binding: push it to the device.  False: not something this plan
         can patch in place (an observation, a state covariance): the caller releases the plan and the graph is bound anew."""
+        self._raise_failed()
         self.flush()
         if node._plan is not self:              # the queue held something only the node-by-node plan serves, or the graph left its handle
             return N._plan_of(node).write(node, name, value)
@@ -506,7 +602,8 @@ class LDSPlan(object):
             return name != "qcov"               # (a covariance is something the recogniser has to look at again)
         g, r, b = self.group, self.r, self.group.batch
         g.invalidate()
-        st = b.get_state()
+        # (the whole state is read back and every row pushed again: rows that are switched off get the values they hold)
+        st = g._sync_call(self, b.get_state)
         if kind == "x" and name == "qmu":
             st["X"][r, i] = np.asarray(value).reshape(-1)
             b.set_state(X=st["X"])
@@ -516,7 +613,7 @@ class LDSPlan(object):
                 st[M][r][:, i] = np.asarray(value).reshape(-1)
                 b.set_state(**{M: st[M]})                       # the mean alone: with Wishart noise the covariances are dense
             elif self.kind == "wishart":
-                covs = list(b.get_column_cov())
+                covs = list(g._sync_call(self, b.get_column_cov))
                 covs[0 if kind == "a" else 1][r, i] = np.asarray(value, dtype=float)
                 b.set_column_cov(**{"A_cov" if kind == "a" else "C_cov": covs[0 if kind == "a" else 1]})
             else:
@@ -526,7 +623,7 @@ class LDSPlan(object):
                 st[V][r, i] = np.diag(cov)
                 b.set_state(**{V: st[V]})
         elif kind in ("q", "r") and name == "qw":
-            w = b.get_wishart_state()
+            w = g._sync_call(self, b.get_wishart_state)
             key = "Q_w" if kind == "q" else "R_w"
             w[key][r] = np.asarray(value, dtype=float).reshape(node.shape)
             b.set_wishart_state(**{key: w[key]})
@@ -538,15 +635,17 @@ class LDSPlan(object):
 
     # -- lower bound -----------------------------------------------------------------------------
     def elbo_parts(self, bound="reference"):
+        self._raise_failed()
         self.flush()
         if self.Xs[0]._plan is not self:        # the graph has moved: to a handle of its own, or to the node-by-node plan
             plan = N._plan_of(self.Xs[0])
             if isinstance(plan, LDSPlan):
                 return plan.elbo_parts(bound)
             raise NotImplementedError("the graph runs node by node now: use Network.learn or the nodes' log_lower_bound()")
-        return self._materialize().elbo(bound)[self.r]
+        return self._materialize().elbo(bound, self)[self.r]
 
     def node_llb(self, node, bound="reference"):
+        self._raise_failed()
         self.flush()
         if node._plan is not self:
             return N._plan_of(node).node_llb(node, bound)
@@ -565,6 +664,7 @@ class LDSPlan(object):
     def mirror(self):
         """A generic (node-by-node) plan holding a copy of this plan's current posteriors: serves single messages
         (pass_up_m1_m2) and single lower-bound terms, which the fused kernels never materialise."""
+        self._raise_failed()
         self.flush()
         if getattr(self, "_mirror", None) is None or self._mirror_of is not self.cache or self.cache is None:
             from .generic import GenericPlan

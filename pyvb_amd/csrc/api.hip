@@ -147,8 +147,15 @@ int pyvb_lds_create(pyvb_lds** out, int device, int N, int T, int D, int K, int 
     TRY(dev_alloc(&h->resQ, n * D)); TRY(dev_alloc(&h->resR, n * K));
     TRY(dev_alloc(&h->elbo, n * 6)); TRY(dev_alloc(&h->elbo_sum, 8));
     TRY(dev_alloc(&h->elbo_hist, (size_t)PYVB_ELBO_HISTORY * 8));
-    TRYHIP(hipMalloc((void**)&h->status, sizeof(int)));
-    TRYHIP(hipMemset(h->status, 0, sizeof(int)));
+    TRYHIP(hipMalloc((void**)&h->status, n * sizeof(int)));
+    TRYHIP(hipMemset(h->status, 0, n * sizeof(int)));
+    TRYHIP(hipMalloc((void**)&h->active, n));
+    TRYHIP(hipMemset(h->active, 1, n));
+    h->active_host = (unsigned char*)malloc(n);
+    memset(h->active_host, 1, n);
+    h->n_active = N;
+    h->status_host = (int*)calloc(n, sizeof(int));
+    h->reported = (int*)calloc(n, sizeof(int));
     // priors block: x0_mean D, x0_prec D*D, A_pm D*D, A_pp D*D, C_pm K*D, C_pp D*K, Q_a0 D, Q_b0 D, R_a0 K, R_b0 K
     size_t pn = (size_t)D + 3 * (size_t)D * D + 2 * (size_t)K * D + 2 * (size_t)D + 2 * (size_t)K + (size_t)D * D + (size_t)K * D + 2 * (size_t)D
                 + (size_t)D * D + (size_t)K * K;
@@ -211,6 +218,8 @@ int pyvb_lds_destroy(pyvb_lds* h) {
     for (double* b : bufs) if (b) (void)hipFree(b);
     if (h->warm) (void)hipFree(h->warm);
     if (h->status) (void)hipFree(h->status);
+    if (h->active) (void)hipFree(h->active);
+    free(h->active_host); free(h->status_host); free(h->reported);
     if (h->pool) {
         for (int i = 0; i < PYVB_EVENT_POOL; ++i) { if (h->pool[i].e0) (void)hipEventDestroy(h->pool[i].e0); if (h->pool[i].e1) (void)hipEventDestroy(h->pool[i].e1); }
         free(h->pool);
@@ -227,6 +236,29 @@ static int join_elbo(pyvb_lds* h);
 // pyvb_lds_iterate may have left in flight on the side stream (it reads states and parameters).
 #define ENTER_RAW(h) do { ARGCHK(h, "handle is NULL"); HIPCHK(hipSetDevice((h)->device)); } while (0)
 #define ENTER(h) do { ENTER_RAW(h); if ((h)->elbo_in_flight) { int _rc = join_elbo(h); if (_rc) return _rc; } } while (0)
+
+// every replicate switched off: the update entries are successful no-ops without a launch
+#define IDLE(h) do { if ((h)->n_active == 0) return PYVB_OK; } while (0)
+
+// Rows of switched-off replicates sit out the two ping-pongs of the handle: the X buffers (a sweep reads one and writes the
+// other) and the covariance classes (k_prep writes Sigma_new, adopt_classes swaps).  They stay where they were when the row
+// was switched off, and are copied across here, before a getter reads every row, before a setter or a staging copy uses the
+// other X buffer, and before the mask changes -- never on the update path.
+static int settle_parked(pyvb_lds* h) {
+    if (h->n_active == h->N) return PYVB_OK;
+    int rc;
+    if (h->x_park != h->cur) {
+        if ((rc = launch_carry(h, h->X[h->x_park], h->X[h->cur], (size_t)h->T * h->L.DP))) return rc;
+        h->x_park = h->cur;
+    }
+    if (h->cls_parked_other) {
+        if ((rc = launch_carry(h, h->Sigma_new, h->Sigma, (size_t)3 * h->D * h->D))) return rc;
+        if ((rc = launch_carry(h, h->qld_x_new, h->qld_x, 3))) return rc;
+        if ((rc = launch_carry(h, h->lnd_x_new, h->lnd_x, 3))) return rc;
+        h->cls_parked_other = false;
+    }
+    return PYVB_OK;
+}
 
 static int h2d(pyvb_lds* h, double* dst, const double* src, size_t n) {
     if (!src) return PYVB_OK;
@@ -497,6 +529,7 @@ int pyvb_lds_set_output_state(pyvb_lds* h, const double* Yq, const double* Yrowv
     ARGCHK(h->has_missing, "the observations hold no NaN: every output is observed");
     ARGCHK(Yq && Yrowvar, "Yq and Yrowvar are required");
     const size_t n = (size_t)h->N * h->T * h->K;
+    { int rc0 = settle_parked(h); if (rc0) return rc0; }
     // staged through buffers that are free until the next sweep / statistics pass
     double* dq = h->U;                  // [N][T][DP] >= [N][T][K]?  not for K > DP: use a temporary then
     double* tmp = nullptr;
@@ -535,6 +568,7 @@ int pyvb_lds_get_outputs(pyvb_lds* h, double* Yq, double* Yvar, double* Yqld) {
 int pyvb_lds_update_Y(pyvb_lds* h) {
     ENTER(h);
     if (!h->has_missing) return PYVB_OK;            // observed nodes never update (gaussian.py:109-110)
+    IDLE(h);
     int rc;
     if (h->dense) {
         if ((rc = ensure_expect(h))) return rc;     // E[R] and its log-determinant
@@ -554,6 +588,7 @@ int pyvb_lds_set_state(pyvb_lds* h, const double* X, const double* A_mean, const
     ENTER(h);
     const size_t N = h->N, T = h->T, D = h->D, K = h->K;
     int rc;
+    if ((rc = settle_parked(h))) return rc;
     if (X) {    // the other buffer is free between sweeps: stage the API layout there, then permute
         if ((rc = h2d(h, h->X[1 - h->cur], X, N * T * D))) return rc;
         if ((rc = launch_permute(h, h->X[1 - h->cur], h->X[h->cur], 1))) return rc;
@@ -579,6 +614,7 @@ int pyvb_lds_get_state(pyvb_lds* h, double* X, double* A_mean, double* A_colvar,
     ENTER(h);
     const size_t N = h->N, T = h->T, D = h->D, K = h->K;
     int rc;
+    if ((rc = settle_parked(h))) return rc;
     if (X) {
         if ((rc = launch_permute(h, h->X[h->cur], h->X[1 - h->cur], 0))) return rc;
         if ((rc = d2h(h, X, h->X[1 - h->cur], N * T * D))) return rc;
@@ -598,6 +634,7 @@ int pyvb_lds_get_posterior_classes(pyvb_lds* h, double* Sigma, double* qld_x) {
     ENTER(h);
     const size_t N = h->N, D = h->D;
     int rc;
+    if ((rc = settle_parked(h))) return rc;
     if ((rc = d2h(h, Sigma, h->Sigma, N * 3 * D * D))) return rc;
     if ((rc = d2h(h, qld_x, h->qld_x, N * 3))) return rc;
     return pyvb_lds_sync(h);
@@ -608,6 +645,7 @@ int pyvb_lds_set_posterior_classes(pyvb_lds* h, const double* Sigma, const doubl
     ARGCHK(Sigma, "Sigma is NULL");
     const size_t N = h->N, D = h->D;
     int rc;
+    if ((rc = settle_parked(h))) return rc;
     if ((rc = h2d(h, h->Sigma, Sigma, N * 3 * D * D))) return rc;
     if ((rc = h2d(h, h->qld_x, qld_x, N * 3))) return rc;
     h->lnd_x_pending = true;        // ln det of these covariances: formed when the exact bound first asks for it (ensure_lnd_x)
@@ -680,6 +718,7 @@ static int ensure_expect(pyvb_lds* h) {        // E[Q], E[R] of the current Wish
 static int ensure_lnd_x(pyvb_lds* h) {
     if (!h->lnd_x_pending) return PYVB_OK;
     const size_t N = h->N, D = h->D;
+    { int rc0 = settle_parked(h); if (rc0) return rc0; }       // every row of Sigma is read, every row of lnd_x written
     std::vector<double> S(N * 3 * D * D), lnd(N * 3), L(D * D);
     HIPCHK(hipMemcpyAsync(S.data(), h->Sigma, S.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
@@ -725,6 +764,7 @@ static void adopt_classes(pyvb_lds* h) {
     t = h->lnd_x; h->lnd_x = h->lnd_x_new; h->lnd_x_new = t;
     h->lnd_x_pending = false;
     h->classes_valid = true;
+    if (h->n_active < h->N) h->cls_parked_other = !h->cls_parked_other;     // the parked rows did not move with the pointers
 }
 
 static void mark_all_fresh(pyvb_lds* h) {
@@ -780,12 +820,14 @@ static int sweep(pyvb_lds* h, int direction, bool keep_x) {
 int pyvb_lds_sweep(pyvb_lds* h, int direction) {
     ENTER(h);
     ARGCHK(direction == PYVB_FORWARD || direction == PYVB_BACKWARD, "direction must be PYVB_FORWARD or PYVB_BACKWARD");
+    IDLE(h);
     return sweep(h, direction, true);
 }
 
 int pyvb_lds_update_x(pyvb_lds* h, int t) {
     ENTER(h);
     ARGCHK(t >= 0 && t < h->T, "t out of range");
+    IDLE(h);
     int rc = ensure_gains(h);
     if (rc) return rc;
     if ((rc = launch_step(h, t))) return rc;
@@ -803,6 +845,7 @@ int pyvb_lds_update_columns(pyvb_lds* h, int which, int col_begin, int col_end) 
     ENTER(h);
     ARGCHK(which == 0 || which == 1, "which must be 0 (A) or 1 (C)");
     ARGCHK(col_begin >= 0 && col_begin < col_end && col_end <= h->D, "bad column range");
+    IDLE(h);
     int rc = ensure_stats(h);
     if (rc) return rc;
     if (h->dense) {
@@ -832,11 +875,12 @@ static int update_noise(pyvb_lds* h, int which) {
     return PYVB_OK;
 }
 
-int pyvb_lds_update_Q(pyvb_lds* h) { ENTER(h); return update_noise(h, 0); }
-int pyvb_lds_update_R(pyvb_lds* h) { ENTER(h); return update_noise(h, 1); }
+int pyvb_lds_update_Q(pyvb_lds* h) { ENTER(h); IDLE(h); return update_noise(h, 0); }
+int pyvb_lds_update_R(pyvb_lds* h) { ENTER(h); IDLE(h); return update_noise(h, 1); }
 
 int pyvb_lds_elbo(pyvb_lds* h) {
     ENTER(h);
+    IDLE(h);
     int rc;
     if ((rc = ensure_resid(h, 0))) return rc;
     if ((rc = ensure_resid(h, 1))) return rc;
@@ -870,7 +914,22 @@ int pyvb_lds_iterate(pyvb_lds* h, int niters) {
     ENTER_RAW(h);
     ARGCHK(niters >= 0, "niters must be >= 0");
     int rc;
+    // Every replicate switched off: no update is launched, but the (empty) sums still go into the history and through the
+    // all-reduce, which the other ranks are waiting in.
+    const bool idle = h->n_active == 0;
     for (int it = 0; it < niters; ++it) {
+        if (idle) {
+            if ((rc = join_elbo(h))) return rc;
+            HIPCHK(hipEventRecord(h->ev_params, h->stream));
+            HIPCHK(hipStreamWaitEvent(h->side, h->ev_params, 0));
+            double* slot = h->elbo_hist + (size_t)(h->hist_count % PYVB_ELBO_HISTORY) * 8;
+            if ((rc = launch_elbo_sum(h, slot, h->side))) return rc;
+            if (h->comm && (rc = pyvb_allreduce_f64(h->comm, slot, 6, h->side))) return rc;
+            h->hist_count += 1;
+            HIPCHK(hipEventRecord(h->ev_elbo, h->side));
+            h->elbo_in_flight = true;
+            continue;
+        }
         // the backward sweep follows at once and reads c_t, not the forward states: those are not written out
         if ((rc = sweep(h, PYVB_FORWARD, false))) return rc;
         if ((rc = join_elbo(h))) return rc;
@@ -941,6 +1000,7 @@ int pyvb_lds_set_bound_mode(pyvb_lds* h, int mode) {
 int pyvb_lds_get_logdets(pyvb_lds* h, double* lnd_x, double* lnd_A, double* lnd_C, double* Ylnd) {
     ENTER(h);
     int rc;
+    if ((rc = settle_parked(h))) return rc;
     if (lnd_x && (rc = ensure_lnd_x(h))) return rc;
     if ((rc = d2h(h, lnd_x, h->lnd_x, (size_t)h->N * 3))) return rc;
     if ((rc = d2h(h, lnd_A, h->lnd_A, (size_t)h->N * h->D))) return rc;
@@ -956,13 +1016,60 @@ int pyvb_lds_sync(pyvb_lds* h) {
     ENTER(h);
     HIPCHK(hipStreamSynchronize(h->stream));
     HIPCHK(hipStreamSynchronize(h->side));
-    int st = 0;
-    HIPCHK(hipMemcpy(&st, h->status, sizeof(int), hipMemcpyDeviceToHost));
-    if (st) {
-        pyvb_set_error("a posterior precision was not positive definite (numpy.linalg.LinAlgError in the reference)");
-        HIPCHK(hipMemset(h->status, 0, sizeof(int)));
+    HIPCHK(hipMemcpy(h->status_host, h->status, (size_t)h->N * sizeof(int), hipMemcpyDeviceToHost));
+    int first = -1, failed = 0;
+    for (int n = 0; n < h->N; ++n)      // the flags of a replicate that was switched off (because it failed) do not raise again
+        if (h->status_host[n] && h->active_host[n]) { if (first < 0) first = n; ++failed; }
+    if (failed) {
+        memcpy(h->reported, h->status_host, (size_t)h->N * sizeof(int));
+        pyvb_set_error("a posterior precision was not positive definite (numpy.linalg.LinAlgError in the reference): "
+                       "first in replicate %d, %d of %d replicates failed (pyvb_lds_get_status)", first, failed, h->N);
+        HIPCHK(hipMemset(h->status, 0, (size_t)h->N * sizeof(int)));
         return PYVB_E_LINALG;
     }
+    memset(h->reported, 0, (size_t)h->N * sizeof(int));
+    return PYVB_OK;
+}
+
+int pyvb_lds_get_status(pyvb_lds* h, int* status) {
+    ARGCHK(h, "handle is NULL");
+    ARGCHK(status, "status is NULL");
+    ENTER(h);
+    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipStreamSynchronize(h->side));
+    HIPCHK(hipMemcpy(h->status_host, h->status, (size_t)h->N * sizeof(int), hipMemcpyDeviceToHost));
+    for (int n = 0; n < h->N; ++n) status[n] = h->status_host[n] | h->reported[n];
+    return PYVB_OK;
+}
+
+int pyvb_lds_set_active(pyvb_lds* h, const unsigned char* active) {
+    ARGCHK(h, "handle is NULL");
+    ARGCHK(active, "active is NULL");
+    for (int n = 0; n < h->N; ++n)
+        if (active[n] && !h->active_host[n]) {
+            pyvb_set_error("replicate %d is switched off and cannot be switched on again: the mask can only shrink "
+                           "(the validity tracking of gains and statistics is per handle)", n);
+            return PYVB_E_ARG;
+        }
+    ENTER(h);
+    int count = 0, changed = 0;
+    for (int n = 0; n < h->N; ++n) { count += active[n] != 0; changed += (active[n] != 0) != (h->active_host[n] != 0); }
+    if (!changed) return PYVB_OK;
+    // rows switched off earlier move to where the rows switched off now are: the current buffers
+    int rc = settle_parked(h);
+    if (rc) return rc;
+    for (int n = 0; n < h->N; ++n) h->active_host[n] = active[n] ? 1 : 0;
+    h->n_active = count;
+    h->x_park = h->cur; h->cls_parked_other = false;
+    HIPCHK(hipMemcpyAsync(h->active, h->active_host, (size_t)h->N, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));       // the mirror may change again as soon as this returns
+    return PYVB_OK;
+}
+
+int pyvb_lds_get_active(pyvb_lds* h, unsigned char* active) {
+    ARGCHK(h, "handle is NULL");
+    ARGCHK(active, "active is NULL");
+    memcpy(active, h->active_host, (size_t)h->N);
     return PYVB_OK;
 }
 

@@ -119,7 +119,14 @@ struct pyvb_lds {
     double *mom;                    // [N][3 D^2 + K D + D] second moments (k_moments)
     double *resQ, *resR;            // [N][D], [N][K]
     double *elbo, *elbo_sum;        // [N][6], [6]
-    int *status;                    // device flag: nonzero if a Cholesky failed
+    int *status;                    // device, [N]: PYVB_FAIL_* bits of the replicates whose factorisations met a non-positive pivot
+    // ---- per-replicate bookkeeping: the activity mask (it can only shrink) and the flags the last failed pyvb_lds_sync reported
+    unsigned char *active;          // device, [N]: 0 = switched off; every update kernel leaves such a replicate's rows alone
+    unsigned char *active_host;     // its host mirror (set_active is stream ordered, the mirror is what the host logic reads)
+    int n_active;
+    int *status_host, *reported;    // [N] staging of a read of status; [N] what the most recent failed sync reported and cleared
+    int x_park;                     // the X buffer that holds the rows of the switched-off replicates (they sit out the ping-pong)
+    bool cls_parked_other;          // their Sigma / qld_x / lnd_x are in the *_new set (adopt_classes swapped since)
     // host-side validity tracking
     bool gains_valid, stats_valid, resQ_valid, resR_valid;
     int fresh_count; unsigned char* fresh;  // X_t updated since the parameters last changed
@@ -160,6 +167,7 @@ int launch_sweep(pyvb_lds* h, int direction, bool keep_x = true);
 int launch_step(pyvb_lds* h, int t);
 int launch_syy(pyvb_lds* h);
 int launch_permute(pyvb_lds* h, const double* src, double* dst, int to_internal);
+int launch_carry(pyvb_lds* h, const double* src, double* dst, size_t per);     // rows of switched-off replicates, per doubles each
 int launch_stats(pyvb_lds* h, bool with_sxx);   // with_sxx = false: Sxx comes from the backward sweep (h->sxx)
 int launch_moments(pyvb_lds* h, bool sxx_from_sweep);
 int launch_observe(pyvb_lds* h);

@@ -53,6 +53,7 @@ struct BigSweepArgs {
                         // (W > 1), a buffer of its own -- a part's warm-up reads G y_t rows of the part before it, which that part's
                         // workgroup overwrites with c_t on its own schedule (within a workgroup a barrier orders the two)
     double* trash;      // [N][W][512]
+    const unsigned char* active;    // [N]: every workgroup (all W parts) of a switched-off replicate leaves at once
     int N, T, D, K, dir, W;
     Layout L;
 };
@@ -103,6 +104,7 @@ __device__ __forceinline__ double big_boundary(bool first, const double* g, cons
 // two products per step and no operand in LDS except the shared state.
 struct BigGyArgs {
     const double* Y; const double* gains; double* U; double* trash;
+    const unsigned char* active;
     int N, T, K, nblk;          // nblk: blocks of 16 time steps per workgroup
     Layout L;
 };
@@ -112,6 +114,7 @@ template <bool YVEC>     // YVEC: K even, a lane's two k of a step are one 16-by
 __global__ void __launch_bounds__(256) k_gy_big(BigGyArgs a) {
     constexpr int NT = 2;       // row tiles per wavefront
     const int n = blockIdx.y, tid = threadIdx.x, w = tid >> 6, lane = tid & 63, c = lane & 15, q = lane >> 4;
+    if (!a.active[n]) return;
     const int T = a.T, K = a.K;
     const double* g = a.gains + (size_t)n * a.L.gains_total + a.L.oGp;
     const double* Yn = a.Y + (size_t)n * T * K;
@@ -179,6 +182,7 @@ template <bool Y4>      // Y4: K a multiple of 4 -- a thread's four entries of a
 __global__ void __launch_bounds__(512) k_gy_big8(BigGyArgs a) {
     __shared__ double yl[2][16 * GY_LDY];
     const int n = blockIdx.y, tid = threadIdx.x, w = tid >> 6, lane = tid & 63, c = lane & 15, q = lane >> 4;
+    if (!a.active[n]) return;
     const int T = a.T, K = a.K;
     const double* g = a.gains + (size_t)n * a.L.gains_total + a.L.oGp;
     const double* Yn = a.Y + (size_t)n * T * K;
@@ -247,6 +251,7 @@ __global__ void __launch_bounds__(512 / NTW) k_sweep_big(BigSweepArgs a) {
     double* xs = lds + 2 * BDS * 64;                // [128] boundary state exchange
     double* vs = xs + BDP;                          // [128] boundary scratch
     const int n = blockIdx.x, tid = threadIdx.x, w = tid >> 6, lane = tid & 63, c = lane & 15, q = lane >> 4;
+    if (!a.active[n]) return;
 #ifdef BIG_CLOCK        // (profiles/build_variant.sh k_big clock "-DBIG_CLOCK": the chip's clock while this kernel runs, from its two time counters)
     const unsigned long long ck_c0 = __builtin_amdgcn_s_memtime(), ck_r0 = __builtin_amdgcn_s_memrealtime();
     struct ClockReport { unsigned long long c0, r0; int on, mode; __device__ ~ClockReport() {
@@ -464,7 +469,7 @@ int launch_sweep_big(pyvb_lds* h, int direction) {
     a.Xold = h->X[h->cur]; a.Xnew = h->X[1 - h->cur]; a.Y = h->Y; a.gains = h->gains; a.warm = h->warm;
     a.A_mean = h->A_mean; a.C_mean = h->C_mean; a.trash = h->trash; a.U = h->U;
     a.QA = h->dense ? h->QA : nullptr; a.RC = h->dense ? h->RC : nullptr;
-    a.N = h->N; a.T = h->T; a.D = h->D; a.K = h->K; a.dir = direction; a.L = h->L;
+    a.N = h->N; a.T = h->T; a.D = h->D; a.K = h->K; a.dir = direction; a.L = h->L; a.active = h->active;
     a.W = h->W; a.Uc = h->W > 1 ? h->U2 : h->U;
     // a backward sweep right behind a forward one (h->u_valid) reads c_t; anything else starts from G y_t
     const bool cached = direction == PYVB_BACKWARD && h->u_valid;
@@ -472,7 +477,7 @@ int launch_sweep_big(pyvb_lds* h, int direction) {
     if (!cached && h->T > 2) {
         BigGyArgs ga;
         ga.Y = h->Y; ga.gains = h->gains; ga.U = h->U; ga.trash = h->trash;
-        ga.N = h->N; ga.T = h->T; ga.K = h->K; ga.L = h->L;
+        ga.N = h->N; ga.T = h->T; ga.K = h->K; ga.L = h->L; ga.active = h->active;
         const int blocks = (h->T - 2 + 15) / 16;
         ga.nblk = blocks < 32 ? ((blocks + 1) & ~1) : 32;
         TimedLaunch tl(h, PYVB_K_GY);
@@ -497,6 +502,7 @@ int launch_sweep_big(pyvb_lds* h, int direction) {
 // Xs[t].update() alone, in place in the current buffer (k_sweep.hip: k_step), thread = row
 struct BigStepArgs {
     double* X; const double* Y; const double* gains; const double *A_mean, *C_mean, *QA, *RC;
+    const unsigned char* active;
     int N, T, D, K, t;
     Layout L;
 };
@@ -504,6 +510,7 @@ struct BigStepArgs {
 __global__ void __launch_bounds__(128) k_step_big(BigStepArgs a) {
     __shared__ double vs[BDP];
     const int n = blockIdx.x, tid = threadIdx.x;
+    if (!a.active[n]) return;
     const int T = a.T, D = a.D, K = a.K, t = a.t;
     const Layout& L = a.L;
     const double* g = a.gains + (size_t)n * L.gains_total;
@@ -533,7 +540,7 @@ int launch_step_big(pyvb_lds* h, int t) {
     BigStepArgs a;
     a.X = h->X[h->cur]; a.Y = h->Y; a.gains = h->gains; a.A_mean = h->A_mean; a.C_mean = h->C_mean;
     a.QA = h->dense ? h->QA : nullptr; a.RC = h->dense ? h->RC : nullptr;
-    a.N = h->N; a.T = h->T; a.D = h->D; a.K = h->K; a.t = t; a.L = h->L;
+    a.N = h->N; a.T = h->T; a.D = h->D; a.K = h->K; a.t = t; a.L = h->L; a.active = h->active;
     TimedLaunch tl(h, PYVB_K_STEP);
     hipLaunchKernelGGL(k_step_big, dim3(h->N), dim3(128), 0, h->stream, a);
     HIPCHK(hipGetLastError());
@@ -545,6 +552,7 @@ int launch_step_big(pyvb_lds* h, int t) {
 // ======================================================================================================================
 struct BigStatsArgs {
     const double* X; const double* Y; double* part; const double* zeros;     // zeros: 128 doubles
+    const unsigned char* active;
     int N, T, D, K, nchunk, chunk_len;
     Layout L;
 };
@@ -556,6 +564,7 @@ struct BigStatsArgs {
 // wavefronts read the same rows, seven of them from L1.
 __global__ void __launch_bounds__(512) k_stats_big(BigStatsArgs a) {
     const int ch = blockIdx.x, n = blockIdx.y;
+    if (!a.active[n]) return;
     const int w = threadIdx.x >> 6, lane = threadIdx.x & 63, r = lane & 15, q = lane >> 4;
     const int T = a.T, K = a.K;
     const double* X = a.X + (size_t)n * T * BDP;
@@ -627,7 +636,7 @@ __global__ void __launch_bounds__(512) k_stats_big(BigStatsArgs a) {
 int launch_stats_big(pyvb_lds* h) {
     BigStatsArgs a;
     a.X = h->X[h->cur]; a.Y = h->Y; a.part = h->stats; a.zeros = h->zeros;
-    a.N = h->N; a.T = h->T; a.D = h->D; a.K = h->K; a.nchunk = h->nchunk; a.chunk_len = h->chunk_len; a.L = h->L;
+    a.N = h->N; a.T = h->T; a.D = h->D; a.K = h->K; a.nchunk = h->nchunk; a.chunk_len = h->chunk_len; a.L = h->L; a.active = h->active;
     {
         TimedLaunch tl(h, PYVB_K_STATS);
         hipLaunchKernelGGL(k_stats_big, dim3(h->nchunk, h->N), dim3(512), 0, h->stream, a);
@@ -645,6 +654,7 @@ struct BigPrepArgs {
     // Wishart noise (dense): E[Q] [D][D], E[Q]<A> [D][D], E[R]<C> [K][D], tr(S_i E[Q]) [D], tr(S'_i E[R]) [D] per replicate
     const double *Qbar, *QA, *RC, *trA, *trC;
     int *warm, *status;
+    const unsigned char* active;
     int N, T, D, K, noise, dense;
     Layout L;
 };
@@ -819,6 +829,7 @@ __global__ void __launch_bounds__(256) k_prep_big(BigPrepArgs a) {
     double* gjrc = colp + BDP;              // [2][GJB_BUF]
     double* pivs = gjrc + 2 * GJB_BUF;      // [128]
     const int n = blockIdx.x, tid = threadIdx.x, D = a.D, K = a.K;
+    if (!a.active[n]) return;
     const int wave = tid >> 6, lane = tid & 63;
     const Layout& L = a.L;
     const double* Am = a.A_mean + (size_t)n * D * D;
@@ -919,7 +930,7 @@ __global__ void __launch_bounds__(256) k_prep_big(BigPrepArgs a) {
             double lp = 0.0;
             for (int k = tid; k < D; k += 64) {
                 const double piv = pivs[k];
-                if (!(piv > 0.0)) atomicOr(a.status, 1);
+                if (!(piv > 0.0)) atomicOr(a.status + n, PYVB_FAIL_STATES);
                 lp += log(piv);
             }
             lp = wave_sum(lp);
@@ -1013,7 +1024,7 @@ int launch_prep_big(pyvb_lds* h) {
     a.x0_mean = h->pri.x0_mean; a.x0_prec = h->pri.x0_prec;
     a.Sigma = h->Sigma_new; a.qld = h->qld_x_new; a.lnd = h->lnd_x_new; a.gains = h->gains; a.scratch = h->scratch;
     a.warm = h->warm; a.status = h->status;
-    a.N = h->N; a.T = h->T; a.D = h->D; a.K = h->K; a.noise = h->noise; a.L = h->L;
+    a.N = h->N; a.T = h->T; a.D = h->D; a.K = h->K; a.noise = h->noise; a.L = h->L; a.active = h->active;
     a.dense = h->dense ? 1 : 0; a.Qbar = h->Qbar; a.QA = h->QA; a.RC = h->RC; a.trA = h->trA; a.trC = h->trC;
     const size_t lds = ((size_t)BDP * BLD + 4 * BDP + 2 * GJB_BUF + BDP) * sizeof(double);
     if (!h->big_attr_prep) {           // per handle: the attribute belongs to the device the handle lives on
@@ -1049,6 +1060,7 @@ __global__ void __launch_bounds__(256) k_cols_big_rows(ParamArgs a) {
     double* gd = pkn + 4 * BDP;             // [128] the diagonal of G
     double* red = gd + BDP;                 // [4]
     const int WHICH = a.which0 + blockIdx.y, n = blockIdx.x, tid = threadIdx.x, D = a.D, K = a.K;
+    if (!a.active[n]) return;
     const int rows = WHICH == 0 ? D : K;
     const int row = tid >> 1, half = tid & 1, lane = tid & 63, wave = tid >> 6;
     double* M = (WHICH == 0 ? a.A_mean : a.C_mean) + (size_t)n * rows * D;
@@ -1198,6 +1210,7 @@ __global__ void __launch_bounds__(256) k_cols_big(ParamArgs a) {
     double* gd = pkn + 4 * BDP;             // [128] the diagonal of G
     double* red = gd + BDP;                 // [8]
     const int WHICH = a.which0 + blockIdx.y, n = blockIdx.x, tid = threadIdx.x, D = a.D, K = a.K;
+    if (!a.active[n]) return;
     const int rows = WHICH == 0 ? D : K;
     const int lane = tid & 63, wave = tid >> 6, c = lane & 15, q = lane >> 4;
     double* panel = red + 8 + wave * (32 * CBP);

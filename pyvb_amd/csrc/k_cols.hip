@@ -49,6 +49,7 @@ __global__ void __launch_bounds__(64) k_cols(ParamArgs a) {
     __shared__ double Gb[16 * GS];      // rows 16b .. 16b+15 of G, zero padded: Gb[ii * GS + j] = G[16b+ii][j]
     __shared__ double Sb[16 * GS];      // Sb[ii * GS + row]: P of the block, then the precisions of column ii
     const int n = blockIdx.x, lane = threadIdx.x, D = a.D, K = a.K, c = lane & 15, q = lane >> 4;
+    if (!a.active[n]) return;
     const int rows = WHICH == 0 ? D : K;
     double* M = (WHICH == 0 ? a.A_mean : a.C_mean) + (size_t)n * rows * D;
     double* V = (WHICH == 0 ? a.A_var : a.C_var) + (size_t)n * D * rows;

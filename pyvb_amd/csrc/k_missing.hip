@@ -23,13 +23,14 @@ struct MissArgs {
     const double* X; const double* C_mean; const double *R_a, *R_b;
     double* Syy; double* Yent; double* YentX;
     const double* Yq0; const double* Yrowvar0;
+    const unsigned char* active;    // [N]: switched-off replicates are skipped
     int N, T, K, D, DP;
 };
 
 // One wavefront per row; a lane handles entries lane and lane + 64 (K <= 128: the second shape class, k_big.hip).
 __global__ void __launch_bounds__(256) k_missing_init(MissArgs a) {
     const int n = blockIdx.y, t = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63, K = a.K;
-    if (t >= a.T) return;
+    if (t >= a.T || !a.active[n]) return;
     const size_t row = ((size_t)n * a.T + t) * K;
     double ob[2];
     bool miss = false;
@@ -55,7 +56,7 @@ __global__ void __launch_bounds__(256) k_missing_init(MissArgs a) {
 
 __global__ void __launch_bounds__(256) k_impute(MissArgs a) {
     const int n = blockIdx.y, t = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63, K = a.K, D = a.D;
-    if (t >= a.T) return;
+    if (t >= a.T || !a.active[n]) return;
     const size_t row = ((size_t)n * a.T + t) * K;
     double ob[2], rbar[2];
     bool miss[2];
@@ -92,6 +93,7 @@ __global__ void __launch_bounds__(256) k_impute(MissArgs a) {
 __global__ void __launch_bounds__(256) k_syy_missing(MissArgs a) {
     __shared__ double red[4][131];
     const int n = blockIdx.x, w = threadIdx.x >> 6, lane = threadIdx.x & 63, K = a.K, T = a.T;
+    if (!a.active[n]) return;
     const double* Y = a.Y + (size_t)n * T * K;
     const double* Yo = a.Yobs + (size_t)n * T * K;
     const double* Yv = a.Yvar + (size_t)n * T * K;
@@ -147,6 +149,7 @@ __global__ void __launch_bounds__(256) k_impute_dense(MissArgs a) {
     __shared__ double gjbuf[4 * (GJW_BUF + 64)];
     __shared__ double vec[4][3][64];
     const int n = blockIdx.x, tid = threadIdx.x, wv = tid >> 6, lane = tid & 63, K = a.K, D = a.D, T = a.T;
+    if (!a.active[n]) return;
     const double* Rbar = a.Rbar + (size_t)n * K * K;
     const double* Rw = a.R_w + (size_t)n * K * K;
     const double qv = a.R_a[(size_t)n * K];
@@ -256,6 +259,7 @@ __global__ void __launch_bounds__(256) k_impute_dense(MissArgs a) {
 __global__ void __launch_bounds__(256) k_missing_ent_dense(MissArgs a) {
     __shared__ double red[4][66];
     const int n = blockIdx.x, w = threadIdx.x >> 6, k = threadIdx.x & 63, K = a.K, T = a.T;
+    if (!a.active[n]) return;
     const double* Yo = a.Yobs + (size_t)n * T * K;
     const double* Yv = a.Yvar + (size_t)n * T * K;
     double s = 0.0, ent = 0.0, entx = 0.0;
@@ -292,7 +296,7 @@ static MissArgs make_margs(pyvb_lds* h) {
     a.Y = h->Y; a.Yobs = h->Yobs; a.Yvar = h->Yvar; a.Yqld = h->Yqld; a.X = h->X[h->cur]; a.C_mean = h->C_mean;
     a.R_a = h->R_a; a.R_b = h->R_b; a.Syy = h->Syy; a.Yent = h->Yent; a.Yq0 = nullptr; a.Yrowvar0 = nullptr;
     a.Ylnd = h->Ylnd; a.YentX = h->YentX;
-    a.N = h->N; a.T = h->T; a.K = h->K; a.D = h->D; a.DP = h->L.DP;
+    a.N = h->N; a.T = h->T; a.K = h->K; a.D = h->D; a.DP = h->L.DP; a.active = h->active;
     a.Rbar = h->Rbar; a.lnd = h->lnd; a.R_w = h->R_w; a.Yld = h->dense ? h->Yld : nullptr; a.YcovS = h->YcovS; a.diag_cov = 0;
     return a;
 }

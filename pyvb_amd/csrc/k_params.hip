@@ -14,6 +14,7 @@
 // (<x x^T> = qmu qmu^T + qcov, gaussian.py:162-168), once per statistics pass, fully parallel.
 __global__ void __launch_bounds__(256) k_moments(ParamArgs a) {
     const int n = blockIdx.x, tid = threadIdx.x, D = a.D, K = a.K, T = a.T, DP = a.L.DP;
+    if (!a.active[n]) return;
     const double* P = a.part + (size_t)n * a.nchunk * a.L.stats_total;
     const double* S = a.Sigma + (size_t)n * 3 * D * D;
     const double* x0 = a.X + (size_t)n * T * DP;       // state rows: stride DP, accumulator order (xpos)
@@ -66,6 +67,7 @@ __global__ void __launch_bounds__(64 * NW) k_noise(ParamArgs a) {
     __shared__ double red[2];
     const int WHICH = a.which0 + blockIdx.y;
     const int n = blockIdx.x, lane = threadIdx.x;
+    if (!a.active[n]) return;
     const int dim = WHICH == 0 ? a.D : a.K;
     const double* res = (WHICH == 0 ? a.resQ : a.resR) + (size_t)n * dim;
     const double* b0 = WHICH == 0 ? a.pri.Q_b0 : a.pri.R_b0;
@@ -92,6 +94,7 @@ template <int NW>
 __global__ void __launch_bounds__(64 * NW) k_elbo(ParamArgs a) {
     __shared__ double red[2];
     const int n = blockIdx.x, lane = threadIdx.x, D = a.D, K = a.K, T = a.T;
+    if (!a.active[n]) return;
     const double* S0 = a.Sigma + (size_t)n * 3 * D * D;
     const double* x0 = a.X + (size_t)n * T * a.L.DP;
     const bool exact = a.bound == PYVB_BOUND_EXACT;
@@ -189,13 +192,15 @@ __global__ void __launch_bounds__(64 * NW) k_elbo(ParamArgs a) {
     }
 }
 
-struct SumArgs { const double* elbo; double* out; int N; };
+// (rows of switched-off replicates keep the parts they had then, for pyvb_lds_get_elbo; the totals leave them out)
+struct SumArgs { const double* elbo; double* out; const unsigned char* active; int N; };
 __global__ void __launch_bounds__(256) k_elbo_sum(SumArgs a) {
     __shared__ double red[256 * 6];
     const int tid = threadIdx.x;
     double s[6] = {0, 0, 0, 0, 0, 0};
     for (int n = tid; n < a.N; n += 256)
-        for (int p = 0; p < 6; ++p) s[p] += a.elbo[(size_t)n * 6 + p];
+        if (a.active[n])
+            for (int p = 0; p < 6; ++p) s[p] += a.elbo[(size_t)n * 6 + p];
     for (int p = 0; p < 6; ++p) red[p * 256 + tid] = s[p];
     __syncthreads();
     if (tid < 6) {
@@ -210,6 +215,7 @@ template <int NW>
 __global__ void __launch_bounds__(64 * NW) k_observe(ParamArgs a) {
     __shared__ double red[2];
     const int WHICH = blockIdx.y, n = blockIdx.x, lane = threadIdx.x, D = a.D;
+    if (!a.active[n]) return;
     const int rows = WHICH == 0 ? a.D : a.K;
     double* M = (WHICH == 0 ? a.A_mean : a.C_mean) + (size_t)n * rows * D;
     double* V = (WHICH == 0 ? a.A_var : a.C_var) + (size_t)n * D * rows;
@@ -229,6 +235,7 @@ ParamArgs make_args(pyvb_lds* h) {
     a.resQ = h->resQ; a.resR = h->resR; a.elbo = h->elbo; a.pri = h->pri; a.Yent = h->has_missing ? h->Yent : nullptr;
     a.lnd_A = h->lnd_A; a.lnd_C = h->lnd_C; a.lnd_x = h->lnd_x; a.YentX = h->has_missing ? h->YentX : nullptr; a.bound = h->bound;
     a.N = h->N; a.T = h->T; a.D = h->D; a.K = h->K; a.noise = h->noise; a.L = h->L; a.c0 = 0; a.c1 = h->D; a.which0 = 0; a.fuse = 0; a.sxx = nullptr; a.W = 1;
+    a.active = h->active;
     return a;
 }
 
@@ -272,7 +279,7 @@ int launch_elbo(pyvb_lds* h, hipStream_t stream) {
 }
 
 int launch_elbo_sum(pyvb_lds* h, double* out, hipStream_t stream) {
-    SumArgs a; a.elbo = h->elbo; a.out = out ? out : h->elbo_sum; a.N = h->N;
+    SumArgs a; a.elbo = h->elbo; a.out = out ? out : h->elbo_sum; a.active = h->active; a.N = h->N;
     hipLaunchKernelGGL(k_elbo_sum, dim3(1), dim3(256), 0, stream ? stream : h->stream, a);
     HIPCHK(hipGetLastError());
     return PYVB_OK;

@@ -20,7 +20,8 @@ struct PrepArgs {
     double *Sigma, *qld, *lnd, *gains, *scratch;     // lnd: ln det Sigma of the three classes beside qld
     // Wishart noise (DENSE): E[Q] [D][D], E[Q] <A> [D][D], E[R] <C> [K][D], tr(S_i E[Q]) [D], tr(S'_i E[R]) [D] per replicate
     const double *Qbar, *QA, *RC, *trA, *trC;
-    int *warm, *status;
+    int *warm, *status;                 // status: [N] PYVB_FAIL_* flags per replicate
+    const unsigned char* active;        // [N]: a workgroup of a switched-off replicate leaves before it touches any row of it
     int N, T, D, K;
     Layout L;
 };
@@ -157,6 +158,7 @@ __global__ void __launch_bounds__(PREP_THREADS) k_prep(PrepArgs a) {
     __shared__ double W[DP * LD];        // work
     __shared__ double qbar[64], rbar[64], rowp[64], colp[64], gjbuf[3 * 2 * GJ_BUF + 192];
     const int n = blockIdx.x, tid = threadIdx.x, D = a.D, K = a.K;
+    if (!a.active[n]) return;
     const int wave = tid >> 6, lane = tid & 63;
     const Layout& L = a.L;
     const double* Am = a.A_mean + (size_t)n * D * D;
@@ -262,7 +264,7 @@ __global__ void __launch_bounds__(PREP_THREADS) k_prep(PrepArgs a) {
             double lp = 0.0;
             if (tid < D) {
                 const double piv = gjbuf[3 * 2 * GJ_BUF + c * 64 + tid];
-                if (!(piv > 0.0)) atomicOr(a.status, 1);
+                if (!(piv > 0.0)) atomicOr(a.status + n, PYVB_FAIL_STATES);
                 lp = log(piv);
             }
 #pragma unroll
@@ -406,7 +408,7 @@ int launch_prep(pyvb_lds* h) {
     a.Q_a = h->Q_a; a.Q_b = h->Q_b; a.R_a = h->R_a; a.R_b = h->R_b;
     a.x0_mean = h->pri.x0_mean; a.x0_prec = h->pri.x0_prec;
     a.Sigma = h->Sigma_new; a.qld = h->qld_x_new; a.lnd = h->lnd_x_new; a.gains = h->gains; a.scratch = h->scratch;
-    a.warm = h->warm; a.status = h->status;
+    a.warm = h->warm; a.status = h->status; a.active = h->active;
     a.Qbar = h->Qbar; a.QA = h->QA; a.RC = h->RC; a.trA = h->trA; a.trC = h->trC;
     a.N = h->N; a.T = h->T; a.D = h->D; a.K = h->K; a.L = h->L;
     {

@@ -15,6 +15,7 @@
 struct StatsArgs {
     const double* X; const double* Y; double* part;
     const double* zeros;    // 64 zeros
+    const unsigned char* active;    // [N]
     int N, T, D, K, nchunk, chunk_len;
     Layout L;
 };
@@ -50,6 +51,7 @@ __global__ void __launch_bounds__(128, STATS_OCC) k_stats(StatsArgs a) {
     using SP = StatsSplit<DT, KT, XX>;
     constexpr int NA = SP::NA, MA = SP::MA, MB0 = SP::MB0, MB = KT - MB0;
     const int ch = blockIdx.x, n = blockIdx.y, wave = threadIdx.x >> 6, lane = threadIdx.x & 63, r = lane & 15, q = lane >> 4;
+    if (!a.active[n]) return;
     const int T = a.T, K = a.K;
     const double* X = a.X + (size_t)n * T * DP;        // rows: stride DP, accumulator order
     const double* Y = a.Y + (size_t)n * T * K;
@@ -224,11 +226,12 @@ __global__ void __launch_bounds__(128, STATS_OCC) k_stats(StatsArgs a) {
 }
 
 // Syy[n][k] = sum_t y_t[k]^2: the observations never change, so this runs once per set_observations.
-struct SyyArgs { const double* Y; double* Syy; int N, T, K; };
+struct SyyArgs { const double* Y; double* Syy; const unsigned char* active; int N, T, K; };
 
 __global__ void __launch_bounds__(256) k_syy(SyyArgs a) {
     __shared__ double red[256];
     const int n = blockIdx.x, tid = threadIdx.x, K = a.K;
+    if (!a.active[n]) return;
     const double* Y = a.Y + (size_t)n * a.T * K;
     // thread owns component tid % K of rows tid / K, tid / K + 256 / K ...
     const int per = 256 / K, k = tid % K, r0 = tid / K;
@@ -253,7 +256,7 @@ static void launch_stats_t(pyvb_lds* h, const StatsArgs& a, bool with_sxx) {
 int launch_stats(pyvb_lds* h, bool with_sxx) {
     if (h->big) return launch_stats_big(h);
     StatsArgs a;
-    a.X = h->X[h->cur]; a.Y = h->Y; a.part = h->stats; a.zeros = h->zeros;
+    a.X = h->X[h->cur]; a.Y = h->Y; a.part = h->stats; a.zeros = h->zeros; a.active = h->active;
     a.N = h->N; a.T = h->T; a.D = h->D; a.K = h->K; a.nchunk = h->nchunk; a.chunk_len = h->chunk_len; a.L = h->L;
     {
         TimedLaunch tl(h, PYVB_K_STATS);
@@ -275,7 +278,7 @@ int launch_stats(pyvb_lds* h, bool with_sxx) {
 }
 
 int launch_syy(pyvb_lds* h) {
-    SyyArgs a; a.Y = h->Y; a.Syy = h->Syy; a.N = h->N; a.T = h->T; a.K = h->K;
+    SyyArgs a; a.Y = h->Y; a.Syy = h->Syy; a.active = h->active; a.N = h->N; a.T = h->T; a.K = h->K;
     hipLaunchKernelGGL(k_syy, dim3(h->N), dim3(256), 0, h->stream, a);
     HIPCHK(hipGetLastError());
     return PYVB_OK;

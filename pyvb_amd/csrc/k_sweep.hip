@@ -26,6 +26,7 @@ struct SweepArgs {
     double* Sxx;        // [N][DP][DP]: sum over the interior nodes of mu_t mu_t^T, written by the MODE 2 sweep
     int N, T, D, K, dir;
     int W;              // wavefronts per replicate: each takes a contiguous part of the interior time range (grid.y)
+    const unsigned char* active;    // [N]: the wavefronts of a switched-off replicate (all W of them) leave at once
     int keep_x;         // 0: the sweep that follows reads only c_t and the rows next to the far boundary, so the interior rows of Xnew are not written
     Layout L;
 };
@@ -95,6 +96,7 @@ __global__ void __launch_bounds__(64) k_sweep(SweepArgs a) {
     __shared__ double xs[64];               // boundary state exchange
     __shared__ double vs[64];               // boundary_update scratch
     const int n = blockIdx.x, w = SPLIT ? blockIdx.y : 0, lane = threadIdx.x, c = lane & 15, q = lane >> 4;
+    if (!a.active[n]) return;
     const int T = a.T, D = a.D, K = a.K;
     const bool fwd = (a.dir == 0);
     const int sgn = fwd ? 1 : -1;
@@ -389,12 +391,14 @@ __global__ void __launch_bounds__(64) k_sweep(SweepArgs a) {
 // Xs[t].update() alone, in place in the current buffer (neighbours as they are now).
 struct StepArgs {
     double* X; const double* Y; const double* gains; const double *A_mean, *C_mean, *QA, *RC;
+    const unsigned char* active;
     int N, T, D, K, t;
     Layout L;
 };
 
 __global__ void __launch_bounds__(64) k_step(StepArgs a) {
     const int n = blockIdx.x, lane = threadIdx.x;
+    if (!a.active[n]) return;
     const int T = a.T, D = a.D, K = a.K, t = a.t, DP = a.L.DP;
     const Layout& L = a.L;
     const double* g = a.gains + (size_t)n * L.gains_total;
@@ -447,7 +451,7 @@ int launch_sweep(pyvb_lds* h, int direction, bool keep_x) {
     a.Xold = h->X[h->cur]; a.Xnew = h->X[1 - h->cur]; a.Y = h->Y; a.gains = h->gains; a.warm = h->warm;
     a.trash = h->trash; a.U = h->U; a.Sxx = h->sxx; a.A_mean = h->A_mean; a.C_mean = h->C_mean;
     a.QA = h->dense ? h->QA : nullptr; a.RC = h->dense ? h->RC : nullptr;
-    a.N = h->N; a.T = h->T; a.D = h->D; a.K = h->K; a.dir = direction; a.L = h->L;
+    a.N = h->N; a.T = h->T; a.D = h->D; a.K = h->K; a.dir = direction; a.L = h->L; a.active = h->active;
     {
         TimedLaunch tl(h, direction == PYVB_FORWARD ? PYVB_K_SWEEP_FWD : PYVB_K_SWEEP_BWD);
         switch (h->L.DT * 10 + h->L.KT) {
@@ -491,12 +495,32 @@ int launch_permute(pyvb_lds* h, const double* src, double* dst, int to_internal)
     return PYVB_OK;
 }
 
+// Rows of switched-off replicates sit out the sweeps, which alternate between the two X buffers (and k_prep / adopt_classes
+// between the two sets of covariance classes): before anything reads such rows, or uses the other buffer as staging, they are
+// copied across (api.hip: settle_parked).  per doubles per replicate; rows of active replicates are not touched.
+struct CarryArgs { const double* src; double* dst; const unsigned char* active; size_t per; };
+__global__ void __launch_bounds__(256) k_carry(CarryArgs a) {
+    const int n = blockIdx.y;
+    if (a.active[n]) return;
+    const double* s = a.src + (size_t)n * a.per;
+    double* d = a.dst + (size_t)n * a.per;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < a.per; i += (size_t)gridDim.x * 256) d[i] = s[i];
+}
+
+int launch_carry(pyvb_lds* h, const double* src, double* dst, size_t per) {
+    CarryArgs a; a.src = src; a.dst = dst; a.active = h->active; a.per = per;
+    const size_t blocks = (per + 255) / 256;
+    hipLaunchKernelGGL(k_carry, dim3((unsigned)(blocks < 64 ? blocks : 64), h->N), dim3(256), 0, h->stream, a);
+    HIPCHK(hipGetLastError());
+    return PYVB_OK;
+}
+
 int launch_step(pyvb_lds* h, int t) {
     if (h->big) return launch_step_big(h, t);
     StepArgs a;
     a.X = h->X[h->cur]; a.Y = h->Y; a.gains = h->gains; a.A_mean = h->A_mean; a.C_mean = h->C_mean;
     a.QA = h->dense ? h->QA : nullptr; a.RC = h->dense ? h->RC : nullptr;
-    a.N = h->N; a.T = h->T; a.D = h->D; a.K = h->K; a.t = t; a.L = h->L;
+    a.N = h->N; a.T = h->T; a.D = h->D; a.K = h->K; a.t = t; a.L = h->L; a.active = h->active;
     TimedLaunch tl(h, PYVB_K_STEP);
     hipLaunchKernelGGL(k_step, dim3(h->N), dim3(64), 0, h->stream, a);
     HIPCHK(hipGetLastError());

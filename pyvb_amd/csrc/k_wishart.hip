@@ -48,7 +48,8 @@ struct WArgs {
     const double *mom, *X, *Sigma, *Y, *qld_x, *lnd_x;
     double* elbo;
     Priors pri;
-    int* status;
+    int* status;        // [N] PYVB_FAIL_* flags per replicate
+    const unsigned char* active;    // [N]: workgroups of switched-off replicates leave at once (the layout copies of the setters / getters do not look)
     int N, T, D, K, DP;
     int which0, c0, c1, update;
     int bound;          // k_elbo_dense: PYVB_BOUND_REFERENCE or PYVB_BOUND_EXACT
@@ -61,7 +62,7 @@ static WArgs make_wargs(pyvb_lds* h) {
     a.Q_a = h->Q_a; a.R_a = h->R_a;
     a.A_mean = h->A_mean; a.A_var = h->A_var; a.C_mean = h->C_mean; a.C_var = h->C_var; a.qld_A = h->qld_A; a.qld_C = h->qld_C;
     a.mom = h->mom; a.X = h->X[h->cur]; a.Sigma = h->Sigma; a.Y = h->Y; a.qld_x = h->qld_x; a.elbo = h->elbo;
-    a.pri = h->pri; a.status = h->status;
+    a.pri = h->pri; a.status = h->status; a.active = h->active;
     a.N = h->N; a.T = h->T; a.D = h->D; a.K = h->K; a.DP = h->L.DP;
     a.which0 = 0; a.c0 = 0; a.c1 = h->D; a.update = 0; a.SG = nullptr; a.ldm = h->ldm;
     a.YcovS = h->has_missing ? h->YcovS : nullptr; a.Yent = h->has_missing ? h->Yent : nullptr;
@@ -74,6 +75,7 @@ static WArgs make_wargs(pyvb_lds* h) {
 __global__ void __launch_bounds__(256) k_wexpect(WArgs a) {
     __shared__ double gjbuf[2 * 2 * GJ_BUF + 128];
     const int n = blockIdx.x, tid = threadIdx.x, D = a.D, K = a.K;
+    if (!a.active[n]) return;
     const double* Qw = a.Q_w + (size_t)n * D * D;
     const double* Rw = a.R_w + (size_t)n * K * K;
     const int ta = tid >> 4, tb = tid & 15;
@@ -97,7 +99,7 @@ __global__ void __launch_bounds__(256) k_wexpect(WArgs a) {
             double lp = 0.0;
             if (tid < dim) {
                 const double piv = gjbuf[2 * 2 * GJ_BUF + c * 64 + tid];
-                if (!(piv > 0.0)) atomicOr(a.status, 1);
+                if (!(piv > 0.0)) atomicOr(a.status + n, PYVB_FAIL_NOISE);
                 lp = log(piv);
             }
             lp = wave_sum(lp);
@@ -123,6 +125,7 @@ __global__ void __launch_bounds__(256) k_wexpect(WArgs a) {
 __global__ void __launch_bounds__(256) k_dense_pre(WArgs a) {
     __shared__ double Lb[64 * WLD], Mb[64 * WLD];
     const int WHICH = blockIdx.y, n = blockIdx.x, tid = threadIdx.x, D = a.D;
+    if (!a.active[n]) return;
     const int rows = WHICH == 0 ? a.D : a.K;
     const double* Lbar = (WHICH == 0 ? a.Qbar : a.Rbar) + (size_t)n * rows * rows;
     const double* M = (WHICH == 0 ? a.A_mean : a.C_mean) + (size_t)n * rows * D;
@@ -187,6 +190,7 @@ __global__ void __launch_bounds__(64 * CW_WAVES) k_cols_wishart(WArgs a) {
     __shared__ int turn, turn2;                 // chain steps done / sums done: the column (counted from c0) whose turn it is
     __shared__ double pre[CW_WAVES][4][64];     // per wavefront: G[i,:], H[:,i], prior_prec_i prior_mean_i, known values (NaN: unknown) of its column, fetched ahead of the chain
     const int WHICH = a.which0 + blockIdx.y, n = blockIdx.x, tid = threadIdx.x, D = a.D, K = a.K;
+    if (!a.active[n]) return;
     const int wv = tid >> 6, lane = tid & 63;
     const int rows = WHICH == 0 ? D : K;
     const double* Lbar = (WHICH == 0 ? a.Qbar : a.Rbar) + (size_t)n * rows * rows;
@@ -245,7 +249,7 @@ __global__ void __launch_bounds__(64 * CW_WAVES) k_cols_wishart(WArgs a) {
             double lp = 0.0;
             if (lane < rows) {
                 const double piv = pivs[lane];
-                if (!(piv > 0.0)) atomicOr(a.status, 1);
+                if (!(piv > 0.0)) atomicOr(a.status + n, PYVB_FAIL_COLUMNS);
                 lp = log(piv);
             }
             lp = wave_sum(lp);
@@ -364,6 +368,7 @@ __global__ void __launch_bounds__(256) k_wresid(WArgs a) {
     // (stride WLD: an A operand's 16 rows of a k-step then fall into different banks).
     __shared__ double Mb[64 * WLD], T1[64 * WLD], Hb[64 * WLD], Gb[64 * WLD];
     const int WHICH = a.which0 + blockIdx.y, n = blockIdx.x, tid = threadIdx.x, D = a.D, K = a.K, T = a.T, DP = a.DP;
+    if (!a.active[n]) return;
     const int w = tid >> 6, lane = tid & 63, r = lane & 15, q = lane >> 4;
     const int rows = WHICH == 0 ? D : K;
     const double* M = (WHICH == 0 ? a.A_mean : a.C_mean) + (size_t)n * rows * D;
@@ -443,6 +448,7 @@ __global__ void __launch_bounds__(256) k_wresid(WArgs a) {
 __global__ void __launch_bounds__(256) k_syy_full(WArgs a) {
     __shared__ double Yb[64 * WLD];
     const int n = blockIdx.x, tid = threadIdx.x, K = a.K, T = a.T;
+    if (!a.active[n]) return;
     const double* Y = a.Y + (size_t)n * T * K;
     double acc[16];
 #pragma unroll
@@ -508,6 +514,7 @@ __global__ void __launch_bounds__(256) k_cov_convert(CovConvArgs c) {
 // (k_observe, k_params.hip, has set the means and the diagonal)
 __global__ void __launch_bounds__(256) k_cov_observe(WArgs a) {
     const int WHICH = blockIdx.z, n = blockIdx.x, i = blockIdx.y, D = a.D;
+    if (!a.active[n]) return;
     const int rows = WHICH == 0 ? a.D : a.K;
     const double* obs = WHICH == 0 ? a.pri.A_obs : a.pri.C_obs;
     for (int k = 0; k < rows; ++k) { const double ob = obs[(size_t)k * D + i]; if (!(ob == ob)) return; }      // block-uniform
@@ -544,6 +551,7 @@ __device__ __forceinline__ double lgamma_multi(double x, int D) {    // ln |Gamm
 // ---- lower bound with Wishart noise: the six class sums as k_elbo (k_params.hip), traces against dense expectations
 __global__ void __launch_bounds__(64) k_elbo_dense(WArgs a) {
     const int n = blockIdx.x, lane = threadIdx.x, D = a.D, K = a.K, T = a.T;
+    if (!a.active[n]) return;
     const double* S0 = a.Sigma + (size_t)n * 3 * D * D;
     const double* x0 = a.X + (size_t)n * T * a.DP;
     const bool exact = a.bound == PYVB_BOUND_EXACT;

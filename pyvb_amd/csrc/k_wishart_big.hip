@@ -26,6 +26,7 @@ struct WBArgs {
     const double *mom, *X, *Sigma, *Y;
     Priors pri;
     int* status;
+    const unsigned char* active;
     int N, T, D, K, DP;
     int which0, c0, c1, update, use_sg;
 };
@@ -39,7 +40,7 @@ static WBArgs make_wbargs(pyvb_lds* h) {
     a.A_mean = h->A_mean; a.A_var = h->A_var; a.C_mean = h->C_mean; a.C_var = h->C_var; a.qld_A = h->qld_A; a.qld_C = h->qld_C;
     a.lnd_A = h->lnd_A; a.lnd_C = h->lnd_C;
     a.mom = h->mom; a.X = h->X[h->cur]; a.Sigma = h->Sigma; a.Y = h->Y;
-    a.pri = h->pri; a.status = h->status;
+    a.pri = h->pri; a.status = h->status; a.active = h->active;
     a.N = h->N; a.T = h->T; a.D = h->D; a.K = h->K; a.DP = h->L.DP;
     a.which0 = 0; a.c0 = 0; a.c1 = h->D; a.update = 0; a.use_sg = 0;
     return a;
@@ -57,6 +58,7 @@ __device__ __forceinline__ size_t covb_pos(int rows, int k, int l) {
 __global__ void __launch_bounds__(256) k_wexpect_big(WBArgs a) {
     __shared__ double rc[2 * GJB_BUF], pivs[128];
     const int n = blockIdx.x, tid = threadIdx.x, ta = tid >> 4, tb = tid & 15;
+    if (!a.active[n]) return;
     for (int c = 0; c < 2; ++c) {
         const int dim = c == 0 ? a.D : a.K;
         const double* W = (c == 0 ? a.Q_w : a.R_w) + (size_t)n * dim * dim;
@@ -76,7 +78,7 @@ __global__ void __launch_bounds__(256) k_wexpect_big(WBArgs a) {
             double lp = 0.0;
             for (int k = tid; k < dim; k += 64) {
                 const double piv = pivs[k];
-                if (!(piv > 0.0)) atomicOr(a.status, 1);
+                if (!(piv > 0.0)) atomicOr(a.status + n, PYVB_FAIL_NOISE);
                 lp += log(piv);
             }
             lp = wave_sum(lp);
@@ -99,6 +101,7 @@ __global__ void __launch_bounds__(256) k_wexpect_big(WBArgs a) {
 // ---- QA = E[Q]<A>, RC = E[R]<C>, trA[i] = tr(S_i E[Q]), trC[i] = tr(S'_i E[R])
 __global__ void __launch_bounds__(256) k_dense_pre_big(WBArgs a) {
     const int WHICH = blockIdx.y, n = blockIdx.x, tid = threadIdx.x, D = a.D;
+    if (!a.active[n]) return;
     const int rows = WHICH == 0 ? a.D : a.K;
     const double* Lbar = (WHICH == 0 ? a.Qbar : a.Rbar) + (size_t)n * rows * rows;
     const double* M = (WHICH == 0 ? a.A_mean : a.C_mean) + (size_t)n * rows * D;
@@ -135,6 +138,7 @@ __global__ void __launch_bounds__(256) k_dense_pre_big(WBArgs a) {
 __global__ void __launch_bounds__(256) k_cols_wishart_big(WBArgs a) {
     __shared__ double rc[2 * GJB_BUF], pivs[128], rv[128], wv[128];
     const int WHICH = a.which0 + blockIdx.y, n = blockIdx.x, tid = threadIdx.x, D = a.D, K = a.K;
+    if (!a.active[n]) return;
     const int ta = tid >> 4, tb = tid & 15;
     const int rows = WHICH == 0 ? D : K;
     const double* Lbar = (WHICH == 0 ? a.Qbar : a.Rbar) + (size_t)n * rows * rows;
@@ -172,7 +176,7 @@ __global__ void __launch_bounds__(256) k_cols_wishart_big(WBArgs a) {
             double lp = 0.0;
             for (int k = tid; k < rows; k += 64) {
                 const double piv = pivs[k];
-                if (!(piv > 0.0)) atomicOr(a.status, 1);
+                if (!(piv > 0.0)) atomicOr(a.status + n, PYVB_FAIL_COLUMNS);
                 lp += log(piv);
             }
             lp = wave_sum(lp);
@@ -240,6 +244,7 @@ __global__ void __launch_bounds__(256) k_cols_wishart_big(WBArgs a) {
 // ---- Wishart.update for Q (which 0) or R (1): Rm = 1/2 (own + <M> G <M>^T + sum_i S_i G[i,i]) - H <M>^T, qw = w0 + Rm
 __global__ void __launch_bounds__(256) k_wresid_big(WBArgs a) {
     const int WHICH = a.which0 + blockIdx.y, n = blockIdx.x, tid = threadIdx.x, D = a.D, K = a.K, T = a.T, DP = a.DP;
+    if (!a.active[n]) return;
     const int rows = WHICH == 0 ? D : K;
     const double* M = (WHICH == 0 ? a.A_mean : a.C_mean) + (size_t)n * rows * D;
     const double* cov = (WHICH == 0 ? a.A_cov : a.C_cov) + (size_t)n * D * cov_stride(rows);
@@ -285,6 +290,7 @@ __global__ void __launch_bounds__(256) k_wresid_big(WBArgs a) {
 // ---- sum_t y_t y_t^T, once per set_observations
 __global__ void __launch_bounds__(256) k_syy_full_big(WBArgs a) {
     const int n = blockIdx.x, tid = threadIdx.x, K = a.K, T = a.T;
+    if (!a.active[n]) return;
     const double* Y = a.Y + (size_t)n * T * K;
     for (int idx = tid; idx < K * K; idx += 256) {
         const int k = idx / K, l = idx % K;

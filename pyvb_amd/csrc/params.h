@@ -22,6 +22,7 @@ struct ParamArgs {
     int N, T, D, K, noise;
     int c0, c1;             // k_cols: columns [c0, c1) are updated
     int fuse;               // k_cols: bit 0 = residuals of the noise node too, bit 1 = and its update
+    const unsigned char* active;    // [N]: workgroups of switched-off replicates leave at once
     int which0;             // blockIdx.y + which0 selects the matrix / noise node (0: A, Q; 1: C, R)
     Layout L;
 };

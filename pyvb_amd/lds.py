@@ -57,33 +57,33 @@ class LDSBatch(object):
             _f64(pri["C_prior_mean"], (K, D), "C_prior_mean"), _f64(pri["C_prior_prec"], (D, K), "C_prior_prec"),
         ]
         if self.noise == "wishart":     # Wishart(dim, v0, w0): Q_a0 / R_a0 hold v0, Q_b0 / R_b0 the matrices w0
-            C.check(C.lib.pyvb_lds_set_priors(self._h, *([C.dptr(a) for a in arrs] + [None] * 4)))
+            self._check(C.lib.pyvb_lds_set_priors(self._h, *([C.dptr(a) for a in arrs] + [None] * 4)))
             qw0, rw0 = _f64(pri["Q_b0"], (D, D), "Q_w0"), _f64(pri["R_b0"], (K, K), "R_w0")
-            C.check(C.lib.pyvb_lds_set_wishart_priors(self._h, float(pri["Q_a0"]), C.dptr(qw0), float(pri["R_a0"]), C.dptr(rw0)))
+            self._check(C.lib.pyvb_lds_set_wishart_priors(self._h, float(pri["Q_a0"]), C.dptr(qw0), float(pri["R_a0"]), C.dptr(rw0)))
             return
         arrs += [bc(pri["Q_a0"], D), bc(pri["Q_b0"], D), bc(pri["R_a0"], K), bc(pri["R_b0"], K)]
-        C.check(C.lib.pyvb_lds_set_priors(self._h, *[C.dptr(a) for a in arrs]))
+        self._check(C.lib.pyvb_lds_set_priors(self._h, *[C.dptr(a) for a in arrs]))
 
     def set_observations(self, Y):
         """Y[N,T,K]; NaN = missing entry (the rows concerned become variational nodes: set_output_state, update_Y)."""
         Y = _f64(Y, (self.N, self.T, self.K), "Y")
-        C.check(C.lib.pyvb_lds_set_observations(self._h, C.dptr(Y)))
+        self._check(C.lib.pyvb_lds_set_observations(self._h, C.dptr(Y)))
 
     def set_output_state(self, Yq, Yrowvar):
         """Initial posterior of the outputs that are not fully observed: means [N,T,K], isotropic variances [N,T]."""
         q, v = _f64(Yq, (self.N, self.T, self.K), "Yq"), _f64(Yrowvar, (self.N, self.T), "Yrowvar")
-        C.check(C.lib.pyvb_lds_set_output_state(self._h, C.dptr(q), C.dptr(v)))
+        self._check(C.lib.pyvb_lds_set_output_state(self._h, C.dptr(q), C.dptr(v)))
 
     def update_Y(self):
         """[y.update() for y in Ys if not y.observed]"""
-        C.check(C.lib.pyvb_lds_update_Y(self._h))
+        self._check(C.lib.pyvb_lds_update_Y(self._h))
 
     def get_outputs(self, with_qld=False):
         """(posterior means [N,T,K], variances [N,T,K]) of the outputs; fully observed rows: (value, 0).
         with_qld: also q_ln_det [N,T] of the rows updated so far (NaN otherwise)."""
         q, v = np.empty((self.N, self.T, self.K)), np.empty((self.N, self.T, self.K))
         ld = np.empty((self.N, self.T)) if with_qld else None
-        C.check(C.lib.pyvb_lds_get_outputs(self._h, C.dptr(q), C.dptr(v), C.dptr(ld)))
+        self._check(C.lib.pyvb_lds_get_outputs(self._h, C.dptr(q), C.dptr(v), C.dptr(ld)))
         return (q, v, ld) if with_qld else (q, v)
 
     def set_state(self, X=None, A_mean=None, A_colvar=None, C_mean=None, C_colvar=None, Q_b=None, R_b=None):
@@ -91,29 +91,29 @@ class LDSBatch(object):
         shapes = [("X", X, (N, T, D)), ("A_mean", A_mean, (N, D, D)), ("A_colvar", A_colvar, (N, D, D)),
                   ("C_mean", C_mean, (N, K, D)), ("C_colvar", C_colvar, (N, D, K)), ("Q_b", Q_b, (N, D)), ("R_b", R_b, (N, K))]
         arrs = [None if a is None else _f64(a, s, nm) for nm, a, s in shapes]
-        C.check(C.lib.pyvb_lds_set_state(self._h, *[C.dptr(a) for a in arrs]))
+        self._check(C.lib.pyvb_lds_set_state(self._h, *[C.dptr(a) for a in arrs]))
 
     def set_wishart_state(self, Q_w=None, R_w=None):
         """Posterior qw of the Wishart nodes, [N,D,D] and [N,K,K] (nodes_todo.py:216-217 draws a random rank-one one)."""
         q = None if Q_w is None else _f64(Q_w, (self.N, self.D, self.D), "Q_w")
         r = None if R_w is None else _f64(R_w, (self.N, self.K, self.K), "R_w")
-        C.check(C.lib.pyvb_lds_set_wishart_state(self._h, C.dptr(q), C.dptr(r)))
+        self._check(C.lib.pyvb_lds_set_wishart_state(self._h, C.dptr(q), C.dptr(r)))
 
     def get_wishart_state(self):
         N, D, K = self.N, self.D, self.K
         out = {"Q_v": np.empty(N), "Q_w": np.empty((N, D, D)), "R_v": np.empty(N), "R_w": np.empty((N, K, K))}
-        C.check(C.lib.pyvb_lds_get_wishart_state(self._h, C.dptr(out["Q_v"]), C.dptr(out["Q_w"]), C.dptr(out["R_v"]), C.dptr(out["R_w"])))
+        self._check(C.lib.pyvb_lds_get_wishart_state(self._h, C.dptr(out["Q_v"]), C.dptr(out["Q_w"]), C.dptr(out["R_v"]), C.dptr(out["R_w"])))
         return out
 
     def set_column_cov(self, A_cov=None, C_cov=None):
         a = None if A_cov is None else _f64(A_cov, (self.N, self.D, self.D, self.D), "A_cov")
         c = None if C_cov is None else _f64(C_cov, (self.N, self.D, self.K, self.K), "C_cov")
-        C.check(C.lib.pyvb_lds_set_column_cov(self._h, C.dptr(a), C.dptr(c)))
+        self._check(C.lib.pyvb_lds_set_column_cov(self._h, C.dptr(a), C.dptr(c)))
 
     def get_column_cov(self):
         """Dense posterior covariances of the columns of A ([N,D,D,D]) and C ([N,D,K,K]); Wishart noise only."""
         A, Cc = np.empty((self.N, self.D, self.D, self.D)), np.empty((self.N, self.D, self.K, self.K))
-        C.check(C.lib.pyvb_lds_get_column_cov(self._h, C.dptr(A), C.dptr(Cc)))
+        self._check(C.lib.pyvb_lds_get_column_cov(self._h, C.dptr(A), C.dptr(Cc)))
         return A, Cc
 
     def set_column_observations(self, A_obs=None, C_obs=None):
@@ -121,7 +121,7 @@ class LDSBatch(object):
         (As[i].observe(...), examples/LDS_knowns_in_A.py:73-74).  Call after set_state."""
         a = None if A_obs is None else _f64(A_obs, (self.D, self.D), "A_obs")
         c = None if C_obs is None else _f64(C_obs, (self.K, self.D), "C_obs")
-        C.check(C.lib.pyvb_lds_set_column_observations(self._h, C.dptr(a), C.dptr(c)))
+        self._check(C.lib.pyvb_lds_set_column_observations(self._h, C.dptr(a), C.dptr(c)))
 
     # -- outputs ----------------------------------------------------------------------------
     def get_state(self, what=("X", "A_mean", "A_colvar", "C_mean", "C_colvar", "Q_a", "Q_b", "R_a", "R_b")):
@@ -130,25 +130,25 @@ class LDSBatch(object):
                   "Q_a": (N, D), "Q_b": (N, D), "R_a": (N, K), "R_b": (N, K)}
         order = ["X", "A_mean", "A_colvar", "C_mean", "C_colvar", "Q_a", "Q_b", "R_a", "R_b"]
         out = {k: np.empty(shapes[k]) for k in order if k in what}
-        C.check(C.lib.pyvb_lds_get_state(self._h, *[C.dptr(out.get(k)) for k in order]))
+        self._check(C.lib.pyvb_lds_get_state(self._h, *[C.dptr(out.get(k)) for k in order]))
         return out
 
     def get_posterior_classes(self):
         """(Sigma[N,3,D,D], q_ln_det[N,3]) of X_0, the interior X_t and X_{T-1} as of their last update."""
         S = np.empty((self.N, 3, self.D, self.D))
         q = np.empty((self.N, 3))
-        C.check(C.lib.pyvb_lds_get_posterior_classes(self._h, C.dptr(S), C.dptr(q)))
+        self._check(C.lib.pyvb_lds_get_posterior_classes(self._h, C.dptr(S), C.dptr(q)))
         return S, q
 
     def set_posterior_classes(self, Sigma, qld_x=None):
         """Initial covariances of X_0, the interior X_t and X_{T-1} ([N,3,D,D]); see include/pyvb_hip.h."""
         S = _f64(Sigma, (self.N, 3, self.D, self.D), "Sigma")
         q = None if qld_x is None else _f64(qld_x, (self.N, 3), "qld_x")
-        C.check(C.lib.pyvb_lds_set_posterior_classes(self._h, C.dptr(S), C.dptr(q)))
+        self._check(C.lib.pyvb_lds_set_posterior_classes(self._h, C.dptr(S), C.dptr(q)))
 
     def get_column_qld(self):
         qa, qc = np.empty((self.N, self.D)), np.empty((self.N, self.D))
-        C.check(C.lib.pyvb_lds_get_column_qld(self._h, C.dptr(qa), C.dptr(qc)))
+        self._check(C.lib.pyvb_lds_get_column_qld(self._h, C.dptr(qa), C.dptr(qc)))
         return qa, qc
 
     def get_logdets(self):
@@ -156,7 +156,7 @@ class LDSBatch(object):
         the outputs with missing entries [N,T] (NaN where the q_ln_det getters give NaN).  Stored in both bound modes."""
         lx, la, lc = np.empty((self.N, 3)), np.empty((self.N, self.D)), np.empty((self.N, self.D))
         ly = np.empty((self.N, self.T))
-        C.check(C.lib.pyvb_lds_get_logdets(self._h, C.dptr(lx), C.dptr(la), C.dptr(lc), C.dptr(ly)))
+        self._check(C.lib.pyvb_lds_get_logdets(self._h, C.dptr(lx), C.dptr(la), C.dptr(lc), C.dptr(ly)))
         return {"X": lx, "A": la, "C": lc, "Y": ly}
 
     def set_bound_mode(self, mode):
@@ -164,81 +164,119 @@ class LDSBatch(object):
         default) or "exact" (E_q[ln p] - E_q[ln q]).  The updates do not depend on it.  Changing it empties the history."""
         if mode not in C.BOUND_MODES:
             raise ValueError("bound mode must be 'reference' or 'exact', not %r" % (mode,))
-        C.check(C.lib.pyvb_lds_set_bound_mode(self._h, C.BOUND_MODES[mode]))
+        self._check(C.lib.pyvb_lds_set_bound_mode(self._h, C.BOUND_MODES[mode]))
         self.bound = mode
 
     def get_warmup(self):
         w = np.empty((self.N, 2), dtype=np.int32)
-        C.check(C.lib.pyvb_lds_get_warmup(self._h, w.ctypes.data_as(C._ip)))
+        self._check(C.lib.pyvb_lds_get_warmup(self._h, w.ctypes.data_as(C._ip)))
         return w
 
     def get_time_split(self):
         w = C.ctypes.c_int()
-        C.check(C.lib.pyvb_lds_get_time_split(self._h, C.ctypes.byref(w)))
+        self._check(C.lib.pyvb_lds_get_time_split(self._h, C.ctypes.byref(w)))
         return w.value
 
     def set_time_split(self, W):
         """Wavefronts per replicate in the sweeps (chosen by the library; tests force W = 1, the headline code path)."""
-        C.check(C.lib.pyvb_lds_set_time_split(self._h, int(W)))
+        self._check(C.lib.pyvb_lds_set_time_split(self._h, int(W)))
 
     # -- updates ----------------------------------------------------------------------------
     def sweep(self, direction="forward"):
-        C.check(C.lib.pyvb_lds_sweep(self._h, C.FORWARD if direction == "forward" else C.BACKWARD))
+        self._check(C.lib.pyvb_lds_sweep(self._h, C.FORWARD if direction == "forward" else C.BACKWARD))
 
     def update_x(self, t):
-        C.check(C.lib.pyvb_lds_update_x(self._h, int(t)))
+        self._check(C.lib.pyvb_lds_update_x(self._h, int(t)))
 
     def update_A(self):
-        C.check(C.lib.pyvb_lds_update_A(self._h))
+        self._check(C.lib.pyvb_lds_update_A(self._h))
 
     def update_C(self):
-        C.check(C.lib.pyvb_lds_update_C(self._h))
+        self._check(C.lib.pyvb_lds_update_C(self._h))
 
     def update_columns(self, which, col_begin, col_end):
         """As[i].update() (which = "A") or Cs[i].update() ("C") for i in [col_begin, col_end), in order."""
-        C.check(C.lib.pyvb_lds_update_columns(self._h, 0 if which == "A" else 1, int(col_begin), int(col_end)))
+        self._check(C.lib.pyvb_lds_update_columns(self._h, 0 if which == "A" else 1, int(col_begin), int(col_end)))
 
     def update_Q(self):
-        C.check(C.lib.pyvb_lds_update_Q(self._h))
+        self._check(C.lib.pyvb_lds_update_Q(self._h))
 
     def update_R(self):
-        C.check(C.lib.pyvb_lds_update_R(self._h))
+        self._check(C.lib.pyvb_lds_update_R(self._h))
 
     def elbo(self):
         """Per-replicate lower-bound parts [N,6] (X, Y, A, C, Q, R) of the current bound mode (set_bound_mode)."""
-        C.check(C.lib.pyvb_lds_elbo(self._h))
+        self._check(C.lib.pyvb_lds_elbo(self._h))
         out = np.empty((self.N, 6))
-        C.check(C.lib.pyvb_lds_get_elbo(self._h, C.dptr(out)))
+        self._check(C.lib.pyvb_lds_get_elbo(self._h, C.dptr(out)))
         return out
 
     def elbo_total(self):
         """Parts summed over replicates (and over ranks when a communicator is attached)."""
         out = np.empty(6)
-        C.check(C.lib.pyvb_lds_elbo_total(self._h, C.dptr(out)))
+        self._check(C.lib.pyvb_lds_elbo_total(self._h, C.dptr(out)))
         return out
 
     def iterate(self, niters=1):
         """niters x (forward sweep, backward sweep, A, C, Q, R, lower bound); asynchronous."""
-        C.check(C.lib.pyvb_lds_iterate(self._h, int(niters)))
+        self._check(C.lib.pyvb_lds_iterate(self._h, int(niters)))
 
     def elbo_history(self, last=4096):
         """Lower-bound parts of the most recent iterate() iterations, [count, 6], summed over the replicates (and over
         the ranks when a communicator is attached); oldest first."""
         out = np.empty((int(last), 6))
         cnt = C.ctypes.c_int()
-        C.check(C.lib.pyvb_lds_get_elbo_history(self._h, C.dptr(out), int(last), C.ctypes.byref(cnt)))
+        self._check(C.lib.pyvb_lds_get_elbo_history(self._h, C.dptr(out), int(last), C.ctypes.byref(cnt)))
         return out[:cnt.value].copy()
 
     def reset_elbo_history(self):
-        C.check(C.lib.pyvb_lds_reset_elbo_history(self._h))
+        self._check(C.lib.pyvb_lds_reset_elbo_history(self._h))
 
     def sync(self):
-        C.check(C.lib.pyvb_lds_sync(self._h))
+        self._check(C.lib.pyvb_lds_sync(self._h))
+
+    # -- per-replicate bookkeeping ----------------------------------------------------------
+    FAIL_BITS = ((C.FAIL_STATES, "X_t"), (C.FAIL_COLUMNS, "columns of A / C"), (C.FAIL_NOISE, "Wishart Q / R"))
+
+    def _check(self, rc):
+        """C.check; a LinAlgError carries .replicates, the indices of the active replicates that failed."""
+        try:
+            C.check(rc)
+        except np.linalg.LinAlgError as e:
+            st = self.status()
+            e.replicates = [int(n) for n in np.nonzero((st != 0) & self.active())[0]]
+            e.status = st
+            raise
+
+    def status(self):
+        """int [N]: C.FAIL_* bits per replicate -- which node family's posterior precision was not positive definite --
+        pending on the device or reported by the most recent failed sync.  Never raises because of a flag."""
+        st = np.zeros(self.N, dtype=np.int32)
+        C.check(C.lib.pyvb_lds_get_status(self._h, st.ctypes.data_as(C._ip)))
+        return st
+
+    @classmethod
+    def describe_status(cls, bits):
+        """The node families named by the FAIL_* bits of one replicate."""
+        return ", ".join(nm for b, nm in cls.FAIL_BITS if int(bits) & b) or "none"
+
+    def set_active(self, mask):
+        """bool [N]: replicates with False are switched off -- no update touches them, their state reads back as it was, the
+        totals leave them out, their flags no longer raise.  The mask can only shrink (switching one on again: error)."""
+        m = np.ascontiguousarray(np.asarray(mask).astype(bool), dtype=np.uint8)
+        if m.shape != (self.N,):
+            raise AssertionError("mask has shape %s, expected (%d,)" % (m.shape, self.N))
+        C.check(C.lib.pyvb_lds_set_active(self._h, m.ctypes.data_as(C._ucp)))
+
+    def active(self):
+        m = np.zeros(self.N, dtype=np.uint8)
+        C.check(C.lib.pyvb_lds_get_active(self._h, m.ctypes.data_as(C._ucp)))
+        return m.astype(bool)
 
     # -- measurement ------------------------------------------------------------------------
     def timing(self, on=True):
-        C.check(C.lib.pyvb_lds_timing_enable(self._h, 1 if on else 0))
-        C.check(C.lib.pyvb_lds_timing_reset(self._h))
+        self._check(C.lib.pyvb_lds_timing_enable(self._h, 1 if on else 0))
+        self._check(C.lib.pyvb_lds_timing_reset(self._h))
 
     def kernel_times(self):
         names = {"prep": C.K_PREP, "sweep_fwd": C.K_SWEEP_FWD, "sweep_bwd": C.K_SWEEP_BWD, "stats": C.K_STATS,
@@ -246,7 +284,7 @@ class LDSBatch(object):
         out = {}
         for nm, k in names.items():
             ms, cnt = C.ctypes.c_double(), C.ctypes.c_int()
-            C.check(C.lib.pyvb_lds_timing_get(self._h, k, C.ctypes.byref(ms), C.ctypes.byref(cnt)))
+            self._check(C.lib.pyvb_lds_timing_get(self._h, k, C.ctypes.byref(ms), C.ctypes.byref(cnt)))
             out[nm] = (ms.value, cnt.value)
         return out
 
@@ -258,14 +296,14 @@ class LDSBatch(object):
         return buf.raw
 
     def comm_init(self, uid, rank, world):
-        C.check(C.lib.pyvb_lds_comm_init(self._h, uid, int(rank), int(world)))
+        self._check(C.lib.pyvb_lds_comm_init(self._h, uid, int(rank), int(world)))
 
     def comm_init_host(self, comm, rank, world):
         """The ELBO all-reduce through a host process group (pyvb_amd.dist) instead of RCCL: rehearsal of the sharded
         path with several ranks on one GPU (pyvb_lds_comm_init_host)."""
         from .dist import host_allreduce_callback
         self._host_cb = host_allreduce_callback(comm)          # kept alive with the handle
-        C.check(C.lib.pyvb_lds_comm_init_host(self._h, self._host_cb, None, int(rank), int(world)))
+        self._check(C.lib.pyvb_lds_comm_init_host(self._h, self._host_cb, None, int(rank), int(world)))
 
     # -- convenience ------------------------------------------------------------------------
     @classmethod

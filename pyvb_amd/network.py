@@ -104,9 +104,10 @@ class _Schedule(object):
         if self.handles is not None:
             rest = []
             for grp, ks, rows, sc, epoch, whole, members, where in self.handles:
-                if whole and grp.epoch == epoch:
-                    vals[where] = grp.elbo(bound)[rows].sum(1)  # one launch and one copy for all graphs of the handle
-                else:
+                parts = grp.elbo(bound) if whole and grp.epoch == epoch else None   # one launch and one copy for all graphs of the handle
+                if parts is not None and grp.epoch == epoch:
+                    vals[where] = parts[rows].sum(1)
+                else:                   # (a graph whose row failed has just been evicted: its own plan raises, the others answer)
                     rest += ks
         for k in rest:
             p, nodes, whole = g[k]
