@@ -48,8 +48,6 @@ void pyvb_timing_resolve(pyvb_lds* h) {
     h->pool_used = 0;
 }
 
-#define ARGCHK(cond, msg) do { if (!(cond)) { pyvb_set_error("%s", msg); return PYVB_E_ARG; } } while (0)
-
 extern "C" {
 
 const char* pyvb_last_error(void) { return g_err; }
@@ -58,12 +56,6 @@ int pyvb_version(void) { return 100; }
 int pyvb_device_count(int* count) {
     ARGCHK(count, "count is NULL");
     HIPCHK(hipGetDeviceCount(count));
-    return PYVB_OK;
-}
-
-static int dev_alloc(double** p, size_t n) {
-    HIPCHK(hipMalloc((void**)p, n * sizeof(double)));
-    HIPCHK(hipMemset(*p, 0, n * sizeof(double)));
     return PYVB_OK;
 }
 
@@ -78,16 +70,17 @@ int pyvb_lds_create(pyvb_lds** out, int device, int N, int T, int D, int K, int 
     HIPCHK(hipGetDeviceCount(&ndev));
     ARGCHK(device >= 0 && device < ndev, "no such device");
     HIPCHK(hipSetDevice(device));
-    pyvb_lds* h = new pyvb_lds();
-    memset(h, 0, sizeof(*h));
+    pyvb_lds* h = new pyvb_lds();       // value-initialised: every pointer null, every flag false
     h->device = device; h->N = N; h->T = T; h->D = D; h->K = K; h->noise = noise_kind;
     h->L = make_layout(D, K);
     h->big = D > 64 || K > 64;           // the workgroup-per-replicate kernels of k_big.hip
     h->dense = noise_kind == PYVB_NOISE_WISHART;
     const Layout& L = h->L;
     int rc = PYVB_OK;
-#define TRY(x) do { rc = (x); if (rc != PYVB_OK) { pyvb_lds_destroy(h); return rc; } } while (0)
-#define TRYHIP(x) do { hipError_t _e = (x); if (_e != hipSuccess) { rc = pyvb_hip_fail(_e, #x, __FILE__, __LINE__); pyvb_lds_destroy(h); return rc; } } while (0)
+#define TRY(x) CREATE_TRY(x, pyvb_lds_destroy, h)
+#define TRYHIP(x) CREATE_TRYHIP(x, pyvb_lds_destroy, h)
+#define dev_alloc(p, n) h->mem.zeros(p, n)
+    if (h->big) TRY(big_prepare_kernels());
     TRYHIP(hipStreamCreate(&h->stream));
     TRYHIP(hipStreamCreate(&h->side));
     TRYHIP(hipEventCreateWithFlags(&h->ev_params, hipEventDisableTiming));
@@ -114,8 +107,7 @@ int pyvb_lds_create(pyvb_lds** out, int device, int N, int T, int D, int K, int 
     TRY(dev_alloc(&h->scratch, h->big ? n * 2 * L.DP * L.DP : n * 2 * D * D));
     TRY(dev_alloc(&h->zeros, 128));
     TRY(dev_alloc(&h->U, n * T * L.DP));                        // the c_t cache between a forward sweep and the backward one behind it
-    TRYHIP(hipMalloc((void**)&h->warm, n * 2 * sizeof(int)));
-    TRYHIP(hipMemset(h->warm, 0, n * 2 * sizeof(int)));
+    TRY(h->mem.alloc((void**)&h->warm, n * 2 * sizeof(int)));
     // time chunks of the statistics kernel: enough wavefronts to fill the chip when N is small
     int nchunk = (1024 + N - 1) / N;
     if (nchunk > 32) nchunk = 32;
@@ -147,10 +139,8 @@ int pyvb_lds_create(pyvb_lds** out, int device, int N, int T, int D, int K, int 
     TRY(dev_alloc(&h->resQ, n * D)); TRY(dev_alloc(&h->resR, n * K));
     TRY(dev_alloc(&h->elbo, n * 6)); TRY(dev_alloc(&h->elbo_sum, 8));
     TRY(dev_alloc(&h->elbo_hist, (size_t)PYVB_ELBO_HISTORY * 8));
-    TRYHIP(hipMalloc((void**)&h->status, n * sizeof(int)));
-    TRYHIP(hipMemset(h->status, 0, n * sizeof(int)));
-    TRYHIP(hipMalloc((void**)&h->active, n));
-    TRYHIP(hipMemset(h->active, 1, n));
+    TRY(h->mem.alloc((void**)&h->status, n * sizeof(int)));
+    TRY(h->mem.alloc((void**)&h->active, n, 1));
     h->active_host = (unsigned char*)malloc(n);
     memset(h->active_host, 1, n);
     h->n_active = N;
@@ -181,7 +171,8 @@ int pyvb_lds_create(pyvb_lds** out, int device, int N, int T, int D, int K, int 
         TRY(dev_alloc(&h->ldm, n * 2 * D));
     }
     TRYHIP(hipMemset(h->pri.A_obs, 0xFF, ((size_t)D * D + (size_t)K * D) * sizeof(double)));     // all-ones bytes = NaN = nothing observed
-    h->fresh = (unsigned char*)calloc(T, 1);
+    h->st.T = T;
+    h->st.fresh = (unsigned char*)calloc(T, 1);
     h->world = 1;
     // q_ln_det is undefined until a node has been updated (the reference raises AttributeError)
     {
@@ -193,6 +184,7 @@ int pyvb_lds_create(pyvb_lds** out, int device, int N, int T, int D, int K, int 
         TRYHIP(hipMemcpy(h->lnd_A, nanv.data(), n * D * sizeof(double), hipMemcpyHostToDevice));
         TRYHIP(hipMemcpy(h->lnd_C, nanv.data(), n * D * sizeof(double), hipMemcpyHostToDevice));
     }
+#undef dev_alloc
 #undef TRY
 #undef TRYHIP
     *out = h;
@@ -205,37 +197,25 @@ int pyvb_lds_destroy(pyvb_lds* h) {
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     if (h->side) (void)hipStreamSynchronize(h->side);
     pyvb_lds_comm_destroy(h);
-    if (h->elbo_hist) (void)hipFree(h->elbo_hist);
     if (h->ev_params) (void)hipEventDestroy(h->ev_params);
     if (h->ev_elbo) (void)hipEventDestroy(h->ev_elbo);
     if (h->side) (void)hipStreamDestroy(h->side);
-    double* bufs[] = {h->Y, h->Syy, h->X[0], h->X[1], h->A_mean, h->A_var, h->C_mean, h->C_var, h->Q_a, h->Q_b, h->R_a, h->R_b,
-                      h->qld_A, h->qld_C, h->Sigma, h->Sigma_new, h->qld_x, h->qld_x_new, h->gains, h->scratch, h->stats,
-                      h->resQ, h->resR, h->elbo, h->elbo_sum, h->pri_block, h->trash, h->zeros, h->mom, h->sxx, h->U,
-                      h->Q_w, h->R_w, h->Qbar, h->Rbar, h->lnd, h->QA, h->RC, h->trA, h->trC, h->A_cov, h->C_cov, h->SyyF, h->RQ, h->RR, h->SG, h->ldm,
-                      h->Yobs, h->Yvar, h->Yqld, h->Yent, h->Yld, h->YcovS, h->U2,
-                      h->lnd_A, h->lnd_C, h->lnd_x, h->lnd_x_new, h->Ylnd, h->YentX};
-    for (double* b : bufs) if (b) (void)hipFree(b);
-    if (h->warm) (void)hipFree(h->warm);
-    if (h->status) (void)hipFree(h->status);
-    if (h->active) (void)hipFree(h->active);
+    h->mem.release_all();
     free(h->active_host); free(h->status_host); free(h->reported);
     if (h->pool) {
         for (int i = 0; i < PYVB_EVENT_POOL; ++i) { if (h->pool[i].e0) (void)hipEventDestroy(h->pool[i].e0); if (h->pool[i].e1) (void)hipEventDestroy(h->pool[i].e1); }
         free(h->pool);
     }
     if (h->stream) (void)hipStreamDestroy(h->stream);
-    free(h->fresh);
+    free(h->st.fresh);
     delete h;
     return PYVB_OK;
 }
 
-static void states_changed(pyvb_lds* h);
 static int join_elbo(pyvb_lds* h);
 // Every entry point but pyvb_lds_iterate first lets the main stream wait for a lower-bound evaluation that the last
 // pyvb_lds_iterate may have left in flight on the side stream (it reads states and parameters).
-#define ENTER_RAW(h) do { ARGCHK(h, "handle is NULL"); HIPCHK(hipSetDevice((h)->device)); } while (0)
-#define ENTER(h) do { ENTER_RAW(h); if ((h)->elbo_in_flight) { int _rc = join_elbo(h); if (_rc) return _rc; } } while (0)
+#define ENTER(h) do { ENTER_DEVICE(h); if ((h)->elbo_in_flight) { int _rc = join_elbo(h); if (_rc) return _rc; } } while (0)
 
 // every replicate switched off: the update entries are successful no-ops without a launch
 #define IDLE(h) do { if ((h)->n_active == 0) return PYVB_OK; } while (0)
@@ -247,36 +227,18 @@ static int join_elbo(pyvb_lds* h);
 static int settle_parked(pyvb_lds* h) {
     if (h->n_active == h->N) return PYVB_OK;
     int rc;
-    if (h->x_park != h->cur) {
-        if ((rc = launch_carry(h, h->X[h->x_park], h->X[h->cur], (size_t)h->T * h->L.DP))) return rc;
-        h->x_park = h->cur;
-    }
-    if (h->cls_parked_other) {
+    if (h->st.x_park != h->st.cur && (rc = launch_carry(h, h->X[h->st.x_park], h->X[h->st.cur], (size_t)h->T * h->L.DP))) return rc;
+    if (h->st.cls_parked_other) {
         if ((rc = launch_carry(h, h->Sigma_new, h->Sigma, (size_t)3 * h->D * h->D))) return rc;
         if ((rc = launch_carry(h, h->qld_x_new, h->qld_x, 3))) return rc;
         if ((rc = launch_carry(h, h->lnd_x_new, h->lnd_x, 3))) return rc;
-        h->cls_parked_other = false;
     }
+    h->st.parked_here();
     return PYVB_OK;
 }
 
-static int h2d(pyvb_lds* h, double* dst, const double* src, size_t n) {
-    if (!src) return PYVB_OK;
-    HIPCHK(hipMemcpyAsync(dst, src, n * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    return PYVB_OK;
-}
-static int d2h(pyvb_lds* h, double* dst, const double* src, size_t n) {
-    if (!dst) return PYVB_OK;
-    HIPCHK(hipMemcpyAsync(dst, src, n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    return PYVB_OK;
-}
-
-static void params_changed(pyvb_lds* h) {
-    if (h->gains_valid && h->fresh_count != 0 && h->fresh_count != h->T) h->mixed_cov = true;
-    h->gains_valid = false;
-    h->u_valid = false;
-}
-static void states_changed(pyvb_lds* h) { h->stats_valid = false; h->resQ_valid = false; h->resR_valid = false; h->sg_valid[0] = h->sg_valid[1] = false; }
+static int h2d(pyvb_lds* h, double* dst, const double* src, size_t n) { return to_device(h->stream, dst, src, n); }
+static int d2h(pyvb_lds* h, double* dst, const double* src, size_t n) { return to_host(h->stream, dst, src, n); }
 
 // ln det of a symmetric positive definite matrix (Constant.lndet, node.py:301-302)
 static int host_lndet(const double* Ain, int D, double* out) {
@@ -324,31 +286,25 @@ int pyvb_lds_set_priors(pyvb_lds* h, const double* x0_mean, const double* x0_pre
         HIPCHK(hipMemcpyAsync(h->pri.A_pld, ld.data(), 2 * (size_t)D * sizeof(double), hipMemcpyHostToDevice, h->stream));
         HIPCHK(hipStreamSynchronize(h->stream));
     }
-    if (h->dense) {         // the Wishart priors come through pyvb_lds_set_wishart_priors
-        HIPCHK(hipStreamSynchronize(h->stream));
-        params_changed(h);
-        h->resQ_valid = h->resR_valid = false;
-        return PYVB_OK;
+    if (!h->dense) {        // (the Wishart priors come through pyvb_lds_set_wishart_priors)
+        if ((rc = h2d(h, h->pri.Q_a0, Q_a0, D))) return rc;
+        if ((rc = h2d(h, h->pri.Q_b0, Q_b0, D))) return rc;
+        if ((rc = h2d(h, h->pri.R_a0, R_a0, K))) return rc;
+        if ((rc = h2d(h, h->pri.R_b0, R_b0, K))) return rc;
+        // qa is fixed by the graph: update_a, nodes_todo.py:125-128 (Gamma: +0.5*child.shape[0] per child)
+        // and :183-186 (DiagonalGamma: +0.5 per child); Q has T-1 children X_1.., R has T children Y_t
+        std::vector<double> qa((size_t)N * D), ra((size_t)N * K);
+        for (int n = 0; n < N; ++n) {
+            for (int k = 0; k < D; ++k)
+                qa[(size_t)n * D + k] = (h->noise == PYVB_NOISE_GAMMA) ? Q_a0[0] + 0.5 * D * (T - 1) : Q_a0[k] + 0.5 * (T - 1);
+            for (int k = 0; k < K; ++k)
+                ra[(size_t)n * K + k] = (h->noise == PYVB_NOISE_GAMMA) ? R_a0[0] + 0.5 * K * T : R_a0[k] + 0.5 * T;
+        }
+        if ((rc = h2d(h, h->Q_a, qa.data(), qa.size()))) return rc;
+        if ((rc = h2d(h, h->R_a, ra.data(), ra.size()))) return rc;
+        HIPCHK(hipStreamSynchronize(h->stream));       // qa, ra are about to go out of scope
     }
-    if ((rc = h2d(h, h->pri.Q_a0, Q_a0, D))) return rc;
-    if ((rc = h2d(h, h->pri.Q_b0, Q_b0, D))) return rc;
-    if ((rc = h2d(h, h->pri.R_a0, R_a0, K))) return rc;
-    if ((rc = h2d(h, h->pri.R_b0, R_b0, K))) return rc;
-    // qa is fixed by the graph: update_a, nodes_todo.py:125-128 (Gamma: +0.5*child.shape[0] per child)
-    // and :183-186 (DiagonalGamma: +0.5 per child); Q has T-1 children X_1.., R has T children Y_t
-    std::vector<double> qa((size_t)N * D), ra((size_t)N * K);
-    for (int n = 0; n < N; ++n) {
-        for (int k = 0; k < D; ++k)
-            qa[(size_t)n * D + k] = (h->noise == PYVB_NOISE_GAMMA) ? Q_a0[0] + 0.5 * D * (T - 1) : Q_a0[k] + 0.5 * (T - 1);
-        for (int k = 0; k < K; ++k)
-            ra[(size_t)n * K + k] = (h->noise == PYVB_NOISE_GAMMA) ? R_a0[0] + 0.5 * K * T : R_a0[k] + 0.5 * T;
-    }
-    if ((rc = h2d(h, h->Q_a, qa.data(), qa.size()))) return rc;
-    if ((rc = h2d(h, h->R_a, ra.data(), ra.size()))) return rc;
-    HIPCHK(hipStreamSynchronize(h->stream));
-    params_changed(h);
-    h->resQ_valid = h->resR_valid = false;
-    h->sg_valid[0] = h->sg_valid[1] = false;
+    h->st.parameters_changed();
     return PYVB_OK;
 }
 
@@ -370,9 +326,8 @@ int pyvb_lds_set_wishart_priors(pyvb_lds* h, double Q_v0, const double* Q_w0, do
     if ((rc = h2d(h, h->Q_a, qa.data(), qa.size()))) return rc;
     if ((rc = h2d(h, h->R_a, ra.data(), ra.size()))) return rc;
     HIPCHK(hipStreamSynchronize(h->stream));
-    h->expect_valid = false;
-    params_changed(h);
-    h->resQ_valid = h->resR_valid = false;
+    h->st.noise_changed();
+    h->st.parameters_changed();
     return PYVB_OK;
 }
 
@@ -383,8 +338,7 @@ int pyvb_lds_set_wishart_state(pyvb_lds* h, const double* Q_w, const double* R_w
     if ((rc = h2d(h, h->Q_w, Q_w, (size_t)h->N * h->D * h->D))) return rc;
     if ((rc = h2d(h, h->R_w, R_w, (size_t)h->N * h->K * h->K))) return rc;
     HIPCHK(hipStreamSynchronize(h->stream));
-    h->expect_valid = false;
-    params_changed(h);
+    h->st.noise_changed();
     return PYVB_OK;
 }
 
@@ -439,9 +393,7 @@ int pyvb_lds_set_column_cov(pyvb_lds* h, const double* A_cov, const double* C_co
     if ((rc = column_cov_io(h, 1, const_cast<double*>(C_cov), true))) return rc;
     if ((A_cov || C_cov) && (rc = launch_cov_to_colvar(h))) return rc;      // the diagonals (what the lower bound reads) follow
     HIPCHK(hipStreamSynchronize(h->stream));
-    params_changed(h);
-    h->resQ_valid = h->resR_valid = false;
-    h->sg_valid[0] = h->sg_valid[1] = false;
+    h->st.columns_changed();
     return PYVB_OK;
 }
 
@@ -464,13 +416,9 @@ int pyvb_lds_set_column_observations(pyvb_lds* h, const double* A_obs, const dou
     if ((rc = h2d(h, h->pri.A_obs, A_obs, (size_t)h->D * h->D))) return rc;
     if ((rc = h2d(h, h->pri.C_obs, C_obs, (size_t)h->K * h->D))) return rc;
     if ((rc = launch_observe(h))) return rc;
-    if (h->dense) {
-        if ((rc = launch_cov_observe(h))) return rc;
-        h->sg_valid[0] = h->sg_valid[1] = false;
-    }
+    if (h->dense && (rc = launch_cov_observe(h))) return rc;
     HIPCHK(hipStreamSynchronize(h->stream));
-    params_changed(h);
-    h->resQ_valid = h->resR_valid = false;
+    h->st.columns_changed();
     return PYVB_OK;
 }
 
@@ -496,15 +444,15 @@ int pyvb_lds_set_observations(pyvb_lds* h, const double* Y) {
     }
     if (missing) {
         if (!h->Yobs) {
-            if ((rc = dev_alloc(&h->Yobs, n))) return rc;
-            if ((rc = dev_alloc(&h->Yvar, n))) return rc;
-            if ((rc = dev_alloc(&h->Yqld, (size_t)h->N * h->T))) return rc;
-            if ((rc = dev_alloc(&h->Yent, h->N))) return rc;
-            if ((rc = dev_alloc(&h->Ylnd, (size_t)h->N * h->T))) return rc;
-            if ((rc = dev_alloc(&h->YentX, h->N))) return rc;
+            if ((rc = h->mem.zeros(&h->Yobs, n))) return rc;
+            if ((rc = h->mem.zeros(&h->Yvar, n))) return rc;
+            if ((rc = h->mem.zeros(&h->Yqld, (size_t)h->N * h->T))) return rc;
+            if ((rc = h->mem.zeros(&h->Yent, h->N))) return rc;
+            if ((rc = h->mem.zeros(&h->Ylnd, (size_t)h->N * h->T))) return rc;
+            if ((rc = h->mem.zeros(&h->YentX, h->N))) return rc;
             if (h->dense) {
-                if ((rc = dev_alloc(&h->Yld, (size_t)h->N * h->T))) return rc;
-                if ((rc = dev_alloc(&h->YcovS, (size_t)h->N * h->K * h->K))) return rc;
+                if ((rc = h->mem.zeros(&h->Yld, (size_t)h->N * h->T))) return rc;
+                if ((rc = h->mem.zeros(&h->YcovS, (size_t)h->N * h->K * h->K))) return rc;
             }
         }
         if ((rc = h2d(h, h->Yobs, Y, n))) return rc;
@@ -518,9 +466,8 @@ int pyvb_lds_set_observations(pyvb_lds* h, const double* Y) {
         if ((rc = launch_syy(h))) return rc;
         if (h->dense && (rc = launch_syy_full(h))) return rc;
     }
-    h->u_valid = false;
     HIPCHK(hipStreamSynchronize(h->stream));
-    states_changed(h);
+    h->st.outputs_changed();
     return PYVB_OK;
 }
 
@@ -534,7 +481,7 @@ int pyvb_lds_set_output_state(pyvb_lds* h, const double* Yq, const double* Yrowv
     double* dq = h->U;                  // [N][T][DP] >= [N][T][K]?  not for K > DP: use a temporary then
     double* tmp = nullptr;
     if ((size_t)h->K > (size_t)h->L.DP) { HIPCHK(hipMalloc((void**)&tmp, n * sizeof(double))); dq = tmp; }
-    double* dv = h->X[1 - h->cur];      // [N][T][DP] >= [N][T]
+    double* dv = h->X[1 - h->st.cur];      // [N][T][DP] >= [N][T]
     int rc;
     if ((rc = h2d(h, dq, Yq, n)) || (rc = h2d(h, dv, Yrowvar, (size_t)h->N * h->T)) ||
         (rc = launch_missing_init(h, dq, dv)) || (rc = h->dense ? outputs_changed_dense(h, 1) : launch_syy_missing(h))) {
@@ -544,8 +491,7 @@ int pyvb_lds_set_output_state(pyvb_lds* h, const double* Yq, const double* Yrowv
     const hipError_t se = hipStreamSynchronize(h->stream);
     if (tmp) (void)hipFree(tmp);
     HIPCHK(se);
-    h->u_valid = false;
-    states_changed(h);
+    h->st.outputs_changed();
     return PYVB_OK;
 }
 
@@ -578,8 +524,7 @@ int pyvb_lds_update_Y(pyvb_lds* h) {
         if ((rc = launch_impute(h))) return rc;
         if ((rc = launch_syy_missing(h))) return rc;
     }
-    h->u_valid = false;                             // c_t = F mu + G y_t was formed with the old y_t
-    states_changed(h);
+    h->st.outputs_changed();
     return PYVB_OK;
 }
 
@@ -590,8 +535,8 @@ int pyvb_lds_set_state(pyvb_lds* h, const double* X, const double* A_mean, const
     int rc;
     if ((rc = settle_parked(h))) return rc;
     if (X) {    // the other buffer is free between sweeps: stage the API layout there, then permute
-        if ((rc = h2d(h, h->X[1 - h->cur], X, N * T * D))) return rc;
-        if ((rc = launch_permute(h, h->X[1 - h->cur], h->X[h->cur], 1))) return rc;
+        if ((rc = h2d(h, h->X[1 - h->st.cur], X, N * T * D))) return rc;
+        if ((rc = launch_permute(h, h->X[1 - h->st.cur], h->X[h->st.cur], 1))) return rc;
     }
     if ((rc = h2d(h, h->A_mean, A_mean, N * D * D))) return rc;
     if ((rc = h2d(h, h->A_var, A_colvar, N * D * D))) return rc;
@@ -599,13 +544,12 @@ int pyvb_lds_set_state(pyvb_lds* h, const double* X, const double* A_mean, const
     if ((rc = h2d(h, h->C_var, C_colvar, N * D * K))) return rc;
     if ((rc = h2d(h, h->Q_b, Q_b, N * D))) return rc;
     if ((rc = h2d(h, h->R_b, R_b, N * K))) return rc;
-    if (h->dense && (A_colvar || C_colvar)) {       // diagonal initial covariances
-        if ((rc = launch_colvar_to_cov(h))) return rc;
-        h->sg_valid[0] = h->sg_valid[1] = false;
-    }
+    const bool covs = h->dense && (A_colvar || C_colvar);       // diagonal initial covariances
+    if (covs && (rc = launch_colvar_to_cov(h))) return rc;
     HIPCHK(hipStreamSynchronize(h->stream));
-    if (X) { states_changed(h); h->u_valid = false; h->sxx_valid = false; }
-    if (A_mean || A_colvar || C_mean || C_colvar || Q_b || R_b) { params_changed(h); h->resQ_valid = h->resR_valid = false; }
+    if (X) h->st.x_changed();
+    if (covs) h->st.columns_changed();
+    else if (A_mean || A_colvar || C_mean || C_colvar || Q_b || R_b) h->st.parameters_changed();
     return PYVB_OK;
 }
 
@@ -616,8 +560,8 @@ int pyvb_lds_get_state(pyvb_lds* h, double* X, double* A_mean, double* A_colvar,
     int rc;
     if ((rc = settle_parked(h))) return rc;
     if (X) {
-        if ((rc = launch_permute(h, h->X[h->cur], h->X[1 - h->cur], 0))) return rc;
-        if ((rc = d2h(h, X, h->X[1 - h->cur], N * T * D))) return rc;
+        if ((rc = launch_permute(h, h->X[h->st.cur], h->X[1 - h->st.cur], 0))) return rc;
+        if ((rc = d2h(h, X, h->X[1 - h->st.cur], N * T * D))) return rc;
     }
     if ((rc = d2h(h, A_mean, h->A_mean, N * D * D))) return rc;
     if ((rc = d2h(h, A_colvar, h->A_var, N * D * D))) return rc;
@@ -648,10 +592,8 @@ int pyvb_lds_set_posterior_classes(pyvb_lds* h, const double* Sigma, const doubl
     if ((rc = settle_parked(h))) return rc;
     if ((rc = h2d(h, h->Sigma, Sigma, N * 3 * D * D))) return rc;
     if ((rc = h2d(h, h->qld_x, qld_x, N * 3))) return rc;
-    h->lnd_x_pending = true;        // ln det of these covariances: formed when the exact bound first asks for it (ensure_lnd_x)
     HIPCHK(hipStreamSynchronize(h->stream));
-    h->classes_valid = true;
-    states_changed(h);
+    h->st.classes_set();
     return PYVB_OK;
 }
 
@@ -677,19 +619,18 @@ int pyvb_lds_set_time_split(pyvb_lds* h, int W) {
     HIPCHK(hipStreamSynchronize(h->stream));
     if (W != h->W) {
         double* p = nullptr;
-        int rc = dev_alloc(&p, h->big ? 8 : (size_t)h->N * W * h->L.DP * h->L.DP);
-        if (rc) return rc;
-        if (h->big && W > 1 && !h->U2 && (rc = dev_alloc(&h->U2, (size_t)h->N * h->T * h->L.DP))) { (void)hipFree(p); return rc; }
+        int rc = h->mem.zeros(&p, h->big ? 8 : (size_t)h->N * W * h->L.DP * h->L.DP);
+        if (rc) { h->mem.release(p); return rc; }
+        if (h->big && W > 1 && !h->U2 && (rc = h->mem.zeros(&h->U2, (size_t)h->N * h->T * h->L.DP))) { h->mem.release(p); return rc; }
         if (h->big) {
             double* tr = nullptr;
-            if ((rc = dev_alloc(&tr, (size_t)h->N * W * 512))) { (void)hipFree(p); return rc; }
-            (void)hipFree(h->trash);
+            if ((rc = h->mem.zeros(&tr, (size_t)h->N * W * 512))) { h->mem.release(tr); h->mem.release(p); return rc; }
+            h->mem.release(h->trash);
             h->trash = tr;
         }
-        (void)hipFree(h->sxx);
+        h->mem.release(h->sxx);
         h->sxx = p; h->W = W;
-        h->sxx_valid = false; h->u_valid = false;
-        states_changed(h);
+        h->st.x_changed();
     }
     return PYVB_OK;
 }
@@ -701,22 +642,19 @@ int pyvb_lds_get_warmup(pyvb_lds* h, int* warm) {
     return pyvb_lds_sync(h);
 }
 
-// ---- dependency tracking -------------------------------------------------------------------
-// gains (k_prep) depend on the parameter posteriors.  The posterior covariance classes that the
-// statistics use are those of the X_t's LAST update; they switch to the freshly prepared ones
-// once every X_t has been updated under the current parameters.
+// ---- recomputing what an event dropped (LdsState, host.h; the table is in DESIGN.md) ---------
 static int ensure_expect(pyvb_lds* h) {        // E[Q], E[R] of the current Wishart posteriors
-    if (h->expect_valid) return PYVB_OK;
+    if (h->st.expect_valid) return PYVB_OK;
     int rc = launch_wexpect(h);
     if (rc) return rc;
-    h->expect_valid = true;
+    h->st.expect_valid = true;
     return PYVB_OK;
 }
 
 // Covariances of the X_t given by pyvb_lds_set_posterior_classes: ln det of each (Cholesky on the host, NaN where one is not
 // positive definite), formed once, when the exact bound or pyvb_lds_get_logdets first needs it -- not on the default path.
 static int ensure_lnd_x(pyvb_lds* h) {
-    if (!h->lnd_x_pending) return PYVB_OK;
+    if (!h->st.lnd_x_pending) return PYVB_OK;
     const size_t N = h->N, D = h->D;
     { int rc0 = settle_parked(h); if (rc0) return rc0; }       // every row of Sigma is read, every row of lnd_x written
     std::vector<double> S(N * 3 * D * D), lnd(N * 3), L(D * D);
@@ -740,70 +678,59 @@ static int ensure_lnd_x(pyvb_lds* h) {
     }
     HIPCHK(hipMemcpyAsync(h->lnd_x, lnd.data(), lnd.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
-    h->lnd_x_pending = false;
+    h->st.lnd_x_pending = false;
     return PYVB_OK;
 }
 
 static int ensure_gains(pyvb_lds* h) {
-    if (h->gains_valid) return PYVB_OK;
+    if (h->st.gains_valid) return PYVB_OK;
     int rc;
     if (h->dense) {
         if ((rc = ensure_expect(h))) return rc;
         if ((rc = launch_dense_pre(h))) return rc;
     }
     if ((rc = launch_prep(h))) return rc;
-    h->gains_valid = true;
-    memset(h->fresh, 0, h->T);
-    h->fresh_count = 0;
+    h->st.gains_formed();
     return PYVB_OK;
 }
 
+// The posterior covariance classes that the statistics use are those of the X_t's LAST update; they switch to the freshly
+// prepared ones once every X_t has been updated under the current parameters (LdsState::node_fresh / all_fresh say when).
 static void adopt_classes(pyvb_lds* h) {
     double* t = h->Sigma; h->Sigma = h->Sigma_new; h->Sigma_new = t;
     t = h->qld_x; h->qld_x = h->qld_x_new; h->qld_x_new = t;
     t = h->lnd_x; h->lnd_x = h->lnd_x_new; h->lnd_x_new = t;
-    h->lnd_x_pending = false;
-    h->classes_valid = true;
-    if (h->n_active < h->N) h->cls_parked_other = !h->cls_parked_other;     // the parked rows did not move with the pointers
-}
-
-static void mark_all_fresh(pyvb_lds* h) {
-    if (h->fresh_count < h->T) {
-        // Sigma_new holds the classes of the current parameters exactly when some node is not fresh yet
-        adopt_classes(h);
-        memset(h->fresh, 1, h->T);
-        h->fresh_count = h->T;
-    }
-    h->mixed_cov = false;
+    h->st.classes_adopted(h->n_active < h->N);
 }
 
 static int ensure_stats(pyvb_lds* h) {
-    if (h->stats_valid) return PYVB_OK;
-    if (!h->classes_valid) {
+    LdsState& st = h->st;
+    if (st.stats_valid) return PYVB_OK;
+    if (!st.classes_valid) {
         // the reference's X_t start with individual random covariances (gaussian.py:70-72); the three-class form the
         // statistics use exists once every X_t has been updated, or once the caller has supplied the classes
         pyvb_set_error("the posterior covariances of the X_t are undefined before the first complete sweep "
                        "(run pyvb_lds_sweep, or give them with pyvb_lds_set_posterior_classes)");
         return PYVB_E_STALE;
     }
-    if (h->mixed_cov || (h->gains_valid && h->fresh_count != 0 && h->fresh_count != h->T)) {
+    if (st.mixed_cov || (st.gains_valid && st.fresh_count != 0 && st.fresh_count != h->T)) {
         pyvb_set_error("%d of %d X_t were updated since the parameters changed: their covariances differ; sweep all states first",
-                       h->fresh_count, h->T);
+                       st.fresh_count, h->T);
         return PYVB_E_STALE;
     }
-    int rc = launch_stats(h, !h->sxx_valid);
+    int rc = launch_stats(h, !st.sxx_valid);
     if (rc) return rc;
-    if ((rc = launch_moments(h, h->sxx_valid))) return rc;
-    h->stats_valid = true;
+    if ((rc = launch_moments(h, st.sxx_valid))) return rc;
+    st.stats_valid = true;
     return PYVB_OK;
 }
 
 static int ensure_resid(pyvb_lds* h, int which) {
-    bool& valid = which == 0 ? h->resQ_valid : h->resR_valid;
+    bool& valid = which == 0 ? h->st.resQ_valid : h->st.resR_valid;
     if (valid) return PYVB_OK;
     int rc = ensure_stats(h);
     if (rc) return rc;
-    if ((rc = h->dense ? launch_wresid(h, which, 0) : launch_resid(h, which))) return rc;
+    if ((rc = h->dense ? launch_wresid(h, which, 0, h->st.sg_valid[which]) : launch_resid(h, which))) return rc;
     valid = true;
     return PYVB_OK;
 }
@@ -811,9 +738,11 @@ static int ensure_resid(pyvb_lds* h, int which) {
 static int sweep(pyvb_lds* h, int direction, bool keep_x) {
     int rc = ensure_gains(h);
     if (rc) return rc;
-    if ((rc = launch_sweep(h, direction, keep_x))) return rc;
-    mark_all_fresh(h);
-    states_changed(h);
+    // a backward sweep right behind a forward one reads the c_t that one left in U; the 128-wide class fuses no Sxx
+    const bool read_cache = direction == PYVB_BACKWARD && h->st.u_valid;
+    if ((rc = launch_sweep(h, direction, h->st.cur, read_cache, keep_x))) return rc;
+    h->st.sweep_ran(direction, read_cache, !h->big);
+    if (h->st.all_fresh()) adopt_classes(h);
     return PYVB_OK;
 }
 
@@ -831,13 +760,8 @@ int pyvb_lds_update_x(pyvb_lds* h, int t) {
     int rc = ensure_gains(h);
     if (rc) return rc;
     if ((rc = launch_step(h, t))) return rc;
-    h->u_valid = false;
-    h->sxx_valid = false;
-    if (!h->fresh[t]) {
-        h->fresh[t] = 1;
-        if (++h->fresh_count == h->T) { adopt_classes(h); h->mixed_cov = false; }
-    }
-    states_changed(h);
+    h->st.x_changed();
+    if (h->st.node_fresh(t)) adopt_classes(h);
     return PYVB_OK;
 }
 
@@ -852,8 +776,7 @@ int pyvb_lds_update_columns(pyvb_lds* h, int which, int col_begin, int col_end) 
         if ((rc = ensure_expect(h))) return rc;
         if ((rc = launch_cols_dense(h, which, col_begin, col_end))) return rc;
     } else if ((rc = launch_cols(h, which, col_begin, col_end))) return rc;
-    params_changed(h);
-    if (which == 0) h->resQ_valid = false; else h->resR_valid = false;
+    h->st.columns_updated(which, h->dense && col_begin == 0 && col_end == h->D);
     return PYVB_OK;
 }
 
@@ -864,14 +787,12 @@ static int update_noise(pyvb_lds* h, int which) {
     int rc;
     if (h->dense) {     // Wishart.update: the residual matrix and qw = w0 + it in one launch
         if ((rc = ensure_stats(h))) return rc;
-        if ((rc = launch_wresid(h, which, 1))) return rc;
-        (which == 0 ? h->resQ_valid : h->resR_valid) = true;
-        h->expect_valid = false;
+        if ((rc = launch_wresid(h, which, 1, h->st.sg_valid[which]))) return rc;
     } else {
         if ((rc = ensure_resid(h, which))) return rc;
         if ((rc = launch_noise(h, which))) return rc;
     }
-    params_changed(h);
+    h->st.noise_updated(which);
     return PYVB_OK;
 }
 
@@ -911,52 +832,42 @@ static int join_elbo(pyvb_lds* h) {
 }
 
 int pyvb_lds_iterate(pyvb_lds* h, int niters) {
-    ENTER_RAW(h);
+    ENTER_DEVICE(h);
     ARGCHK(niters >= 0, "niters must be >= 0");
     int rc;
     // Every replicate switched off: no update is launched, but the (empty) sums still go into the history and through the
     // all-reduce, which the other ranks are waiting in.
     const bool idle = h->n_active == 0;
     for (int it = 0; it < niters; ++it) {
-        if (idle) {
+        if (idle) { if ((rc = join_elbo(h))) return rc; }
+        else {
+            // the backward sweep follows at once and reads c_t, not the forward states: those are not written out
+            if ((rc = sweep(h, PYVB_FORWARD, false))) return rc;
             if ((rc = join_elbo(h))) return rc;
-            HIPCHK(hipEventRecord(h->ev_params, h->stream));
-            HIPCHK(hipStreamWaitEvent(h->side, h->ev_params, 0));
-            double* slot = h->elbo_hist + (size_t)(h->hist_count % PYVB_ELBO_HISTORY) * 8;
-            if ((rc = launch_elbo_sum(h, slot, h->side))) return rc;
-            if (h->comm && (rc = pyvb_allreduce_f64(h->comm, slot, 6, h->side))) return rc;
-            h->hist_count += 1;
-            HIPCHK(hipEventRecord(h->ev_elbo, h->side));
-            h->elbo_in_flight = true;
-            continue;
+            if ((rc = sweep(h, PYVB_BACKWARD, true))) return rc;
+            // A and C are independent given the statistics, and so are Q and R given A and C: the pairs
+            // share launches here (same arithmetic as update_A, update_C, update_Q, update_R in turn)
+            if ((rc = ensure_stats(h))) return rc;
+            if (h->dense) {
+                if ((rc = ensure_expect(h))) return rc;
+                if ((rc = launch_cols_dense(h, 2, 0, h->D))) return rc;
+                h->st.columns_updated(2, true);
+                if ((rc = launch_wresid(h, 2, 1, true))) return rc;    // both residual matrices and both qw = w0 + residual
+                h->st.noise_updated(2);
+                if ((rc = ensure_expect(h))) return rc;                // E[Q], E[R] of the new posteriors: the bound and the next k_prep read them
+            } else {
+                if ((rc = launch_cols(h, 2, 0, h->D, 3))) return rc;       // columns, residuals and noise update in one launch
+                h->st.columns_updated(2, false);
+                h->st.noise_updated(2);
+            }
+            if (h->bound == PYVB_BOUND_EXACT && (rc = ensure_lnd_x(h))) return rc;       // (only before the first complete sweep)
         }
-        // the backward sweep follows at once and reads c_t, not the forward states: those are not written out
-        if ((rc = sweep(h, PYVB_FORWARD, false))) return rc;
-        if ((rc = join_elbo(h))) return rc;
-        if ((rc = sweep(h, PYVB_BACKWARD, true))) return rc;
-        // A and C are independent given the statistics, and so are Q and R given A and C: the pairs
-        // share launches here (same arithmetic as update_A, update_C, update_Q, update_R in turn)
-        if ((rc = ensure_stats(h))) return rc;
-        if (h->dense) {
-            if ((rc = ensure_expect(h))) return rc;
-            if ((rc = launch_cols_dense(h, 2, 0, h->D))) return rc;
-            params_changed(h);
-            if ((rc = launch_wresid(h, 2, 1))) return rc;          // both residual matrices and both qw = w0 + residual
-            h->expect_valid = false;
-            params_changed(h);
-            if ((rc = ensure_expect(h))) return rc;                // E[Q], E[R] of the new posteriors: the bound and the next k_prep read them
-        } else {
-            if ((rc = launch_cols(h, 2, 0, h->D, 3))) return rc;       // columns, residuals and noise update in one launch
-            params_changed(h);
-        }
-        h->resQ_valid = h->resR_valid = true;
-        if (h->bound == PYVB_BOUND_EXACT && (rc = ensure_lnd_x(h))) return rc;       // (only before the first complete sweep)
         // The lower bound (network.py:49) feeds nothing in the next iteration: it is evaluated on the side stream while
         // the main one goes on with k_prep and the forward sweep.  Its per-iteration totals (summed over the replicates,
         // and over the ranks when a communicator is attached) go into a history ring (pyvb_lds_get_elbo_history).
         HIPCHK(hipEventRecord(h->ev_params, h->stream));
         HIPCHK(hipStreamWaitEvent(h->side, h->ev_params, 0));
-        if ((rc = h->dense ? launch_elbo_dense(h, h->side) : launch_elbo(h, h->side))) return rc;
+        if (!idle && (rc = h->dense ? launch_elbo_dense(h, h->side) : launch_elbo(h, h->side))) return rc;
         double* slot = h->elbo_hist + (size_t)(h->hist_count % PYVB_ELBO_HISTORY) * 8;
         if ((rc = launch_elbo_sum(h, slot, h->side))) return rc;
         if (h->comm && (rc = pyvb_allreduce_f64(h->comm, slot, 6, h->side))) return rc;
@@ -1060,7 +971,7 @@ int pyvb_lds_set_active(pyvb_lds* h, const unsigned char* active) {
     if (rc) return rc;
     for (int n = 0; n < h->N; ++n) h->active_host[n] = active[n] ? 1 : 0;
     h->n_active = count;
-    h->x_park = h->cur; h->cls_parked_other = false;
+    h->st.parked_here();
     HIPCHK(hipMemcpyAsync(h->active, h->active_host, (size_t)h->N, hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));       // the mirror may change again as soon as this returns
     return PYVB_OK;

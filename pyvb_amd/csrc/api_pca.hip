@@ -6,9 +6,7 @@
 #include <cstring>
 #include <vector>
 
-#define ARGCHK(cond, msg) do { if (!(cond)) { pyvb_set_error("%s", msg); return PYVB_E_ARG; } } while (0)
-#define ENTER(h) do { ARGCHK(h, "handle is NULL"); HIPCHK(hipSetDevice((h)->device)); } while (0)
-
+#define ENTER(h) ENTER_DEVICE(h)
 
 // digamma for x > 0 (recurrence up to 10, then the asymptotic series), as the device code had it
 static double digamma_host(double x) {
@@ -20,12 +18,6 @@ static double digamma_host(double x) {
     return r + std::log(x) - 0.5 / x - ser;
 }
 
-static int alloc_d(double** p, size_t n) {
-    HIPCHK(hipMalloc((void**)p, n * sizeof(double)));
-    HIPCHK(hipMemset(*p, 0, n * sizeof(double)));
-    return PYVB_OK;
-}
-
 extern "C" {
 
 int pyvb_pca_destroy(pyvb_pca* h) {
@@ -33,10 +25,7 @@ int pyvb_pca_destroy(pyvb_pca* h) {
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     if (h->comm) pyvb_comm_free(h->comm);
-    void* bufs[] = {h->X, h->M, h->xvar, h->nmiss, h->Z, h->W_mean, h->W_var, h->Mu_mean, h->Mu_var, h->Z_cov, h->qld_W, h->lnd_W, h->W_pm, h->W_pp,
-                    h->Mu_pm, h->Mu_pp, h->scal, h->Gz, h->g0, h->part, h->stats, h->aux, h->elbo, h->status, h->red2, h->Xdata, h->pinned, h->sx_local,
-                    h->W_x, h->Mu_x};
-    for (void* b : bufs) if (b) (void)hipFree(b);
+    h->mem.release_all();
     if (h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
     return PYVB_OK;
@@ -51,8 +40,7 @@ int pyvb_pca_create(pyvb_pca** out, int device, long N, int d, int q, long N_tot
     HIPCHK(hipGetDeviceCount(&ndev));
     ARGCHK(device >= 0 && device < ndev, "no such device");
     HIPCHK(hipSetDevice(device));
-    pyvb_pca* h = new pyvb_pca();
-    memset(h, 0, sizeof(*h));
+    pyvb_pca* h = new pyvb_pca();       // value-initialised: every pointer null, every flag false
     h->device = device; h->N = N; h->N_total = N_total; h->row_offset = row_offset; h->d = d; h->q = q;
     h->DP = (d + 15) & ~15; h->QP = (q + 15) & ~15; h->DT = h->DP / 16; h->QT = h->QP / 16;
     h->SL = pca_stats_layout(h->DP, h->QP);
@@ -74,21 +62,22 @@ int pyvb_pca_create(pyvb_pca** out, int device, long N, int d, int q, long N_tot
     nchunk = (N + rows - 1) / rows;
     h->nchunk = (int)nchunk; h->chunk_rows = rows;
     int rc = PYVB_OK;
-#define TRY(x) do { rc = (x); if (rc != PYVB_OK) { pyvb_pca_destroy(h); return rc; } } while (0)
-#define TRYHIP(x) do { hipError_t _e = (x); if (_e != hipSuccess) { rc = pyvb_hip_fail(_e, #x, __FILE__, __LINE__); pyvb_pca_destroy(h); return rc; } } while (0)
+#define TRY(x) CREATE_TRY(x, pyvb_pca_destroy, h)
+#define TRYHIP(x) CREATE_TRYHIP(x, pyvb_pca_destroy, h)
+#define alloc_d(p, n) h->mem.zeros(p, n)
     TRYHIP(hipStreamCreate(&h->stream));
     const size_t n = (size_t)N, DP = h->DP, QP = h->QP;
     TRY(alloc_d(&h->X, n * DP));
-    TRYHIP(hipMalloc((void**)&h->M, n * DP)); TRYHIP(hipMemset(h->M, 1, n * DP));
+    TRY(h->mem.alloc((void**)&h->M, n * DP, 1));
     TRY(alloc_d(&h->xvar, n));
-    TRYHIP(hipMalloc((void**)&h->nmiss, n * sizeof(int))); TRYHIP(hipMemset(h->nmiss, 0, n * sizeof(int)));
+    TRY(h->mem.alloc((void**)&h->nmiss, n * sizeof(int)));
     TRY(alloc_d(&h->Z, n * QP));
     TRY(alloc_d(&h->W_mean, (size_t)d * q)); TRY(alloc_d(&h->W_var, (size_t)q * d));
     TRY(alloc_d(&h->Mu_mean, d)); TRY(alloc_d(&h->Mu_var, d)); TRY(alloc_d(&h->Z_cov, (size_t)q * q)); TRY(alloc_d(&h->qld_W, q)); TRY(alloc_d(&h->lnd_W, q));
     TRY(alloc_d(&h->W_pm, (size_t)d * q)); TRY(alloc_d(&h->W_pp, (size_t)q * d)); TRY(alloc_d(&h->Mu_pm, d)); TRY(alloc_d(&h->Mu_pp, d));
     TRY(alloc_d(&h->W_x, (size_t)d * q)); TRY(alloc_d(&h->Mu_x, d));
     { const char* e = getenv("PYVB_PCA_WRITEBACK"); h->lazy_ok = !(e && e[0] == '1'); }
-    {   // k_pca_rows: one workgroup of four wavefronts per CU, the rows dealt out in multiples of 16
+    {   // k_pca_pairs: one workgroup per CU, the rows dealt out in multiples of 16
         int ncu = 0;
         TRYHIP(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device));
         if (ncu < 1) ncu = 1;
@@ -98,14 +87,14 @@ int pyvb_pca_create(pyvb_pca** out, int device, long N, int d, int q, long N_tot
         long ncB = (N + rowsB - 1) / rowsB;
         if (ncB > nchunk) { ncB = nchunk; rowsB = ((N + ncB - 1) / ncB + 15) & ~15L; ncB = (N + rowsB - 1) / rowsB; }
         h->nchunkB = (int)ncB; h->chunk_rowsB = rowsB;
-        // which kernel the lazy sweep is (k_pca.hip): PYVB_PCA_SWEEP = columns (k_pca_pass12<.., LAZY>) / rows (k_pca_rows) / pairs
-        // (k_pca_pairs); unset: pairs where a CU's share is long enough to stream (measured at 10^6 x 256: 0.95 against 0.97 ms per
+        // which kernel the lazy sweep is (k_pca.hip): PYVB_PCA_SWEEP = columns (k_pca_pass12<.., LAZY>) / pairs (k_pca_pairs);
+        // unset: pairs where a CU's share is long enough to stream (measured at 10^6 x 256: 0.95 against 0.97 ms per
         // iteration), columns otherwise
         const char* e = getenv("PYVB_PCA_SWEEP");
-        if (e && e[0] == 'r') h->rows_ok = 1;
-        else if (e && e[0] == 'p') h->rows_ok = 2;
-        else if (e && e[0] == 'c') h->rows_ok = 0;
-        else h->rows_ok = (h->DT >= 13 && N >= 512L * ncu) ? 2 : 0;
+        if (e && e[0] == 'p') h->pairs = true;
+        else if (e && e[0] == 'c') h->pairs = false;
+        else h->pairs = h->DT >= 13 && N >= 512L * ncu;
+        if (h->pairs) TRY(pca_prepare_pairs());
     }
     TRY(alloc_d(&h->scal, PS_COUNT));
     TRY(alloc_d(&h->Gz, (size_t)h->QT * (DP / 4) * 64)); TRY(alloc_d(&h->g0, QP));
@@ -115,33 +104,57 @@ int pyvb_pca_create(pyvb_pca** out, int device, long N, int d, int q, long N_tot
     TRY(alloc_d(&h->red2, (size_t)PCA_RED * h->SL.total));
     TRY(alloc_d(&h->aux, (size_t)4 * h->nchunk * QP + QP + DP));
     TRY(alloc_d(&h->elbo, 8));
-    TRYHIP(hipMalloc((void**)&h->status, sizeof(int))); TRYHIP(hipMemset(h->status, 0, sizeof(int)));
+    TRY(h->mem.alloc((void**)&h->status, sizeof(int)));
+#undef alloc_d
 #undef TRY
 #undef TRYHIP
     *out = h;
     return PYVB_OK;
 }
 
-static int up(pyvb_pca* h, double* dst, const double* src, size_t n) {
-    if (!src) return PYVB_OK;
-    HIPCHK(hipMemcpyAsync(dst, src, n * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    return PYVB_OK;
-}
-static int down(pyvb_pca* h, double* dst, const double* src, size_t n) {
-    if (!dst) return PYVB_OK;
-    HIPCHK(hipMemcpyAsync(dst, src, n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+static int up(pyvb_pca* h, double* dst, const double* src, size_t n) { return to_device(h->stream, dst, src, n); }
+static int down(pyvb_pca* h, double* dst, const double* src, size_t n) { return to_host(h->stream, dst, src, n); }
+
+// Rows [lo, hi) of X are about to be read outside a sweep: where a lazy sweep left their imputed entries unstored (PcaState:
+// xlazy, [vlo, vhi)), they are put into X first.  Every such reader calls this.
+static int x_read(pyvb_pca* h, long lo, long hi) {
+    PcaState& st = h->st;
+    if (!st.xlazy || !(lo < st.vhi && st.vlo < hi)) return PYVB_OK;
+    int rc = pca_materialize_x(h, st.vlo, st.vhi);
+    if (rc) return rc;
+    st.xlazy = false;
     return PYVB_OK;
 }
 
 // A requested Z update whose rows have not been written (see pyvb_pca_update_Z) is carried out: pass 1 on its own.  Called by
 // everything that reads or replaces Z, X or the parameters outside the fused sweep.
 static int resolve_z(pyvb_pca* h) {
-    int rc = pca_materialize_x(h);          // the same callers want X as it stands, and Z is about to change or be replaced
+    int rc = x_read(h, 0, h->N);            // the same callers want X as it stands, and Z is about to change or be replaced
     if (rc) return rc;
-    if (!h->z_pending) return PYVB_OK;
-    rc = pca_launch_pass1(h);
-    h->z_pending = false; h->z0_done = false;
+    if (!h->st.z_pending) return PYVB_OK;
+    rc = pca_launch_pass1(h, h->st.z0_done);
+    h->st.z_written();
     return rc;
+}
+
+// What the next pass over the rows is, for the update of rows [lo_upd, hi_upd) of X: pass 2, or pass 1+2 where a Z update is
+// pending.  The standard sweep of an iteration -- all rows, or all but row 0, which the crawl order updates on its own -- leaves
+// the imputed entries to be recomputed by the next one (lazy); any other range, latent dimensions beyond 16 (the register budget)
+// and rows that still wait for their first update take the write-back, and entries an earlier sweep left unstored that the new
+// range does not cover are stored first.
+static PcaSweepPlan plan_sweep(const pyvb_pca* h, long lo_upd, long hi_upd) {
+    const PcaState& st = h->st;
+    PcaSweepPlan p;
+    p.lo_upd = lo_upd; p.hi_upd = hi_upd;
+    p.with_z = st.z_pending;
+    p.keep_z0 = st.z0_done;
+    p.lazy = p.with_z && h->lazy_ok && h->QT == 1 && !h->Xdata && lo_upd <= 1 && hi_upd == h->N && hi_upd > lo_upd
+             && (!st.xlazy || (lo_upd <= st.vlo && st.vhi <= hi_upd));
+    p.pairs = p.lazy && h->pairs;
+    p.materialize = st.xlazy && !p.lazy;
+    p.vin_lo = st.xlazy ? st.vlo : 0; p.vin_hi = st.xlazy ? st.vhi : 0;
+    p.part_chunks = p.pairs ? h->nchunkB : h->nchunk;
+    return p;
 }
 
 int pyvb_pca_set_priors(pyvb_pca* h, const double* W_pm, const double* W_pp, const double* Mu_pm, const double* Mu_pp,
@@ -212,7 +225,7 @@ int pyvb_pca_set_data(pyvb_pca* h, const double* X) {
         HIPCHK(hipMemcpy(counts, h->elbo, sizeof(counts), hipMemcpyDeviceToHost));
     }
     h->n_part_missing = (long)counts[0]; h->n_none_rows = (long)counts[1]; h->n_part_rows = (long)counts[2];
-    h->full_valid = h->lin_valid = false; h->res_valid = false;
+    h->st.inputs_changed();
     return PYVB_OK;
 }
 
@@ -238,7 +251,7 @@ int pyvb_pca_set_state(pyvb_pca* h, const double* X_missing, const double* W_mea
     if ((rc = up(h, h->Mu_mean, Mu_mean, d))) return rc;
     if (beta_b) HIPCHK(hipMemcpyAsync(h->scal + PS_BETA_B, beta_b, sizeof(double), hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
-    h->full_valid = h->lin_valid = false; h->res_valid = false;
+    h->st.inputs_changed();
     return PYVB_OK;
 }
 
@@ -249,7 +262,7 @@ int pyvb_pca_set_initial_variances(pyvb_pca* h, const double* W_var, const doubl
     if ((rc = up(h, h->W_var, W_var, (size_t)h->q * h->d))) return rc;
     if ((rc = up(h, h->Mu_var, Mu_var, h->d))) return rc;
     HIPCHK(hipStreamSynchronize(h->stream));
-    h->res_valid = false;
+    h->st.res_valid = false;
     return PYVB_OK;
 }
 
@@ -276,15 +289,15 @@ int pyvb_pca_set_unpinned_rows(pyvb_pca* h, const double* X_full, const double* 
     }
     if (unpinned > 0) {
         if (!h->Xdata) {
-            HIPCHK(hipMalloc((void**)&h->Xdata, xb.size() * sizeof(double)));
-            HIPCHK(hipMalloc((void**)&h->pinned, (size_t)N));
+            int rc;
+            if ((rc = h->mem.alloc((void**)&h->Xdata, xb.size() * sizeof(double))) || (rc = h->mem.alloc((void**)&h->pinned, (size_t)N))) return rc;
         }
         HIPCHK(hipMemcpy(h->Xdata, data.data(), data.size() * sizeof(double), hipMemcpyHostToDevice));
         HIPCHK(hipMemcpy(h->pinned, pin.data(), (size_t)N, hipMemcpyHostToDevice));
     }
     HIPCHK(hipMemcpy(h->X, xb.data(), xb.size() * sizeof(double), hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(h->xvar, xv.data(), N * sizeof(double), hipMemcpyHostToDevice));
-    h->full_valid = h->lin_valid = false; h->res_valid = false;
+    h->st.inputs_changed();
     return PYVB_OK;
 }
 
@@ -320,17 +333,17 @@ int pyvb_pca_get_state(pyvb_pca* h, double* X, double* X_rowvar, double* W_mean,
     return pyvb_pca_sync(h);
 }
 
-int pyvb_pca_get_qld(pyvb_pca* h, double* qld_W, double* qld_Z, double* qld_Mu, double* qld_X) {
-    ENTER(h);
+// q_ln_det (logdet = 0) or ln det qcov (1) of the W columns, of the Z_n, of Mu, and of every latent row of X
+static int get_dets(pyvb_pca* h, int logdet, double* of_W, double* of_Z, double* of_Mu, double* of_X) {
     int rc;
     double sc[PS_COUNT];
     HIPCHK(hipStreamSynchronize(h->stream));
-    if ((rc = down(h, qld_W, h->qld_W, (size_t)h->q))) return rc;
+    if ((rc = down(h, of_W, logdet ? h->lnd_W : h->qld_W, (size_t)h->q))) return rc;
     HIPCHK(hipMemcpyAsync(sc, h->scal, sizeof(sc), hipMemcpyDeviceToHost, h->stream));
     double* tmp = nullptr;
-    if (qld_X) {
+    if (of_X) {
         HIPCHK(hipMalloc((void**)&tmp, (size_t)h->N * sizeof(double)));
-        if ((rc = pca_launch_rowqld(h, tmp)) || (rc = down(h, qld_X, tmp, (size_t)h->N))) {
+        if ((rc = pca_launch_rowqld(h, tmp, logdet)) || (rc = down(h, of_X, tmp, (size_t)h->N))) {
             (void)hipStreamSynchronize(h->stream); (void)hipFree(tmp);
             return rc;
         }
@@ -338,9 +351,19 @@ int pyvb_pca_get_qld(pyvb_pca* h, double* qld_W, double* qld_Z, double* qld_Mu, 
     const hipError_t se = hipStreamSynchronize(h->stream);
     if (tmp) (void)hipFree(tmp);
     HIPCHK(se);
-    if (qld_Z) *qld_Z = sc[PS_QLD_Z];
-    if (qld_Mu) *qld_Mu = sc[PS_QLD_MU];
+    if (of_Z) *of_Z = sc[logdet ? PS_LND_Z : PS_QLD_Z];
+    if (of_Mu) *of_Mu = sc[logdet ? PS_LND_MU : PS_QLD_MU];
     return PYVB_OK;
+}
+
+int pyvb_pca_get_qld(pyvb_pca* h, double* qld_W, double* qld_Z, double* qld_Mu, double* qld_X) {
+    ENTER(h);
+    return get_dets(h, 0, qld_W, qld_Z, qld_Mu, qld_X);
+}
+
+int pyvb_pca_get_logdets(pyvb_pca* h, double* lnd_W, double* lnd_Z, double* lnd_Mu, double* lnd_X) {
+    ENTER(h);
+    return get_dets(h, 1, lnd_W, lnd_Z, lnd_Mu, lnd_X);
 }
 
 int pyvb_pca_set_bound_mode(pyvb_pca* h, int mode) {
@@ -351,50 +374,29 @@ int pyvb_pca_set_bound_mode(pyvb_pca* h, int mode) {
     return PYVB_OK;
 }
 
-int pyvb_pca_get_logdets(pyvb_pca* h, double* lnd_W, double* lnd_Z, double* lnd_Mu, double* lnd_X) {
-    ENTER(h);
-    int rc;
-    double sc[PS_COUNT];
-    HIPCHK(hipStreamSynchronize(h->stream));
-    if ((rc = down(h, lnd_W, h->lnd_W, (size_t)h->q))) return rc;
-    HIPCHK(hipMemcpyAsync(sc, h->scal, sizeof(sc), hipMemcpyDeviceToHost, h->stream));
-    double* tmp = nullptr;
-    if (lnd_X) {
-        HIPCHK(hipMalloc((void**)&tmp, (size_t)h->N * sizeof(double)));
-        if ((rc = pca_launch_rowqld(h, tmp, 1)) || (rc = down(h, lnd_X, tmp, (size_t)h->N))) {
-            (void)hipStreamSynchronize(h->stream); (void)hipFree(tmp);
-            return rc;
-        }
-    }
-    const hipError_t se = hipStreamSynchronize(h->stream);
-    if (tmp) (void)hipFree(tmp);
-    HIPCHK(se);
-    if (lnd_Z) *lnd_Z = sc[PS_LND_Z];
-    if (lnd_Mu) *lnd_Mu = sc[PS_LND_MU];
-    return PYVB_OK;
-}
-
 // ---- dependency tracking: "full" = every sum current, "lin" = at least sum x and sum z ----
 static int full_stats(pyvb_pca* h, long lo_upd, long hi_upd) {
-    int rc;
-    if (h->z_pending) {          // the Z update rides along: one sweep over X instead of two
-        rc = pca_launch_pass12(h, lo_upd, hi_upd);
-        h->z_pending = false; h->z0_done = false;
-        if (rc) return rc;
-    } else if ((rc = pca_launch_pass2(h, lo_upd, hi_upd))) return rc;
+    PcaState& st = h->st;
+    const PcaSweepPlan p = plan_sweep(h, lo_upd, hi_upd);
+    int rc = pca_launch_sweep(h, p);
+    if (p.with_z) st.z_written();           // the Z update rode along: one sweep over X instead of two
+    if (rc) return rc;
+    st.part_chunks = p.part_chunks;
+    if (p.materialize) st.xlazy = false;
+    if (p.lazy) { st.xlazy = true; st.vlo = lo_upd; st.vhi = hi_upd; }
     if ((rc = pca_launch_reduce(h, 0))) return rc;
     if (h->comm && (rc = pyvb_allreduce_f64(h->comm, h->stats, h->SL.total, h->stream))) return rc;
-    h->full_valid = h->lin_valid = true;
-    if (hi_upd > lo_upd) h->res_valid = false;          // rows changed: the cached residual of the last Beta update is stale
+    st.full_valid = st.lin_valid = true;
+    if (hi_upd > lo_upd) st.res_valid = false;          // rows changed: the cached residual of the last Beta update is stale
     return PYVB_OK;
 }
-static int ensure_full(pyvb_pca* h) { return h->full_valid ? PYVB_OK : full_stats(h, 0, 0); }
+static int ensure_full(pyvb_pca* h) { return h->st.full_valid ? PYVB_OK : full_stats(h, 0, 0); }
 
 int pyvb_pca_update_W(pyvb_pca* h) {
     ENTER(h);
     int rc = ensure_full(h);
     if (rc) return rc;
-    h->res_valid = false;
+    h->st.res_valid = false;
     return pca_launch_small(h, PCA_W);
 }
 
@@ -413,11 +415,11 @@ int pyvb_pca_update_Z(pyvb_pca* h) {
     // formed now (sum z = Gz sum x - N g0 over this rank's rows, from the sum of x kept from the last sweep; all-reduced like
     // the sum a pass over the rows would give); the rows of Z are written by the next sweep over X -- normally the X update
     // that follows (k_pca_pass12) -- or by resolve_z() if something asks for them first.
-    if (!h->lin_valid && (rc = ensure_full(h))) return rc;      // may carry out an earlier pending request
-    h->z_pending = true; h->z0_done = false;
-    if ((rc = pca_launch_small(h, PCA_PREPZ))) { h->z_pending = false; return rc; }
+    if (!h->st.lin_valid && (rc = ensure_full(h))) return rc;   // may carry out an earlier pending request
+    h->st.z_requested();
+    if ((rc = pca_launch_small(h, PCA_PREPZ))) { h->st.z_pending = false; return rc; }
     if ((rc = exchange_lin(h))) return rc;
-    h->full_valid = false; h->res_valid = false;                // lin_valid stays: sum x is unchanged, sum z is the new one
+    h->st.linear_step();                                        // sum x is unchanged, sum z is the new one
     return PYVB_OK;
 }
 
@@ -426,16 +428,16 @@ int pyvb_pca_update_Z(pyvb_pca* h) {
 // updates it, everyone exchanges [sum z | delta of sum x]; the sum of z travels once, from the owner.
 static int x0_step(pyvb_pca* h) {
     int rc;
-    if (!h->lin_valid && (rc = ensure_full(h))) return rc;
-    if (h->xlazy && h->row_offset == 0 && h->vlo == 0 && (rc = pca_materialize_x(h))) return rc;     // row 0 itself is read here
+    if (!h->st.lin_valid && (rc = ensure_full(h))) return rc;
+    if ((rc = x_read(h, 0, h->row_offset == 0 ? 1 : 0))) return rc;        // row 0 itself is read here, by the rank that holds it
     double* v = h->aux + (size_t)4 * h->nchunk * h->QP;
     HIPCHK(hipMemcpyAsync(v, h->stats + h->SL.osz, h->QP * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
     if (h->comm && h->row_offset != 0)
         HIPCHK(hipMemsetAsync(v, 0, h->QP * sizeof(double), h->stream));
     if ((rc = pca_launch_small(h, PCA_X0))) return rc;      // a no-op for the data of the other ranks (k_pca.hip checks row_offset)
-    if (h->z_pending && h->row_offset == 0) h->z0_done = true;     // the kernel has stored z_0 from the row as it was
+    if (h->st.z_pending && h->row_offset == 0) h->st.z0_done = true;     // the kernel has stored z_0 from the row as it was
     if ((rc = exchange_lin(h))) return rc;
-    h->full_valid = false; h->res_valid = false;
+    h->st.linear_step();
     return PYVB_OK;
 }
 
@@ -463,8 +465,8 @@ int pyvb_pca_update_X0(pyvb_pca* h) {
 int pyvb_pca_update_Mu(pyvb_pca* h) {
     ENTER(h);
     int rc;
-    if (!h->lin_valid && (rc = ensure_full(h))) return rc;
-    h->res_valid = false;
+    if (!h->st.lin_valid && (rc = ensure_full(h))) return rc;
+    h->st.res_valid = false;
     return pca_launch_small(h, PCA_MU);
 }
 
@@ -473,7 +475,7 @@ int pyvb_pca_update_Beta(pyvb_pca* h) {
     int rc = ensure_full(h);
     if (rc) return rc;
     if ((rc = pca_launch_small(h, PCA_BETA))) return rc;
-    h->res_valid = true;        // the residual does not depend on Beta: the lower bound can reuse it
+    h->st.res_valid = true;     // the residual does not depend on Beta: the lower bound can reuse it
     return PYVB_OK;
 }
 
@@ -500,15 +502,18 @@ int pyvb_pca_iterate(pyvb_pca* h, int niters) {
             // launches (W, Z-prepare | X_0, Mu | Beta, bound) around the one sweep over the rows; same code, same order, same flags
             // as the calls of the general path below.
             if ((rc = ensure_full(h))) return rc;                       // update_W
-            h->z_pending = true; h->z0_done = false;                    // update_Z, deferred (lin_valid holds after ensure_full)
-            if ((rc = pca_launch_small(h, PCA_RUN_HEAD))) { h->z_pending = false; return rc; }
-            h->full_valid = false; h->res_valid = false;
+            h->st.z_requested();                                        // update_Z, deferred (lin_valid holds after ensure_full)
+            if ((rc = pca_launch_small(h, PCA_RUN_HEAD))) { h->st.z_pending = false; return rc; }
+            h->st.linear_step();
+            // the X_0 step reads row 0: a no-op after an iteration of this loop (its sweep left vlo == 1), but not after a
+            // stage-wise pyvb_pca_update_X(0, N)
+            if ((rc = x_read(h, 0, h->row_offset == 0 ? 1 : 0))) return rc;
             if ((rc = pca_launch_small(h, PCA_RUN_MID))) return rc;     // x0_step, update_Mu
-            h->z0_done = h->row_offset == 0;                            // the kernel stored z_0 if this handle holds global row 0
+            h->st.z0_done = h->row_offset == 0;                         // the kernel stored z_0 if this handle holds global row 0
             if ((rc = x_rows(h, h->row_offset == 0 ? 1 : 0, h->N))) return rc;
             if ((rc = ensure_full(h))) return rc;                       // N == 1: no row left for x_rows, the sweep still has to run
             if ((rc = pca_launch_small(h, PCA_RUN_TAIL))) return rc;    // update_Beta, elbo
-            h->res_valid = true;
+            h->st.res_valid = true;
             continue;
         }
         if ((rc = pyvb_pca_update_W(h))) return rc;

@@ -1,9 +1,7 @@
 // Internal definitions shared by the translation units of libpyvb_hip.so (gfx950 only).
 #pragma once
-#include <hip/hip_runtime.h>
-#include <cstddef>
 #include <cstdint>
-#include "../../include/pyvb_hip.h"
+#include "host.h"
 
 struct pyvb_comm;
 typedef double d4 __attribute__((ext_vector_type(4)));
@@ -87,14 +85,13 @@ struct KernelTimer {
 struct pyvb_lds {
     int device, N, T, D, K, noise;
     bool big;                       // 64 < max(D, K) <= 128: the workgroup-per-replicate kernels of k_big.hip
-    bool big_attr_prep, big_attr_cols;      // their dynamic-LDS limits have been raised on this handle's device
     double* U2;                     // 128-wide class with the time axis split (W > 1): the c_t of a forward sweep (k_big.hip: BigSweepArgs.Uc)
     Layout L;
     hipStream_t stream;
     struct EventPair* pool; int pool_used;
     // state
     double *Y, *Syy;                // [N][T][K], [N][K] (sum_t y^2)
-    double *X[2]; int cur;          // ping-pong [N][T][DP], rows in accumulator order (xpos)
+    double *X[2];                   // ping-pong [N][T][DP], rows in accumulator order (xpos); st.cur is the one that holds the states
     double *A_mean, *A_var, *C_mean, *C_var;
     double *Q_a, *Q_b, *R_a, *R_b;
     double *qld_A, *qld_C;          // [N][D]
@@ -106,16 +103,15 @@ struct pyvb_lds {
     double *Sigma, *qld_x;          // as of the last X update: [N][3][D][D], [N][3]
     double *Sigma_new, *qld_x_new;  // written by k_prep for the current parameters
     double *lnd_x, *lnd_x_new;      // [N][3] ln det Sigma beside qld_x / qld_x_new (swapped with them)
-    bool lnd_x_pending;             // Sigma was set by the caller: lnd_x is formed from it when first needed (api.hip: ensure_lnd_x)
     double *gains;                  // [N][L.gains_total]
     double *scratch;                // [N][2][DP][DP] (M_C, M_A + M_C)
     int *warm;                      // [N][2]
     double *zeros;                  // [64] zeros: the row that k_stats reads where there is no row
     double *trash;                  // [N][256] dump rows for masked-out stores of the sweep
-    double *U; bool u_valid;        // [N][T][DP] c_t = F mu_{t-1} + G y_t written by the forward sweep for the backward one that follows it
+    double *U;                      // [N][T][DP] c_t = F mu_{t-1} + G y_t written by the forward sweep for the backward one that follows it
     double *stats; int nchunk, chunk_len;   // [N][nchunk][L.stats_total]
     int W;                          // wavefronts per replicate in the sweeps (time split; 1 unless N is small)
-    double *sxx; bool sxx_valid;    // [N][W][DP][DP] interior sum of mu mu^T from the backward sweep (valid while X is that sweep's result)
+    double *sxx;                    // [N][W][DP][DP] interior sum of mu mu^T from the backward sweep
     double *mom;                    // [N][3 D^2 + K D + D] second moments (k_moments)
     double *resQ, *resR;            // [N][D], [N][K]
     double *elbo, *elbo_sum;        // [N][6], [6]
@@ -125,13 +121,8 @@ struct pyvb_lds {
     unsigned char *active_host;     // its host mirror (set_active is stream ordered, the mirror is what the host logic reads)
     int n_active;
     int *status_host, *reported;    // [N] staging of a read of status; [N] what the most recent failed sync reported and cleared
-    int x_park;                     // the X buffer that holds the rows of the switched-off replicates (they sit out the ping-pong)
-    bool cls_parked_other;          // their Sigma / qld_x / lnd_x are in the *_new set (adopt_classes swapped since)
-    // host-side validity tracking
-    bool gains_valid, stats_valid, resQ_valid, resR_valid;
-    int fresh_count; unsigned char* fresh;  // X_t updated since the parameters last changed
-    bool mixed_cov;                         // the X_t hold covariances of different parameter generations
-    bool classes_valid;                     // Sigma / qld_x describe the X_t (after the first complete sweep, or set by the caller)
+    LdsState st;                    // what is current on the device (host.h); written by the events of api.hip only
+    DeviceBuffers mem;              // every device allocation of this handle
     bool timing; KernelTimer timers[PYVB_K_COUNT]; int timing_errors;
     pyvb_comm* comm; int rank, world;
     // ---- Wishart noise precisions (nodes_todo.py:205-234): dense expectations, dense column covariances
@@ -144,10 +135,8 @@ struct pyvb_lds {
     double *A_cov, *C_cov;          // [N][D][cov_stride(D)], [N][D][cov_stride(K)] column covariances, upper 8 x 8 tiles (k_wishart.hip)
     double *SyyF;                   // [N][K][K] sum_t y y^T
     double *RQ, *RR;                // [N][D][D], [N][K][K]: sum over children of 1/2<xx^T> + 1/2<mu mu^T> - <x><mu>^T
-    bool expect_valid;              // Qbar, Rbar, lnd belong to the current Q_w, R_w
     double *ldm;                    // [N][2][D] ln det of the covariance of the unknown entries of partially known columns of A / C
-    double *SG; bool sg_valid[2];   // [N][2][64][64] sum_i G[i,i] S_i over the columns of A / C (k_cols_wishart); valid while neither the
-                                    // covariances nor the statistics have changed since
+    double *SG;                     // [N][2][64][64] sum_i G[i,i] S_i over the columns of A / C (k_cols_wishart)
     // ---- outputs with missing entries (k_missing.hip); allocated when set_observations sees NaN
     bool has_missing;
     double *Yobs, *Yvar, *Yqld, *Yent;      // [N][T][K] observations (NaN = missing), [N][T][K] variances, [N][T], [N]
@@ -163,7 +152,9 @@ struct pyvb_lds {
 
 // ---- launchers implemented in the kernel translation units ----
 int launch_prep(pyvb_lds* h);
-int launch_sweep(pyvb_lds* h, int direction, bool keep_x = true);
+// A sweep reads X[src] and writes X[1 - src]; read_cache: a backward sweep that starts from the c_t a forward one left in U.
+// keep_x = false: a forward sweep whose states nobody reads (the backward one follows and reads c_t).
+int launch_sweep(pyvb_lds* h, int direction, int src, bool read_cache, bool keep_x);
 int launch_step(pyvb_lds* h, int t);
 int launch_syy(pyvb_lds* h);
 int launch_permute(pyvb_lds* h, const double* src, double* dst, int to_internal);
@@ -178,7 +169,8 @@ int launch_elbo(pyvb_lds* h, hipStream_t stream = nullptr);                     
 int launch_elbo_sum(pyvb_lds* h, double* out = nullptr, hipStream_t stream = nullptr);    // out: h->elbo_sum unless given
 // k_big.hip
 int launch_prep_big(pyvb_lds* h);
-int launch_sweep_big(pyvb_lds* h, int direction);
+int big_prepare_kernels();              // once per device, before the first launch: the dynamic-LDS limits of k_prep_big, k_cols_big
+int launch_sweep_big(pyvb_lds* h, int direction, int src, bool cached);
 int launch_step_big(pyvb_lds* h, int t);
 int launch_stats_big(pyvb_lds* h);
 int launch_cols_big(pyvb_lds* h, int which, int c0, int c1, int fuse);
@@ -186,7 +178,7 @@ int launch_cols_big(pyvb_lds* h, int which, int c0, int c1, int fuse);
 int launch_wexpect(pyvb_lds* h);                    // Qbar, Rbar, lnd from Q_w, R_w
 int launch_dense_pre(pyvb_lds* h);                  // QA, RC, trA, trC
 int launch_cols_dense(pyvb_lds* h, int which, int c0, int c1);
-int launch_wresid(pyvb_lds* h, int which, int update);
+int launch_wresid(pyvb_lds* h, int which, int update, bool use_sg);      // use_sg: SG holds the sums over the columns (LdsState.sg_valid)
 int launch_syy_full(pyvb_lds* h);
 int launch_elbo_dense(pyvb_lds* h, hipStream_t stream = nullptr);
 int launch_colvar_to_cov(pyvb_lds* h);              // A_var/C_var (diagonals) -> A_cov/C_cov
@@ -197,7 +189,7 @@ int launch_cov_convert(pyvb_lds* h, int which, double* dense, int n0, int count,
 int launch_wexpect_big(pyvb_lds* h);
 int launch_dense_pre_big(pyvb_lds* h);
 int launch_cols_dense_big(pyvb_lds* h, int which, int c0, int c1);
-int launch_wresid_big(pyvb_lds* h, int which, int update);
+int launch_wresid_big(pyvb_lds* h, int which, int update, bool use_sg);
 int launch_syy_full_big(pyvb_lds* h);
 // k_missing.hip
 int launch_missing_init(pyvb_lds* h, const double* Yq0, const double* Yrowvar0);     // device pointers or null
@@ -217,10 +209,6 @@ int pyvb_comm_create(pyvb_comm** comm, const char id[128], int rank, int world);
 int pyvb_comm_create_host(pyvb_comm** comm, pyvb_host_allreduce_fn fn, void* user);
 void pyvb_comm_free(pyvb_comm* comm);
 int pyvb_allreduce_f64(pyvb_comm* comm, double* buf, size_t count, hipStream_t stream);
-
-void pyvb_set_error(const char* fmt, ...);
-int pyvb_hip_fail(hipError_t e, const char* what, const char* file, int line);
-#define HIPCHK(x) do { hipError_t _e = (x); if (_e != hipSuccess) return pyvb_hip_fail(_e, #x, __FILE__, __LINE__); } while (0)
 
 // Timed launch bracket.  When timing is on, an event pair from the handle's pool is recorded
 // around the launch on the handle's stream; nothing synchronises until pyvb_lds_timing_get(),

@@ -1,0 +1,160 @@
+// Host-side plumbing shared by the two handle types (pyvb_lds: api.hip, pyvb_pca: api_pca.hip): argument and error checks,
+// the record of the device buffers a handle owns, copies on a handle's stream -- and the state each handle tracks on the host
+// about what is current on the device, with the events that change it.  Kernel files read this state; only the API files
+// (through the events below) write it.  DESIGN.md, "What is current: the host-side state of a handle", has the dependency table.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <cstddef>
+#include <cstring>
+#include <vector>
+#include "../../include/pyvb_hip.h"
+
+void pyvb_set_error(const char* fmt, ...);
+int pyvb_hip_fail(hipError_t e, const char* what, const char* file, int line);
+#define HIPCHK(x) do { hipError_t _e = (x); if (_e != hipSuccess) return pyvb_hip_fail(_e, #x, __FILE__, __LINE__); } while (0)
+#define ARGCHK(cond, msg) do { if (!(cond)) { pyvb_set_error("%s", msg); return PYVB_E_ARG; } } while (0)
+// first line of an entry point: a handle, and its device current for this thread
+#define ENTER_DEVICE(h) do { ARGCHK(h, "handle is NULL"); HIPCHK(hipSetDevice((h)->device)); } while (0)
+// inside *_create (an int rc in scope): a failure destroys the half-built handle h with DESTROY and returns the code
+#define CREATE_TRY(x, DESTROY, h) do { rc = (x); if (rc != PYVB_OK) { DESTROY(h); return rc; } } while (0)
+#define CREATE_TRYHIP(x, DESTROY, h) do { hipError_t _e = (x); if (_e != hipSuccess) { rc = pyvb_hip_fail(_e, #x, __FILE__, __LINE__); DESTROY(h); return rc; } } while (0)
+
+// Every device allocation made for a handle, recorded when it is made; *_destroy walks the record.
+struct DeviceBuffers {
+    std::vector<void*> owned;
+    int alloc(void** p, size_t bytes, int fill_byte = 0) {
+        HIPCHK(hipMalloc(p, bytes));
+        owned.push_back(*p);
+        HIPCHK(hipMemset(*p, fill_byte, bytes));
+        return PYVB_OK;
+    }
+    int zeros(double** p, size_t n) { return alloc((void**)p, n * sizeof(double)); }
+    void release(void* p) {         // a buffer replaced during the handle's life
+        for (size_t i = 0; i < owned.size(); ++i)
+            if (owned[i] == p) { (void)hipFree(p); owned[i] = owned.back(); owned.pop_back(); return; }
+    }
+    void release_all() { for (void* p : owned) (void)hipFree(p); owned.clear(); }
+};
+
+// copies on a handle's stream; a null host pointer means "not asked for"
+static inline int to_device(hipStream_t s, double* dst, const double* src, size_t n) {
+    if (!src) return PYVB_OK;
+    HIPCHK(hipMemcpyAsync(dst, src, n * sizeof(double), hipMemcpyHostToDevice, s));
+    return PYVB_OK;
+}
+static inline int to_host(hipStream_t s, double* dst, const double* src, size_t n) {
+    if (!dst) return PYVB_OK;
+    HIPCHK(hipMemcpyAsync(dst, src, n * sizeof(double), hipMemcpyDeviceToHost, s));
+    return PYVB_OK;
+}
+
+// ---- pyvb_lds: what is current ---------------------------------------------------------------------------------------------
+// One field per derived buffer (or per property of the states), each with what it describes and which events drop it; the
+// ensure_* helpers of api.hip recompute a buffer and set its field.  Every entry point of api.hip ends in one or more events.
+struct LdsState {
+    int T;
+    int cur;                    // X[cur] holds the states; a sweep reads it and writes the other (sweep_ran flips)
+    bool gains_valid;           // gains, Sigma_new / qld_x_new / lnd_x_new (k_prep; Wishart: QA, RC, trA, trC) belong to the current
+                                // parameter posteriors.  Dropped by every event that changes a parameter (params_touched).
+    bool expect_valid;          // Wishart: Qbar, Rbar, lnd belong to the current Q_w, R_w, qv.  Dropped by noise_changed, noise_updated.
+    bool stats_valid;           // stats, mom are sums over the current states and outputs.  Dropped by x_changed, outputs_changed,
+                                // sweep_ran, classes_set (the moments hold the covariance classes).
+    bool resQ_valid, resR_valid;    // resQ / resR (Wishart: RQ / RR) belong to the statistics AND the columns of A / C.  Dropped with
+                                // stats_valid, and by parameters_changed, columns_changed, columns_updated (of that matrix).
+    bool sg_valid[2];           // Wishart: SG[0 / 1] sums every column covariance of A / C as it is now, weighted with the current
+                                // statistics.  Set by columns_updated over all columns; dropped with stats_valid, by a partial
+                                // columns_updated and by columns_changed.  Never set for the Gamma kinds (nothing reads it there).
+    bool u_valid;               // U holds c_t = F mu_{t-1} + G y_t of the current gains, outputs and of X as the last forward sweep left
+                                // it: the backward sweep right behind reads it.  Set by a forward sweep_ran, dropped by everything else
+                                // that changes gains, outputs or states.
+    bool sxx_valid;             // sxx is the interior sum of mu mu^T of the current states (written by a backward sweep that read U; not
+                                // in the 128-wide class).  Dropped by x_changed and by every other sweep_ran.
+    unsigned char* fresh;       // [T] X_t updated since gains were last formed; fresh_count of them.  All of them: the classes of
+    int fresh_count;            // Sigma_new describe every X_t and are adopted (api.hip: adopt_classes).  Reset by gains_formed.
+    bool mixed_cov;             // the X_t hold covariances of different parameter generations: a parameter changed while only some were
+                                // fresh.  Cleared when all are fresh again.
+    bool classes_valid;         // Sigma / qld_x describe the X_t (after the first complete sweep, or classes_set)
+    bool lnd_x_pending;         // Sigma came from the caller (classes_set): lnd_x is formed from it when first needed (ensure_lnd_x)
+    int x_park;                 // the X buffer that holds the rows of the switched-off replicates (they sit out the ping-pong)
+    bool cls_parked_other;      // their Sigma / qld_x / lnd_x are in the *_new set (adopt_classes swapped since)
+
+    // -- the events.  Shared parts first.
+    void params_touched() {
+        if (gains_valid && fresh_count != 0 && fresh_count != T) mixed_cov = true;
+        gains_valid = false;
+        u_valid = false;
+    }
+    void sums_stale() { stats_valid = false; resQ_valid = resR_valid = false; sg_valid[0] = sg_valid[1] = false; }
+
+    // Priors, known entries, or posterior means / variances / rates given by the caller.  (pyvb_lds_set_priors used to drop sg_valid
+    // too, for the Gamma kinds only, where the field is never set: no difference.  SG does not depend on priors.)
+    void parameters_changed() { params_touched(); resQ_valid = resR_valid = false; }
+    // the same, where the column covariances themselves were replaced (Wishart: set_column_cov, set_state with variances,
+    // set_column_observations, which zeroes those of known columns; for the Gamma kinds sg_valid is false already)
+    void columns_changed() { parameters_changed(); sg_valid[0] = sg_valid[1] = false; }
+    // Q_w / R_w / qv given by the caller.  The residual matrices RQ, RR are sums over states and columns only and stay;
+    // pyvb_lds_set_wishart_priors, which also changes w0 (added to them by the update), raises parameters_changed beside this.
+    void noise_changed() { expect_valid = false; params_touched(); }
+    // Q / R (which: 0, 1, 2 = both) updated by a launch that also left their residuals current
+    void noise_updated(int which) {
+        if (which != 1) resQ_valid = true;
+        if (which != 0) resR_valid = true;
+        noise_changed();
+    }
+    // columns [c0, c1) of A / C / both updated from the current statistics; sums_all: Wishart, and every column went through
+    void columns_updated(int which, bool sums_all) {
+        if (which != 1) { sg_valid[0] = sums_all; resQ_valid = false; }
+        if (which != 0) { sg_valid[1] = sums_all; resR_valid = false; }
+        params_touched();
+    }
+    void outputs_changed() { u_valid = false; sums_stale(); }           // Y replaced or imputed
+    void x_changed() { u_valid = false; sxx_valid = false; sums_stale(); }      // states replaced or one updated; also a new time split,
+                                                                                // which re-shapes sxx and the parts U was written for
+    void classes_set() { lnd_x_pending = true; classes_valid = true; sums_stale(); }
+    void gains_formed() { gains_valid = true; memset(fresh, 0, T); fresh_count = 0; }
+    // X_t / every X_t updated under the current gains.  True: all are fresh now and the caller adopts the new classes.
+    bool node_fresh(int t) {
+        if (fresh[t]) return false;
+        fresh[t] = 1;
+        if (++fresh_count < T) return false;
+        mixed_cov = false;
+        return true;
+    }
+    bool all_fresh() {
+        const bool adopt = fresh_count < T;     // Sigma_new holds the classes of the current parameters exactly when some node is not fresh yet
+        if (adopt) { memset(fresh, 1, T); fresh_count = T; }
+        mixed_cov = false;
+        return adopt;
+    }
+    // a sweep wrote X[1 - cur]; read_cache: it was the backward kernel that reads U; fused_sxx: that kernel also writes sxx
+    void sweep_ran(int direction, bool read_cache, bool fused_sxx) {
+        cur = 1 - cur;
+        sxx_valid = read_cache && fused_sxx;
+        u_valid = direction == PYVB_FORWARD;
+        sums_stale();
+    }
+    void classes_adopted(bool some_parked) {
+        lnd_x_pending = false;
+        classes_valid = true;
+        if (some_parked) cls_parked_other = !cls_parked_other;      // the parked rows did not move with the pointers
+    }
+    void parked_here() { x_park = cur; cls_parked_other = false; }      // settled, or the mask changed: parked rows are in the current buffers
+};
+
+// ---- pyvb_pca: what is current ---------------------------------------------------------------------------------------------
+struct PcaState {
+    bool full_valid, lin_valid; // stats: every sum current / at least sum x and sum z current.  Dropped by every setter of data or state;
+                                // full_valid also by the deferred Z update and the X_0 step, which keep only the linear sums current.
+    bool res_valid;             // scal[PS_RES] is the residual of the current W, Z, X, Mu (nothing but Beta updated since)
+    bool z_pending;             // [z.update() for z in Zs] has been requested and its operands (Gz, g0, sum z) are set, but the
+                                // rows of Z are not written yet: the next pass over X does it on its way (k_pca_pass12)
+    bool z0_done;               // while z_pending: Xs[0].update() has run and stored z_0 itself
+    bool xlazy; long vlo, vhi;  // the missing entries of rows [vlo, vhi) are not in X: they stand for <W>_x z_n + <Mu>_x
+                                // (k_pca_pass12<.., LAZY>, k_pca_pairs); k_pca_materialize puts them there
+    int part_chunks;            // chunks of the partial statistics in `part` now (the partition of the sweep that wrote them)
+
+    void inputs_changed() { full_valid = lin_valid = false; res_valid = false; }
+    void z_requested() { z_pending = true; z0_done = false; }
+    void z_written() { z_pending = false; z0_done = false; }
+    void linear_step() { full_valid = false; res_valid = false; }      // lin_valid stays: sum x and sum z were kept current
+};

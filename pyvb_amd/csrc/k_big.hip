@@ -168,70 +168,10 @@ __global__ void __launch_bounds__(256) k_gy_big(BigGyArgs a) {
     }
 }
 
-// Round 4: the same product with EIGHT wavefronts, one row tile each, two to a SIMD -- and the block of y shared through LDS.
-// At one wavefront per SIMD a chain of dependent MFMAs sustains 70 % of the pipe (profiles/r01/microbench_f64.txt; k_gy_big: 69 %
-// busy by the counters), with two it sustains 92 %; what stopped round 3's eight-wavefront form (11.0 against 7.3 ms) was that every
-// wavefront fetched all of y from memory.  Here the workgroup's 512 threads fetch a block of 16 time steps once (a block ahead, into
-// registers, then into the other of two LDS buffers: one barrier per block) and every wavefront reads its B operands from there.
-// Measured at N = 1024, T = 10^4, D = K = 128: lds_d128 49.24 ms against 49.41 with k_gy_big on the same box -- the product moves
-// 21 GB (Y in, G y_t out) in 7.5 ms, and reads and writes together do not pass 5 TB/s on this part (profiles/microbench/hbm_read.hip:
-// a copy makes 2.4-2.8 TB/s each way): it is the traffic of the c_t buffer, not the matrix pipe, that the kernel waits for.  Kept
-// behind PYVB_GY_BIG=8 with the tests of the class run through it once; k_gy_big stays the kernel in use.
-#define GY_LDY 130      // row stride of a y block in LDS: the 16 lanes of a 16-byte operand read fall into 64 different banks
-template <bool Y4>      // Y4: K a multiple of 4 -- a thread's four entries of a block are one 32-byte load
-__global__ void __launch_bounds__(512) k_gy_big8(BigGyArgs a) {
-    __shared__ double yl[2][16 * GY_LDY];
-    const int n = blockIdx.y, tid = threadIdx.x, w = tid >> 6, lane = tid & 63, c = lane & 15, q = lane >> 4;
-    if (!a.active[n]) return;
-    const int T = a.T, K = a.K;
-    const double* g = a.gains + (size_t)n * a.L.gains_total + a.L.oGp;
-    const double* Yn = a.Y + (size_t)n * T * K;
-    double* Un = a.U + (size_t)n * T * BDP;
-    double* const trash = a.trash + (size_t)n * 512 + 256;
-    double gr[BDS];
-#pragma unroll
-    for (int s = 0; s < BDS; ++s) gr[s] = g[((size_t)w * BDS + s) * 64 + lane];
-    // staging: thread -> time step srow of the block, entries scol .. scol + 3
-    const int srow = tid >> 5, scol = (tid & 31) * 4;
-    const int tb0 = 1 + blockIdx.x * a.nblk * 16;
-    d4 stage;
-    auto fetch = [&](int tb) {
-        const int t = tb + srow;
-        const double* yp = Yn + (size_t)(t <= T - 2 ? t : 1) * K;
-        if constexpr (Y4) {
-            const d4 v = *reinterpret_cast<const d4*>(yp + (scol < K ? scol : 0));
-            stage = scol < K ? v : d4{0.0, 0.0, 0.0, 0.0};
-        } else {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) { const double v = yp[scol + e < K ? scol + e : K - 1]; stage[e] = scol + e < K ? v : 0.0; }
-        }
-    };
-    auto put = [&](int buf) {
-        double* d = yl[buf] + srow * GY_LDY + scol;
-        *reinterpret_cast<d2*>(d) = d2{stage[0], stage[1]};
-        *reinterpret_cast<d2*>(d + 2) = d2{stage[2], stage[3]};
-    };
-    fetch(tb0); put(0);
-    __syncthreads();
-    for (int b = 0; b < a.nblk; ++b) {
-        const int tb = tb0 + b * 16;
-        if (tb > T - 2) break;                                  // block-uniform
-        const bool more = b + 1 < a.nblk && tb + 16 <= T - 2;
-        if (more) fetch(tb + 16);
-        const double* yb = yl[b & 1] + c * GY_LDY + 2 * q;      // B operand of step s = 2 i + j: y_t[8 i + 2 q + j], t = tb + c
-        d2 yv[BDS / 2];
-#pragma unroll
-        for (int i = 0; i < BDS / 2; ++i) yv[i] = *reinterpret_cast<const d2*>(yb + 8 * i);
-        d4 acc = d4{0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-        for (int s = 0; s < BDS; ++s) acc = MFMA(gr[s], yv[s >> 1][s & 1], acc);
-        const int t = tb + c;
-        double* ur = (t <= T - 2) ? Un + (size_t)t * BDP : trash;
-        *reinterpret_cast<d4*>(ur + (w * 4 + q) * 4) = acc;
-        if (more) put((b + 1) & 1);
-        __syncthreads();
-    }
-}
+// (An eight-wavefront form that shares the block of y through LDS, one row tile per wavefront and two wavefronts per SIMD, measured the
+// same: lds_d128 49.24 ms against 49.41 at N = 1024, T = 10^4, D = K = 128.  The product moves 21 GB (Y in, G y_t out) in 7.5 ms, and
+// reads and writes together do not pass 5 TB/s on this part (profiles/microbench/hbm_read.hip): it is the traffic of the c_t buffer,
+// not the matrix pipe, that the kernel waits for.)
 
 // The sweep proper.  The parameters are frozen between the two sweeps of an iteration, and the backward update
 //   mu_t <- B mu_{t+1}(new) + F mu_{t-1}(forward result) + G y_t
@@ -464,15 +404,14 @@ __global__ void __launch_bounds__(512 / NTW) k_sweep_big(BigSweepArgs a) {
     }
 }
 
-int launch_sweep_big(pyvb_lds* h, int direction) {
+// cached: a backward sweep right behind a forward one reads its c_t; anything else starts from G y_t
+int launch_sweep_big(pyvb_lds* h, int direction, int src, bool cached) {
     BigSweepArgs a;
-    a.Xold = h->X[h->cur]; a.Xnew = h->X[1 - h->cur]; a.Y = h->Y; a.gains = h->gains; a.warm = h->warm;
+    a.Xold = h->X[src]; a.Xnew = h->X[1 - src]; a.Y = h->Y; a.gains = h->gains; a.warm = h->warm;
     a.A_mean = h->A_mean; a.C_mean = h->C_mean; a.trash = h->trash; a.U = h->U;
     a.QA = h->dense ? h->QA : nullptr; a.RC = h->dense ? h->RC : nullptr;
     a.N = h->N; a.T = h->T; a.D = h->D; a.K = h->K; a.dir = direction; a.L = h->L; a.active = h->active;
     a.W = h->W; a.Uc = h->W > 1 ? h->U2 : h->U;
-    // a backward sweep right behind a forward one (h->u_valid) reads c_t; anything else starts from G y_t
-    const bool cached = direction == PYVB_BACKWARD && h->u_valid;
     const size_t lds = ((size_t)2 * BDS * 64 + 2 * BDP + (cached ? 0 : 3 * BDS * 64)) * sizeof(double);        // MODE 3: + the neighbour ring
     if (!cached && h->T > 2) {
         BigGyArgs ga;
@@ -482,13 +421,8 @@ int launch_sweep_big(pyvb_lds* h, int direction) {
         ga.nblk = blocks < 32 ? ((blocks + 1) & ~1) : 32;
         TimedLaunch tl(h, PYVB_K_GY);
         const dim3 grid((blocks + ga.nblk - 1) / ga.nblk, h->N);
-        static const bool four = [] { const char* e = getenv("PYVB_GY_BIG"); return !(e && e[0] == '8'); }();     // PYVB_GY_BIG=8: k_gy_big8 (measured the same: see there)
-        if (four) {
-            if ((h->K & 1) == 0) hipLaunchKernelGGL(k_gy_big<true>, grid, dim3(256), 0, h->stream, ga);
-            else hipLaunchKernelGGL(k_gy_big<false>, grid, dim3(256), 0, h->stream, ga);
-        }
-        else if ((h->K & 3) == 0) hipLaunchKernelGGL(k_gy_big8<true>, grid, dim3(512), 0, h->stream, ga);
-        else hipLaunchKernelGGL(k_gy_big8<false>, grid, dim3(512), 0, h->stream, ga);
+        if ((h->K & 1) == 0) hipLaunchKernelGGL(k_gy_big<true>, grid, dim3(256), 0, h->stream, ga);
+        else hipLaunchKernelGGL(k_gy_big<false>, grid, dim3(256), 0, h->stream, ga);
     }
     {
         TimedLaunch tl(h, direction == PYVB_FORWARD ? PYVB_K_SWEEP_FWD : PYVB_K_SWEEP_BWD);
@@ -538,7 +472,7 @@ __global__ void __launch_bounds__(128) k_step_big(BigStepArgs a) {
 
 int launch_step_big(pyvb_lds* h, int t) {
     BigStepArgs a;
-    a.X = h->X[h->cur]; a.Y = h->Y; a.gains = h->gains; a.A_mean = h->A_mean; a.C_mean = h->C_mean;
+    a.X = h->X[h->st.cur]; a.Y = h->Y; a.gains = h->gains; a.A_mean = h->A_mean; a.C_mean = h->C_mean;
     a.QA = h->dense ? h->QA : nullptr; a.RC = h->dense ? h->RC : nullptr;
     a.N = h->N; a.T = h->T; a.D = h->D; a.K = h->K; a.t = t; a.L = h->L; a.active = h->active;
     TimedLaunch tl(h, PYVB_K_STEP);
@@ -635,7 +569,7 @@ __global__ void __launch_bounds__(512) k_stats_big(BigStatsArgs a) {
 
 int launch_stats_big(pyvb_lds* h) {
     BigStatsArgs a;
-    a.X = h->X[h->cur]; a.Y = h->Y; a.part = h->stats; a.zeros = h->zeros;
+    a.X = h->X[h->st.cur]; a.Y = h->Y; a.part = h->stats; a.zeros = h->zeros;
     a.N = h->N; a.T = h->T; a.D = h->D; a.K = h->K; a.nchunk = h->nchunk; a.chunk_len = h->chunk_len; a.L = h->L; a.active = h->active;
     {
         TimedLaunch tl(h, PYVB_K_STATS);
@@ -1017,6 +951,7 @@ __global__ void __launch_bounds__(256) k_prep_big(BigPrepArgs a) {
 #endif
 }
 
+static constexpr size_t PREP_BIG_LDS = ((size_t)BDP * BLD + 4 * BDP + 2 * GJB_BUF + BDP) * sizeof(double);
 int launch_prep_big(pyvb_lds* h) {
     BigPrepArgs a;
     a.A_mean = h->A_mean; a.A_var = h->A_var; a.C_mean = h->C_mean; a.C_var = h->C_var;
@@ -1026,14 +961,9 @@ int launch_prep_big(pyvb_lds* h) {
     a.warm = h->warm; a.status = h->status;
     a.N = h->N; a.T = h->T; a.D = h->D; a.K = h->K; a.noise = h->noise; a.L = h->L; a.active = h->active;
     a.dense = h->dense ? 1 : 0; a.Qbar = h->Qbar; a.QA = h->QA; a.RC = h->RC; a.trA = h->trA; a.trC = h->trC;
-    const size_t lds = ((size_t)BDP * BLD + 4 * BDP + 2 * GJB_BUF + BDP) * sizeof(double);
-    if (!h->big_attr_prep) {           // per handle: the attribute belongs to the device the handle lives on
-        HIPCHK(hipFuncSetAttribute((const void*)k_prep_big, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        h->big_attr_prep = true;
-    }
     {
         TimedLaunch tl(h, PYVB_K_PREP);
-        hipLaunchKernelGGL(k_prep_big, dim3(h->N), dim3(256), lds, h->stream, a);
+        hipLaunchKernelGGL(k_prep_big, dim3(h->N), dim3(256), PREP_BIG_LDS, h->stream, a);
     }
     HIPCHK(hipGetLastError());
     return PYVB_OK;
@@ -1043,147 +973,11 @@ int launch_prep_big(pyvb_lds* h) {
 // columns of A and C, residuals, noise update
 // ======================================================================================================================
 // k_cols.hip for up to 128 rows, columns in order (Gauss-Seidel); fuse bit 0: residuals of the noise node, bit 1: and its update.
-// The rows of the matrix decouple (diagonal noise, diagonal column priors): a row belongs to TWO neighbouring lanes, each with one
-// half of it (64 columns) in registers; a column's update is a dot product of the row with a row of G -- the two halves meet in
-// one cross-lane add -- and a write of one register, which for a run-time column index is a chain of 64 selects on the lane that
-// owns that half.  G sits in LDS (128 KB, read-only after the start), so the column loop has no barrier at all; what a column needs
-// from global memory (its prior, the linear term, a known entry) is fetched two columns ahead; the block sums of a column (the log
-// determinant of its precision, its number of known entries) are wavefront sums left in LDS and added up after the loop.
-// (The first version kept the matrix as [col][row] in LDS, one thread per row: two wavefronts per CU, five barriers and four
-// dependent global loads per column -- 7.4 ms at N = 1024, D = K = 128.)
-#define CB_H 64         // columns per lane
-__global__ void __launch_bounds__(256) k_cols_big_rows(ParamArgs a) {
-    extern __shared__ double lds[];
-    double* Gl = lds;                       // [128][128] zero padded
-    double* plp = Gl + BDP * BDP;           // [4 wavefronts][128 columns] sums of log precision
-    double* pkn = plp + 4 * BDP;            // [4][128] numbers of known entries
-    double* gd = pkn + 4 * BDP;             // [128] the diagonal of G
-    double* red = gd + BDP;                 // [4]
-    const int WHICH = a.which0 + blockIdx.y, n = blockIdx.x, tid = threadIdx.x, D = a.D, K = a.K;
-    if (!a.active[n]) return;
-    const int rows = WHICH == 0 ? D : K;
-    const int row = tid >> 1, half = tid & 1, lane = tid & 63, wave = tid >> 6;
-    double* M = (WHICH == 0 ? a.A_mean : a.C_mean) + (size_t)n * rows * D;
-    double* V = (WHICH == 0 ? a.A_var : a.C_var) + (size_t)n * D * rows;
-    double* qld = (WHICH == 0 ? a.qld_A : a.qld_C) + (size_t)n * D;
-    double* lnd = (WHICH == 0 ? a.lnd_A : a.lnd_C) + (size_t)n * D;
-    const double* pm = WHICH == 0 ? a.pri.A_pm : a.pri.C_pm;    // [row][col]
-    const double* pp = WHICH == 0 ? a.pri.A_pp : a.pri.C_pp;    // [col][row]
-    const double* obs = WHICH == 0 ? a.pri.A_obs : a.pri.C_obs; // [row][col], NaN = not known
-    const double* mo = a.mom + (size_t)n * mom_total(D, K);
-    const double* G = mo + (WHICH == 0 ? MOM_GA(D, K) : MOM_GC(D, K));
-    const double* H = mo + (WHICH == 0 ? MOM_HA(D, K) : MOM_HC(D, K));
-    const bool live = row < rows;
-    const int lr = live ? row : 0;
-    for (int idx = tid; idx < BDP * BDP; idx += 256) {
-        const int i = idx >> 7, j = idx & 127;
-        Gl[idx] = (i < D && j < D && i != j) ? G[(size_t)i * D + j] : 0.0;            // without the diagonal: a column's own entry does
-    }                                                                                   // not enter its update; gd holds it
-    if (tid < BDP) gd[tid] = tid < D ? G[(size_t)tid * D + tid] : 0.0;
-    double Mr[CB_H];                        // columns 64 half .. 64 half + 63 of this row
-#pragma unroll
-    for (int j = 0; j < CB_H; ++j) { const int col = CB_H * half + j; Mr[j] = (live && col < D) ? M[(size_t)lr * D + col] : 0.0; }
-    const double lam = live ? (WHICH == 0 ? a.Q_a[(size_t)n * D + lr] / a.Q_b[(size_t)n * D + lr]
-                                          : a.R_a[(size_t)n * K + lr] / a.R_b[(size_t)n * K + lr]) : 0.0;
-    __syncthreads();
-    // the dot product of this row with row i of G without its diagonal entry: this lane's half, then the neighbour's
-    auto rowdot = [&](int i) {
-        const double* gr = Gl + i * BDP + CB_H * half;
-        double acc0 = 0.0, acc1 = 0.0;
-#pragma unroll
-        for (int j = 0; j < CB_H; j += 2) {
-            const d2 g = *reinterpret_cast<const d2*>(gr + j);
-            acc0 = __builtin_fma(Mr[j], g[0], acc0);
-            acc1 = __builtin_fma(Mr[j + 1], g[1], acc1);
-        }
-        const double s = acc0 + acc1;
-        return s + __shfl_xor(s, 1, 64);
-    };
-    struct ColIn { double p0, pmv, hv, ob; };
-    auto fetch = [&](int i) {
-        ColIn c;
-        const int ic = i < D ? i : D - 1;
-        c.p0 = pp[(size_t)ic * rows + lr]; c.pmv = pm[(size_t)lr * D + ic]; c.hv = H[(size_t)lr * D + ic]; c.ob = obs[(size_t)lr * D + ic];
-        return c;
-    };
-    ColIn c0 = fetch(a.c0), c1 = fetch(a.c0 + 1);
-    for (int i = a.c0; i < a.c1; ++i) {
-        const ColIn cur = c0;
-        c0 = c1; c1 = fetch(i + 2);
-        const double dot = rowdot(i);
-        const double gii = gd[i];
-        const double prec = cur.p0 + lam * gii;                                         // qprec  gaussian.py:117
-        double var = 1.0 / prec;                                                        // qcov   gaussian.py:118-119
-        double val = (cur.p0 * cur.pmv + lam * (cur.hv - dot)) * var;                   // qmu :122-123
-        // known entries (Gaussian.observe on a column, LDS_knowns_in_A.py:73-74): conditioning a diagonal Gaussian on them
-        // (gaussian.py:125-134) pins those entries and leaves the others alone; a column whose entries are all known is
-        // never changed (gaussian.py:109-110)
-        const bool known = live && (cur.ob == cur.ob);
-        if (known) { val = cur.ob; var = 0.0; }
-        const bool mine = live && half == 0;
-        const double lp = wave_sum(mine ? log(prec) : 0.0);
-        const double nk = wave_sum((mine && known) ? 1.0 : 0.0);
-        if (lane == 0) { plp[wave * BDP + i] = lp; pkn[wave * BDP + i] = nk; }
-        if (mine) V[(size_t)i * rows + row] = var;
-        if (live && half == (i >> 6)) {
-            const int jj = i & (CB_H - 1);
-#pragma unroll
-            for (int j = 0; j < CB_H; ++j) Mr[j] = (j == jj) ? val : Mr[j];
-        }
-    }
-    __syncthreads();
-    if (tid >= a.c0 && tid < a.c1 && tid < BDP) {
-        const double lp = ((plp[tid] + plp[BDP + tid]) + plp[2 * BDP + tid]) + plp[3 * BDP + tid];
-        const double nk = ((pkn[tid] + pkn[BDP + tid]) + pkn[2 * BDP + tid]) + pkn[3 * BDP + tid];
-        if ((int)nk < rows) { qld[tid] = 0.5 / (0.5 * lp); lnd[tid] = -lp; }          // quirk Q1, gaussian.py:120: of the whole precision
-    }
-    if (a.c0 < a.c1 && live) {
-#pragma unroll
-        for (int j = 0; j < CB_H; ++j) { const int col = CB_H * half + j; if (col >= a.c0 && col < a.c1 && col < D) M[(size_t)row * D + col] = Mr[j]; }
-    }
-    if (a.fuse & 1) {
-        // res[k] = 1/2 own[k] + 1/2 (sum_ij M[k,i] G[i,j] M[k,j] + sum_i var_i[k] G[i,i]) - sum_i H[k,i] M[k,i]   (node.py:260-271)
-        double e = 0.0, hm = 0.0;
-        auto fetch2 = [&](int i, double& vv, double& hh) { const int ic = i < D ? i : D - 1; vv = V[(size_t)ic * rows + lr]; hh = H[(size_t)lr * D + ic]; };
-        __syncthreads();                    // this workgroup's variances of all columns are in memory (written by the lanes with half == 0)
-        double v0, h0, v1, h1;
-        fetch2(0, v0, h0); fetch2(1, v1, h1);
-        for (int i = 0; i < D; ++i) {
-            const double vi = v0, hi = h0;
-            v0 = v1; h0 = h1; fetch2(i + 2, v1, h1);
-            const int jj = i & (CB_H - 1);
-            double mi = 0.0;
-#pragma unroll
-            for (int j = 0; j < CB_H; ++j) mi = (j == jj) ? Mr[j] : mi;
-            mi = __shfl(mi, (lane & ~1) | (i >> 6), 64);                                // from the lane that owns column i of this row
-            const double s = rowdot(i) + mi * gd[i];
-            e += mi * s + vi * gd[i];
-            hm += hi * mi;
-        }
-        const double own = WHICH == 0 ? mo[MOM_DP(D, K) + lr] : a.Syy[(size_t)n * K + lr];
-        double r = 0.5 * own + 0.5 * e - hm;
-        const bool mine = live && half == 0;
-        if (mine) (WHICH == 0 ? a.resQ : a.resR)[(size_t)n * rows + row] = r;
-        if (a.fuse & 2) {
-            const double* b0 = WHICH == 0 ? a.pri.Q_b0 : a.pri.R_b0;
-            double* qb = (WHICH == 0 ? a.Q_b : a.R_b) + (size_t)n * rows;
-            if (a.noise == PYVB_NOISE_GAMMA) {
-                double t = wave_sum(mine ? r : 0.0);
-                __syncthreads();
-                if (lane == 0) red[wave] = t;
-                __syncthreads();
-                t = ((red[0] + red[1]) + red[2]) + red[3];
-                if (mine) qb[row] = b0[0] + t;
-            } else if (mine) {
-                qb[row] = b0[row] + r;
-            }
-        }
-    }
-}
-
-// ---- Round 4: the same pass on the matrix cores, blocked.
-// What paced k_cols_big_rows (3.9 ms at N = 1024, D = K = 128, no MFMA at all) is that every column costs every wavefront a pass over
-// a row of G in LDS (the broadcast reads of four wavefronts: ~1000 LDS cycles per column) and a 64-deep select chain.  Here a wavefront
+// The rows of the matrix decouple (diagonal noise, diagonal column priors), and G sits in LDS (128 KB, read-only after the start).
+// The pass runs on the matrix cores, blocked.  (Its predecessor gave a row to two neighbouring lanes, each with 64 columns in
+// registers, and formed a column's update as a dot product of the row with a row of G: no MFMA at all, and every column cost every
+// wavefront a pass over a row of G in LDS -- the broadcast reads of four wavefronts, ~1000 LDS cycles per column -- and a 64-deep select
+// chain: 3.9 ms at N = 1024, D = K = 128, lds_d128 51.80 against 49.02 ms, profiles/r04/cols_big_stamps.txt.)  Here a wavefront
 // owns 32 ROWS of the matrix outright (row tiles 2w, 2w+1) and keeps, in MFMA accumulator layout (lane (q, c), register e of tile
 // (m, nn) = element (16 m + 4 e + q, 16 nn + c)),
 //     Mx  the matrix itself, and
@@ -1194,7 +988,7 @@ __global__ void __launch_bounds__(256) k_cols_big_rows(ParamArgs a) {
 // lane), and when the block is done its 32 x 16 panel of changes updates S for the other column tiles by MFMA (panel through 4 KB
 // of the wavefront's own LDS into A-operand order).  No workgroup barrier in the pass; precisions, variances, logarithms are
 // elementwise per block.  The residual of the noise node, sum_i M (S + M g_ii) + var g_ii, is elementwise on S = M_new G_off, formed afresh.
-// Same formulas, other summation order than k_cols_big_rows (kept: PYVB_COLS_BIG=rows).
+// Same formulas, other summation order than that predecessor.
 #define CBP 17      // row stride of a wavefront's panel
 __global__ void __launch_bounds__(256) k_cols_big(ParamArgs a) {
     extern __shared__ double lds[];
@@ -1535,20 +1329,20 @@ __global__ void __launch_bounds__(256) k_cols_big(ParamArgs a) {
 #endif
 }
 
+static constexpr size_t COLS_BIG_LDS = ((size_t)BDP * BDP + 9 * BDP + 8 + 4 * 32 * CBP) * sizeof(double);
 int launch_cols_big(pyvb_lds* h, int which, int c0, int c1, int fuse) {
     ParamArgs a = make_args(h);
     a.c0 = c0; a.c1 = c1; a.which0 = which == 1 ? 1 : 0; a.fuse = fuse;
-    static const bool by_rows = [] { const char* e = getenv("PYVB_COLS_BIG"); return e && e[0] == 'r'; }();     // the kernel of round 3, for comparison
-    const size_t lds_rows = ((size_t)BDP * BDP + 9 * BDP + 8) * sizeof(double);
-    const size_t lds = ((size_t)BDP * BDP + 9 * BDP + 8 + 4 * 32 * CBP) * sizeof(double);
-    if (!h->big_attr_cols) {
-        HIPCHK(hipFuncSetAttribute((const void*)k_cols_big_rows, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_rows));
-        HIPCHK(hipFuncSetAttribute((const void*)k_cols_big, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        h->big_attr_cols = true;
-    }
     TimedLaunch tl(h, PYVB_K_PARAMS);
-    if (by_rows) hipLaunchKernelGGL(k_cols_big_rows, dim3(h->N, which == 2 ? 2 : 1), dim3(256), lds_rows, h->stream, a);
-    else hipLaunchKernelGGL(k_cols_big, dim3(h->N, which == 2 ? 2 : 1), dim3(256), lds, h->stream, a);
+    hipLaunchKernelGGL(k_cols_big, dim3(h->N, which == 2 ? 2 : 1), dim3(256), COLS_BIG_LDS, h->stream, a);
     HIPCHK(hipGetLastError());
+    return PYVB_OK;
+}
+
+// The two kernels above that need more than 64 KB of dynamic LDS: the limit is raised once per device, from handle creation
+// (the attribute belongs to the current device).
+int big_prepare_kernels() {
+    HIPCHK(hipFuncSetAttribute((const void*)k_prep_big, hipFuncAttributeMaxDynamicSharedMemorySize, (int)PREP_BIG_LDS));
+    HIPCHK(hipFuncSetAttribute((const void*)k_cols_big, hipFuncAttributeMaxDynamicSharedMemorySize, (int)COLS_BIG_LDS));
     return PYVB_OK;
 }

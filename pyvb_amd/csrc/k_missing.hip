@@ -293,7 +293,7 @@ __global__ void __launch_bounds__(256) k_missing_ent_dense(MissArgs a) {
 
 static MissArgs make_margs(pyvb_lds* h) {
     MissArgs a;
-    a.Y = h->Y; a.Yobs = h->Yobs; a.Yvar = h->Yvar; a.Yqld = h->Yqld; a.X = h->X[h->cur]; a.C_mean = h->C_mean;
+    a.Y = h->Y; a.Yobs = h->Yobs; a.Yvar = h->Yvar; a.Yqld = h->Yqld; a.X = h->X[h->st.cur]; a.C_mean = h->C_mean;
     a.R_a = h->R_a; a.R_b = h->R_b; a.Syy = h->Syy; a.Yent = h->Yent; a.Yq0 = nullptr; a.Yrowvar0 = nullptr;
     a.Ylnd = h->Ylnd; a.YentX = h->YentX;
     a.N = h->N; a.T = h->T; a.K = h->K; a.D = h->D; a.DP = h->L.DP; a.active = h->active;

@@ -425,9 +425,9 @@ __global__ void __launch_bounds__(64) k_step(StepArgs a) {
 }
 
 template <int DT, int KT>
-static int launch_sweep_t(pyvb_lds* h, const SweepArgs& a) {
+static int launch_sweep_t(pyvb_lds* h, const SweepArgs& a, bool read_cache) {
     const bool full = h->D == 16 * DT && h->K == 16 * KT;
-    const int mode = a.dir == PYVB_FORWARD ? 1 : (h->u_valid ? 2 : 0);
+    const int mode = a.dir == PYVB_FORWARD ? 1 : (read_cache ? 2 : 0);      // MODE 2 reads c_t from U and writes the interior Sxx (h->sxx)
 #define PYVB_SWEEP_CASE(F, M) do { if (h->W > 1) hipLaunchKernelGGL((k_sweep<DT, KT, F, M, true>), dim3(h->N, h->W), dim3(64), 0, h->stream, a); \
                                    else hipLaunchKernelGGL((k_sweep<DT, KT, F, M, false>), dim3(h->N), dim3(64), 0, h->stream, a); } while (0)
     if (full) { if (mode == 1) PYVB_SWEEP_CASE(true, 1); else if (mode == 2) PYVB_SWEEP_CASE(true, 2); else PYVB_SWEEP_CASE(true, 0); }
@@ -436,42 +436,31 @@ static int launch_sweep_t(pyvb_lds* h, const SweepArgs& a) {
     return PYVB_OK;
 }
 
-int launch_sweep(pyvb_lds* h, int direction, bool keep_x) {
-    if (h->big) {       // k_big.hip: every state is written (keep_x ignored), no fused Sxx; the c_t cache as below
-        int rc = launch_sweep_big(h, direction);
-        if (rc) return rc;
-        h->cur = 1 - h->cur;
-        h->sxx_valid = false;
-        h->u_valid = (direction == PYVB_FORWARD);
-        return PYVB_OK;
-    }
+int launch_sweep(pyvb_lds* h, int direction, int src, bool read_cache, bool keep_x) {
+    if (h->big) return launch_sweep_big(h, direction, src, read_cache);      // k_big.hip: every state is written (keep_x ignored), no fused Sxx
     SweepArgs a;
     a.keep_x = (keep_x || direction != PYVB_FORWARD) ? 1 : 0;
     a.W = h->W;
-    a.Xold = h->X[h->cur]; a.Xnew = h->X[1 - h->cur]; a.Y = h->Y; a.gains = h->gains; a.warm = h->warm;
+    a.Xold = h->X[src]; a.Xnew = h->X[1 - src]; a.Y = h->Y; a.gains = h->gains; a.warm = h->warm;
     a.trash = h->trash; a.U = h->U; a.Sxx = h->sxx; a.A_mean = h->A_mean; a.C_mean = h->C_mean;
     a.QA = h->dense ? h->QA : nullptr; a.RC = h->dense ? h->RC : nullptr;
     a.N = h->N; a.T = h->T; a.D = h->D; a.K = h->K; a.dir = direction; a.L = h->L; a.active = h->active;
     {
         TimedLaunch tl(h, direction == PYVB_FORWARD ? PYVB_K_SWEEP_FWD : PYVB_K_SWEEP_BWD);
         switch (h->L.DT * 10 + h->L.KT) {
-            case 11: launch_sweep_t<1, 1>(h, a); break;
-            case 12: launch_sweep_t<1, 2>(h, a); break;
-            case 14: launch_sweep_t<1, 4>(h, a); break;
-            case 21: launch_sweep_t<2, 1>(h, a); break;
-            case 22: launch_sweep_t<2, 2>(h, a); break;
-            case 24: launch_sweep_t<2, 4>(h, a); break;
-            case 41: launch_sweep_t<4, 1>(h, a); break;
-            case 42: launch_sweep_t<4, 2>(h, a); break;
-            case 44: launch_sweep_t<4, 4>(h, a); break;
+            case 11: launch_sweep_t<1, 1>(h, a, read_cache); break;
+            case 12: launch_sweep_t<1, 2>(h, a, read_cache); break;
+            case 14: launch_sweep_t<1, 4>(h, a, read_cache); break;
+            case 21: launch_sweep_t<2, 1>(h, a, read_cache); break;
+            case 22: launch_sweep_t<2, 2>(h, a, read_cache); break;
+            case 24: launch_sweep_t<2, 4>(h, a, read_cache); break;
+            case 41: launch_sweep_t<4, 1>(h, a, read_cache); break;
+            case 42: launch_sweep_t<4, 2>(h, a, read_cache); break;
+            case 44: launch_sweep_t<4, 4>(h, a, read_cache); break;
             default: pyvb_set_error("unsupported tile shape"); return PYVB_E_ARG;
         }
     }
     HIPCHK(hipGetLastError());
-    h->cur = 1 - h->cur;
-    // U holds c_t for the current gains and for THIS forward result; any other change of X drops it
-    h->sxx_valid = direction == PYVB_BACKWARD && h->u_valid;     // that launch was the MODE 2 kernel: h->sxx is Sxx of the new states
-    h->u_valid = (direction == PYVB_FORWARD);
     return PYVB_OK;
 }
 
@@ -518,7 +507,7 @@ int launch_carry(pyvb_lds* h, const double* src, double* dst, size_t per) {
 int launch_step(pyvb_lds* h, int t) {
     if (h->big) return launch_step_big(h, t);
     StepArgs a;
-    a.X = h->X[h->cur]; a.Y = h->Y; a.gains = h->gains; a.A_mean = h->A_mean; a.C_mean = h->C_mean;
+    a.X = h->X[h->st.cur]; a.Y = h->Y; a.gains = h->gains; a.A_mean = h->A_mean; a.C_mean = h->C_mean;
     a.QA = h->dense ? h->QA : nullptr; a.RC = h->dense ? h->RC : nullptr;
     a.N = h->N; a.T = h->T; a.D = h->D; a.K = h->K; a.t = t; a.L = h->L; a.active = h->active;
     TimedLaunch tl(h, PYVB_K_STEP);

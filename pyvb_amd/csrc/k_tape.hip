@@ -390,7 +390,6 @@ struct pyvb_graph {
     std::vector<int> c_nblocks;                      // per tape: blocks in the window form (c_meta = block table [nb][2], then the window table)
 };
 
-#define ARGCHK(cond, msg) do { if (!(cond)) { pyvb_set_error("%s", msg); return PYVB_E_ARG; } } while (0)
 static void tape_cache_free(pyvb_graph* g, int id);
 
 extern "C" {

@@ -61,7 +61,7 @@ static WArgs make_wargs(pyvb_lds* h) {
     a.trA = h->trA; a.trC = h->trC; a.A_cov = h->A_cov; a.C_cov = h->C_cov; a.RQ = h->RQ; a.RR = h->RR; a.SyyF = h->SyyF;
     a.Q_a = h->Q_a; a.R_a = h->R_a;
     a.A_mean = h->A_mean; a.A_var = h->A_var; a.C_mean = h->C_mean; a.C_var = h->C_var; a.qld_A = h->qld_A; a.qld_C = h->qld_C;
-    a.mom = h->mom; a.X = h->X[h->cur]; a.Sigma = h->Sigma; a.Y = h->Y; a.qld_x = h->qld_x; a.elbo = h->elbo;
+    a.mom = h->mom; a.X = h->X[h->st.cur]; a.Sigma = h->Sigma; a.Y = h->Y; a.qld_x = h->qld_x; a.elbo = h->elbo;
     a.pri = h->pri; a.status = h->status; a.active = h->active;
     a.N = h->N; a.T = h->T; a.D = h->D; a.K = h->K; a.DP = h->L.DP;
     a.which0 = 0; a.c0 = 0; a.c1 = h->D; a.update = 0; a.SG = nullptr; a.ldm = h->ldm;
@@ -655,20 +655,14 @@ int launch_cols_dense(pyvb_lds* h, int which, int c0, int c1) {
     TimedLaunch tl(h, PYVB_K_PARAMS);
     hipLaunchKernelGGL(k_cols_wishart, dim3(h->N, nw), dim3(64 * CW_WAVES), 0, h->stream, a);
     HIPCHK(hipGetLastError());
-    // the sums hold every column's covariance as it is now only when all columns went through the launch (and the
-    // statistics they were weighted with stay the current ones: states_changed() drops them)
-    const bool all = c0 == 0 && c1 == h->D;
-    if (which == 0 || which == 2) h->sg_valid[0] = all;
-    if (which == 1 || which == 2) h->sg_valid[1] = all;
     return PYVB_OK;
 }
 
-int launch_wresid(pyvb_lds* h, int which, int update) {
-    if (h->big) return launch_wresid_big(h, which, update);
+int launch_wresid(pyvb_lds* h, int which, int update, bool use_sg) {
+    if (h->big) return launch_wresid_big(h, which, update, use_sg);
     WArgs a = make_wargs(h);
     a.which0 = which == 1 ? 1 : 0; a.update = update;
-    const bool need0 = which != 1, need1 = which != 0;
-    a.SG = ((!need0 || h->sg_valid[0]) && (!need1 || h->sg_valid[1])) ? h->SG : nullptr;
+    a.SG = use_sg ? h->SG : nullptr;
     TimedLaunch tl(h, PYVB_K_PARAMS);
     hipLaunchKernelGGL(k_wresid, dim3(h->N, which == 2 ? 2 : 1), dim3(256), 0, h->stream, a);
     HIPCHK(hipGetLastError());

@@ -39,7 +39,7 @@ static WBArgs make_wbargs(pyvb_lds* h) {
     a.Q_a = h->Q_a; a.R_a = h->R_a;
     a.A_mean = h->A_mean; a.A_var = h->A_var; a.C_mean = h->C_mean; a.C_var = h->C_var; a.qld_A = h->qld_A; a.qld_C = h->qld_C;
     a.lnd_A = h->lnd_A; a.lnd_C = h->lnd_C;
-    a.mom = h->mom; a.X = h->X[h->cur]; a.Sigma = h->Sigma; a.Y = h->Y;
+    a.mom = h->mom; a.X = h->X[h->st.cur]; a.Sigma = h->Sigma; a.Y = h->Y;
     a.pri = h->pri; a.status = h->status; a.active = h->active;
     a.N = h->N; a.T = h->T; a.D = h->D; a.K = h->K; a.DP = h->L.DP;
     a.which0 = 0; a.c0 = 0; a.c1 = h->D; a.update = 0; a.use_sg = 0;
@@ -322,17 +322,13 @@ int launch_cols_dense_big(pyvb_lds* h, int which, int c0, int c1) {
     TimedLaunch tl(h, PYVB_K_PARAMS);
     hipLaunchKernelGGL(k_cols_wishart_big, dim3(h->N, which == 2 ? 2 : 1), dim3(256), 0, h->stream, a);
     HIPCHK(hipGetLastError());
-    const bool all = c0 == 0 && c1 == h->D;
-    if (which == 0 || which == 2) h->sg_valid[0] = all;
-    if (which == 1 || which == 2) h->sg_valid[1] = all;
     return PYVB_OK;
 }
 
-int launch_wresid_big(pyvb_lds* h, int which, int update) {
+int launch_wresid_big(pyvb_lds* h, int which, int update, bool use_sg) {
     WBArgs a = make_wbargs(h);
     a.which0 = which == 1 ? 1 : 0; a.update = update;
-    const bool need0 = which != 1, need1 = which != 0;
-    a.use_sg = ((!need0 || h->sg_valid[0]) && (!need1 || h->sg_valid[1])) ? 1 : 0;
+    a.use_sg = use_sg ? 1 : 0;
     TimedLaunch tl(h, PYVB_K_PARAMS);
     hipLaunchKernelGGL(k_wresid_big, dim3(h->N, which == 2 ? 2 : 1), dim3(256), 0, h->stream, a);
     HIPCHK(hipGetLastError());

@@ -55,27 +55,33 @@ struct pyvb_pca {
     int *status;
     PcaStatsLayout SL;
     long n_part_missing, n_none_rows, n_part_rows;   // global counts (from the mask)
-    bool full_valid, lin_valid;          // all statistics current / at least sum x and sum z current
-    bool res_valid;                      // scal[PS_RES] is the residual of the current W, Z, X, Mu (nothing but Beta updated since)
-    bool z_pending;                      // [z.update() for z in Zs] has been requested and its operands (Gz, g0, sum z) are set, but the
-                                         // rows of Z are not written yet: the next pass over X does it on its way (k_pca_pass12)
-    bool z0_done;                        // while z_pending: Xs[0].update() has run and stored z_0 itself
+    PcaState st;                         // what is current on the device (host.h); written by api_pca.hip only
+    DeviceBuffers mem;                   // every device allocation of this handle
     double *W_x, *Mu_x;                  // [d][q], [d]: the parameters the last lazy sweep imputed with
-    bool xlazy; long vlo, vhi;           // the missing entries of rows [vlo, vhi) are not in X: they stand for <W>_x z_n + <Mu>_x
-                                         // (k_pca_pass12<.., LAZY>); pca_materialize_x puts them there
     bool lazy_ok;                        // PYVB_PCA_WRITEBACK=1 in the environment at creation turns the lazy sweep off (A/B measurements)
-    int rows_ok;                         // the lazy sweep is k_pca_pass12<.., LAZY> (0), k_pca_rows (1) or k_pca_pairs (2): chosen at creation (api_pca.hip, PYVB_PCA_SWEEP)
-    int nchunkB; long chunk_rowsB;       // k_pca_rows' partition of the rows: a workgroup per CU
-    int part_chunks;                     // chunks of the partial statistics in `part` now
-    bool rows_attr_set;
+    bool pairs;                          // the lazy sweep is k_pca_pairs, not k_pca_pass12<.., LAZY>: chosen at creation (api_pca.hip, PYVB_PCA_SWEEP)
+    int nchunkB; long chunk_rowsB;       // k_pca_pairs' partition of the rows: a workgroup per CU
     pyvb_comm* comm; int rank, world;
 };
 
+// What the next pass over the rows is (api_pca.hip: plan_sweep decides, from the requested range and PcaState; the launchers below
+// carry it out and assign nothing on the handle).
+struct PcaSweepPlan {
+    long lo_upd, hi_upd;                 // rows of X to update
+    bool with_z;                         // the deferred Z update rides along (k_pca_pass12 / k_pca_pairs); false: k_pca_pass2 alone
+    bool keep_z0;                        // z_0 was stored by the X_0 step already
+    bool lazy;                           // the imputed entries stay unstored; then the rows [lo_upd, hi_upd) are the new lazy range
+    bool pairs;                          // lazy, by k_pca_pairs on its own partition of the rows
+    bool materialize;                    // rows [vin_lo, vin_hi) hold unstored entries that this pass cannot take in: store them first
+    long vin_lo, vin_hi;                 // the incoming lazy range (empty: none)
+    int part_chunks;                     // chunks of partial statistics the pass leaves in `part`
+};
+
 int pca_launch_small(pyvb_pca* h, int mode);
-int pca_launch_pass1(pyvb_pca* h);
-int pca_launch_pass2(pyvb_pca* h, long lo_upd, long hi_upd);
-int pca_launch_pass12(pyvb_pca* h, long lo_upd, long hi_upd);
-int pca_materialize_x(pyvb_pca* h);
+int pca_prepare_pairs();                                    // once per device, before the first k_pca_pairs: its dynamic-LDS limit
+int pca_launch_pass1(pyvb_pca* h, bool keep_z0);            // the rows of Z alone; X must be stored
+int pca_launch_sweep(pyvb_pca* h, const PcaSweepPlan& p);   // (materialise,) pass 2 or pass 1+2, the row variances
+int pca_materialize_x(pyvb_pca* h, long vlo, long vhi);     // the unstored entries of rows [vlo, vhi) into X
 int pca_launch_reduce(pyvb_pca* h, int what);
 int pca_launch_rowqld(pyvb_pca* h, double* out, int logdet = 0);      // out: device [N]; logdet: ln det qcov instead of q_ln_det
 enum { PCA_W = 0, PCA_PREPZ = 1, PCA_MU = 2, PCA_BETA = 3, PCA_ELBO = 4, PCA_X0 = 5, PCA_APPLY = 6,
