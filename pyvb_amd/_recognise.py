@@ -19,6 +19,8 @@ import weakref
 import numpy as np
 
 from . import nodes as N
+from ._plan import Plan, component
+from .generic import GenericPlan
 
 
 # Requests as the queue holds them: what update() records -- ("x", t), ("y", t), ("a", i), ("c", i), ("q", 0), ("r", 0) --
@@ -28,7 +30,6 @@ from . import nodes as N
 _BATCH_OPS = ("F", "B", "Y", "A", "C", "Q", "R")
 
 _pool = {}          # signature -> weak references to LDSPlans that are bound but not yet on the device, in binding order
-
 
 
 def exact_elbo(batch):
@@ -261,7 +262,39 @@ class LDSGroup(object):
         return self._elbo
 
 
-class LDSPlan(object):
+class FusedPlan(Plan):
+    """What the two fused plans share literally: the walk from `self.root`, the hand-over test of their entries, the mirror."""
+
+    def __init__(self, root):
+        self.root = root
+        self.pending = []
+        self._mirror = self._mirror_of = None
+        self._adopt()
+
+    def _graph_nodes(self):
+        return component(self.root)
+
+    def _flushed(self, node):
+        """Flush; then the plan the entry forwards to if that moved `node` (a request only the node-by-node plan serves, a
+        graph that left its handle), None while this plan serves it."""
+        self.flush()
+        return None if node._plan is self else N._plan_of(node)
+
+    def mirror(self):
+        """A generic (node-by-node) plan holding a copy of this plan's current posteriors: serves single messages
+        (pass_up_m1_m2) and single lower-bound terms, which the fused kernels never materialise."""
+        self.flush()
+        if self._mirror is None or self._mirror_of is not self.cache or self.cache is None:
+            c = self._pull()
+            self._sync_host()
+            if self._mirror is not None:
+                self._mirror.ex and self._mirror.ex.close()
+            self._mirror = GenericPlan(self.root, adopt=False)
+            self._mirror_of = c
+        return self._mirror
+
+
+class LDSPlan(FusedPlan):
     """One LDS graph on the fused kernels: replicate `r` of its group's handle (LDSGroup)."""
     resume_left = 3         # how often a graph handed to the generic plan may still come back (GenericPlan._resume_fused)
     _count = 0
@@ -274,33 +307,19 @@ class LDSPlan(object):
         self.kind = pri["noise"]
         self.classes = classes          # (Sigma[3,D,D], q_ln_det[3]) of the states' last update on another handle, or None
         self.free_ys = [t for t, y in enumerate(Ys) if not y.observed]      # outputs with missing entries: nodes of their own
-        self.index = {}
-        for t, x in enumerate(Xs):
-            self.index[id(x)] = ("x", t)
-        for t, y in enumerate(Ys):
-            self.index[id(y)] = ("y", t)
-        for i, a in enumerate(As):
-            self.index[id(a)] = ("a", i)
-        for i, c in enumerate(Cs):
-            self.index[id(c)] = ("c", i)
-        self.index[id(Q)] = ("q", 0)
-        self.index[id(R)] = ("r", 0)
+        self.index = {id(n): (kind, i) for kind, row in (("x", Xs), ("y", Ys), ("a", As), ("c", Cs), ("q", [Q]), ("r", [R]))
+                      for i, n in enumerate(row)}
         self._fwd = [("x", t) for t in range(T)]
         self._bwd = self._fwd[::-1]
         self._ys = [("y", t) for t in self.free_ys]
-        self.pending, self._pos = [], 0
-        self.group, self.r = None, -1
-        self.stale = False              # set when a node of the graph gains a child or an observation after binding
-        self.closed = False
-        self.failed = None              # the LinAlgError of a graph evicted from its handle, until it has been raised (LDSGroup._evict)
+        self._pos, self.r = 0, -1
         self.n_random_nodes = 2 * self.T + 2 * self.D + 2
         self.sig = _signature(self)
         LDSPlan._count += 1
         self._serial = LDSPlan._count
         waiting = [ref for ref in _pool.get(self.sig, []) if ref() is not None]
         _pool[self.sig] = waiting + [weakref.ref(self)]
-        for n in _component(Xs[0]):         # the operation nodes and Constants too: their messages go through mirror()
-            n._plan = self
+        FusedPlan.__init__(self, Xs[0])
 
     # -- the handle ------------------------------------------------------------------------------
     def _host_state(self):
@@ -333,7 +352,7 @@ class LDSPlan(object):
         want = self._peek()
         for ref in _pool.pop(self.sig, []):
             p = ref()
-            if p is None or p is self or p.group is not None or p.closed or p.stale or p.Xs[0]._plan is not p:
+            if p is None or p is self or p.group is not None or not p.bound_to(p.root):
                 continue
             (peers if want[1] and p._peek() == want else later).append(p)
         if later:
@@ -362,20 +381,15 @@ class LDSPlan(object):
 
     # -- failure ---------------------------------------------------------------------------------
     def _evicted(self, err):
-        """The graph's row failed on the device (LDSGroup._evict): nothing is copied back, the queue is dropped, the nodes
-        stay pointed at this plan until the error has been raised."""
-        self.failed = err
-        self.closed = True
+        """LDSGroup._evict: dead with a pending error; nothing is copied back, the queue is dropped."""
+        self.failed, self.dead = err, True
         self.pending, self._pos = [], 0
 
     def _raise_failed(self):
-        """First thing in every entry of the plan: raise the error of an evicted graph, once, and let go of the nodes (the graph
-        is bound anew, from the host attributes it kept, at its next use)."""
+        """First thing in every entry of the plan (in flush(), for those that begin with it): raise the error of an evicted graph, once, and let go of the nodes."""
         err, self.failed = self.failed, None
         if err is not None:
-            for n in _component(self.Xs[0]):
-                if n._plan is self:
-                    n._plan = None
+            self._unbind()
             raise err
 
     # -- queue -----------------------------------------------------------------------------------
@@ -510,29 +524,21 @@ class LDSPlan(object):
         self._sync_host(reader=False)
         if self.failed is not None:
             return
-        for n in _component(self.Xs[0]):
-            if n._plan is self:
-                n._plan = None
-        self.closed = True
+        self._unbind()
         if self.group is not None:
             self.group.drop(self)
 
     def release(self):
         """Device state back into the nodes and the graph unbound (it is bound anew, as it is now, at the next use)."""
-        self._raise_failed()
         self.flush()
-        if self.Xs[0]._plan is not self:
-            return
-        self._leave()
+        if self.root._plan is self:
+            self._leave()
 
     def _demote(self, rest):
         """Hand the graph to the generic node-by-node plan and replay the remaining update() requests there."""
-        from .generic import GenericPlan
         self._sync_host(reader=False)
         self._raise_failed()            # (the request that brought the graph here was its own)
-        for n in _component(self.Xs[0]):
-            n._plan = None
-        self.closed = True
+        self._unbind(every=True)
         if self.group is not None:
             self.group.drop(self)
         gp = GenericPlan(self.Xs[0])
@@ -554,9 +560,9 @@ class LDSPlan(object):
         kind, i = self.index[id(node)]
         if kind == "y" and (node.observed or name not in ("qmu", "qcov", "q_ln_det")):
             return node.__dict__.get("_h_" + name)          # observations: host copy
-        self.flush()
-        if node._plan is not self:
-            return N._plan_of(node).read(node, name)
+        heir = self._flushed(node)
+        if heir is not None:
+            return heir.read(node, name)
         if not self.ran:
             return node.__dict__.get("_h_" + name)          # nothing has run on the device: the host attributes are the state
         if kind == "x" and name != "qmu" and not self.x_updated:
@@ -589,10 +595,9 @@ class LDSPlan(object):
     def write(self, node, name, value):
         """A user assignment to a posterior attribute after binding: push it to the device.  False: not something this plan
         can patch in place (an observation, a state covariance): the caller releases the plan and the graph is bound anew."""
-        self._raise_failed()
-        self.flush()
-        if node._plan is not self:              # the queue held something only the node-by-node plan serves, or the graph left its handle
-            return N._plan_of(node).write(node, name, value)
+        heir = self._flushed(node)
+        if heir is not None:
+            return heir.write(node, name, value)
         if name not in ("qmu", "qcov", "qb", "qw"):
             return True                         # q_ln_det, qprec: host-only bookkeeping
         kind, i = self.index[id(node)]
@@ -635,20 +640,17 @@ class LDSPlan(object):
 
     # -- lower bound -----------------------------------------------------------------------------
     def elbo_parts(self, bound="reference"):
-        self._raise_failed()
-        self.flush()
-        if self.Xs[0]._plan is not self:        # the graph has moved: to a handle of its own, or to the node-by-node plan
-            plan = N._plan_of(self.Xs[0])
-            if isinstance(plan, LDSPlan):
-                return plan.elbo_parts(bound)
+        heir = self._flushed(self.root)
+        if heir is not None:                    # the graph has moved: to a handle of its own, or to the node-by-node plan
+            if isinstance(heir, LDSPlan):
+                return heir.elbo_parts(bound)
             raise NotImplementedError("the graph runs node by node now: use Network.learn or the nodes' log_lower_bound()")
         return self._materialize().elbo(bound, self)[self.r]
 
     def node_llb(self, node, bound="reference"):
-        self._raise_failed()
-        self.flush()
-        if node._plan is not self:
-            return N._plan_of(node).node_llb(node, bound)
+        heir = self._flushed(node)
+        if heir is not None:
+            return heir.node_llb(node, bound)
         if not self.x_updated:                  # single terms before any sweep: only the generic plan knows the initial covariances
             self._demote(self._rest())
             return N._plan_of(node).node_llb(node, bound)
@@ -660,21 +662,6 @@ class LDSPlan(object):
         # a single state / output / column node: the fused kernels only form class sums, so the term is evaluated by the
         # generic tape path on a mirror of the current state (gaussian.py:136-151)
         return self.mirror().node_llb(node, bound)
-
-    def mirror(self):
-        """A generic (node-by-node) plan holding a copy of this plan's current posteriors: serves single messages
-        (pass_up_m1_m2) and single lower-bound terms, which the fused kernels never materialise."""
-        self._raise_failed()
-        self.flush()
-        if getattr(self, "_mirror", None) is None or self._mirror_of is not self.cache or self.cache is None:
-            from .generic import GenericPlan
-            c = self._pull()
-            self._sync_host()
-            if getattr(self, "_mirror", None) is not None:
-                self._mirror.ex and self._mirror.ex.close()
-            self._mirror = GenericPlan(self.Xs[0], adopt=False)
-            self._mirror_of = c
-        return self._mirror
 
 
 def _signature(p):
@@ -689,24 +676,6 @@ def _signature(p):
 
 
 # -------------------------------------------------------------------------------------------------
-def _component(start):
-    """All nodes connected to `start` (parents and children), in discovery order."""
-    seen, order, stack = set(), [], [start]
-    while stack:
-        n = stack.pop()
-        if id(n) in seen:
-            continue
-        seen.add(id(n))
-        order.append(n)
-        nxt = list(getattr(n, "children", []))
-        for attr in ("mean_parent", "precision_parent", "A", "B"):
-            if hasattr(n, attr):
-                nxt.append(getattr(n, attr))
-        nxt.extend(getattr(n, "parents", []))
-        stack.extend(nxt)
-    return order
-
-
 def _fail(why):
     """Not the graph a fused plan serves: `bind` catches this and gives the graph the node-by-node plan."""
     raise NotImplementedError("not a graph of the fused kernels (%s)" % why)
@@ -723,7 +692,7 @@ def _diag_constant(node, what):
 
 def describe(start):
     """Recognise the LDS graph around `start`; returns the pieces and the priors (no GPU involved)."""
-    comp = _component(start)
+    comp = component(start)
     stacks = [n for n in comp if isinstance(n, N.hstack)]
     noise = [n for n in comp if isinstance(n, (N.Gamma, N.DiagonalGamma, N.Wishart))]
     if len(stacks) != 2 or len(noise) != 2:
@@ -844,13 +813,12 @@ def _state_classes(Xs):
 def bind(node):
     """Give the graph `node` belongs to an execution plan: the fused LDS or VB-PCA plan if it is one of those graphs,
     else the generic node-by-node plan (pyvb_amd/generic.py).  All three run on the device."""
-    comp = _component(node)
+    comp = component(node)
     try:
         if any(isinstance(n, N.Addition) for n in comp):
             return PCAPlan(**describe_pca(node))
         return LDSPlan(**describe(node))
     except NotImplementedError:
-        from .generic import GenericPlan
         return GenericPlan(node)
 
 
@@ -860,7 +828,7 @@ def bind(node):
 def describe_pca(start):
     """Recognise  X_n ~ N(W * Z_n + Mu, Beta)  with W = hstack of Gaussian columns, Mu Gaussian, Beta Gamma,
     Z_n ~ N(0, I); returns the pieces, the priors and the observation mask (no GPU involved)."""
-    comp = _component(start)
+    comp = component(start)
     stacks = [n for n in comp if isinstance(n, N.hstack)]
     gammas = [n for n in comp if isinstance(n, (N.Gamma, N.DiagonalGamma, N.Wishart))]
     adds = [n for n in comp if isinstance(n, N.Addition)]
@@ -939,7 +907,7 @@ def describe_pca(start):
     return dict(Ws=Ws, W=W, Mu=Mu, Beta=Beta, Zs=Zs, Xs=Xs, init=init, pri=pri)
 
 
-class PCAPlan(object):
+class PCAPlan(FusedPlan):
     def __init__(self, Ws, W, Mu, Beta, Zs, Xs, init, pri):
         from .pca import PCABatch
         self.Ws, self.W, self.Mu, self.Beta, self.Zs, self.Xs = Ws, W, Mu, Beta, Zs, Xs
@@ -948,21 +916,12 @@ class PCAPlan(object):
         nmiss = (~self.obs).sum(1)
         self.unpinned = (nmiss > 0) & (nmiss < self.d)       # rows not yet conditioned on their observed entries (first update)
         self.batch = PCABatch.from_problem(init, pri)
-        self.index = {}
-        for i, w in enumerate(Ws):
-            self.index[id(w)] = ("w", i)
-        for n, z in enumerate(Zs):
-            self.index[id(z)] = ("z", n)
-        for n, x in enumerate(Xs):
-            self.index[id(x)] = ("x", n)
-        self.index[id(Mu)] = ("mu", 0)
-        self.index[id(Beta)] = ("beta", 0)
-        self.pending, self.cache = [], None
-        self.stale = False
+        self.index = {id(n): (kind, i) for kind, row in (("w", Ws), ("z", Zs), ("x", Xs), ("mu", [Mu]), ("beta", [Beta]))
+                      for i, n in enumerate(row)}
+        self.cache = None
         self.z_updated = False          # until then Z_n.qcov reads the node's own initial covariance (host)
         self.n_random_nodes = 2 * self.N + self.q + 2
-        for n in _component(W):
-            n._plan = self
+        FusedPlan.__init__(self, W)
 
     def enqueue(self, node):
         self.pending.append(self.index[id(node)])
@@ -1005,9 +964,9 @@ class PCAPlan(object):
 
     def read(self, node, name):
         kind, i = self.index[id(node)]
-        self.flush()
-        if node._plan is not self:
-            return node._plan.read(node, name)
+        heir = self._flushed(node)
+        if heir is not None:
+            return heir.read(node, name)
         st = self._pull()
         if kind == "w":
             return st["W_mean"][:, [i]].copy() if name == "qmu" else (np.diag(st["W_var"][i]) if name == "qcov" else node.__dict__.get("_h_" + name))
@@ -1029,21 +988,20 @@ class PCAPlan(object):
 
     def write(self, node, name, value):
         """Nothing is patched in place: the caller releases the plan and the graph is bound anew with the assignment."""
-        self.flush()
-        if node._plan is not self:
-            return node._plan.write(node, name, value)
+        heir = self._flushed(node)
+        if heir is not None:
+            return heir.write(node, name, value)
         return name not in ("qmu", "qcov", "qb", "qw")
 
     def elbo_parts(self, bound="reference"):
-        self.flush()
-        if self.W._plan is not self:
+        if self._flushed(self.root) is not None:
             raise NotImplementedError("the graph runs node by node now: use Network.learn or the nodes' log_lower_bound()")
         return exact_elbo(self.batch) if bound == "exact" else self.batch.elbo()
 
     def node_llb(self, node, bound="reference"):
-        self.flush()
-        if node._plan is not self:
-            return node._plan.node_llb(node, bound)
+        heir = self._flushed(node)
+        if heir is not None:
+            return heir.node_llb(node, bound)
         kind, _ = self.index[id(node)]
         if kind == "beta":
             return float(self.elbo_parts(bound)[4])
@@ -1077,36 +1035,18 @@ class PCAPlan(object):
         if self.W._plan is not self:
             return
         self._sync_host()
-        for n in _component(self.W):
-            if n._plan is self:
-                n._plan = None
+        self._unbind()
         self.batch.close()
 
     def _demote(self, rest):
         """See LDSPlan._demote."""
-        from .generic import GenericPlan
-        lookup = {v: k for k, v in self.index.items()}
-        by_id = {id(n): n for n in self.Ws + self.Zs + self.Xs + [self.Mu, self.Beta]}
+        node_of = {self.index[id(n)]: n for n in self.Ws + self.Zs + self.Xs + [self.Mu, self.Beta]}
         self._sync_host()
-        for n in _component(self.W):
-            n._plan = None
+        self._unbind(every=True)
         self.batch.close()
         gp = GenericPlan(self.W)
         for key in rest:
-            node = by_id[lookup[key]]
+            node = node_of[key]
             if not getattr(node, "observed", False):
                 gp.enqueue(node)
         return gp
-
-    def mirror(self):
-        """See LDSPlan.mirror."""
-        self.flush()
-        if getattr(self, "_mirror", None) is None or self._mirror_of is not self.cache or self.cache is None:
-            from .generic import GenericPlan
-            c = self._pull()
-            self._sync_host()
-            if getattr(self, "_mirror", None) is not None:
-                self._mirror.ex and self._mirror.ex.close()
-            self._mirror = GenericPlan(self.W, adopt=False)
-            self._mirror_of = c
-        return self._mirror

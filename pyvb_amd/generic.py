@@ -29,6 +29,7 @@ import bisect
 import numpy as np
 
 from . import nodes as N
+from ._plan import Plan, component
 
 (T_NOP, T_COPY2D, T_FILL, T_AXPBY, T_GEMM, T_SCALE, T_TRACE, T_DIAG, T_CHOLINV, T_DOT, T_UNARY, T_GATHER, T_SCATTER,
  T_MUL) = range(14)
@@ -258,18 +259,11 @@ class DeviceExecutor(object):
             pass
 
 
-def _component(start):
-    from ._recognise import _component as comp
-    return comp(start)
-
-
-class GenericPlan(object):
+class GenericPlan(Plan):
     generic = True
 
     def __init__(self, start, executor_factory=None, adopt=True):
-        self.nodes = _component(start)
-        self.stale = False
-        self.temp_high = 0
+        self.nodes = component(start)
         self._consts, self._const_vals, self._const_dirty = {}, [], True
         self._ones = None
         # ---- state layout
@@ -343,10 +337,11 @@ class GenericPlan(object):
         self._buf = []
         self._node_temp = {}            # per-node tape -> doubles of temporaries it uses
         self._pending = []              # update() requests not yet issued: a run of them becomes ONE tape (see _flush_pending)
-        self.released = False
         if adopt:
-            for nd in self.nodes:
-                nd._plan = self
+            self._adopt()
+
+    def _graph_nodes(self):
+        return self.nodes               # the graph as it was bound (a graph that has grown since is stale)
 
     # -- constants ------------------------------------------------------------------------------
     def const(self, v):
@@ -373,7 +368,7 @@ class GenericPlan(object):
 
     # -- running --------------------------------------------------------------------------------
     def _ensure_executor(self, need):
-        if self.released:
+        if self.dead:
             raise RuntimeError("this plan has been released: its graph is bound to another plan now")
         if self.ex is None or need > self.ex.size:
             old = self.ex
@@ -607,12 +602,11 @@ class GenericPlan(object):
         """A forward and a backward sweep have queued up with nothing in between: the standard loop is back.  The state goes
         to the host attributes, the recogniser binds the graph anew (the fused plan, if it still is that graph) and the two
         sweeps are its first requests."""
-        from . import _recognise
         buf, self._buf = self._buf, []
         left = self.resume["left"] - 1
         self.resume = None
         self.release()
-        plan = _recognise.bind(buf[0])
+        plan = N._plan_of(buf[0])
         plan.resume_left = left
         for nd in buf:
             plan.enqueue(nd)
@@ -670,13 +664,10 @@ class GenericPlan(object):
 
     def release(self):
         self.pull()
-        for nd in self.nodes:
-            if nd._plan is self:
-                nd._plan = None
+        self._unbind()
         if self.ex is not None:
             self.ex.close()
             self.ex = None
-        self.released = True
 
     def node_llb(self, node, bound="reference"):
         self._flush_buf()
@@ -698,6 +689,9 @@ class GenericPlan(object):
             return parts
         return self._read(self._run(key, build)).reshape(-1)
 
+    def llb_nodes(self, nodes, whole, bound="reference"):
+        return float(self.llb_sum(nodes, bound).sum())
+
     def update_all(self, node_list):
         """[n.update() for n in node_list] as one launch (Network.learn, network.py:46-48)."""
         self._flush_buf()
@@ -713,6 +707,8 @@ class GenericPlan(object):
                     self._emit_update_noise(t, n)
             return None
         self._run(key, build)
+
+    update_nodes = update_all
 
     def message(self, node, requester):
         """node.pass_up_m1_m2(requester) evaluated on the device; returns numpy arrays."""

@@ -6,11 +6,6 @@ from . import nodes as N
 __all__ = ["Network"]
 
 
-def _bound(p, nodes):
-    """The nodes still sit on the plan they were grouped under (a plan covers one connected graph, so one node tells)."""
-    return nodes[0]._plan is p and not (getattr(p, "stale", False) or getattr(p, "released", False) or getattr(p, "closed", False))
-
-
 class _Schedule(object):
     """One pass of Network.learn over a node list whose graphs are bound: groups = [[plan, nodes, whole], ...] in list
     order (Network._groups).  Graphs on the fused LDS kernels that share a device handle (_recognise.LDSGroup) are served
@@ -27,10 +22,10 @@ class _Schedule(object):
 
     def valid(self):
         g = self.groups
-        if not all(_bound(g[k][0], g[k][1]) for k in self.other):
+        if not all(g[k][0].bound_to(g[k][1][0]) for k in self.other):       # the nodes still sit on the plan they were grouped under
             return False
         if self.handles is None:
-            return all(_bound(g[k][0], g[k][1]) for k in self.lds)
+            return all(g[k][0].bound_to(g[k][1][0]) for k in self.lds)
         return all(h[0].epoch == h[4] for h in self.handles)
 
     def settle(self):
@@ -57,13 +52,7 @@ class _Schedule(object):
     def update(self):
         g = self.groups
         for k in self.other:
-            p, nodes, _ = g[k]
-            if getattr(p, "generic", False):
-                p.update_all(nodes)
-            else:
-                for n in nodes:
-                    n.update()
-                p.flush()
+            g[k][0].update_nodes(g[k][1])
         if self.handles is None:        # first pass: the calls themselves, queued on every graph before anything runs
             for k in self.lds:
                 p, nodes, _ = g[k]
@@ -73,7 +62,7 @@ class _Schedule(object):
                 self.scripts[k] = p._spell(first)
             for k in self.lds:
                 g[k][0].flush()
-            if all(_bound(g[k][0], g[k][1]) for k in self.lds):
+            if all(g[k][0].bound_to(g[k][1][0]) for k in self.lds):
                 self._summarise()
             return
         for grp, ks, rows, sc, epoch, whole, members, _ in self.handles:
@@ -93,13 +82,7 @@ class _Schedule(object):
         g = self.groups
         vals = np.zeros(len(g))
         for k in self.other:
-            p, nodes, whole = g[k]
-            if getattr(p, "generic", False):
-                vals[k] = float(p.llb_sum(nodes, bound).sum())
-            elif whole:
-                vals[k] = float(np.sum(p.elbo_parts(bound)))    # every random node of the graph is listed, once: the class sums
-            else:
-                vals[k] = float(sum(n.log_lower_bound(bound) for n in nodes))   # a part of a fused graph: its terms one by one
+            vals[k] = g[k][0].llb_nodes(g[k][1], g[k][2], bound)
         rest = self.lds
         if self.handles is not None:
             rest = []
@@ -110,8 +93,7 @@ class _Schedule(object):
                 else:                   # (a graph whose row failed has just been evicted: its own plan raises, the others answer)
                     rest += ks
         for k in rest:
-            p, nodes, whole = g[k]
-            vals[k] = float(np.sum(p.elbo_parts(bound))) if whole else float(sum(n.log_lower_bound(bound) for n in nodes))
+            vals[k] = g[k][0].llb_nodes(g[k][1], g[k][2], bound)
         llb = 0.0
         for v in vals.tolist():
             llb += v

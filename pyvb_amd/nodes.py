@@ -27,11 +27,11 @@ __all__ = ["Node", "Addition", "Multiplication", "Constant", "hstack", "Transpos
            "DiagonalGaussian", "Gamma", "DiagonalGamma", "Wishart", "ConjugacyError"]
 
 
-
 def _bound_arg(bound):
     if bound not in ("reference", "exact"):
         raise ValueError("bound must be 'reference' or 'exact', not %r" % (bound,))
     return bound
+
 
 class ConjugacyError(ValueError):            # nodes_todo.py:8-10
     def __init__(self, message):
@@ -63,7 +63,7 @@ class Node(object):
     def pass_up_m1_m2(self, requester):
         """The two messages a parent needs from this node (gaussian.py:179-183, node.py:95-110, :182-232,
         nodes_todo.py:43-62), evaluated on the device; returns numpy arrays like the reference."""
-        return _messages_of(self, requester)
+        return _generic_view(self).message(self, requester)
 
     def __add__(self, other):
         return Addition(self, other)
@@ -80,19 +80,17 @@ def _wrap(x):
 
 
 def _graph_changed(node):
-    """A node gained a child or an observation: the plan that was built for the old graph is stale (the generic plan's
-    tapes spell the old message structure, a fused plan was recognised on the old graph).  At the next use its state is
-    pulled back into the nodes and the graph is bound again as it is then."""
+    """A node gained a child or an observation: the plan that was built for the old graph is stale.
+    At the next use its state is pulled back into the nodes and the graph is bound again as it is then."""
     plan = getattr(node, "_plan", None)
     if plan is not None:
-        # requests made so far refer to the graph as it was: they are issued before it changes (the node-by-node plan keeps
-        # update() calls back until a result is needed, and builds a node's tape from its attributes)
-        if not getattr(plan, "stale", False) and not getattr(plan, "released", False):
+        # requests made so far refer to the graph as it was: they are issued before it changes.  (A dead plan that a node still
+        # points at has nothing queued: it keeps the error of an evicted graph, which this flush raises.)
+        if not plan.stale:
             plan.flush()
         plan.stale = True
-        handle = getattr(plan, "group", None)
-        if handle is not None:
-            handle.epoch += 1           # Network.learn's schedule for this handle is void (network._Schedule.valid)
+        if plan.group is not None:
+            plan.group.epoch += 1       # Network.learn's schedule for this handle is void (network._Schedule.valid)
 
 
 class Addition(Node):
@@ -196,7 +194,7 @@ class Transpose(Node):
 # -------------------------------------------------------------------------------------------------
 def _plan_of(node):
     plan = node._plan
-    if plan is not None and getattr(plan, "stale", False):
+    if plan is not None and plan.stale:
         plan.release()                  # device state back into the nodes, then bind the graph as it is now
     if node._plan is None:
         from . import _recognise
@@ -207,20 +205,15 @@ def _plan_of(node):
 def _generic_view(node):
     """The generic (tape) plan that can evaluate single messages / single lower-bound terms / expectations for `node`: its own
     plan if the graph runs node by node, else a mirror of the fused plan's current state.  Issuing the fused plan's queued
-    requests can itself hand the graph to the node-by-node plan (a request no fused kernel serves): looked at again after
-    the flush."""
+    requests can itself hand the graph to the node-by-node plan: looked at again after the flush."""
     for _ in range(4):
         plan = _plan_of(node)
-        if getattr(plan, "generic", False):
+        if plan.generic:
             return plan
         plan.flush()
-        if node._plan is plan and not getattr(plan, "stale", False):
+        if plan.bound_to(node):
             return plan.mirror()
     raise RuntimeError("the graph kept changing plans")
-
-
-def _messages_of(node, requester):
-    return _generic_view(node).message(node, requester)
 
 
 def _expectation_of(node, what):
@@ -243,14 +236,13 @@ class _DeviceAttr(object):
 
     def __set__(self, obj, value):
         # The assignment must win.  A bound plan either patches its device state (write() returns True) or gives the graph
-        # up: its state goes back into the nodes, the value is stored below, and the next use binds the graph anew.  A
-        # release can itself leave the graph with another plan (queued requests that only the node-by-node plan serves;
-        # sweeps among them that bring the fused plan back), bound from the OLD host value: hence the loop.
+        # up: its state goes back into the nodes, the value is stored below, and the next use binds the graph anew.  A release
+        # can itself leave the graph with another plan, bound from the OLD host value: hence the loop.
         for _ in range(8):
             plan = getattr(obj, "_plan", None)
             if plan is None:
                 break
-            if getattr(plan, "stale", False):
+            if plan.stale:
                 plan.release()
                 continue
             if plan.write(obj, self.name, value):
@@ -321,7 +313,7 @@ class Gaussian(Node):
         return _plan_of(self).node_llb(self, _bound_arg(bound))
 
     def pass_up_m1_m2(self, requester):         # gaussian.py:179-183
-        return _messages_of(self, requester)
+        return _generic_view(self).message(self, requester)
 
     def pass_down_Ex(self):                     # gaussian.py:154-160: the posterior mean as it is
         return self.qmu
