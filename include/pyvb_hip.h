@@ -82,6 +82,25 @@ int pyvb_device_count(int* count);
 int pyvb_lds_create(pyvb_lds** out, int device, int N, int T, int D, int K, int noise_kind);
 int pyvb_lds_destroy(pyvb_lds* h);
 
+/* The same with a chain length of its own per replicate: replicate n is the graph of Linear_Dynamic_System.py:46-66 whose
+ * loop (:58-66) runs over T_n = lengths[n] time steps, 2 <= T_n <= T.  lengths[N]; NULL = pyvb_lds_create.  The lengths are
+ * part of graph construction and cannot change afterwards; pyvb_lds_get_lengths reads them back (all T on a plain handle).
+ *   - Storage stays [N][T][..]: rows t >= T_n of replicate n are padding, not nodes.  Setters accept anything there (NaN
+ *     included) and nothing derived from such a row reaches a result; getters return 0.0 in padding rows of X and of the
+ *     outputs, NaN in padding entries of Yqld / Ylnd.
+ *   - Q of replicate n has T_n - 1 children and R has T_n, so qa follows nodes_todo.py:125-128, 183-186 per replicate; the
+ *     three posterior classes are X_0, the interior and X_{T_n - 1} (T_n = 2: no interior).
+ *   - pyvb_lds_update_x(h, t) is Xs_n[t].update() for every active n with t < T_n; node T_n - 1 is the last node of its own
+ *     replicate.  pyvb_lds_set_time_split's limit and the staleness check of the statistics count the handle's T.
+ *   - the ELBO totals, the history and the all-reduce sum the replicates as before.
+ * PYVB_E_ARG when some T_n < 2 or T_n > T (the message names the first such replicate).  Served: max(D, K) <= 64 with
+ * PYVB_NOISE_DIAGONAL_GAMMA or PYVB_NOISE_GAMMA, with everything else such a handle does (known entries of A / C, both bound
+ * modes, every time split, the activity mask and status, communicators).  Follow-ups, refused with PYVB_E_UNSUPPORTED when the
+ * lengths are not all equal to T: Wishart noise and max(D, K) > 64 (here, before any HIP call), and NaN in a row t < T_n of Y
+ * (pyvb_lds_set_observations) -- k_wishart*.hip, k_big.hip and k_missing.hip read T as the chain length throughout. */
+int pyvb_lds_create_lengths(pyvb_lds** out, int device, int N, int T, int D, int K, int noise_kind, const int* lengths);
+int pyvb_lds_get_lengths(pyvb_lds* h, int* lengths);
+
 /* Constant parents (node.py:279-311), shared by all replicates:
  *   x0_mean[D], x0_prec[D][D]                     Gaussian(q, pmu, pprec) for X_0  (:58)
  *   A_prior_mean[D][D] (row,col), A_prior_prec[D][D] (column i, diagonal entry k)   (:47)

@@ -51,7 +51,7 @@ void pyvb_timing_resolve(pyvb_lds* h) {
 extern "C" {
 
 const char* pyvb_last_error(void) { return g_err; }
-int pyvb_version(void) { return 100; }
+int pyvb_version(void) { return 101; }
 
 int pyvb_device_count(int* count) {
     ARGCHK(count, "count is NULL");
@@ -60,12 +60,33 @@ int pyvb_device_count(int* count) {
 }
 
 int pyvb_lds_create(pyvb_lds** out, int device, int N, int T, int D, int K, int noise_kind) {
+    return pyvb_lds_create_lengths(out, device, N, T, D, K, noise_kind, nullptr);
+}
+
+int pyvb_lds_create_lengths(pyvb_lds** out, int device, int N, int T, int D, int K, int noise_kind, const int* lengths) {
     ARGCHK(out, "out is NULL");
     ARGCHK(N >= 1, "N must be >= 1");
     ARGCHK(T >= 2, "T must be >= 2 (a chain needs X_0 and X_{T-1})");
     ARGCHK(D >= 1 && D <= 128, "latent dimension D must be in 1..128");
     ARGCHK(K >= 1 && K <= 128, "observed dimension K must be in 1..128");
     ARGCHK(noise_kind == PYVB_NOISE_DIAGONAL_GAMMA || noise_kind == PYVB_NOISE_GAMMA || noise_kind == PYVB_NOISE_WISHART, "unknown noise kind");
+    // chain lengths: checked and, where the combination is not served, refused before the first HIP call
+    bool ragged = false;
+    for (int n = 0; lengths && n < N; ++n) {
+        if (lengths[n] < 2 || lengths[n] > T) {
+            pyvb_set_error("replicate %d has length %d: every chain needs 2 <= T_n <= T = %d", n, lengths[n], T);
+            return PYVB_E_ARG;
+        }
+        ragged = ragged || lengths[n] != T;
+    }
+    if (ragged && noise_kind == PYVB_NOISE_WISHART) {
+        pyvb_set_error("chains of unequal length are served with DiagonalGamma and Gamma noise only, not with Wishart noise (k_wishart.hip)");
+        return PYVB_E_UNSUPPORTED;
+    }
+    if (ragged && (D > 64 || K > 64)) {
+        pyvb_set_error("chains of unequal length are served for max(D, K) <= 64 only, not in the 128-wide class (k_big.hip): D = %d, K = %d", D, K);
+        return PYVB_E_UNSUPPORTED;
+    }
     int ndev = 0;
     HIPCHK(hipGetDeviceCount(&ndev));
     ARGCHK(device >= 0 && device < ndev, "no such device");
@@ -141,6 +162,12 @@ int pyvb_lds_create(pyvb_lds** out, int device, int N, int T, int D, int K, int 
     TRY(dev_alloc(&h->elbo_hist, (size_t)PYVB_ELBO_HISTORY * 8));
     TRY(h->mem.alloc((void**)&h->status, n * sizeof(int)));
     TRY(h->mem.alloc((void**)&h->active, n, 1));
+    if (ragged) {       // (lengths that all equal T: a plain handle, len stays null)
+        TRY(h->mem.alloc((void**)&h->len, n * sizeof(int)));
+        h->len_host = (int*)malloc(n * sizeof(int));
+        memcpy(h->len_host, lengths, n * sizeof(int));
+        TRYHIP(hipMemcpy(h->len, lengths, n * sizeof(int), hipMemcpyHostToDevice));
+    }
     h->active_host = (unsigned char*)malloc(n);
     memset(h->active_host, 1, n);
     h->n_active = N;
@@ -201,7 +228,7 @@ int pyvb_lds_destroy(pyvb_lds* h) {
     if (h->ev_elbo) (void)hipEventDestroy(h->ev_elbo);
     if (h->side) (void)hipStreamDestroy(h->side);
     h->mem.release_all();
-    free(h->active_host); free(h->status_host); free(h->reported);
+    free(h->active_host); free(h->status_host); free(h->reported); free(h->len_host);
     if (h->pool) {
         for (int i = 0; i < PYVB_EVENT_POOL; ++i) { if (h->pool[i].e0) (void)hipEventDestroy(h->pool[i].e0); if (h->pool[i].e1) (void)hipEventDestroy(h->pool[i].e1); }
         free(h->pool);
@@ -239,6 +266,14 @@ static int settle_parked(pyvb_lds* h) {
 
 static int h2d(pyvb_lds* h, double* dst, const double* src, size_t n) { return to_device(h->stream, dst, src, n); }
 static int d2h(pyvb_lds* h, double* dst, const double* src, size_t n) { return to_host(h->stream, dst, src, n); }
+
+// A handle with chain lengths: rows t >= T_n of a host array [N][T][per] that a getter has just filled (after the sync) are
+// padding, not nodes; they read as `value` whatever the device buffer holds there.
+static void fill_padding(const pyvb_lds* h, double* a, size_t per, double value) {
+    if (!h->len_host || !a) return;
+    for (size_t n = 0; n < (size_t)h->N; ++n)
+        for (size_t i = ((size_t)n * h->T + h->len_host[n]) * per; i < (size_t)(n + 1) * h->T * per; ++i) a[i] = value;
+}
 
 // ln det of a symmetric positive definite matrix (Constant.lndet, node.py:301-302)
 static int host_lndet(const double* Ain, int D, double* out) {
@@ -295,10 +330,11 @@ int pyvb_lds_set_priors(pyvb_lds* h, const double* x0_mean, const double* x0_pre
         // and :183-186 (DiagonalGamma: +0.5 per child); Q has T-1 children X_1.., R has T children Y_t
         std::vector<double> qa((size_t)N * D), ra((size_t)N * K);
         for (int n = 0; n < N; ++n) {
+            const int Tn = h->len_host ? h->len_host[n] : T;       // the children of replicate n's own Q and R
             for (int k = 0; k < D; ++k)
-                qa[(size_t)n * D + k] = (h->noise == PYVB_NOISE_GAMMA) ? Q_a0[0] + 0.5 * D * (T - 1) : Q_a0[k] + 0.5 * (T - 1);
+                qa[(size_t)n * D + k] = (h->noise == PYVB_NOISE_GAMMA) ? Q_a0[0] + 0.5 * D * (Tn - 1) : Q_a0[k] + 0.5 * (Tn - 1);
             for (int k = 0; k < K; ++k)
-                ra[(size_t)n * K + k] = (h->noise == PYVB_NOISE_GAMMA) ? R_a0[0] + 0.5 * K * T : R_a0[k] + 0.5 * T;
+                ra[(size_t)n * K + k] = (h->noise == PYVB_NOISE_GAMMA) ? R_a0[0] + 0.5 * K * Tn : R_a0[k] + 0.5 * Tn;
         }
         if ((rc = h2d(h, h->Q_a, qa.data(), qa.size()))) return rc;
         if ((rc = h2d(h, h->R_a, ra.data(), ra.size()))) return rc;
@@ -436,7 +472,18 @@ int pyvb_lds_set_observations(pyvb_lds* h, const double* Y) {
     ARGCHK(Y, "Y is NULL");
     const size_t n = (size_t)h->N * h->T * h->K;
     bool missing = false;
-    for (size_t i = 0; i < n && !missing; ++i) missing = Y[i] != Y[i];
+    if (h->len_host) {      // padding rows may hold anything, NaN included: they are not outputs of any graph
+        for (int r = 0; r < h->N; ++r) {
+            const double* Yr = Y + (size_t)r * h->T * h->K;
+            for (size_t i = 0; i < (size_t)h->len_host[r] * h->K; ++i)
+                if (Yr[i] != Yr[i]) {
+                    pyvb_set_error("outputs that hold NaN are not served together with chains of unequal length (k_missing.hip): "
+                                   "replicate %d, t = %d of its %d nodes", r, (int)(i / h->K), h->len_host[r]);
+                    return PYVB_E_UNSUPPORTED;
+                }
+        }
+    } else
+        for (size_t i = 0; i < n && !missing; ++i) missing = Y[i] != Y[i];
     int rc;
     if (missing && h->dense && h->big) {
         pyvb_set_error("with Wishart noise, outputs that hold NaN are served for D, K <= 64 only (k_wishart_big.hip)");
@@ -508,7 +555,9 @@ int pyvb_lds_get_outputs(pyvb_lds* h, double* Yq, double* Yvar, double* Yqld) {
         if (h->has_missing) { if ((rc = d2h(h, Yqld, h->Yqld, (size_t)h->N * h->T))) return rc; }
         else for (size_t i = 0; i < (size_t)h->N * h->T; ++i) Yqld[i] = NAN;
     }
-    return pyvb_lds_sync(h);
+    if ((rc = pyvb_lds_sync(h))) return rc;
+    fill_padding(h, Yq, h->K, 0.0);
+    return PYVB_OK;
 }
 
 int pyvb_lds_update_Y(pyvb_lds* h) {
@@ -571,7 +620,9 @@ int pyvb_lds_get_state(pyvb_lds* h, double* X, double* A_mean, double* A_colvar,
     if ((rc = d2h(h, Q_b, h->Q_b, N * D))) return rc;
     if ((rc = d2h(h, R_a, h->R_a, N * K))) return rc;
     if ((rc = d2h(h, R_b, h->R_b, N * K))) return rc;
-    return pyvb_lds_sync(h);
+    if ((rc = pyvb_lds_sync(h))) return rc;
+    fill_padding(h, X, D, 0.0);
+    return PYVB_OK;
 }
 
 int pyvb_lds_get_posterior_classes(pyvb_lds* h, double* Sigma, double* qld_x) {
@@ -603,6 +654,13 @@ int pyvb_lds_get_column_qld(pyvb_lds* h, double* qld_A, double* qld_C) {
     if ((rc = d2h(h, qld_A, h->qld_A, (size_t)h->N * h->D))) return rc;
     if ((rc = d2h(h, qld_C, h->qld_C, (size_t)h->N * h->D))) return rc;
     return pyvb_lds_sync(h);
+}
+
+int pyvb_lds_get_lengths(pyvb_lds* h, int* lengths) {
+    ARGCHK(h, "handle is NULL");
+    ARGCHK(lengths, "lengths is NULL");
+    for (int n = 0; n < h->N; ++n) lengths[n] = h->len_host ? h->len_host[n] : h->T;
+    return PYVB_OK;
 }
 
 int pyvb_lds_get_time_split(pyvb_lds* h, int* W) {

@@ -120,6 +120,9 @@ struct pyvb_lds {
     unsigned char *active;          // device, [N]: 0 = switched off; every update kernel leaves such a replicate's rows alone
     unsigned char *active_host;     // its host mirror (set_active is stream ordered, the mirror is what the host logic reads)
     int n_active;
+    // ---- per-replicate chain lengths (pyvb_lds_create_lengths): null on a handle whose chains all have T nodes
+    int *len;                       // device, [N]: T_n.  T stays the row stride of every [N][T][..] buffer; rows t >= T_n are padding
+    int *len_host;                  // its host copy (setters and getters: which rows are padding)
     int *status_host, *reported;    // [N] staging of a read of status; [N] what the most recent failed sync reported and cleared
     LdsState st;                    // what is current on the device (host.h); written by the events of api.hip only
     DeviceBuffers mem;              // every device allocation of this handle

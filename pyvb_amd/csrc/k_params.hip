@@ -18,9 +18,17 @@ __global__ void __launch_bounds__(256) k_moments(ParamArgs a) {
     const double* P = a.part + (size_t)n * a.nchunk * a.L.stats_total;
     const double* S = a.Sigma + (size_t)n * 3 * D * D;
     const double* x0 = a.X + (size_t)n * T * DP;       // state rows: stride DP, accumulator order (xpos)
-    const double* xL = x0 + (size_t)(T - 1) * DP;
+    const int TL = a.len ? a.len[n] : T;              // nodes of this replicate's chain; T is the row stride
+    const double* xL = x0 + (size_t)(TL - 1) * DP;
     double* mo = a.mom + (size_t)n * mom_total(D, K);
-    const double nint = (double)(T - 2);
+    const double nint = (double)(TL - 2);
+    // parts of sxx this replicate's sweep wrote: a chain shorter than the handle's leaves the parts beyond its last interior
+    // node unwritten (k_sweep: Tw <= 0)
+    int nparts = a.W;
+    if (a.len) {
+        const int live = TL - 2 <= 0 ? 0 : (a.W == 1 ? 1 : (TL - 2 + a.Lw - 1) / a.Lw);
+        nparts = live < a.W ? live : a.W;
+    }
     for (int idx = tid; idx < D * D; idx += 256) {
         const int i = idx / D, j = idx % D;
         double xx = 0.0, h = 0.0;
@@ -33,7 +41,7 @@ __global__ void __launch_bounds__(256) k_moments(ParamArgs a) {
         if (a.sxx) {
             xx = x0[xpos(i)] * x0[xpos(j)] + xL[xpos(i)] * xL[xpos(j)];
 #pragma unroll 8
-            for (int w = 0; w < a.W; ++w) xx += a.sxx[((size_t)n * a.W + w) * DP * DP + (size_t)i * DP + j];
+            for (int w = 0; w < nparts; ++w) xx += a.sxx[((size_t)n * a.W + w) * DP * DP + (size_t)i * DP + j];
         }
         const double s0 = S[idx], s1 = S[D * D + idx], s2 = S[2 * D * D + idx];
         mo[MOM_GA(D, K) + idx] = xx - xL[xpos(i)] * xL[xpos(j)] + s0 + nint * s1;
@@ -97,6 +105,7 @@ __global__ void __launch_bounds__(64 * NW) k_elbo(ParamArgs a) {
     if (!a.active[n]) return;
     const double* S0 = a.Sigma + (size_t)n * 3 * D * D;
     const double* x0 = a.X + (size_t)n * T * a.L.DP;
+    const int TL = a.len ? a.len[n] : T;              // nodes of this replicate's chain: Q has TL - 1 children, R has TL
     const bool exact = a.bound == PYVB_BOUND_EXACT;
     // the entropy of the X_t: quirk Q1's q_ln_det (reference) or ln det Sigma (exact)
     const double* qx = (exact ? a.lnd_x : a.qld_x) + (size_t)n * 3;
@@ -130,11 +139,11 @@ __global__ void __launch_bounds__(64 * NW) k_elbo(ParamArgs a) {
         }
     }
     e0 = blk_sum<NW>(e0, red);
-    const double nint = (double)(T - 2);
+    const double nint = (double)(TL - 2);
     double LX = -0.5 * D * LN2PI + 0.5 * a.pri.x0_lndet - 0.5 * e0;
-    LX += (double)(T - 1) * (-0.5 * D * LN2PI + 0.5 * lndQ) - trQ;
-    LX += (double)T * (0.5 * D * LN2PI + 0.5 * D) + 0.5 * (qx[0] + nint * qx[1] + qx[2]);
-    double LY = (double)T * (-0.5 * K * LN2PI + 0.5 * lndR) - trR;
+    LX += (double)(TL - 1) * (-0.5 * D * LN2PI + 0.5 * lndQ) - trQ;
+    LX += (double)TL * (0.5 * D * LN2PI + 0.5 * D) + 0.5 * (qx[0] + nint * qx[1] + qx[2]);
+    double LY = (double)TL * (-0.5 * K * LN2PI + 0.5 * lndR) - trR;
     if (exact) { if (a.YentX) LY += a.YentX[n]; }
     else if (a.Yent) LY -= a.Yent[n];
     // --- columns of A and C against their Constant parents (gaussian.py:141-150).  The last term depends
@@ -236,6 +245,7 @@ ParamArgs make_args(pyvb_lds* h) {
     a.lnd_A = h->lnd_A; a.lnd_C = h->lnd_C; a.lnd_x = h->lnd_x; a.YentX = h->has_missing ? h->YentX : nullptr; a.bound = h->bound;
     a.N = h->N; a.T = h->T; a.D = h->D; a.K = h->K; a.noise = h->noise; a.L = h->L; a.c0 = 0; a.c1 = h->D; a.which0 = 0; a.fuse = 0; a.sxx = nullptr; a.W = 1;
     a.active = h->active;
+    a.len = h->len; a.Lw = 0;
     return a;
 }
 
@@ -251,6 +261,7 @@ int launch_moments(pyvb_lds* h, bool sxx_from_sweep) {
     ParamArgs a = make_args(h);
     a.sxx = sxx_from_sweep ? h->sxx : nullptr;
     a.W = h->W;
+    a.Lw = h->W > 1 ? ((((h->T - 2 + h->W - 1) / h->W) + 15) & ~15) : h->T - 2;      // as k_sweep cuts the parts
     TimedLaunch tl(h, PYVB_K_PARAMS);
     hipLaunchKernelGGL(k_moments, dim3(h->N), dim3(256), 0, h->stream, a);
     HIPCHK(hipGetLastError());

@@ -16,6 +16,8 @@ struct StatsArgs {
     const double* X; const double* Y; double* part;
     const double* zeros;    // 64 zeros
     const unsigned char* active;    // [N]
+    const int* len;         // [N] chain length T_n of each replicate, or null: a.T.  Chunks are cut from a.T (the row stride) for
+                            // every replicate; a chunk sums its rows t < T_n and writes its partial even when it has none
     int N, T, D, K, nchunk, chunk_len;
     Layout L;
 };
@@ -53,11 +55,12 @@ __global__ void __launch_bounds__(128, STATS_OCC) k_stats(StatsArgs a) {
     const int ch = blockIdx.x, n = blockIdx.y, wave = threadIdx.x >> 6, lane = threadIdx.x & 63, r = lane & 15, q = lane >> 4;
     if (!a.active[n]) return;
     const int T = a.T, K = a.K;
+    const int TL = a.len ? a.len[n] : T;
     const double* X = a.X + (size_t)n * T * DP;        // rows: stride DP, accumulator order
     const double* Y = a.Y + (size_t)n * T * K;
     const double* Z = a.zeros;                         // a row of zeros: what rows outside the chunk read as
     const int t0 = ch * a.chunk_len;
-    const int t1 = (t0 + a.chunk_len < T) ? t0 + a.chunk_len : T;
+    const int t1 = (t0 + a.chunk_len < TL) ? t0 + a.chunk_len : TL;
     double* P = a.part + ((size_t)n * a.nchunk + ch) * a.L.stats_total;
 
     // Rows are fetched two halves of PF k-steps ahead into a ring of registers (the loop is unrolled so
@@ -74,7 +77,7 @@ __global__ void __launch_bounds__(128, STATS_OCC) k_stats(StatsArgs a) {
         for (int m = 0; m < DT; ++m) dst[m] = p[xoff[m]];
     };
     auto row_x1 = [&](int t, double* dst) {             // row t + 1 for the lanes of row t
-        const double* p = (t < t1 && t + 1 < T) ? X + (size_t)(t + 1) * DP : Z;
+        const double* p = (t < t1 && t + 1 < TL) ? X + (size_t)(t + 1) * DP : Z;
 #pragma unroll
         for (int m = 0; m < DT; ++m) dst[m] = p[xoff[m]];
     };
@@ -226,18 +229,19 @@ __global__ void __launch_bounds__(128, STATS_OCC) k_stats(StatsArgs a) {
 }
 
 // Syy[n][k] = sum_t y_t[k]^2: the observations never change, so this runs once per set_observations.
-struct SyyArgs { const double* Y; double* Syy; const unsigned char* active; int N, T, K; };
+struct SyyArgs { const double* Y; double* Syy; const unsigned char* active; const int* len; int N, T, K; };
 
 __global__ void __launch_bounds__(256) k_syy(SyyArgs a) {
     __shared__ double red[256];
     const int n = blockIdx.x, tid = threadIdx.x, K = a.K;
     if (!a.active[n]) return;
     const double* Y = a.Y + (size_t)n * a.T * K;
+    const int TL = a.len ? a.len[n] : a.T;      // rows beyond the replicate's chain are padding
     // thread owns component tid % K of rows tid / K, tid / K + 256 / K ...
     const int per = 256 / K, k = tid % K, r0 = tid / K;
     double s = 0.0;
     if (r0 < per)
-        for (int t = r0; t < a.T; t += per) { double v = Y[(size_t)t * K + k]; s += v * v; }
+        for (int t = r0; t < TL; t += per) { double v = Y[(size_t)t * K + k]; s += v * v; }
     red[tid] = (r0 < per) ? s : 0.0;
     __syncthreads();
     if (tid < K) {
@@ -256,7 +260,7 @@ static void launch_stats_t(pyvb_lds* h, const StatsArgs& a, bool with_sxx) {
 int launch_stats(pyvb_lds* h, bool with_sxx) {
     if (h->big) return launch_stats_big(h);
     StatsArgs a;
-    a.X = h->X[h->st.cur]; a.Y = h->Y; a.part = h->stats; a.zeros = h->zeros; a.active = h->active;
+    a.X = h->X[h->st.cur]; a.Y = h->Y; a.part = h->stats; a.zeros = h->zeros; a.active = h->active; a.len = h->len;
     a.N = h->N; a.T = h->T; a.D = h->D; a.K = h->K; a.nchunk = h->nchunk; a.chunk_len = h->chunk_len; a.L = h->L;
     {
         TimedLaunch tl(h, PYVB_K_STATS);
@@ -278,7 +282,7 @@ int launch_stats(pyvb_lds* h, bool with_sxx) {
 }
 
 int launch_syy(pyvb_lds* h) {
-    SyyArgs a; a.Y = h->Y; a.Syy = h->Syy; a.active = h->active; a.N = h->N; a.T = h->T; a.K = h->K;
+    SyyArgs a; a.Y = h->Y; a.Syy = h->Syy; a.active = h->active; a.len = h->len; a.N = h->N; a.T = h->T; a.K = h->K;
     hipLaunchKernelGGL(k_syy, dim3(h->N), dim3(256), 0, h->stream, a);
     HIPCHK(hipGetLastError());
     return PYVB_OK;

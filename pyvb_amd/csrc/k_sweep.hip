@@ -27,6 +27,8 @@ struct SweepArgs {
     int N, T, D, K, dir;
     int W;              // wavefronts per replicate: each takes a contiguous part of the interior time range (grid.y)
     const unsigned char* active;    // [N]: the wavefronts of a switched-off replicate (all W of them) leave at once
+    const int* len;     // [N] chain length T_n of each replicate (pyvb_lds_create_lengths), or null: every chain has a.T nodes.
+                        // a.T stays the row stride of X, Y and U; rows t >= T_n are padding that no lane reads or writes
     int keep_x;         // 0: the sweep that follows reads only c_t and the rows next to the far boundary, so the interior rows of Xnew are not written
     Layout L;
 };
@@ -98,6 +100,7 @@ __global__ void __launch_bounds__(64) k_sweep(SweepArgs a) {
     const int n = blockIdx.x, w = SPLIT ? blockIdx.y : 0, lane = threadIdx.x, c = lane & 15, q = lane >> 4;
     if (!a.active[n]) return;
     const int T = a.T, D = a.D, K = a.K;
+    const int TL = a.len ? a.len[n] : T;    // nodes of this replicate's chain: wave-uniform, so it lives in a scalar register
     const bool fwd = (a.dir == 0);
     const int sgn = fwd ? 1 : -1;
     const Layout& L = a.L;
@@ -125,18 +128,20 @@ __global__ void __launch_bounds__(64) k_sweep(SweepArgs a) {
     }
 
     // ---- the part of the interior this wavefront owns.  With few replicates the interior time range
-    // (nodes 1 .. T-2, counted from the side the sweep starts at) is dealt out to a.W wavefronts per
+    // (nodes 1 .. T_n-2, counted from the side the sweep starts at) is dealt out to a.W wavefronts per
     // replicate in contiguous parts of Lw nodes; every part is again cut into 16 segments.  All
     // segments but those that reach the chain's first node within J steps warm up from zero.
-    const int Tint = T - 2;
-    const int Lw = SPLIT ? ((((Tint + a.W - 1) / a.W) + 15) & ~15) : Tint;
+    // Lw is cut from the handle's T for every replicate (k_moments counts a replicate's parts the same way):
+    // a shorter chain fills the first parts and leaves the others without nodes (Tw <= 0).
+    const int Tint = TL - 2;
+    const int Lw = SPLIT ? ((((T - 2 + a.W - 1) / a.W) + 15) & ~15) : Tint;
     const int ow = SPLIT ? w * Lw : 0;                       // interior nodes before this part
     const int Tw = (Tint - ow < Lw) ? Tint - ow : Lw;        // interior nodes of this part (<= 0: none)
     const int J = a.warm[n * 2 + a.dir];
 
     // ---- first boundary node (t = 0 forward, T-1 backward): only the old neighbour.  Every wavefront
     // whose warm-up can reach it computes it; the first one stores it.
-    const int t_first = fwd ? 0 : T - 1, t_last = fwd ? T - 1 : 0;
+    const int t_first = fwd ? 0 : TL - 1, t_last = fwd ? TL - 1 : 0;
     const double* Am = a.A_mean + (size_t)n * D * D;
     const double* Cm = a.C_mean + (size_t)n * K * D;
     const double* QAm = a.QA ? a.QA + (size_t)n * D * D : nullptr;
@@ -167,8 +172,8 @@ __global__ void __launch_bounds__(64) k_sweep(SweepArgs a) {
             for (int r = 0; r < 4; ++r) x[m][r] = (jc == -before) ? xs[16 * m + 4 * r + q] : 0.0;
 
         // time index of this column at loop index j:  t = tbase + sgn * j
-        const int tbase = fwd ? (1 + before) : (T - 2 - before);
-        const int tsafe = fwd ? 1 : T - 2;      // an interior row that always exists: what inactive columns read
+        const int tbase = fwd ? (1 + before) : (TL - 2 - before);
+        const int tsafe = fwd ? 1 : TL - 2;      // an interior row that always exists: what inactive columns read
         auto active = [&](int j) { int tt = cL + j; return j >= jc && j < Lseg && tt < Tw; };
         // input registers: y_t and the old neighbour mean, as B operands in permuted k order.
         // Loads are unconditional and unmasked: an inactive column reads a valid row and computes
@@ -379,7 +384,7 @@ __global__ void __launch_bounds__(64) k_sweep(SweepArgs a) {
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
     }
 
-    // ---- closing boundary node (t = T-1 forward, 0 backward): only the new neighbour; done by the
+    // ---- closing boundary node (t = T_n-1 forward, 0 backward): only the new neighbour; done by the
     // wavefront that owns the last interior node
     if (!SPLIT || w == ((Tint > 0) ? (Tint - 1) / Lw : 0)) {
         const double s = boundary_update(!fwd, g, L, Am, Cm, D, K, lane, [&](int j) { return xs[j]; },
@@ -392,6 +397,7 @@ __global__ void __launch_bounds__(64) k_sweep(SweepArgs a) {
 struct StepArgs {
     double* X; const double* Y; const double* gains; const double *A_mean, *C_mean, *QA, *RC;
     const unsigned char* active;
+    const int* len;     // [N] chain lengths or null, as in SweepArgs
     int N, T, D, K, t;
     Layout L;
 };
@@ -400,15 +406,17 @@ __global__ void __launch_bounds__(64) k_step(StepArgs a) {
     const int n = blockIdx.x, lane = threadIdx.x;
     if (!a.active[n]) return;
     const int T = a.T, D = a.D, K = a.K, t = a.t, DP = a.L.DP;
+    const int TL = a.len ? a.len[n] : T;
+    if (t >= TL) return;        // X_t is not a node of this replicate's graph
     const Layout& L = a.L;
     const double* g = a.gains + (size_t)n * L.gains_total;
     double* X = a.X + (size_t)n * T * DP;
     const double* y = a.Y + ((size_t)n * T + t) * K;
-    const int cls = (t == 0) ? 0 : (t == T - 1 ? 2 : 1);
+    const int cls = (t == 0) ? 0 : (t == TL - 1 ? 2 : 1);
     const int row = lane % DP;
     if (cls != 1) {
         __shared__ double vs[64];
-        const double* nbr = X + (size_t)(cls == 0 ? 1 : T - 2) * DP;
+        const double* nbr = X + (size_t)(cls == 0 ? 1 : TL - 2) * DP;
         const double s = boundary_update(cls == 0, g, L, a.A_mean + (size_t)n * D * D, a.C_mean + (size_t)n * K * D, D, K, lane,
                                          [&](int j) { return nbr[xpos(j)]; }, y, vs,
                                          a.QA ? a.QA + (size_t)n * D * D : nullptr, a.RC ? a.RC + (size_t)n * K * D : nullptr);
@@ -444,7 +452,7 @@ int launch_sweep(pyvb_lds* h, int direction, int src, bool read_cache, bool keep
     a.Xold = h->X[src]; a.Xnew = h->X[1 - src]; a.Y = h->Y; a.gains = h->gains; a.warm = h->warm;
     a.trash = h->trash; a.U = h->U; a.Sxx = h->sxx; a.A_mean = h->A_mean; a.C_mean = h->C_mean;
     a.QA = h->dense ? h->QA : nullptr; a.RC = h->dense ? h->RC : nullptr;
-    a.N = h->N; a.T = h->T; a.D = h->D; a.K = h->K; a.dir = direction; a.L = h->L; a.active = h->active;
+    a.N = h->N; a.T = h->T; a.D = h->D; a.K = h->K; a.dir = direction; a.L = h->L; a.active = h->active; a.len = h->len;
     {
         TimedLaunch tl(h, direction == PYVB_FORWARD ? PYVB_K_SWEEP_FWD : PYVB_K_SWEEP_BWD);
         switch (h->L.DT * 10 + h->L.KT) {
@@ -509,7 +517,7 @@ int launch_step(pyvb_lds* h, int t) {
     StepArgs a;
     a.X = h->X[h->st.cur]; a.Y = h->Y; a.gains = h->gains; a.A_mean = h->A_mean; a.C_mean = h->C_mean;
     a.QA = h->dense ? h->QA : nullptr; a.RC = h->dense ? h->RC : nullptr;
-    a.N = h->N; a.T = h->T; a.D = h->D; a.K = h->K; a.t = t; a.L = h->L; a.active = h->active;
+    a.N = h->N; a.T = h->T; a.D = h->D; a.K = h->K; a.t = t; a.L = h->L; a.active = h->active; a.len = h->len;
     TimedLaunch tl(h, PYVB_K_STEP);
     hipLaunchKernelGGL(k_step, dim3(h->N), dim3(64), 0, h->stream, a);
     HIPCHK(hipGetLastError());

@@ -25,9 +25,12 @@ struct ParamArgs {
     const unsigned char* active;    // [N]: workgroups of switched-off replicates leave at once
     int which0;             // blockIdx.y + which0 selects the matrix / noise node (0: A, Q; 1: C, R)
     Layout L;
+    const int* len;         // [N] chain length T_n of each replicate (pyvb_lds_create_lengths), or null: T.  T stays the row stride of X
+    int Lw;                 // k_moments: interior nodes per part of sxx, cut from the handle's T as k_sweep cuts them
 };
 
 // layout of the per-replicate moment block written by k_moments (all row-major, no padding)
+// (T: the replicate's own chain length T_n on a handle with lengths)
 //   GA [D][D]  = sum_{t=0}^{T-2} <x x^T>      (children of hstack A: Mult(A, X_t))
 //   GC [D][D]  = sum_{t=0}^{T-1} <x x^T>      (children of hstack C)
 //   HA [D][D]  = sum_t mu_{t+1} mu_t^T        HC [K][D] = sum_t y_t mu_t^T

@@ -9,7 +9,7 @@ import numpy as np
 
 from . import _capi as C
 
-__all__ = ["LDSBatch"]
+__all__ = ["LDSBatch", "pad_series"]
 
 _NOISE = {"diagonal_gamma": C.NOISE_DIAGONAL_GAMMA, "gamma": C.NOISE_GAMMA, "wishart": C.NOISE_WISHART}
 
@@ -21,16 +21,56 @@ def _f64(a, shape, name):
     return a
 
 
+_STATE_KEYS = ("X", "A_mean", "A_colvar", "C_mean", "C_colvar", "Q_b", "R_b")
+
+
+def pad_series(series):
+    """series: list of (Y_n[T_n, K], st0_n), st0_n as synth.initial_state(T_n, D, K, 1) gives it.  Returns (Y[N, T, K],
+    st0, lengths) with T = max T_n: the inputs of a handle with chain lengths.  Rows t >= T_n of Y and of st0["X"] are
+    padding (zeros here); no result depends on what they hold."""
+    N = len(series)
+    if N == 0:
+        raise ValueError("no series")
+    lengths = np.array([np.shape(y)[0] for y, _ in series], dtype=np.int32)
+    T, K = int(lengths.max()), np.shape(series[0][0])[1]
+    D = np.shape(series[0][1]["X"])[-1]
+    Y, X = np.zeros((N, T, K)), np.zeros((N, T, D))
+    for n, (y, st) in enumerate(series):
+        y = np.asarray(y, dtype=np.float64)
+        x = np.asarray(st["X"], dtype=np.float64).reshape(-1, D)
+        if y.shape != (lengths[n], K) or x.shape != (lengths[n], D):
+            raise AssertionError("series %d: Y has shape %s and X %s, expected (%d, %d) and (%d, %d)"
+                                 % (n, y.shape, x.shape, lengths[n], K, lengths[n], D))
+        Y[n, :lengths[n]], X[n, :lengths[n]] = y, x
+    st0 = {"X": X}
+    for k in _STATE_KEYS[1:]:
+        st0[k] = np.concatenate([np.asarray(st[k], dtype=np.float64) for _, st in series])       # each [1, ...]
+    return Y, st0, lengths
+
+
 class LDSBatch(object):
     ELBO_PARTS = ("X", "Y", "A", "C", "Q", "R")
 
-    def __init__(self, N, T, D, K, noise="diagonal_gamma", device=0):
+    def __init__(self, N, T, D, K, noise="diagonal_gamma", device=0, lengths=None):
+        """lengths: int [N], the chain length T_n of each replicate, 2 <= T_n <= T (pyvb_lds_create_lengths); None: all T.
+        Arrays stay [N, T, ...]; rows t >= T_n of replicate n are padding: setters accept anything there, getters return
+        0.0 in X and in the outputs."""
         if noise not in _NOISE:
             raise NotImplementedError("noise precision %r has no HIP path (DiagonalGamma, Gamma and Wishart do)" % (noise,))
         self.N, self.T, self.D, self.K, self.noise, self.device = int(N), int(T), int(D), int(K), noise, int(device)
         self.bound = "reference"
         h = C.ctypes.c_void_p()
-        C.check(C.lib.pyvb_lds_create(C.ctypes.byref(h), self.device, self.N, self.T, self.D, self.K, _NOISE[noise]))
+        if lengths is None:
+            C.check(C.lib.pyvb_lds_create(C.ctypes.byref(h), self.device, self.N, self.T, self.D, self.K, _NOISE[noise]))
+            self.lengths = np.full(self.N, self.T, dtype=np.int32)
+        else:
+            ln = np.ascontiguousarray(lengths, dtype=np.int32)
+            if ln.shape != (self.N,):
+                raise AssertionError("lengths has shape %s, expected (%d,)" % (ln.shape, self.N))
+            C.check(C.lib.pyvb_lds_create_lengths(C.ctypes.byref(h), self.device, self.N, self.T, self.D, self.K, _NOISE[noise],
+                                                  ln.ctypes.data_as(C._ip)))
+            self.lengths = np.empty(self.N, dtype=np.int32)
+            C.check(C.lib.pyvb_lds_get_lengths(h, self.lengths.ctypes.data_as(C._ip)))
         self._h = h
 
     # -- lifetime ---------------------------------------------------------------------------
@@ -65,7 +105,8 @@ class LDSBatch(object):
         self._check(C.lib.pyvb_lds_set_priors(self._h, *[C.dptr(a) for a in arrs]))
 
     def set_observations(self, Y):
-        """Y[N,T,K]; NaN = missing entry (the rows concerned become variational nodes: set_output_state, update_Y)."""
+        """Y[N,T,K]; NaN = missing entry (the rows concerned become variational nodes: set_output_state, update_Y).
+        With chain lengths, rows t >= T_n may hold anything; NaN in a row t < T_n is refused (E_UNSUPPORTED)."""
         Y = _f64(Y, (self.N, self.T, self.K), "Y")
         self._check(C.lib.pyvb_lds_set_observations(self._h, C.dptr(Y)))
 
@@ -80,13 +121,14 @@ class LDSBatch(object):
 
     def get_outputs(self, with_qld=False):
         """(posterior means [N,T,K], variances [N,T,K]) of the outputs; fully observed rows: (value, 0).
-        with_qld: also q_ln_det [N,T] of the rows updated so far (NaN otherwise)."""
+        with_qld: also q_ln_det [N,T] of the rows updated so far (NaN otherwise).  Padding rows (t >= T_n): 0, 0, NaN."""
         q, v = np.empty((self.N, self.T, self.K)), np.empty((self.N, self.T, self.K))
         ld = np.empty((self.N, self.T)) if with_qld else None
         self._check(C.lib.pyvb_lds_get_outputs(self._h, C.dptr(q), C.dptr(v), C.dptr(ld)))
         return (q, v, ld) if with_qld else (q, v)
 
     def set_state(self, X=None, A_mean=None, A_colvar=None, C_mean=None, C_colvar=None, Q_b=None, R_b=None):
+        """X[N,T,D] and the parameter posteriors; padding rows of X (t >= T_n) may hold anything."""
         N, T, D, K = self.N, self.T, self.D, self.K
         shapes = [("X", X, (N, T, D)), ("A_mean", A_mean, (N, D, D)), ("A_colvar", A_colvar, (N, D, D)),
                   ("C_mean", C_mean, (N, K, D)), ("C_colvar", C_colvar, (N, D, K)), ("Q_b", Q_b, (N, D)), ("R_b", R_b, (N, K))]
@@ -125,6 +167,8 @@ class LDSBatch(object):
 
     # -- outputs ----------------------------------------------------------------------------
     def get_state(self, what=("X", "A_mean", "A_colvar", "C_mean", "C_colvar", "Q_a", "Q_b", "R_a", "R_b")):
+        """Posterior means of the states and the parameter posteriors.  Padding rows of X (t >= T_n) read as 0.0; Q_a / R_a
+        count the children of each replicate's own Q (T_n - 1) and R (T_n)."""
         N, T, D, K = self.N, self.T, self.D, self.K
         shapes = {"X": (N, T, D), "A_mean": (N, D, D), "A_colvar": (N, D, D), "C_mean": (N, K, D), "C_colvar": (N, D, K),
                   "Q_a": (N, D), "Q_b": (N, D), "R_a": (N, K), "R_b": (N, K)}
@@ -134,7 +178,8 @@ class LDSBatch(object):
         return out
 
     def get_posterior_classes(self):
-        """(Sigma[N,3,D,D], q_ln_det[N,3]) of X_0, the interior X_t and X_{T-1} as of their last update."""
+        """(Sigma[N,3,D,D], q_ln_det[N,3]) of X_0, the interior X_t and X_{T-1} as of their last update (with chain lengths:
+        of replicate n's X_0, its interior and its X_{T_n-1}; T_n = 2 has no interior)."""
         S = np.empty((self.N, 3, self.D, self.D))
         q = np.empty((self.N, 3))
         self._check(C.lib.pyvb_lds_get_posterior_classes(self._h, C.dptr(S), C.dptr(q)))
@@ -186,6 +231,7 @@ class LDSBatch(object):
         self._check(C.lib.pyvb_lds_sweep(self._h, C.FORWARD if direction == "forward" else C.BACKWARD))
 
     def update_x(self, t):
+        """Xs[t].update() in every active replicate that has a node t (t < T_n)."""
         self._check(C.lib.pyvb_lds_update_x(self._h, int(t)))
 
     def update_A(self):
@@ -306,14 +352,29 @@ class LDSBatch(object):
         self._check(C.lib.pyvb_lds_comm_init_host(self._h, self._host_cb, None, int(rank), int(world)))
 
     # -- convenience ------------------------------------------------------------------------
+    def live_rows(self):
+        """bool [N, T]: True where row t is a node of replicate n's chain (t < T_n)."""
+        return np.arange(self.T)[None, :] < self.lengths[:, None]
+
+    def has_missing_outputs(self, Y):
+        """NaN in a row of Y that is an output of some graph (padding rows do not count)."""
+        return bool(np.isnan(np.asarray(Y))[self.live_rows()].any())
+
     @classmethod
-    def from_problem(cls, Y, st0, pri, device=0):
+    def from_series(cls, series, pri, device=0):
+        """One handle for time series of different lengths: series is a list of (Y_n[T_n, K], st0_n) with st0_n as
+        synth.initial_state(T_n, D, K, 1) gives it; replicate n is the graph with T_n time steps (pad_series)."""
+        Y, st0, lengths = pad_series(series)
+        return cls.from_problem(Y, st0, pri, device, lengths=lengths)
+
+    @classmethod
+    def from_problem(cls, Y, st0, pri, device=0, lengths=None):
         N, T, K = Y.shape
         D = st0["A_mean"].shape[1]
-        b = cls(N, T, D, K, pri.get("noise", "diagonal_gamma"), device)
+        b = cls(N, T, D, K, pri.get("noise", "diagonal_gamma"), device, lengths=lengths)
         b.set_priors(pri)
         b.set_observations(Y)
-        if "Yq" in st0 and np.isnan(Y).any():
+        if "Yq" in st0 and b.has_missing_outputs(Y):
             b.set_output_state(st0["Yq"], st0["Yrowvar"])
         if b.noise == "wishart":        # the compact initial state carries the diagonal of qw in Q_b / R_b
             b.set_state(**{k: st0[k] for k in ("X", "A_mean", "A_colvar", "C_mean", "C_colvar")})
