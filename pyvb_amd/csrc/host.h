@@ -1,6 +1,7 @@
-// Host-side plumbing shared by the two handle types (pyvb_lds: api.hip, pyvb_pca: api_pca.hip): argument and error checks,
-// the record of the device buffers a handle owns, copies on a handle's stream -- and the state each handle tracks on the host
-// about what is current on the device, with the events that change it.  Kernel files read this state; only the API files
+// Host-side plumbing shared by the three handle types (pyvb_lds: api.hip, pyvb_pca: api_pca.hip, pyvb_graph: k_tape.hip): argument
+// and error checks, the record of the device buffers a handle owns, copies on a handle's stream -- and the state the two fused
+// handles track on the host about what is current on the device, with the events that change it (a pyvb_graph keeps none: its
+// tapes are planned on the host once, tape_plan.h).  Kernel files read this state; only the API files
 // (through the events below) write it.  DESIGN.md, "What is current: the host-side state of a handle", has the dependency table.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -22,9 +23,14 @@ int pyvb_hip_fail(hipError_t e, const char* what, const char* file, int line);
 // Every device allocation made for a handle, recorded when it is made; *_destroy walks the record.
 struct DeviceBuffers {
     std::vector<void*> owned;
-    int alloc(void** p, size_t bytes, int fill_byte = 0) {
+    int alloc_raw(void** p, size_t bytes) {         // not filled: the caller overwrites all of it
         HIPCHK(hipMalloc(p, bytes));
         owned.push_back(*p);
+        return PYVB_OK;
+    }
+    int alloc(void** p, size_t bytes, int fill_byte = 0) {
+        const int rc = alloc_raw(p, bytes);
+        if (rc != PYVB_OK) return rc;
         HIPCHK(hipMemset(*p, fill_byte, bytes));
         return PYVB_OK;
     }

@@ -13,6 +13,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(HERE, "golden"))
 sys.path.insert(0, HERE)
 import generic_scenarios as GS  # noqa: E402
+import tape_cases as TC  # noqa: E402
 from test_generic_cpu import check_scenario, _close  # noqa: E402
 
 
@@ -138,21 +139,37 @@ def test_malformed_tapes_are_refused_and_bad_indices_skipped():
     """pyvb_graph_tape_create checks every extent a record touches against the arena; gather indices are data and are
     checked by the kernel (error reported at the next sync, nothing read or written outside)."""
     from pyvb_amd import _capi, generic
-    ex = generic.DeviceExecutor(64)
+    ex = generic.DeviceExecutor(TC.VALIDATION_ARENA)
     G = generic
-    bad = [
-        [G.T_GEMM, 0, 16, 32, 4, 4, 4, 0],          # b = 32..47 fine, a = 16..31 fine, dst fine -> but k * n beyond: see next
-        [G.T_GEMM, 56, 0, 16, 4, 4, 4, 0],          # dst 56..71 leaves the arena of 64
-        [G.T_COPY2D, 0, 8, 2, 3, 4, 4, 0],          # leading dimension of dst (2) smaller than n (4)
-        [G.T_CHOLINV, 0, 16, 32, 4, 0, 40, 0],      # scratch 40 .. 40 + 2 * 16 leaves the arena
-        [G.T_UNARY, 0, 8, 0, 2, 2, 0, 9],           # no such function
-        [99, 0, 0, 0, 1, 1, 0, 0],                  # no such opcode
-        [G.T_AXPBY, 0, 8, -1, 70, 1, 1, 0],         # 70 elements
-    ]
-    ex.tape([bad[0]])                                # the first one is well formed
-    for rec in bad[1:]:
-        with pytest.raises(_capi.PyvbHipError):
-            ex.tape([rec])
+    # the list of tests/tape_cases.py (the CPU test runs it through the host-only planner): the seven records this test has
+    # always held -- the first one well formed, six refused -- and the boundary cases beside them
+    assert [ok for _, ok in TC.VALIDATION[:7]] == [True] + [False] * 6
+    for rec, ok in TC.VALIDATION:
+        if ok:
+            ex.drop(ex.tape([rec]))
+        else:
+            with pytest.raises(_capi.PyvbHipError):
+                ex.tape([rec])
+    # the refusals that need a live handle: tape ids, and programs that do not tile (messages of include/pyvb_hip.h's entries)
+    t = ex.tape([TC.VALIDATION[0][0]] * 4)
+    tables = {k: np.ascontiguousarray(v, dtype=np.int32) for k, v in dict(
+        ok=[[0, 2], [2, 2]], gap=[[0, 2], [3, 1]], short=[[0, 2], [2, 1]], l_ok=[[0, 2]], l_gap=[[0, 1], [2, 1]], l_short=[[0, 1]]).items()}
+    ptr = lambda k: tables[k].ctypes.data_as(_capi._ip)
+
+    def refused(rc, msg):
+        assert rc == _capi.E_ARG and msg in _capi.lib.pyvb_last_error()
+    prog = _capi.lib.pyvb_graph_tape_set_program
+    refused(_capi.lib.pyvb_graph_tape_run(ex._h, t + 1), b"no such tape")
+    refused(_capi.lib.pyvb_graph_tape_run(ex._h, -1), b"no such tape")
+    refused(_capi.lib.pyvb_graph_tape_destroy(ex._h, t + 1), b"no such tape")
+    refused(prog(ex._h, t + 1, ptr("ok"), 2, ptr("l_ok"), 1), b"no such tape")
+    refused(prog(ex._h, t, None, 2, ptr("l_ok"), 1), b"bad arguments")
+    refused(prog(ex._h, t, ptr("gap"), 2, ptr("l_ok"), 1), b"the blocks of a program must tile the tape in order")
+    refused(prog(ex._h, t, ptr("short"), 2, ptr("l_ok"), 1), b"the blocks of a program must cover every record of the tape")
+    refused(prog(ex._h, t, ptr("ok"), 2, ptr("l_gap"), 2), b"the launches of a program must tile the blocks in order")
+    refused(prog(ex._h, t, ptr("ok"), 2, ptr("l_short"), 1), b"the launches of a program must cover every block")
+    assert prog(ex._h, t, ptr("ok"), 2, ptr("l_ok"), 1) == _capi.OK
+    ex.drop(t)
     # gather with a row index that points outside: rows at 40, cols at 44
     ex.write(0, np.arange(16.0))
     ex.write(40, np.array([1.0, 1e6])); ex.write(44, np.array([0.0, 2.0]))
@@ -426,38 +443,16 @@ def test_expectation_of_a_product_when_the_queue_hands_the_graph_over():
         _close(exxt, exxt2, "pass_down_ExxT after the hand-over", 1e-10)
 
 
-def _plan_stub():
-    from pyvb_amd import generic as G
-
-    class P(object):
-        temp_base, temp_high = 4096, 4096
-        vals = []
-
-        def const(self, v):
-            self.vals.append(float(v))
-            return G.Ref(len(self.vals) - 1, 1, 1)
-
-        def ones(self, n):
-            o = len(self.vals)
-            self.vals.extend([1.0] * n)
-            return G.Ref(o, n, 1)
-    return P()
-
-
-def _run_both(t, plan, fill, size):
+def _run_both(ops, arena):
     """The tape on the device and in the numpy interpreter, same arena."""
     from oracle import tape_ref as R
     from pyvb_amd import generic as G
-    arena = np.zeros(size)
-    arena[:len(plan.vals)] = plan.vals
-    for off, arr in fill:
-        arena[off:off + arr.size] = arr.reshape(-1)
     ref = arena.copy()
-    R.run(ref, t.array())
-    ex = G.DeviceExecutor(size)
+    R.run(ref, ops)
+    ex = G.DeviceExecutor(arena.size)
     ex.write(0, arena)
-    ex.run(ex.tape(t.array()))
-    got = ex.read(0, size)
+    ex.run(ex.tape(ops))
+    got = ex.read(0, arena.size)
     ex.close()
     return got, ref
 
@@ -466,46 +461,24 @@ def test_long_tapes_are_staged_in_chunks_and_windows_that_do_not_fit_fall_back()
     """The interpreter keeps a block's working set in LDS when it fits (k_tape.hip): (a) a tape of 1700 records -- more than
     the 512 staged at a time -- on a small working set, (b) a tape whose working set (three 80 x 80 matrices and their
     products) exceeds the window and stays on global memory, (c) a tape with a gather record (addresses that are data: never
-    cached).  All three against the numpy interpreter on the same arena."""
-    from pyvb_amd import generic as G
-    rng = np.random.default_rng(4)
+    cached).  All three (tests/tape_cases.py: long_tapes) against the numpy interpreter on the same arena."""
+    tapes = TC.long_tapes()
     # (a)
-    plan = _plan_stub()
-    a = G.Ref(2048, 6, 6); b = G.Ref(2100, 6, 6)
-    A = rng.standard_normal((6, 6)) * 0.3; B = rng.standard_normal((6, 6)) * 0.3
-    t = G.Tape(plan)
-    acc = t.copy(a)
-    for k in range(560):                    # three records per turn
-        g = t.gemm(acc, b)
-        t.axpby(0.5, g, 0.5, a, dst=acc)
-        t.mul(acc, acc) if k % 7 == 0 else t.unary(acc, G.U_NEG)
-    assert len(t.ops) > 3 * 512
-    got, ref = _run_both(t, plan, [(a.off, A), (b.off, B)], plan.temp_high + 64)
+    ops, arena, refs = tapes["a"]
+    acc = refs["acc"]
+    got, ref = _run_both(ops, arena)
     _close(got[acc.off:acc.off + 36], ref[acc.off:acc.off + 36], "result of the long tape", 1e-11)
     # (b)
-    plan = _plan_stub()
-    m = 80
-    x, y, z = G.Ref(8192, m, m), G.Ref(8192 + m * m, m, m), G.Ref(8192 + 2 * m * m, m, m)
-    plan.temp_base = plan.temp_high = 8192 + 3 * m * m
-    t = G.Tape(plan)
-    p1 = t.gemm(x, y); p2 = t.gemm(p1, z, tb=True); p3 = t.add(p2, t.transpose(p1))
-    tr = t.trace(p3)
-    mats = [rng.standard_normal((m, m)) / m for _ in range(3)]
-    got, ref = _run_both(t, plan, [(x.off, mats[0]), (y.off, mats[1]), (z.off, mats[2])], plan.temp_high + 64)
-    assert (plan.temp_high - 8192) > 12288      # larger than the LDS window
+    ops, arena, refs = tapes["b"]
+    p3, tr, mats, m = refs["p3"], refs["tr"], refs["mats"], refs["m"]
+    got, ref = _run_both(ops, arena)
     _close(got[p3.off:p3.off + m * m], ref[p3.off:p3.off + m * m], "products beyond the window", 1e-11)
     _close(got[tr.off:tr.off + 1], ref[tr.off:tr.off + 1], "their trace", 1e-11)
     _close(ref[p3.off:p3.off + m * m].reshape(m, m), (mats[0] @ mats[1]) @ mats[2].T + (mats[0] @ mats[1]).T, "against numpy", 1e-11)
     # (c)
-    plan = _plan_stub()
-    s = G.Ref(2048, 5, 5); rows = G.Ref(2100, 2, 1); cols = G.Ref(2110, 3, 1)
-    t = G.Tape(plan)
-    sq = t.gemm(s, s, tb=True)
-    ga = t.gather(sq, rows, cols)
-    out = t.scale(ga, 2.0)
-    t.axpby(1.0, out, 1.0, out, dst=out)
-    S = rng.standard_normal((5, 5))
-    got, ref = _run_both(t, plan, [(s.off, S), (rows.off, np.array([4.0, 1.0])), (cols.off, np.array([0.0, 2.0, 3.0]))], plan.temp_high + 64)
+    ops, arena, refs = tapes["c"]
+    out, S = refs["out"], refs["S"]
+    got, ref = _run_both(ops, arena)
     _close(got[out.off:out.off + 6], ref[out.off:out.off + 6], "gather inside a tape", 1e-12)
     _close(ref[out.off:out.off + 6].reshape(2, 3), 4.0 * (S @ S.T)[[4, 1]][:, [0, 2, 3]], "against numpy", 1e-12)
 
@@ -518,48 +491,9 @@ def test_records_scheduled_into_bundles_compute_what_the_tape_order_computes():
     records in tape order.  The last case is a chain whose working set is larger than one window: it is cut into several."""
     from pyvb_amd import generic as G
     from oracle import tape_ref as R
-    rng = np.random.default_rng(11)
-    for case in range(12):
-        size = 4096 if case < 11 else 40000
-        nslot = 24 if case < 11 else 4000
-        base = 64
-        shapes = [(2, 2), (3, 3), (2, 1), (3, 1), (1, 1), (4, 4)]
-        slots = []                              # (offset, m, n): matrices laid out back to back, so neighbours never overlap
-        off = base
-        for k in range(nslot):
-            m, n = shapes[int(rng.integers(len(shapes)))]
-            slots.append((off, m, n)); off += m * n
-        assert off + 64 < size
-        by_shape = {}
-        for sl in slots:
-            by_shape.setdefault((sl[1], sl[2]), []).append(sl)
-        scal = [o for o, m, n in slots if (m, n) == (1, 1)] or [base]
-        ops = []
-        nrec = 700 if case < 11 else 6000
-        idx_rows, idx_cols = size - 40, size - 30
-        for r in range(nrec):
-            kind = int(rng.integers(9))
-            (m, n) = shapes[int(rng.integers(len(shapes)))]
-            cand = by_shape.get((m, n), [])
-            if len(cand) < 3:
-                continue
-            pick = lambda: cand[int(rng.integers(len(cand)))][0] if case < 11 else cand[min(len(cand) - 1, (r * len(cand)) // nrec + int(rng.integers(3)))][0]
-            d_, a_, b_ = pick(), pick(), pick()
-            if kind == 0 and d_ != a_: ops.append([G.T_COPY2D, d_, a_, n, m, n, n, 0])
-            elif kind == 1 and len({d_, a_, b_}) == 3: ops.append([G.T_AXPBY, d_, a_, b_, m, n, int(rng.choice(scal)), int(rng.choice(scal))])
-            elif kind == 2 and m == n and len({d_, a_, b_}) == 3: ops.append([G.T_GEMM, d_, a_, b_, m, n, m, int(rng.integers(8)) & 7])
-            elif kind == 3 and len({d_, a_, b_}) == 3: ops.append([G.T_MUL, d_, a_, b_, m, n, 0, 0])
-            elif kind == 4 and d_ != a_: ops.append([G.T_UNARY, d_, a_, 0, m, n, 0, 4])
-            elif kind == 5 and m == n: ops.append([G.T_TRACE, int(rng.choice(scal)), a_, 0, m, m, 0, int(rng.integers(2)) * 4])
-            elif kind == 6 and len({a_, b_}) == 2: ops.append([G.T_DOT, int(rng.choice(scal)), a_, b_, m, n, 0, 0])
-            elif kind == 7 and d_ != a_: ops.append([G.T_FILL, d_, 0, n, m, n, 0, int(rng.integers(2))])
-            elif kind == 8 and case % 3 == 2 and r % 50 == 49 and m == n and m >= 2:
-                ops.append([G.T_GATHER, d_, a_, idx_rows, m, n, n, idx_cols])
-        ops = np.asarray(ops, dtype=np.int32)
-        arena = np.zeros(size)
-        arena[base:off] = rng.uniform(-0.9, 0.9, off - base)        # |values| < 1: products and sums of a few hundred records stay finite
-        arena[idx_rows:idx_rows + 4] = [1, 0, 2, 1]; arena[idx_cols:idx_cols + 4] = [0, 1, 1, 0]
-        # keep magnitudes in check: the tape is random, a chain of products may blow up -- rescale through a dry run
+    for case, ops, arena in TC.random_tapes():
+        size = arena.size
+        # the tape is random, a chain of products may blow up: such a case is left out
         ref = arena.copy()
         R.run(ref, ops)
         if not np.all(np.isfinite(ref)) or np.abs(ref).max() > 1e100:
