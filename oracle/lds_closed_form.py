@@ -37,6 +37,8 @@ Outputs with missing entries (Y holds NaN there; gaussian.py:90-96): the Y_t are
 import numpy as np
 from scipy.special import digamma, gammaln
 
+from . import _xlinalg as XL
+
 LN2PI = np.log(2.0 * np.pi)
 
 
@@ -54,7 +56,7 @@ def noise_expect(kind, a, b, dim):
     if kind == "wishart":
         # The reference's update leaves qw non-symmetric (its -<x><mu>^T term, nodes_todo.py:231); the build takes the
         # expectation of the symmetric part, which is the same thing for the first update (the parity target).
-        return a[:, None, None] * np.linalg.inv(0.5 * (b + np.swapaxes(b, -1, -2)))
+        return a[:, None, None] * XL.inv(0.5 * (b + np.swapaxes(b, -1, -2)))
     raise ValueError(kind)
 
 
@@ -68,7 +70,7 @@ def noise_lndet(kind, a, b, dim):
     if kind == "wishart":
         # NOT in the reference (Wishart has no pass_down_lndet): ln det of the expectation, like the Gamma
         # nodes (quirk Q2).  Parity unpinned.
-        return dim * np.log(a) - np.linalg.slogdet(0.5 * (b + np.swapaxes(b, -1, -2)))[1]
+        return dim * np.log(a) - XL.slogdet(0.5 * (b + np.swapaxes(b, -1, -2)))[1]
     raise ValueError(kind)
 
 
@@ -94,11 +96,11 @@ def wishart_llb(a0, B0, a, B):
     (nodes_todo.py:149-157) for D = 1.  NOT in the reference: derived, parity unpinned."""
     dim = B.shape[-1]
     Bs = 0.5 * (B + np.swapaxes(B, -1, -2))
-    lndB = np.linalg.slogdet(Bs)[1]
-    EL = a[:, None, None] * np.linalg.inv(Bs)
+    lndB = XL.slogdet(Bs)[1]
+    EL = a[:, None, None] * XL.inv(Bs)
     Eln = _psi_multi(a, dim) - lndB
     half = 0.5 * (dim + 1)
-    ret = (a0 - half) * Eln - _lgamma_multi(a0, dim) + a0 * np.linalg.slogdet(B0)[1] - np.einsum("ij,nji->n", B0, EL)
+    ret = (a0 - half) * Eln - _lgamma_multi(a0, dim) + a0 * XL.slogdet(B0)[1] - np.einsum("ij,nji->n", B0, EL)
     ret = ret - ((a - half) * Eln - _lgamma_multi(a, dim) + a * lndB - a * dim)
     return ret
 
@@ -139,7 +141,7 @@ def outer_expect(M, Mcov, G):
 
 def _chol_qld(P):
     """cho_factor + the reference's q_ln_det (gaussian.py:118-120, quirk Q1)."""
-    L = np.linalg.cholesky(P)
+    L = XL.cholesky(P)
     s = np.sum(np.log(np.einsum("nii->ni", L)), axis=-1)
     return 0.5 / s
 
@@ -162,7 +164,7 @@ def state_posteriors(st, pri):
     MC = quad_expect(st["C_mean"], st["C_cov"], Rb)
     L0 = np.broadcast_to(pri["x0_prec"], MA.shape)
     P = np.stack([L0 + (MC + MA if T > 1 else MC), Qb + (MC + MA), Qb + MC], axis=1)
-    Sig = np.linalg.inv(P)
+    Sig = XL.inv(P)
     qld = np.stack([_chol_qld(P[:, c]) for c in range(3)], axis=1)
     return {"Qbar": Qb, "Rbar": Rb, "P": P, "Sigma": Sig, "qld": qld}
 
@@ -253,7 +255,7 @@ def init_missing(st, pri, Yobs, Yq0, Yrowvar0):
     st["Yobs"] = Yobs
     st["Yq"] = np.where(full[:, :, None], np.nan_to_num(Yobs), Yq0)
     st["Yvar"] = np.where(full[:, :, None], 0.0, Yrowvar0[:, :, None] * np.ones_like(Yobs))
-    st["Yqld"] = np.full(Yobs.shape[:2], np.nan)
+    st["Yqld"] = np.full(Yobs.shape[:2], np.nan, dtype=st["Yq"].dtype)
 
 
 def update_Y(st, pri):
@@ -269,16 +271,16 @@ def update_Y(st, pri):
     if kind == "wishart":
         # dense <R>: the general form of gaussian.py:117-134, row by row (every row has its own set of known entries)
         N, T = upd.shape
-        cov_full = np.linalg.inv(Rb)
+        cov_full = XL.inv(Rb)
         qld = np.array([_chol_qld(Rb[n:n + 1])[0] for n in range(N)])
-        st.setdefault("Yld", np.full((N, T), np.nan))
-        st["Ycovsum"] = np.zeros((N, K, K))
+        st.setdefault("Yld", np.full((N, T), np.nan, dtype=Rb.dtype))
+        st["Ycovsum"] = np.zeros((N, K, K), dtype=Rb.dtype)
         for n in range(N):
             for t in np.nonzero(upd[n])[0]:
                 mu, cov = pmu[n, t].copy(), cov_full[n].copy()
                 oi = np.nonzero(~miss[n, t])[0]
                 if len(oi):
-                    cov_obs_inv = np.linalg.inv(cov[np.ix_(oi, oi)])
+                    cov_obs_inv = XL.inv(cov[np.ix_(oi, oi)])
                     cov_obs_all = cov[:, oi]
                     gain = cov_obs_all @ cov_obs_inv
                     mu = mu + gain @ (st["Yobs"][n, t, oi] - mu[oi])
@@ -287,7 +289,7 @@ def update_Y(st, pri):
                     cov[oi, :] = 0.0
                     cov[:, oi] = 0.0
                     mi = np.nonzero(miss[n, t])[0]
-                    st["Yld"][n, t] = np.linalg.slogdet(cov[np.ix_(mi, mi)])[1]
+                    st["Yld"][n, t] = XL.slogdet(cov[np.ix_(mi, mi)])[1]
                 st["Yq"][n, t] = mu
                 st["Yvar"][n, t] = np.diag(cov)
                 st["Yqld"][n, t] = qld[n]
@@ -331,7 +333,7 @@ def _update_columns(M, Mcov, prior_mean, prior_prec, Lam, G, H, obs=None, cols=N
     updates (gaussian.py:109-110); a partially observed one is conditioned on its known
     entries after the update (gaussian.py:125-134)."""
     N, rows, D = M.shape
-    qld = np.full((N, D), np.nan)
+    qld = np.full((N, D), np.nan, dtype=M.dtype)
     LH = np.einsum("nkl,nli->nki", Lam, H)
     for i in (range(D) if cols is None else range(*cols)):          # cols = (first, last + 1): [a.update() for a in As[first:last + 1]]
         known = None if obs is None else ~np.isnan(obs[:, i])
@@ -342,12 +344,12 @@ def _update_columns(M, Mcov, prior_mean, prior_prec, Lam, G, H, obs=None, cols=N
         Gi[:, i] = 0.0
         m2 = LH[:, :, i] - np.einsum("nkl,nl->nk", Lam, np.einsum("nlj,nj->nl", M, Gi))
         w = (prior_prec[i] * prior_mean[:, i])[None] + m2
-        cov = np.linalg.inv(prec)
+        cov = XL.inv(prec)
         mu = np.einsum("nkl,nl->nk", cov, w)
         qld[:, i] = _chol_qld(prec)
         if known is not None and known.any():
             oi = np.nonzero(known)[0]
-            cov_obs_inv = np.linalg.inv(cov[:, oi][:, :, oi])
+            cov_obs_inv = XL.inv(cov[:, oi][:, :, oi])
             cov_obs_all = cov[:, :, oi]
             gain = np.einsum("nko,nop->nkp", cov_obs_all, cov_obs_inv)
             mu = mu + np.einsum("nko,no->nk", gain, obs[oi, i][None] - mu[:, oi])
@@ -429,9 +431,10 @@ def update_R(st, pri, S, T):
 
 
 def _bcast_a(a, b, kind):
+    a = np.asarray(a, dtype=np.result_type(b.dtype, np.float64))        # float64, or what b holds beyond it (an extended-precision run)
     if kind == "wishart":
-        return np.broadcast_to(np.asarray(a, dtype=float), b.shape[:1]).copy()
-    return np.broadcast_to(np.asarray(a, dtype=float), b.shape).copy()
+        return np.broadcast_to(a, b.shape[:1]).copy()
+    return np.broadcast_to(a, b.shape).copy()
 
 
 def init_noise_a(st, pri, T):
@@ -519,7 +522,7 @@ def expand_state(st0, pri, T, Y=None):
         st["Q_b"] = np.einsum("nd,de->nde", st["Q_b"], np.eye(st["Q_b"].shape[1]))
         st["R_b"] = np.einsum("nd,de->nde", st["R_b"], np.eye(st["R_b"].shape[1]))
     init_noise_a(st, pri, T)
-    st["qld_A"] = np.full(st["A_mean"].shape[:1] + st["A_mean"].shape[2:], np.nan)
+    st["qld_A"] = np.full(st["A_mean"].shape[:1] + st["A_mean"].shape[2:], np.nan, dtype=st["A_mean"].dtype)
     st["qld_C"] = st["qld_A"].copy()
     for which in ("A", "C"):
         if pri.get(which + "_obs") is not None:

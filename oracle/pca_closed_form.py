@@ -26,6 +26,8 @@ qld_W [q], qld_Z, qld_X (of never-observed rows), qld_Mu.  obs [N,d] bool.
 import numpy as np
 from scipy.special import digamma, gammaln
 
+from . import _xlinalg as XL
+
 LN2PI = np.log(2.0 * np.pi)
 
 
@@ -65,8 +67,8 @@ def update_Z(st, pri):
     beta = st["beta_a"] / st["beta_b"]
     q = st["Z"].shape[1]
     prec = np.eye(q) + beta * _WtW(st)
-    st["Z_cov"] = np.linalg.inv(prec)
-    st["qld_Z"] = 0.5 / np.sum(np.log(np.diag(np.linalg.cholesky(prec))))
+    st["Z_cov"] = XL.inv(prec)
+    st["qld_Z"] = 0.5 / np.sum(np.log(np.diag(XL.cholesky(prec))))
     st["Z"] = (beta * (st["X"] - st["Mu_mean"]) @ st["W_mean"]) @ st["Z_cov"]
 
 
@@ -170,21 +172,23 @@ def iterate(st, pri):
 
 
 def make_state(init, pri, N, d, q):
-    """Copy an explicit initial state (tests/golden/make_golden.py: pca_initial_state) into the layout above."""
-    st = {k: np.array(v, dtype=float, copy=True) for k, v in init.items() if k not in ("obs", "X_full", "X_var0")}
+    """Copy an explicit initial state (tests/golden/make_golden.py: pca_initial_state) into the layout above.  The state is
+    float64 unless init["X"] holds a wider type (np.longdouble: an extended-precision run), which it then keeps."""
+    dt = np.result_type(np.asarray(init["X"]).dtype, np.float64)
+    st = {k: np.array(v, dtype=dt, copy=True) for k, v in init.items() if k not in ("obs", "X_full", "X_var0")}
     st["obs"] = np.array(init["obs"], dtype=bool)
-    st["X_var"] = np.zeros((N, d))
+    st["X_var"] = np.zeros((N, d), dtype=dt)
     st["Xdata"] = st["X"].copy()            # the observations (where obs)
     if "X_full" in init:
         # the X_n as their constructors drew them (gaussian.py:70-72): a row that is not fully observed carries a mean at
         # ALL its entries and the covariance c_n I until its first update conditions it on the observed ones (:90-96, :125-134)
         free = ~st["obs"].all(1)
-        st["X"][free] = np.asarray(init["X_full"], dtype=float)[free]
-        st["X_var"][free] = np.asarray(init["X_var0"], dtype=float)[free, None]
-    st["W_var"] = np.zeros((q, d))
-    st["Mu_var"] = np.zeros(d)
-    st["qld_W"] = np.full(q, np.nan)
+        st["X"][free] = np.asarray(init["X_full"], dtype=dt)[free]
+        st["X_var"][free] = np.asarray(init["X_var0"], dtype=dt)[free, None]
+    st["W_var"] = np.zeros((q, d), dtype=dt)
+    st["Mu_var"] = np.zeros(d, dtype=dt)
+    st["qld_W"] = np.full(q, np.nan, dtype=dt)
     st["qld_Z"] = st["qld_X"] = st["qld_Mu"] = np.nan
     st["beta_a"] = pri["beta_a0"] + 0.5 * d * N
-    st["beta_b"] = float(init["beta_b"])
+    st["beta_b"] = float(init["beta_b"]) if dt == np.float64 else dt.type(init["beta_b"])
     return st

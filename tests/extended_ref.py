@@ -1,0 +1,438 @@
+"""TEST INFRASTRUCTURE: the oracles run in extended precision (np.longdouble, 64-bit significand), the yardstick that
+measures the float64 oracle and the HIP kernels against that run, and the cases both are measured on.
+
+The algorithm is not restated: oracle/lds_closed_form.py and oracle/pca_closed_form.py preserve the dtype of what they are
+given, and their inversions / factorisations go through oracle/_xlinalg.py, which has a long-double version.  to_long()
+casts a problem; *_trace() runs the example's loop stage by stage and records every compared quantity after the stage
+that produces it.  The same trace function drives the float64 oracle, the extended run and (tests/test_envelope_gpu.py) the
+handle, so the three sequences of (key, array) line up by construction.
+
+Yardstick.  For a quantity q after a stage, with rel() the suite's max-norm relative error,
+    e64   = rel(float64 oracle, extended run)          what LAPACK / einsum in float64 lose on this problem
+    y     = max(e64, n 2^-52),  n = max(D, K, T)       (max(d, q, N) for PCA): never below one length-n float64 accumulation
+    e_gpu = rel(handle, extended run) <= FACTOR y,     FACTOR = 16
+and every case must have e64 <= CAP = 1e-11 on every quantity, so the bound never exceeds 1.6e-10.  The lower bound is not
+part of this: digamma and gammaln exist in float64 only, elbo_parts keeps its 1e-8 tests.
+"""
+import functools
+import importlib.util
+import os
+
+import numpy as np
+
+from oracle import lds_closed_form as O
+from oracle import pca_closed_form as P
+from pyvb_amd import synth
+
+LD = np.longdouble
+U64 = 2.0 ** -52
+FACTOR = 16.0
+CAP = 1e-11
+HERE = os.path.dirname(os.path.abspath(__file__))
+
+
+def require_extended():
+    """The reference must carry at least 11 bits more than float64; a platform whose long double is float64 cannot run these
+    tests, and that is a failure, not a skip."""
+    eps = float(np.finfo(LD).eps)
+    if eps > 2.0 ** -63:
+        raise RuntimeError("np.longdouble has eps = %.3e > 2^-63 on this platform: no extended-precision reference, "
+                           "the accuracy-envelope tests cannot run here" % eps)
+
+
+def _cast(v):
+    if isinstance(v, np.ndarray):
+        return v.astype(LD) if v.dtype.kind == "f" else v.copy()
+    if isinstance(v, (float, np.floating)):
+        return LD(v)
+    return v
+
+
+def to_long(d):
+    """A copy of a dict of states, priors or initial values -- or of one array -- with every floating-point entry cast to
+    np.longdouble (exactly); masks, integers and strings stay."""
+    require_extended()
+    if isinstance(d, dict):
+        return {k: _cast(v) for k, v in d.items()}
+    return _cast(np.asarray(d))
+
+
+def rel(a, b):
+    """max |a - b| / max |b| (tests/test_gpu_parity.py: _rel), formed in long double."""
+    a, b = np.asarray(a, dtype=LD), np.asarray(b, dtype=LD)
+    return float(np.abs(a - b).max() / max(np.abs(b).max(), LD(1e-300)))
+
+
+def yardstick(e64, n):
+    return max(e64, n * U64)
+
+
+# ----------------------------------------------------------------------------------------------------------------------------
+# LDS cases (the smallest shapes that reach each kernel instantiation)
+# ----------------------------------------------------------------------------------------------------------------------------
+def _wishart_priors(pri, D, K, rng):
+    """tests/test_gpu_parity.py: _wishart_priors with a generator -- proper priors: v0 > (dim - 1) / 2, dense w0"""
+    pri["noise"] = "wishart"
+    W = rng.standard_normal((D, D)); pri["Q_b0"] = 0.05 * (W @ W.T + D * np.eye(D)); pri["Q_a0"] = np.float64(0.5 * D + 1.0)
+    W = rng.standard_normal((K, K)); pri["R_b0"] = 0.05 * (W @ W.T + K * np.eye(K)); pri["R_a0"] = np.float64(0.5 * K + 0.5)
+
+
+def _plain(T, D, K, N, seed, **kw):
+    Y, st0, pri = synth.make_problem(T, D, K, N, seed=seed)
+    return dict(Y=Y, st0=st0, pri=pri, iters=2, **kw)
+
+
+def _gamma(T, D, K, N, seed):
+    c = _plain(T, D, K, N, seed)
+    c["pri"]["noise"] = "gamma"
+    for k in ("Q_a0", "Q_b0", "R_a0", "R_b0"):
+        c["pri"][k] = np.float64(1e-3)
+    return c
+
+
+def _hard(T, D, K, N, seed):
+    """tests/test_gpu_parity.py: test_warmup_is_data_driven_and_exact_fallback -- F close to its spectral bound"""
+    c = _plain(T, D, K, N, seed)
+    c["st0"]["R_b"] = c["st0"]["R_b"] * 1e8
+    c["st0"]["Q_b"] = c["st0"]["Q_b"] * 1e-6
+    return c
+
+
+def _wishart(T, D, K, N, seed, iters=2, known=False):
+    c = _plain(T, D, K, N, seed)
+    c["iters"] = iters
+    _wishart_priors(c["pri"], D, K, np.random.default_rng(T))
+    if known:           # tests/test_gpu_parity.py: test_known_matrix_entries_with_wishart_noise
+        rng = np.random.default_rng(5)
+        A_obs = np.full((D, D), np.nan); C_obs = np.full((K, D), np.nan)
+        A_obs[0, 0] = 0.9; A_obs[min(3, D - 1), 2] = -0.25; A_obs[D - 1, 2] = 0.1
+        A_obs[:, D - 1] = np.linspace(-0.2, 0.2, D)
+        C_obs[rng.random((K, D)) < 0.15] = 0.5
+        C_obs[:, 1] = np.arange(K) * 0.1 - 0.2
+        C_obs[:, 0] = np.nan
+        c["pri"]["A_obs"], c["pri"]["C_obs"] = A_obs, C_obs
+    return c
+
+
+def _missing(T, D, K, N, seed):
+    """tests/test_gpu_parity.py: test_outputs_with_missing_entries"""
+    c = _plain(T, D, K, N, seed)
+    rng = np.random.default_rng(T + K)
+    mask = rng.random((N, T, K)) < 0.15
+    mask[:, 1] = True; mask[:, T // 2] = True; mask[:, 0, 0] = True; mask[:, 3] = False
+    c["Y"] = np.where(mask, np.nan, c["Y"])
+    c["st0"]["Yq"] = rng.standard_normal((N, T, K)); c["st0"]["Yrowvar"] = 1.0 / rng.uniform(0.5, 1.5, size=(N, T))
+    return c
+
+
+def _known(T, D, K, N, seed):
+    """tests/test_gpu_parity.py: test_known_matrix_entries_vs_oracle"""
+    c = _plain(T, D, K, N, seed)
+    A_obs = np.full((D, D), np.nan); C_obs = np.full((K, D), np.nan)
+    A_obs[0, 0] = 1.0; A_obs[1, 0] = 1e-2; A_obs[3, 2] = -0.5
+    A_obs[:, 4] = np.linspace(-0.2, 0.2, D)
+    C_obs[2, 1] = 3.0; C_obs[:, 3] = np.arange(K) - 2.0
+    c["pri"]["A_obs"], c["pri"]["C_obs"] = A_obs, C_obs
+    return c
+
+
+def _lengths(lengths, D, K, seed):
+    """tests/test_lengths_gpu.py: _problem -- one handle, a chain length per replicate, padding rows zero"""
+    T, N = max(lengths), len(lengths)
+    c = _plain(T, D, K, N, seed)
+    live = np.arange(T)[None, :] < np.asarray(lengths)[:, None]
+    c["Y"] = np.where(live[:, :, None], c["Y"], 0.0)
+    c["st0"]["X"] = np.where(live[:, :, None], c["st0"]["X"], 0.0)
+    c["lengths"] = tuple(lengths)
+    return c
+
+
+# name -> (builder, in the warm-up contract?)
+LDS_CASES = {
+    "t19_d6_k4":            (lambda: _plain(19, 6, 4, 2, 101), False),
+    "t77_d16_k16":          (lambda: _plain(77, 16, 16, 2, 102), True),
+    "t77_d33_k17_gamma":    (lambda: _gamma(77, 33, 17, 2, 103), False),
+    "t40_d64_k64":          (lambda: _plain(40, 64, 64, 1, 104), True),
+    "t700_d8_k8_split":     (lambda: _plain(700, 8, 8, 1, 105, split_chosen=True), True),
+    "t2402_d64_k64_w1":     (lambda: dict(_plain(2402, 64, 64, 1, 106, W=1, headline=True), iters=1), True),
+    "t400_d4_k4_hard":      (lambda: _hard(400, 4, 4, 2, 2), True),
+    "t12_d72_k66_big":      (lambda: _plain(12, 72, 66, 1, 108), True),
+    "t600_d72_k66_big_w3":  (lambda: dict(_plain(600, 72, 66, 1, 109, W=3), iters=1), True),
+    "t40_d16_k16_wishart":  (lambda: _wishart(40, 16, 16, 2, 110), False),
+    "t30_d33_k17_wishart":  (lambda: _wishart(30, 33, 17, 1, 111), False),
+    "t30_d17_k9_wishart_known": (lambda: _wishart(30, 17, 9, 1, 112, known=True), False),
+    "t6_d72_k9_wishart_big": (lambda: _wishart(6, 72, 9, 1, 113, iters=1), False),
+    "t60_d5_k6_missing":    (lambda: _missing(60, 5, 6, 2, 114), False),
+    "t80_d5_k6_known":      (lambda: _known(80, 5, 6, 2, 115), False),
+    "lengths_3_19_60_77_d16_k16": (lambda: _lengths((3, 19, 60, 77), 16, 16, 116), True),
+}
+WARMUP_CASES = [k for k, v in LDS_CASES.items() if v[1]]
+
+
+def lds_case(name):
+    return LDS_CASES[name][0]()
+
+
+class OracleLDS(object):
+    """The stage calls of pyvb_amd.lds.LDSBatch on one oracle state, in the dtype of what it is given."""
+
+    def __init__(self, Y, st0, pri):
+        self.Y, self.pri, self.T = Y, pri, Y.shape[1]
+        self.st = O.expand_state(st0, pri, self.T, Y)
+        self.noise = pri["noise"]
+        self.post = self.S = None
+        self.recurrences = []
+
+    def sweep(self, direction):
+        if direction == "forward":
+            self.post = O.state_posteriors(self.st, self.pri)
+            if self.T > 2:      # the recurrence matrices of the segmented sweeps: F = Sigma_1 <Q><A>, B = Sigma_1 <A>^T<Q>
+                S1, Qb, A = self.post["Sigma"][:, 1], self.post["Qbar"], self.st["A_mean"]
+                self.recurrences.append((S1 @ (Qb @ A), S1 @ (np.swapaxes(A, -1, -2) @ Qb)))
+        O.sweep(self.st, self.pri, self.Y, direction, self.post)
+
+    def update_Y(self):
+        O.update_Y(self.st, self.pri)
+
+    def update_A(self):
+        self.S = O.statistics(self.st, self.Y)
+        O.update_A(self.st, self.pri, self.S)
+
+    def update_C(self):
+        O.update_C(self.st, self.pri, self.S)
+
+    def update_Q(self):
+        O.update_Q(self.st, self.pri, self.S, self.T)
+
+    def update_R(self):
+        O.update_R(self.st, self.pri, self.S, self.T)
+
+    # readers, shaped as the handle's
+    def read(self, name):
+        st = self.st
+        if name == "Sigma":
+            return st["Sigma"]
+        if name in ("A_colvar", "C_colvar"):
+            return np.einsum("nikk->nik", st[name[0] + "_cov"])
+        if name in ("Q_v", "R_v"):
+            return st[name[0] + "_a"]
+        if name in ("Q_w", "R_w"):
+            return st[name[0] + "_b"]
+        if name in ("Q_b", "R_b") and st[name].ndim == 1:       # Gamma: one scalar per replicate, the handle repeats it
+            dim = st["A_mean"].shape[1] if name == "Q_b" else st["C_mean"].shape[1]
+            return np.repeat(st[name][:, None], dim, axis=1)
+        return st[name]
+
+
+class HandleLDS(object):
+    """The same calls and readers on an LDSBatch."""
+
+    def __init__(self, b):
+        self.b, self.noise, self.T = b, b.noise, b.T
+
+    def __getattr__(self, name):
+        return getattr(self.b, name)
+
+    def read(self, name):
+        b = self.b
+        if name == "Sigma":
+            return b.get_posterior_classes()[0]
+        if name in ("Yq", "Yvar"):
+            return b.get_outputs()[name == "Yvar"]
+        if name in ("Q_v", "Q_w", "R_v", "R_w"):
+            return b.get_wishart_state()[name]
+        if name in ("A_cov", "C_cov"):
+            return b.get_column_cov()[name == "C_cov"]
+        return b.get_state((name,))[name]
+
+
+def lds_trace(m, iters, missing):
+    """Drive m (OracleLDS or HandleLDS) through `iters` passes of the example's loop; yields ((iteration, stage, name), array)
+    after every stage for every quantity the envelope compares."""
+    wishart = m.noise == "wishart"
+    for it in range(iters):
+        m.sweep("forward")
+        yield (it, "forward sweep", "X"), np.array(m.read("X"))
+        m.sweep("backward")
+        yield (it, "backward sweep", "X"), np.array(m.read("X"))
+        yield (it, "backward sweep", "Sigma"), np.array(m.read("Sigma"))
+        if missing:
+            m.update_Y()
+            yield (it, "update_Y", "Yq"), np.array(m.read("Yq"))
+            yield (it, "update_Y", "Yvar"), np.array(m.read("Yvar"))
+        m.update_A()
+        yield (it, "update_A", "A_mean"), np.array(m.read("A_mean"))
+        m.update_C()
+        yield (it, "update_C", "C_mean"), np.array(m.read("C_mean"))
+        m.update_Q()
+        m.update_R()
+        names = ["A_colvar", "C_colvar"] + (["Q_v", "Q_w", "R_v", "R_w", "A_cov", "C_cov"] if wishart else ["Q_b", "R_b"])
+        for nm in names:
+            yield (it, "update_R", nm), np.array(m.read(nm))
+
+
+def _alone(c, n, Tn):
+    """Replicate n of a case with chain lengths, as a problem of its own (tests/test_lengths_gpu.py: _alone)."""
+    Y = c["Y"][n:n + 1, :Tn].copy()
+    st0 = {k: (v[n:n + 1, :Tn] if k == "X" else v[n:n + 1]).copy() for k, v in c["st0"].items()}
+    return Y, st0
+
+
+def _cut(key, arr, rows, T):
+    """The part of a handle-shaped array that a reference run covers: all replicates, or replicate `rows` of a handle with
+    chain lengths (its first T rows of X); of Sigma the classes that are alive (no interior class at T = 2)."""
+    if rows is not None:
+        arr = arr[rows:rows + 1]
+        if key[2] == "X":
+            arr = arr[:, :T]
+    if key[2] == "Sigma" and T <= 2:
+        arr = arr[:, [0, 2]]
+    return arr
+
+
+@functools.lru_cache(maxsize=None)
+def lds_reference(name):
+    """[(rows, T, n, ext, e64, recurrences, run)] for a case: one entry for the whole batch, or one per replicate when the
+    replicates have lengths of their own.  ext: {key: long-double array}; e64: {key: distance of the float64 oracle from it};
+    recurrences: per iteration (F, B) [N, D, D] of the extended run; run: the extended OracleLDS as the last stage left it.
+    Computed once per process, never modified."""
+    require_extended()
+    c = lds_case(name)
+    D, K = c["st0"]["A_mean"].shape[1], c["Y"].shape[2]
+    missing = bool(np.isnan(c["Y"]).any())
+    if c.get("lengths"):
+        parts = [(n, Tn) + _alone(c, n, Tn) for n, Tn in enumerate(c["lengths"])]
+    else:
+        parts = [(None, c["Y"].shape[1], c["Y"], c["st0"])]
+    runs = []
+    for rows, T, Y, st0 in parts:
+        m64 = OracleLDS(Y.copy(), {k: v.copy() for k, v in st0.items()}, c["pri"])
+        mx = OracleLDS(to_long(Y), to_long(st0), to_long(c["pri"]))
+        ext, e64 = {}, {}
+        for (k64, a64), (kx, ax) in zip(lds_trace(m64, c["iters"], missing), lds_trace(mx, c["iters"], missing)):
+            assert k64 == kx and ax.dtype == LD, (k64, kx, ax.dtype)
+            ext[kx] = _cut(kx, ax, None, T)
+            e64[kx] = rel(_cut(k64, a64, None, T), ext[kx])
+            ext[kx].setflags(write=False)
+        runs.append((rows, T, max(D, K, T), ext, e64, mx.recurrences, mx))
+    return runs
+
+
+def compare_with_reference(name, handle_trace):
+    """Measure a handle's trace against lds_reference(name): [(run, key, e64, e_gpu, ratio = e_gpu / yardstick)]."""
+    rows_out = []
+    runs = lds_reference(name)
+    for key, arr in handle_trace:
+        for rows, T, n, ext, e64, _, _ in runs:
+            got = _cut(key, arr, rows, T)
+            assert np.all(np.isfinite(got)), "%s: non-finite values in %r" % (name, key)
+            e_gpu = rel(got, ext[key])
+            rows_out.append((rows, key, e64[key], e_gpu, e_gpu / yardstick(e64[key], n)))
+    return rows_out
+
+
+# ----------------------------------------------------------------------------------------------------------------------------
+# the warm-up rule of k_prep.hip / k_big.hip, in NumPy
+# ----------------------------------------------------------------------------------------------------------------------------
+LN_TOL = float(np.log(LD(1e-18)))
+
+
+def induced_norm(M, which):
+    """inf: max row sum; 1: max column sum"""
+    return float(np.abs(M).sum(axis=-1 if which == "inf" else -2).max())
+
+
+def warmup_rule(M, which):
+    """J*: the smallest J = 4a + 8b + 16c + 32d (a, b, c in {0, 1}, d <= 16) whose bound n_2^a n_3^b n_4^c n_5^d on ||M^J||,
+    n_k = ||M^(2^k)||, is at most 1e-18; 1 << 30 if there is none.
+
+    This is the device's documented rule (pyvb_amd/csrc/k_prep.hip, k_big.hip) restated, not an independent optimum: J <= J* + 4
+    shows that a kernel follows its own rule on the right matrices and norms, no more.  The independent evidence that a
+    warm-up is long enough is power_norm(): ||M^J|| itself, taken in long double."""
+    l, Pw = {}, M
+    for k in range(1, 6):
+        Pw = Pw @ Pw
+        if k >= 2:
+            nrm = induced_norm(Pw, which)
+            l[k] = (np.log(nrm) if nrm > 0.0 else -1e300) if nrm < 1.0 else None
+    best = 1 << 30
+    for d in range(17):
+        for abc in range(8):
+            use = {2: abc & 1, 3: (abc >> 1) & 1, 4: abc >> 2, 5: d}
+            if any(use[k] and l[k] is None for k in use):
+                continue
+            bound = sum(use[k] * l[k] for k in use if use[k])
+            J = 4 * use[2] + 8 * use[3] + 16 * use[4] + 32 * d
+            if J > 0 and bound <= LN_TOL and J < best:
+                best = J
+    return best
+
+
+def power_norm(M, J, which):
+    """||M^J|| in long double"""
+    return induced_norm(np.linalg.matrix_power(M, int(J)), which)
+
+
+# ----------------------------------------------------------------------------------------------------------------------------
+# VB-PCA with missing data
+# ----------------------------------------------------------------------------------------------------------------------------
+PCA_CASES = [(300, 20, 4), (77, 33, 17), (17, 250, 31), (600, 250, 16)]
+PCA_NAMES = ("W_mean", "W_var", "Z", "Z_cov", "X", "Mu_mean", "Mu_var", "beta_a", "beta_b")
+
+
+def pca_problem(N, d, q):
+    spec = importlib.util.spec_from_file_location("make_golden", os.path.join(HERE, "golden", "make_golden.py"))
+    G = importlib.util.module_from_spec(spec); spec.loader.exec_module(G)
+    return G.pca_problem(N, d, q, seed=1000 + N + d)
+
+
+class OraclePCA(object):
+    def __init__(self, init, pri, N, d, q):
+        self.st, self.pri, self.N = P.make_state(init, pri, N, d, q), pri, N
+
+    def update_W(self): P.update_W(self.st, self.pri)
+    def update_Z(self): P.update_Z(self.st, self.pri)
+    def update_X(self, lo, hi): P.update_X(self.st, self.pri, lo, hi)
+    def update_Mu(self): P.update_Mu(self.st, self.pri)
+    def update_Beta(self): P.update_Beta(self.st, self.pri)
+    def get_state(self): return self.st
+
+
+def pca_trace(m, N, iters=2, stage_reads=True):
+    """The stages of tests/test_pca_gpu.py: test_stagewise_vs_oracle on m (OraclePCA or a PCABatch).  stage_reads=False reads
+    only at the end of each iteration: a read between update_Z and update_X(1, N) makes a handle carry the Z update out on its
+    own, and the fused sweep over the rows (pyvb_amd/csrc/k_pca.hip: PYVB_PCA_SWEEP = columns / pairs) is then never run."""
+    for it in range(iters):
+        m.update_W()
+        if stage_reads:
+            yield (it, "update_W", "W_mean"), np.array(m.get_state()["W_mean"])
+        m.update_Z()
+        if stage_reads:
+            yield (it, "update_Z", "Z"), np.array(m.get_state()["Z"])
+        m.update_X(0, 1)
+        m.update_Mu()
+        if stage_reads:
+            yield (it, "update_Mu", "Mu_mean"), np.array(m.get_state()["Mu_mean"])
+        m.update_X(1, N)
+        if stage_reads:
+            yield (it, "update_X", "X"), np.array(m.get_state()["X"])
+        m.update_Beta()
+        g = m.get_state()
+        for nm in PCA_NAMES:
+            yield (it, "update_Beta", nm), np.array(g[nm])
+
+
+@functools.lru_cache(maxsize=None)
+def pca_reference(N, d, q):
+    """(n, ext, e64, extended state) as lds_reference."""
+    require_extended()
+    init, pri = pca_problem(N, d, q)
+    m64 = OraclePCA(init, pri, N, d, q)
+    mx = OraclePCA(to_long(init), to_long(pri), N, d, q)
+    ext, e64 = {}, {}
+    for (k64, a64), (kx, ax) in zip(pca_trace(m64, N), pca_trace(mx, N)):
+        assert k64 == kx and ax.dtype == LD, (k64, kx, ax.dtype)
+        ext[kx] = ax
+        e64[kx] = rel(a64, ax)
+        ax.setflags(write=False)
+    return max(d, q, N), ext, e64, mx.st
