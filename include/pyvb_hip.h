@@ -220,6 +220,36 @@ int pyvb_lds_get_status(pyvb_lds* h, int* status);
 int pyvb_lds_set_active(pyvb_lds* h, const unsigned char* active);
 int pyvb_lds_get_active(pyvb_lds* h, unsigned char* active);
 
+/* Converging on its own: Network.learn's stopping test (network.py:40-56, the test is on line 53) applied by every replicate to
+ * itself, on the device.
+ *   pyvb_lds_iterate_until   at most max_iters passes of pyvb_lds_iterate's loop body, same launches in the same order.  For every
+ *                        running replicate n: old_n = -inf when the call starts; after iteration i, llb_n = the sum of its six
+ *                        parts in the handle's bound mode; llb_n - old_n < tol: converged at i, otherwise old_n = llb_n.  The
+ *                        first iteration of a call stops nobody, a decrease stops a replicate too (quirk Q9 of SURVEY.md), a bound
+ *                        that is not finite never does (failure flags stay pyvb_lds_sync's business).  A converged replicate is
+ *                        frozen from the next launch on exactly as pyvb_lds_set_active would do it -- no update kernel loads or
+ *                        stores a row of it; state, classes and parts read back as iteration i left them -- for the life of the
+ *                        handle: pyvb_lds_iterate, pyvb_lds_sweep and the other update entries skip it afterwards.  Unlike a
+ *                        replicate the caller switched off it stays counted: pyvb_lds_get_active keeps returning the caller's
+ *                        mask, and pyvb_lds_elbo_total, the history and the all-reduce sum the running replicates at their
+ *                        current bound and the converged ones at their final one.  Returns when no replicate is left running or
+ *                        after max_iters, both streams synchronised; *iters_run = iterations launched, one history row each.  The
+ *                        host learns the number still running from an 8-byte copy to pinned memory and an event, every
+ *                        check_every (>= 1) iterations: check_every affects nothing but iters_run, which may overshoot the last
+ *                        stop by at most check_every - 1 idle iterations.  With a communicator the stop is collective: the rank's
+ *                        running count rides as a seventh double through this entry's all-reduce and every rank stops in the
+ *                        iteration where the sum is 0 (all ranks pass the same max_iters and check_every).  Inside this entry the
+ *                        bound does not overlap the next iteration (the decision must precede the next k_prep).
+ *                        PYVB_E_ARG before any HIP call: NULL handle, max_iters < 0, check_every < 1, NaN tol, NULL iters_run.
+ *   pyvb_lds_get_convergence  iters[N]: iterations replicate n has carried out under pyvb_lds_iterate_until, summed over calls (0 for
+ *                        one switched off before its first); converged[N]: 1 once it has converged; llb[N]: the last bound the
+ *                        test saw for it (NaN before the first).  Any pointer may be NULL.
+ * Served on every handle pyvb_lds_iterate serves.  Not built: thawing a converged replicate (the mask cannot grow), freezing
+ * replicates that failed, the node front end (Network.learn over one list keeps the reference's single test on the summed
+ * bound), VB-PCA (one model, nothing per replicate). */
+int pyvb_lds_iterate_until(pyvb_lds* h, int max_iters, double tol, int check_every, int* iters_run);
+int pyvb_lds_get_convergence(pyvb_lds* h, int* iters, unsigned char* converged, double* llb);
+
 /* HIP-event timing of the kernels on the handle's stream (for bench.py's roofline figures). */
 int pyvb_lds_timing_enable(pyvb_lds* h, int on);
 int pyvb_lds_timing_reset(pyvb_lds* h);

@@ -162,6 +162,12 @@ int pyvb_lds_create_lengths(pyvb_lds** out, int device, int N, int T, int D, int
     TRY(dev_alloc(&h->elbo_hist, (size_t)PYVB_ELBO_HISTORY * 8));
     TRY(h->mem.alloc((void**)&h->status, n * sizeof(int)));
     TRY(h->mem.alloc((void**)&h->active, n, 1));
+    TRY(h->mem.alloc((void**)&h->counted, n, 1));
+    TRY(h->mem.alloc((void**)&h->conv, n));
+    TRY(h->mem.alloc((void**)&h->conv_iters, n * sizeof(int)));
+    TRY(h->mem.alloc((void**)&h->conv_llb, n * sizeof(double), 0xFF));     // (all-ones bytes = NaN: no test has seen a bound yet)
+    TRYHIP(hipHostMalloc((void**)&h->running_host, sizeof(double), hipHostMallocDefault));
+    TRYHIP(hipEventCreateWithFlags(&h->ev_check, hipEventDisableTiming));
     if (ragged) {       // (lengths that all equal T: a plain handle, len stays null)
         TRY(h->mem.alloc((void**)&h->len, n * sizeof(int)));
         h->len_host = (int*)malloc(n * sizeof(int));
@@ -170,6 +176,7 @@ int pyvb_lds_create_lengths(pyvb_lds** out, int device, int N, int T, int D, int
     }
     h->active_host = (unsigned char*)malloc(n);
     memset(h->active_host, 1, n);
+    h->conv_host = (unsigned char*)calloc(n, 1);
     h->n_active = N;
     h->status_host = (int*)calloc(n, sizeof(int));
     h->reported = (int*)calloc(n, sizeof(int));
@@ -226,9 +233,11 @@ int pyvb_lds_destroy(pyvb_lds* h) {
     pyvb_lds_comm_destroy(h);
     if (h->ev_params) (void)hipEventDestroy(h->ev_params);
     if (h->ev_elbo) (void)hipEventDestroy(h->ev_elbo);
+    if (h->ev_check) (void)hipEventDestroy(h->ev_check);
+    if (h->running_host) (void)hipHostFree(h->running_host);
     if (h->side) (void)hipStreamDestroy(h->side);
     h->mem.release_all();
-    free(h->active_host); free(h->status_host); free(h->reported); free(h->len_host);
+    free(h->active_host); free(h->conv_host); free(h->status_host); free(h->reported); free(h->len_host);
     if (h->pool) {
         for (int i = 0; i < PYVB_EVENT_POOL; ++i) { if (h->pool[i].e0) (void)hipEventDestroy(h->pool[i].e0); if (h->pool[i].e1) (void)hipEventDestroy(h->pool[i].e1); }
         free(h->pool);
@@ -889,6 +898,32 @@ static int join_elbo(pyvb_lds* h) {
     return PYVB_OK;
 }
 
+// The updates of one iteration: forward sweep, backward sweep, A, C, Q, R (the example's loop body, Linear_Dynamic_System.py:70-79)
+static int iterate_updates(pyvb_lds* h) {
+    int rc;
+    // the backward sweep follows at once and reads c_t, not the forward states: those are not written out
+    if ((rc = sweep(h, PYVB_FORWARD, false))) return rc;
+    if ((rc = join_elbo(h))) return rc;
+    if ((rc = sweep(h, PYVB_BACKWARD, true))) return rc;
+    // A and C are independent given the statistics, and so are Q and R given A and C: the pairs
+    // share launches here (same arithmetic as update_A, update_C, update_Q, update_R in turn)
+    if ((rc = ensure_stats(h))) return rc;
+    if (h->dense) {
+        if ((rc = ensure_expect(h))) return rc;
+        if ((rc = launch_cols_dense(h, 2, 0, h->D))) return rc;
+        h->st.columns_updated(2, true);
+        if ((rc = launch_wresid(h, 2, 1, true))) return rc;    // both residual matrices and both qw = w0 + residual
+        h->st.noise_updated(2);
+        if ((rc = ensure_expect(h))) return rc;                // E[Q], E[R] of the new posteriors: the bound and the next k_prep read them
+    } else {
+        if ((rc = launch_cols(h, 2, 0, h->D, 3))) return rc;       // columns, residuals and noise update in one launch
+        h->st.columns_updated(2, false);
+        h->st.noise_updated(2);
+    }
+    if (h->bound == PYVB_BOUND_EXACT && (rc = ensure_lnd_x(h))) return rc;       // (only before the first complete sweep)
+    return PYVB_OK;
+}
+
 int pyvb_lds_iterate(pyvb_lds* h, int niters) {
     ENTER_DEVICE(h);
     ARGCHK(niters >= 0, "niters must be >= 0");
@@ -897,29 +932,7 @@ int pyvb_lds_iterate(pyvb_lds* h, int niters) {
     // all-reduce, which the other ranks are waiting in.
     const bool idle = h->n_active == 0;
     for (int it = 0; it < niters; ++it) {
-        if (idle) { if ((rc = join_elbo(h))) return rc; }
-        else {
-            // the backward sweep follows at once and reads c_t, not the forward states: those are not written out
-            if ((rc = sweep(h, PYVB_FORWARD, false))) return rc;
-            if ((rc = join_elbo(h))) return rc;
-            if ((rc = sweep(h, PYVB_BACKWARD, true))) return rc;
-            // A and C are independent given the statistics, and so are Q and R given A and C: the pairs
-            // share launches here (same arithmetic as update_A, update_C, update_Q, update_R in turn)
-            if ((rc = ensure_stats(h))) return rc;
-            if (h->dense) {
-                if ((rc = ensure_expect(h))) return rc;
-                if ((rc = launch_cols_dense(h, 2, 0, h->D))) return rc;
-                h->st.columns_updated(2, true);
-                if ((rc = launch_wresid(h, 2, 1, true))) return rc;    // both residual matrices and both qw = w0 + residual
-                h->st.noise_updated(2);
-                if ((rc = ensure_expect(h))) return rc;                // E[Q], E[R] of the new posteriors: the bound and the next k_prep read them
-            } else {
-                if ((rc = launch_cols(h, 2, 0, h->D, 3))) return rc;       // columns, residuals and noise update in one launch
-                h->st.columns_updated(2, false);
-                h->st.noise_updated(2);
-            }
-            if (h->bound == PYVB_BOUND_EXACT && (rc = ensure_lnd_x(h))) return rc;       // (only before the first complete sweep)
-        }
+        if ((rc = idle ? join_elbo(h) : iterate_updates(h))) return rc;
         // The lower bound (network.py:49) feeds nothing in the next iteration: it is evaluated on the side stream while
         // the main one goes on with k_prep and the forward sweep.  Its per-iteration totals (summed over the replicates,
         // and over the ranks when a communicator is attached) go into a history ring (pyvb_lds_get_elbo_history).
@@ -935,6 +948,63 @@ int pyvb_lds_iterate(pyvb_lds* h, int niters) {
     }
     // the last lower bound may still be in flight: the next pyvb_lds_iterate overlaps it with its k_prep and forward
     // sweep, any other entry point joins it first (ENTER), pyvb_lds_sync waits for both streams
+    return PYVB_OK;
+}
+
+// pyvb_lds_iterate with the stopping test of network.py:53 applied by every replicate to itself (k_converge.hip).  The decision of
+// iteration i must be in force before the k_prep of i + 1 reads the mask, so here the bound, the test and the totals run on the
+// main stream, in order, and nothing overlaps the next iteration (has what that costs).
+int pyvb_lds_iterate_until(pyvb_lds* h, int max_iters, double tol, int check_every, int* iters_run) {
+    ARGCHK(h, "handle is NULL");
+    ARGCHK(max_iters >= 0, "max_iters must be >= 0");
+    ARGCHK(check_every >= 1, "check_every must be >= 1");
+    ARGCHK(tol == tol, "tol is NaN");
+    ARGCHK(iters_run, "iters_run is NULL");
+    ENTER(h);
+    *iters_run = 0;
+    int rc, it = 0;
+    // Nothing to run on this rank: no update is launched, but with a communicator the totals and the running count (0 here)
+    // still go through the all-reduce the other ranks are waiting in, until every rank has stopped.
+    const bool idle = h->n_active == 0;
+    bool done = idle && !h->comm;
+    while (!done && it < max_iters) {
+        if (!idle) {
+            if ((rc = iterate_updates(h))) return rc;
+            if ((rc = h->dense ? launch_elbo_dense(h, h->stream) : launch_elbo(h, h->stream))) return rc;
+            if ((rc = launch_converge(h, tol, it == 0, h->stream))) return rc;
+        }
+        double* slot = h->elbo_hist + (size_t)(h->hist_count % PYVB_ELBO_HISTORY) * 8;
+        if ((rc = launch_elbo_sum_running(h, slot, h->stream))) return rc;
+        if (h->comm && (rc = pyvb_allreduce_f64(h->comm, slot, 7, h->stream))) return rc;
+        h->hist_count += 1;
+        it += 1;
+        if (it % check_every == 0 && it < max_iters) {
+            // how many replicates (of all ranks) are still running: a small copy to pinned memory and an event, not a spin
+            HIPCHK(hipMemcpyAsync(h->running_host, slot + 6, sizeof(double), hipMemcpyDeviceToHost, h->stream));
+            HIPCHK(hipEventRecord(h->ev_check, h->stream));
+            HIPCHK(hipEventSynchronize(h->ev_check));
+            done = *h->running_host == 0.0;
+        }
+    }
+    *iters_run = it;
+    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipStreamSynchronize(h->side));
+    // the host mirrors: which replicates the test has frozen, and how many are left for IDLE, settle_parked and adopt_classes.
+    // The rows frozen in this call are identical in both X buffers and both class sets, so x_park / cls_parked_other are
+    // right for them whatever they say.
+    HIPCHK(hipMemcpy(h->conv_host, h->conv, (size_t)h->N, hipMemcpyDeviceToHost));
+    h->n_active = 0;
+    for (int n = 0; n < h->N; ++n) h->n_active += h->active_host[n] && !h->conv_host[n];
+    return PYVB_OK;
+}
+
+int pyvb_lds_get_convergence(pyvb_lds* h, int* iters, unsigned char* converged, double* llb) {
+    ENTER(h);
+    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipStreamSynchronize(h->side));
+    if (iters) HIPCHK(hipMemcpy(iters, h->conv_iters, (size_t)h->N * sizeof(int), hipMemcpyDeviceToHost));
+    if (converged) HIPCHK(hipMemcpy(converged, h->conv, (size_t)h->N, hipMemcpyDeviceToHost));
+    if (llb) HIPCHK(hipMemcpy(llb, h->conv_llb, (size_t)h->N * sizeof(double), hipMemcpyDeviceToHost));
     return PYVB_OK;
 }
 
@@ -1011,6 +1081,18 @@ int pyvb_lds_get_status(pyvb_lds* h, int* status) {
     return PYVB_OK;
 }
 
+// The two device masks from their host mirrors: what the totals count is the caller's mask, what the update kernels run is that
+// without the converged replicates (the same bytes until pyvb_lds_iterate_until has stopped one).
+static int upload_masks(pyvb_lds* h) {
+    std::vector<unsigned char> run((size_t)h->N);
+    h->n_active = 0;
+    for (int n = 0; n < h->N; ++n) { run[n] = h->active_host[n] && !h->conv_host[n]; h->n_active += run[n]; }
+    HIPCHK(hipMemcpyAsync(h->counted, h->active_host, (size_t)h->N, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(h->active, run.data(), (size_t)h->N, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));       // the mirrors may change again as soon as this returns
+    return PYVB_OK;
+}
+
 int pyvb_lds_set_active(pyvb_lds* h, const unsigned char* active) {
     ARGCHK(h, "handle is NULL");
     ARGCHK(active, "active is NULL");
@@ -1021,18 +1103,15 @@ int pyvb_lds_set_active(pyvb_lds* h, const unsigned char* active) {
             return PYVB_E_ARG;
         }
     ENTER(h);
-    int count = 0, changed = 0;
-    for (int n = 0; n < h->N; ++n) { count += active[n] != 0; changed += (active[n] != 0) != (h->active_host[n] != 0); }
+    int changed = 0;
+    for (int n = 0; n < h->N; ++n) changed += (active[n] != 0) != (h->active_host[n] != 0);
     if (!changed) return PYVB_OK;
     // rows switched off earlier move to where the rows switched off now are: the current buffers
     int rc = settle_parked(h);
     if (rc) return rc;
     for (int n = 0; n < h->N; ++n) h->active_host[n] = active[n] ? 1 : 0;
-    h->n_active = count;
     h->st.parked_here();
-    HIPCHK(hipMemcpyAsync(h->active, h->active_host, (size_t)h->N, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));       // the mirror may change again as soon as this returns
-    return PYVB_OK;
+    return upload_masks(h);
 }
 
 int pyvb_lds_get_active(pyvb_lds* h, unsigned char* active) {

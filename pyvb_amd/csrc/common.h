@@ -117,9 +117,19 @@ struct pyvb_lds {
     double *elbo, *elbo_sum;        // [N][6], [6]
     int *status;                    // device, [N]: PYVB_FAIL_* bits of the replicates whose factorisations met a non-positive pivot
     // ---- per-replicate bookkeeping: the activity mask (it can only shrink) and the flags the last failed pyvb_lds_sync reported
-    unsigned char *active;          // device, [N]: 0 = switched off; every update kernel leaves such a replicate's rows alone
-    unsigned char *active_host;     // its host mirror (set_active is stream ordered, the mirror is what the host logic reads)
-    int n_active;
+    unsigned char *active;          // device, [N]: 0 = switched off or converged; every update kernel leaves such a replicate's rows alone
+    unsigned char *active_host;     // the caller's mask on the host (set_active is stream ordered, the mirror is what the host logic reads)
+    int n_active;                   // replicates the update kernels run: switched on and not converged
+    // ---- per-replicate convergence (pyvb_lds_iterate_until, k_converge.hip).  `active` above is the mask the update kernels run:
+    // the caller's mask without the converged replicates.  `counted` is the mask the totals count: the caller's mask alone
+    // (active_host mirrors it).  The two are equal until a replicate converges.
+    unsigned char *counted;         // device, [N]
+    unsigned char *conv;            // device, [N]: 1 = converged, frozen for the life of the handle
+    unsigned char *conv_host;       // its host mirror, reconciled when pyvb_lds_iterate_until returns
+    int *conv_iters;                // device, [N]: iterations carried out under pyvb_lds_iterate_until
+    double *conv_llb;               // device, [N]: the last bound the test saw (the next test's `old`); NaN before the first
+    double *running_host;           // pinned, [1]: the number of running replicates (all ranks) as of the last check
+    hipEvent_t ev_check;            // that copy has arrived
     // ---- per-replicate chain lengths (pyvb_lds_create_lengths): null on a handle whose chains all have T nodes
     int *len;                       // device, [N]: T_n.  T stays the row stride of every [N][T][..] buffer; rows t >= T_n are padding
     int *len_host;                  // its host copy (setters and getters: which rows are padding)
@@ -170,6 +180,10 @@ int launch_resid(pyvb_lds* h, int which);     // 0 = Q, 1 = R
 int launch_noise(pyvb_lds* h, int which);
 int launch_elbo(pyvb_lds* h, hipStream_t stream = nullptr);                           // stream: the handle's main one unless given
 int launch_elbo_sum(pyvb_lds* h, double* out = nullptr, hipStream_t stream = nullptr);    // out: h->elbo_sum unless given
+// k_converge.hip: the stopping test of network.py:53 per replicate with the freeze of those it stops (first: old = -inf), and
+// the totals of an iteration with out[6] = the number of replicates still running
+int launch_converge(pyvb_lds* h, double tol, bool first, hipStream_t stream);
+int launch_elbo_sum_running(pyvb_lds* h, double* out, hipStream_t stream);
 // k_big.hip
 int launch_prep_big(pyvb_lds* h);
 int big_prepare_kernels();              // once per device, before the first launch: the dynamic-LDS limits of k_prep_big, k_cols_big

@@ -290,7 +290,8 @@ int launch_elbo(pyvb_lds* h, hipStream_t stream) {
 }
 
 int launch_elbo_sum(pyvb_lds* h, double* out, hipStream_t stream) {
-    SumArgs a; a.elbo = h->elbo; a.out = out ? out : h->elbo_sum; a.active = h->active; a.N = h->N;
+    // the mask the totals count: a converged replicate stays in them at its final bound (common.h: counted)
+    SumArgs a; a.elbo = h->elbo; a.out = out ? out : h->elbo_sum; a.active = h->counted; a.N = h->N;
     hipLaunchKernelGGL(k_elbo_sum, dim3(1), dim3(256), 0, stream ? stream : h->stream, a);
     HIPCHK(hipGetLastError());
     return PYVB_OK;

@@ -319,6 +319,22 @@ class LDSBatch(object):
         C.check(C.lib.pyvb_lds_get_active(self._h, m.ctypes.data_as(C._ucp)))
         return m.astype(bool)
 
+    def iterate_until(self, max_iters, tol=1e-3, check_every=8):
+        """iterate(), with Network.learn's stopping test (network.py:53: the bound improved by less than tol) applied by every
+        replicate to itself on the device.  A replicate that converges is frozen for the life of the handle and stays in the
+        totals at its final bound.  Returns the number of iterations launched: it ends when no replicate is left running
+        (seen every check_every iterations) or after max_iters.  Synchronises."""
+        n = C.ctypes.c_int()
+        self._check(C.lib.pyvb_lds_iterate_until(self._h, int(max_iters), float(tol), int(check_every), C.ctypes.byref(n)))
+        return n.value
+
+    def convergence(self):
+        """(iters int [N], converged bool [N], llb float [N]): the iterations each replicate has carried out under
+        iterate_until, whether it has converged, and the last bound its test saw (NaN before the first)."""
+        it, cv, llb = np.zeros(self.N, dtype=np.int32), np.zeros(self.N, dtype=np.uint8), np.empty(self.N)
+        self._check(C.lib.pyvb_lds_get_convergence(self._h, it.ctypes.data_as(C._ip), cv.ctypes.data_as(C._ucp), C.dptr(llb)))
+        return it, cv.astype(bool), llb
+
     # -- measurement ------------------------------------------------------------------------
     def timing(self, on=True):
         self._check(C.lib.pyvb_lds_timing_enable(self._h, 1 if on else 0))

@@ -1,0 +1,146 @@
+"""The comparator of per-replicate convergence (include/pyvb_hip.h: pyvb_lds_iterate_until): the oracle run alone on one
+replicate (N = 1, T = T_n) with Network.learn's stopping test (network.py:40-56, the test is on line 53) applied on the host.
+
+Which inputs may be compared.  A test may assert equal stop iterations only where the reference's own decision is not a
+rounding matter: every delta llb - old the run meets must lie at least GUARD * max(1, |llb|) from tol -- 100 x the suite's
+1e-8 tolerance on the bound.  alone() asserts that on the oracle before it returns anything to compare with.
+"""
+import functools
+
+import numpy as np
+
+import exact_bound_ref as XR
+from oracle import lds_closed_form as O
+from pyvb_amd import synth
+
+GUARD = 1e-6
+
+
+def _gamma(pri):
+    pri["noise"] = "gamma"
+    for k in ("Q_a0", "Q_b0", "R_a0", "R_b0"):
+        pri[k] = np.float64(1e-3)
+
+
+def _wishart(pri, D, K):
+    rng = np.random.default_rng(D + K)
+    pri["noise"] = "wishart"
+    W = rng.standard_normal((D, D)); pri["Q_b0"] = 0.05 * (W @ W.T + D * np.eye(D)); pri["Q_a0"] = np.float64(0.5 * D + 1.0)
+    W = rng.standard_normal((K, K)); pri["R_b0"] = 0.05 * (W @ W.T + K * np.eye(K)); pri["R_a0"] = np.float64(0.5 * K + 0.5)
+
+
+# name -> the handle (T, D, K, N, seed, noise, lengths, outputs with NaN) and the run (bound mode, tol, max_iters)
+CASES = {
+    "A": dict(T=30, D=4, K=5, N=6, seed=8100, bound="reference", tol=2.0, max_iters=40),
+    "B": dict(T=30, D=4, K=5, N=6, seed=8100, bound="exact", tol=0.6, max_iters=40),
+    "C_reference": dict(T=8, D=72, K=66, N=2, seed=8200, bound="reference", tol=1e-3, max_iters=12),
+    "C_exact": dict(T=8, D=72, K=66, N=2, seed=8200, bound="exact", tol=100.0, max_iters=12),
+    "D": dict(T=30, D=4, K=5, N=4, seed=8100, lengths=(30, 7, 2, 19), bound="reference", tol=2.0, max_iters=40),
+    "E": dict(T=30, D=4, K=5, N=4, seed=8100, noise="gamma", bound="reference", tol=2.0, max_iters=40),
+    "F": dict(T=30, D=4, K=5, N=6, seed=8100, bound="reference", tol=50.0, max_iters=40),
+    "wishart": dict(T=30, D=4, K=5, N=4, seed=8301, noise="wishart", bound="reference", tol=0.3, max_iters=30),
+    "split": dict(T=40, D=4, K=5, N=4, seed=8100, bound="reference", tol=2.0, max_iters=30),      # T - 2 >= 2 * 16: W = 2 is allowed
+    "nan": dict(T=30, D=4, K=5, N=3, seed=8402, nan=True, bound="reference", tol=5.0, max_iters=30),
+}
+
+
+@functools.lru_cache(maxsize=None)
+def problem(name):
+    """(Y, st0, pri, lengths or None) of a case; the arrays are shared between the tests and must not be written to."""
+    c = CASES[name]
+    T, D, K = c["T"], c["D"], c["K"]
+    Y, st0, pri = synth.make_problem(T, D, K, c["N"], seed=c["seed"])
+    if c.get("noise") == "gamma":
+        _gamma(pri)
+    elif c.get("noise") == "wishart":
+        _wishart(pri, D, K)
+    lengths = c.get("lengths")
+    if lengths is not None:
+        live = np.arange(T)[None, :] < np.asarray(lengths)[:, None]
+        Y = np.where(live[:, :, None], Y, 0.0)
+        st0["X"] = np.where(live[:, :, None], st0["X"], 0.0)
+    if c.get("nan"):
+        rng = np.random.default_rng(5)
+        Y[rng.random(Y.shape) < 0.1] = np.nan
+        Y[:, 3] = np.nan                              # a row that is not observed at all
+        st0["Yq"] = rng.standard_normal(Y.shape)
+        st0["Yrowvar"] = 0.5 + rng.random(Y.shape[:2])
+    for a in [Y] + list(st0.values()):
+        a.setflags(write=False)
+    return Y, st0, pri, (None if lengths is None else np.asarray(lengths, dtype=np.int32))
+
+
+def learn_alone(Yn, st, pri, bound, tol, max_iters, old=-np.inf):
+    """Network.learn's loop (network.py:46-56) on one replicate in the oracle, st updated in place.  Returns (iterations
+    carried out, converged, parts [iterations, 6], the smallest distance of a delta from tol relative to max(1, |llb|))."""
+    step = XR.iterate_exact if bound == "exact" else O.iterate
+    trace, margin, converged = [], np.inf, False
+    for i in range(max_iters):
+        parts = step(st, pri, Yn)[0]
+        trace.append(parts)
+        llb = parts.sum()
+        if i > 0:
+            margin = min(margin, abs((llb - old) - tol) / max(1.0, abs(llb)))
+        if llb - old < tol:                             # network.py:53 (old = -inf: the first iteration stops nobody)
+            converged = True
+            break
+        old = llb
+    return len(trace), converged, np.array(trace).reshape(-1, 6), margin
+
+
+def start_alone(name, n):
+    """Replicate n of a case on its own, as the oracle takes it: (Y[1, T_n, K], dense state), the outputs with NaN updated once
+    (the bound is undefined before; the tests call update_Y() on the handle where this does)."""
+    Y, st0, pri, lengths = problem(name)
+    Tn = Y.shape[1] if lengths is None else int(lengths[n])
+    Yn = Y[n:n + 1, :Tn].copy()
+    sn = {k: (v[n:n + 1, :Tn] if k == "X" else v[n:n + 1]).copy() for k, v in st0.items()}
+    st = O.expand_state(sn, pri, Tn, Yn)
+    if CASES[name].get("nan"):
+        O.update_Y(st, pri)
+    return Yn, st
+
+
+@functools.lru_cache(maxsize=None)
+def alone(name, tol=None, max_iters=None):
+    """Every replicate of a case run alone to its own stop: a list of dicts with iters, converged, trace [iters, 6], margin and
+    st, the oracle's state where it stopped (shared: do not write to it).  Asserts the guard on every replicate."""
+    c = CASES[name]
+    tol = c["tol"] if tol is None else tol
+    max_iters = c["max_iters"] if max_iters is None else max_iters
+    Y, _, pri, _ = problem(name)
+    out = []
+    for n in range(Y.shape[0]):
+        Yn, st = start_alone(name, n)
+        iters, converged, trace, margin = learn_alone(Yn, st, pri, c["bound"], tol, max_iters)
+        assert margin >= GUARD, "case %s, replicate %d: a delta of the reference lies %.2e (relative) from tol = %g" % (name, n, margin, tol)
+        out.append(dict(iters=iters, converged=converged, trace=trace, margin=margin, st=st, Y=Yn))
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def resumed(name, tol, max_iters):
+    """A second call on the same handle: the replicates of alone(name) that have not converged go on from where they are, with
+    old = -inf again; the others stay.  Same dicts, iters summed over both calls, trace of the second call alone."""
+    import copy
+    c, pri = CASES[name], problem(name)[2]
+    out = []
+    for r in alone(name):
+        if r["converged"]:
+            out.append(dict(r, trace=r["trace"][-1:], moved=False))
+            continue
+        st = copy.deepcopy(r["st"])
+        iters, converged, trace, margin = learn_alone(r["Y"], st, pri, c["bound"], tol, max_iters)
+        assert margin >= GUARD, "case %s resumed: a delta of the reference lies %.2e (relative) from tol = %g" % (name, margin, tol)
+        out.append(dict(iters=r["iters"] + iters, converged=converged, trace=trace, margin=margin, st=st, Y=r["Y"], moved=True))
+    return out
+
+
+def totals(runs, iters_run):
+    """What the history of iterate_until holds: per launched iteration the parts summed over the replicates, the converged ones
+    held at their final bound.  [iters_run, 6]"""
+    out = np.zeros((iters_run, 6))
+    for r in runs:
+        for i in range(iters_run):
+            out[i] += r["trace"][min(i, len(r["trace"]) - 1)]
+    return out
