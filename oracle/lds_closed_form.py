@@ -35,11 +35,21 @@ Outputs with missing entries (Y holds NaN there; gaussian.py:90-96): the Y_t are
   Yqld     [N,T]     q_ln_det of the rows nothing of which is observed (NaN until updated)
 """
 import numpy as np
-from scipy.special import digamma, gammaln
-
 from . import _xlinalg as XL
+from ._xspecial import digamma, gammaln, ln2pi as _ln2pi, lnpi as _lnpi
 
 LN2PI = np.log(2.0 * np.pi)
+
+
+def _lndet(a):
+    """ln det of a positive definite matrix (or a batch): float64 as the oracle has always formed it, ln(det), so that the
+    fixtures stay bitwise; long double from the Cholesky factor."""
+    return XL.slogdet(a)[1] if XL._is_ext(a) else np.log(np.linalg.det(a))
+
+
+def _lndet_diag(d):
+    """ln det diag(d)"""
+    return np.sum(np.log(d)) if XL._is_ext(d) else np.log(np.linalg.det(np.diag(d)))
 
 
 # ----------------------------------------------------------------------------
@@ -87,7 +97,7 @@ def _psi_multi(x, dim):
 
 
 def _lgamma_multi(x, dim):
-    return 0.25 * dim * (dim - 1) * np.log(np.pi) + sum(gammaln(x - 0.5 * i) for i in range(dim))
+    return 0.25 * dim * (dim - 1) * _lnpi(x) + sum(gammaln(x - 0.5 * i) for i in range(dim))
 
 
 def wishart_llb(a0, B0, a, B):
@@ -307,6 +317,7 @@ def _y_entropy_terms(st):
     miss = np.isnan(st["Yobs"])
     K = miss.shape[2]
     nm = miss.sum(axis=2)
+    LN2PI = _ln2pi(st["Yvar"])
     latent, partial = nm == K, (nm > 0) & (nm < K)
     with np.errstate(divide="ignore", invalid="ignore"):
         lv = np.where(miss, np.log(st["Yvar"]), 0.0).sum(axis=2)
@@ -458,6 +469,7 @@ def elbo_parts(st, pri, S, T):
     kind = pri["noise"]
     N, D = st["A_mean"].shape[:2]
     K = st["C_mean"].shape[1]
+    LN2PI = _ln2pi(st["X"])
     Qb = noise_expect(kind, st["Q_a"], st["Q_b"], D)
     Rb = noise_expect(kind, st["R_a"], st["R_b"], K)
     lndQ = noise_lndet(kind, st["Q_a"], st["Q_b"], D)
@@ -466,7 +478,7 @@ def elbo_parts(st, pri, S, T):
     nint = max(T - 2, 0)
     # X_0: Constant parents (mean m0, precision L0; Constant.lndet node.py:301-302)
     L0, m0 = pri["x0_prec"], pri["x0_mean"]
-    lnd0 = np.log(np.linalg.det(L0))
+    lnd0 = _lndet(L0)
     ex0 = S["x0x0"] + np.outer(m0, m0)[None] - 2 * np.einsum("ni,j->nij", st["X"][:, 0], m0)
     LX = -0.5 * D * LN2PI + 0.5 * lnd0 - 0.5 * np.einsum("ij,nji->n", L0, ex0)
     # X_t, t >= 1
@@ -482,19 +494,19 @@ def elbo_parts(st, pri, S, T):
 
     def cols(M, Mcov, pm, pp, qldc, rows, obs):
         # column i: Constant mean pm[:,i], Constant precision diag(pp[i])
-        tot = np.zeros(N)
+        tot = np.zeros(N, dtype=M.dtype)
         for i in range(D):
             known = np.zeros(rows, dtype=bool) if obs is None else ~np.isnan(obs[:, i])
             ex = np.einsum("nk,nl->nkl", M[:, :, i], M[:, :, i]) + Mcov[:, i] \
                 + np.outer(pm[:, i], pm[:, i])[None] - 2 * np.einsum("nk,l->nkl", M[:, :, i], pm[:, i])
-            tot += -0.5 * rows * LN2PI + 0.5 * np.log(np.linalg.det(np.diag(pp[i]))) \
+            tot += -0.5 * rows * LN2PI + 0.5 * _lndet_diag(pp[i]) \
                 - 0.5 * np.einsum("k,nkk->n", pp[i], ex)
             if not known.any():             # gaussian.py:145-147
                 tot += 0.5 * rows * LN2PI + 0.5 * qldc[:, i] + 0.5 * rows
             elif not known.all():           # gaussian.py:148-150 (the sign of the 2 pi term is the reference's)
                 mi = np.nonzero(~known)[0]
                 cm = Mcov[:, i][:, mi][:, :, mi]
-                tot -= 0.5 * len(mi) * LN2PI - 0.5 * np.log(np.linalg.det(cm)) - 0.5 * len(mi)
+                tot -= 0.5 * len(mi) * LN2PI - 0.5 * _lndet(cm) - 0.5 * len(mi)
         return tot
 
     LA = cols(st["A_mean"], st["A_cov"], pri["A_prior_mean"], pri["A_prior_prec"], st["qld_A"], D, pri.get("A_obs"))

@@ -24,9 +24,9 @@ X [N,d] (qmu: data where observed, imputed elsewhere), X_var [N,d], Mu_mean [d],
 qld_W [q], qld_Z, qld_X (of never-observed rows), qld_Mu.  obs [N,d] bool.
 """
 import numpy as np
-from scipy.special import digamma, gammaln
 
 from . import _xlinalg as XL
+from ._xspecial import digamma, gammaln, ln2pi
 
 LN2PI = np.log(2.0 * np.pi)
 
@@ -125,6 +125,7 @@ def elbo_parts(st, pri):
     N, d = st["X"].shape
     q = st["Z"].shape[1]
     a, b = st["beta_a"], st["beta_b"]
+    LN2PI = ln2pi(st["X"])
     beta = a / b
     lnd_beta = d * (np.log(a) - np.log(b))                            # Gamma.pass_down_lndet (quirk Q2)
     # X_n

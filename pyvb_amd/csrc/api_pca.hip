@@ -8,7 +8,8 @@
 
 #define ENTER(h) ENTER_DEVICE(h)
 
-// digamma for x > 0 (recurrence up to 10, then the asymptotic series), as the device code had it
+// digamma for x > 0 on the host (recurrence up to 10, then the asymptotic series: the positive branch of digamma.h's digamma_pos,
+// kept apart because this translation unit calls it from host code); reached by the tests through L_Beta of the PCA bound only
 static double digamma_host(double x) {
     if (!(x > 0.0)) return NAN;
     double r = 0.0;

@@ -6,6 +6,7 @@
 // one launch per node update, or per whole Network.learn iteration, instead of one launch per numpy call.
 // The matrices of this path are tiny (dimensions of single nodes); the interpreter favours generality over speed.
 #include "common.h"
+#include "digamma.h"         // digamma_pos: U_DIGAMMA
 #include "tape_plan.h"          // tape.h: opcodes, record layout, the window form
 #include <cstdio>
 #include <cstdlib>
@@ -17,18 +18,6 @@ struct TapeArgs { double* arena; size_t arena_n; const int* ops; int nops; int* 
 #ifndef TAPE_THREADS
 #define TAPE_THREADS 256    // (one wavefront, 64, measured the same on the node-sized matrices of this path: the barrier per record is not what a record costs)
 #endif
-
-__device__ static double tape_digamma(double x) {
-    // the recurrence below takes 10 - x steps: bounded here, so that no argument (a degenerate qv, -inf, a NaN from bad
-    // state) can keep a workgroup spinning.  Not finite: NaN (+inf: +inf); below -64: the reflection formula.
-    if (!(x - x == 0.0) || x < -4.5e15) return x > 0 ? x : __builtin_nan("");      // below -2^52 every double is an integer: a pole
-    double r = 0.0;
-    if (x < -64.0) { r = -M_PI / tan(M_PI * x); x = 1.0 - x; }
-    while (x < 10.0) { r -= 1.0 / x; x += 1.0; }
-    const double f = 1.0 / (x * x);
-    const double ser = f * (1.0 / 12 - f * (1.0 / 120 - f * (1.0 / 252 - f * (1.0 / 240 - f * (1.0 / 132 - f * (691.0 / 32760 - f / 12))))));
-    return r + log(x) - 0.5 / x - ser;
-}
 
 // `count` records starting at `recs` (global memory, or a chunk staged in LDS), interpreted by the calling workgroup.
 // WIN: every operand of every record lies in the workgroup's LDS window `win` (the offsets are window positions, tagged
@@ -213,7 +202,7 @@ __device__ static void tape_exec(const TapeArgs& t, const int* recs, int count, 
                 double y;
                 switch (flags) {
                     case 0: y = log(x); break;
-                    case 1: y = tape_digamma(x); break;
+                    case 1: y = digamma_pos(x); break;
                     case 2: y = lgamma(x); break;
                     case 3: y = 1.0 / x; break;
                     case 4: y = -x; break;

@@ -1,6 +1,7 @@
 // Shared by the parameter-update translation units (k_params.hip, k_cols.hip).
 #pragma once
 #include "common.h"
+#include "digamma.h"
 
 #define LN2PI 1.8378770664093453
 
@@ -54,17 +55,5 @@ __device__ __forceinline__ double bcast(double v, int j) {
     const int hi = __builtin_amdgcn_readlane(__double2hiint(v), j);
     return __hiloint2double(hi, lo);
 }
-
-// digamma for positive and for negative non-integer arguments (recurrence up to x >= 10, then the asymptotic series)
-__device__ static inline double digamma_pos(double x) {
-    if (!(x - x == 0.0) || x < -4.5e15) return x > 0 ? x : __builtin_nan("");      // below -2^52 every double is an integer: a pole      // bounded recurrence: see tape_digamma (k_tape.hip)
-    double r = 0.0;
-    if (x < -64.0) { r = -M_PI / tan(M_PI * x); x = 1.0 - x; }
-    while (x < 10.0) { r -= 1.0 / x; x += 1.0; }
-    const double f = 1.0 / (x * x);
-    const double ser = f * (1.0 / 12 - f * (1.0 / 120 - f * (1.0 / 252 - f * (1.0 / 240 - f * (1.0 / 132 - f * (691.0 / 32760 - f / 12))))));
-    return r + log(x) - 0.5 / x - ser;
-}
-
 
 ParamArgs make_args(pyvb_lds* h);

@@ -11,12 +11,16 @@ The exact parts differ from the oracle's reference parts (quirks Q1, Q2 of SURVE
 The lower-bound terms of the noise nodes and of the Constant parents are the reference's already.
 """
 import numpy as np
-from scipy.special import digamma
-
+from oracle import _xlinalg as XL
 from oracle import lds_closed_form as O
 from oracle import pca_closed_form as P
+from oracle._xspecial import digamma, ln2pi
 
 LN2PI = O.LN2PI
+
+# Every function below keeps the dtype of the state it is given (float64: bitwise what it always returned; np.longdouble: the
+# extended-precision reference of tests/extended_ref.py): log-determinants go through oracle/_xlinalg.py, digamma through
+# oracle/_xspecial.py, accumulators take the dtype of the state.
 
 
 def noise_eln(kind, a, b, dim):
@@ -26,7 +30,7 @@ def noise_eln(kind, a, b, dim):
     if kind == "gamma":
         return dim * (digamma(a) - np.log(b))
     if kind == "wishart":
-        return O._psi_multi(a, dim) - np.linalg.slogdet(0.5 * (b + np.swapaxes(b, -1, -2)))[1]
+        return O._psi_multi(a, dim) - XL.slogdet(0.5 * (b + np.swapaxes(b, -1, -2)))[1]
     raise ValueError(kind)
 
 
@@ -34,23 +38,29 @@ def logdets(st, pri):
     """ln det qcov of what the HIP handle stores it for: the X_t classes [N,3], the columns of A and C [N,D], the outputs
     with missing entries [N,T] (of inv <R>; NaN before their first update).  NaN for a column that has not been updated and
     for one with known entries (the handle keeps ln det of its covariance BEFORE the conditioning, which st does not hold)."""
-    out = {"X": np.linalg.slogdet(st["Sigma"])[1]}
+    out = {"X": XL.slogdet(st["Sigma"])[1]}
     for w in ("A", "C"):
-        ld = _column_logdets(st, w)
         obs = pri.get(w + "_obs")
+        ld = _column_logdets(st, w, obs)
         latent = np.ones(ld.shape[1], dtype=bool) if obs is None else np.isnan(obs).all(axis=0)
         out[w] = np.where(np.isnan(st["qld_" + w]) | ~latent[None], np.nan, ld)
     if "Yobs" in st:
         kind = pri["noise"]
         K = st["C_mean"].shape[1]
-        lr = -np.linalg.slogdet(O.noise_expect(kind, st["R_a"], st["R_b"], K))[1]
+        lr = -XL.slogdet(O.noise_expect(kind, st["R_a"], st["R_b"], K))[1]
         out["Y"] = np.where(np.isnan(st["Yqld"]), np.nan, lr[:, None])
     return out
 
 
-def _column_logdets(st, which):
-    """ln det of the whole covariance of a latent column (the one the handle stores)."""
-    return np.linalg.slogdet(st[which + "_cov"])[1]
+def _column_logdets(st, which, obs=None):
+    """ln det of the whole covariance of a latent column (the one the handle stores); NaN for a column with known entries,
+    whose covariance is singular and whose value no caller uses (a Cholesky-based slogdet refuses such a matrix)."""
+    cov = st[which + "_cov"]
+    latent = np.ones(cov.shape[1], dtype=bool) if obs is None else np.isnan(obs).all(axis=0)
+    out = np.full(cov.shape[:2], np.nan, dtype=cov.dtype)
+    if latent.any():
+        out[:, latent] = XL.slogdet(cov[:, latent])[1]
+    return out
 
 
 def _y_entropy_exact(st):
@@ -58,6 +68,7 @@ def _y_entropy_exact(st):
     miss = np.isnan(st["Yobs"])
     K = miss.shape[2]
     nm = miss.sum(axis=2)
+    LN2PI = ln2pi(st["Yvar"])
     latent, partial = nm == K, (nm > 0) & (nm < K)
     with np.errstate(divide="ignore", invalid="ignore"):
         lv = np.where(miss, np.log(st["Yvar"]), 0.0).sum(axis=2)
@@ -69,7 +80,7 @@ def _y_entropy_exact(st):
         # the latent rows carry qcov = inv <R> (Yvar its diagonal under diagonal noise); Wishart: -ln det <R>
         if "Yld" in st:
             K_ = st["C_mean"].shape[1]
-            lrow = -np.linalg.slogdet(O.noise_expect("wishart", st["R_a"], st["R_b"], K_))[1]
+            lrow = -XL.slogdet(O.noise_expect("wishart", st["R_a"], st["R_b"], K_))[1]
             lq = lq + lrow[:, None]
         else:
             with np.errstate(divide="ignore", invalid="ignore"):
@@ -86,11 +97,12 @@ def elbo_parts_exact(st, pri, S, T):
     N, D = st["A_mean"].shape[:2]
     K = st["C_mean"].shape[1]
     ref = O.elbo_parts(st, pri, S, T)
+    LN2PI = ln2pi(ref)
     LX, LY, LA, LC, LQ, LR = [ref[:, i].copy() for i in range(6)]
     nint = max(T - 2, 0)
     # X_t: the entropy from ln det Sigma; E ln det Q in the T - 1 own terms
     qld = st["qld_x"]
-    lnd = np.linalg.slogdet(st["Sigma"])[1]
+    lnd = XL.slogdet(st["Sigma"])[1]
     LX += -0.5 * (qld[:, 0] + nint * qld[:, 1] + qld[:, 2]) + 0.5 * (lnd[:, 0] + nint * lnd[:, 1] + lnd[:, 2])
     LX += (T - 1) * 0.5 * (noise_eln(kind, st["Q_a"], st["Q_b"], D) - O.noise_lndet(kind, st["Q_a"], st["Q_b"], D))
     # Y_t: E ln det R in the T own terms; the true entropy of the outputs with missing entries
@@ -100,8 +112,8 @@ def elbo_parts_exact(st, pri, S, T):
 
     def cols(which, rows):
         M, Mcov, qldc, obs = st[which + "_mean"], st[which + "_cov"], st["qld_" + which], pri.get(which + "_obs")
-        lndc = _column_logdets(st, which)
-        tot = np.zeros(N)
+        lndc = _column_logdets(st, which, obs)
+        tot = np.zeros(N, dtype=M.dtype)
         for i in range(D):
             known = np.zeros(rows, dtype=bool) if obs is None else ~np.isnan(obs[:, i])
             if not known.any():
@@ -109,7 +121,7 @@ def elbo_parts_exact(st, pri, S, T):
             elif not known.all():
                 mi = np.nonzero(~known)[0]
                 m = len(mi)
-                ldm = np.linalg.slogdet(Mcov[:, i][:, mi][:, :, mi])[1]
+                ldm = XL.slogdet(Mcov[:, i][:, mi][:, :, mi])[1]
                 tot += (0.5 * m * LN2PI - 0.5 * ldm - 0.5 * m) + (0.5 * m * LN2PI + 0.5 * ldm + 0.5 * m)
         return tot
 
@@ -134,7 +146,7 @@ def pca_logdets(st):
     before a node's first update, like q_ln_det)."""
     d = st["X"].shape[1]
     w = np.where(np.isnan(st["qld_W"]), np.nan, np.log(st["W_var"]).sum(axis=1))
-    z = np.nan if np.isnan(st["qld_Z"]) else np.linalg.slogdet(st["Z_cov"])[1]
+    z = np.nan if np.isnan(st["qld_Z"]) else XL.slogdet(st["Z_cov"])[1]
     m = np.nan if np.isnan(st["qld_Mu"]) else np.log(st["Mu_var"]).sum()
     none = (~st["obs"]).all(axis=1)
     with np.errstate(divide="ignore", invalid="ignore"):
@@ -146,6 +158,7 @@ def pca_elbo_parts_exact(st, pri):
     ref = P.elbo_parts(st, pri)
     LW, LZ, LX, LM, LB = ref
     N, d = st["X"].shape
+    LN2PI = ln2pi(st["X"])
     a, b = st["beta_a"], st["beta_b"]
     ld = pca_logdets(st)
     # E ln det (beta I) in the N own terms of the X_n

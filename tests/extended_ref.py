@@ -11,8 +11,14 @@ Yardstick.  For a quantity q after a stage, with rel() th
     e64   = rel(float64 oracle, extended run)          what LAPACK / einsum in float64 lose on this problem
     y     = max(e64, n 2^-52),  n = max(D, K, T)       (max(d, q, N) for PCA): never below one length-n float64 accumulation
     e_gpu = rel(handle, extended run) <= FACTOR y,     FACTOR = 16
-and every case must have e64 <= CAP = 1e-11 on every quantity, so the bound never exceeds 1.6e-10.  The lower bound is not
-part of this: digamma and gammaln exist in float64 only, elbo_parts keeps its 1e-8 tests.
+and every case must have e64 <= CAP = 1e-11 on every quantity, so the bound never exceeds 1.6e-10.
+
+The lower bound.  digamma and gammaln have a long-double version (oracle/_xspecial.py), so elbo_parts and
+tests/exact_bound_ref.py: elbo_parts_exact run in extended precision too, and the traces yield the parts [N, 6] (PCA: [5])
+after each iteration under the key (iteration, "bound", mode).  A part is measured in units of its replicate's
+s_r = sum_p |part_p| of the extended run (the parity suite's convention for the parts):
+    e64 = |p64 - pext| / s_r,   e_gpu = |pgpu - pext| / s_r <= FACTOR max(e64, n 2^-52),   e64 <= CAP
+part by part and replicate by replicate (bound_errors, compare_bound).
 """
 import functools
 import importlib.util
@@ -20,6 +26,7 @@ import os
 
 import numpy as np
 
+import exact_bound_ref as XR
 from oracle import lds_closed_form as O
 from oracle import pca_closed_form as P
 from pyvb_amd import synth
@@ -65,6 +72,33 @@ def rel(a, b):
 
 def yardstick(e64, n):
     return max(e64, n * U64)
+
+
+BOUND_MODES = ("reference", "exact")
+LDS_PARTS = ("L_X", "L_Y", "L_A", "L_C", "L_Q", "L_R")
+PCA_PARTS = ("L_W", "L_Z", "L_X", "L_Mu", "L_Beta")
+
+
+def bound_errors(got, ext):
+    """The yardstick's unit for the parts of a bound.  got, ext: [N, P] (or [P]: one replicate).  Returns
+    (|got - ext| / s_r, |got - ext| / |ext|) as float64 [N, P], s_r = sum_p |ext[r, p]|; the second is for the record only
+    (a part that is exactly 0 in the extended run reports 0 or inf there)."""
+    got, ext = np.atleast_2d(np.asarray(got, dtype=LD)), np.atleast_2d(np.asarray(ext, dtype=LD))
+    assert got.shape == ext.shape, (got.shape, ext.shape)
+    d = np.abs(got - ext)
+    s = np.abs(ext).sum(axis=1, keepdims=True)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        own = np.where(d == 0, LD(0), d / np.abs(ext))
+    return (d / s).astype(float), own.astype(float)
+
+
+def compare_bound(got, ext, e64, n):
+    """[(replicate, part index, e64, e_gpu, e_gpu / y, error relative to the part itself)] for parts `got` [N, P] against the
+    extended run's `ext`, with e64 [N, P] the float64 oracle's distance from it in the same unit."""
+    e_gpu, own = bound_errors(got, ext)
+    e64 = np.atleast_2d(e64)
+    return [(r, p, float(e64[r, p]), float(e_gpu[r, p]), float(e_gpu[r, p] / yardstick(float(e64[r, p]), n)), float(own[r, p]))
+            for r in range(e_gpu.shape[0]) for p in range(e_gpu.shape[1])]
 
 
 # ----------------------------------------------------------------------------------------------------------------------------
@@ -165,8 +199,14 @@ LDS_CASES = {
     "t60_d5_k6_missing":    (lambda: _missing(60, 5, 6, 2, 114), False),
     "t80_d5_k6_known":      (lambda: _known(80, 5, 6, 2, 115), False),
     "lengths_3_19_60_77_d16_k16": (lambda: _lengths((3, 19, 60, 77), 16, 16, 116), True),
+    # length 2 is the shortest chain a handle accepts: no interior class, nint = 0 in the bound (no recurrence matrices either,
+    # so the case is not in the warm-up contract)
+    "lengths_2_17_33_d16_k16": (lambda: _lengths((2, 17, 33), 16, 16, 117), False),
 }
 WARMUP_CASES = [k for k, v in LDS_CASES.items() if v[1]]
+# The exact bound needs a handle of its own (the mode is set before the first update); these two reach no
+# other instantiation of the bound than t40_d64_k64 and t12_d72_k66_big do, so their long runs are not repeated.
+EXACT_BOUND_CASES = [k for k in LDS_CASES if k not in ("t2402_d64_k64_w1", "t600_d72_k66_big_w3")]
 
 
 def lds_case(name):
@@ -207,6 +247,11 @@ class OracleLDS(object):
     def update_R(self):
         O.update_R(self.st, self.pri, self.S, self.T)
 
+    def elbo_parts(self, mode):
+        """[N, 6] of the state as it is, from the statistics the parameter updates of this iteration read (O.iterate)."""
+        fn = O.elbo_parts if mode == "reference" else XR.elbo_parts_exact
+        return fn(self.st, self.pri, self.S, self.T)
+
     # readers, shaped as the handle's
     def read(self, name):
         st = self.st
@@ -233,6 +278,10 @@ class HandleLDS(object):
     def __getattr__(self, name):
         return getattr(self.b, name)
 
+    def elbo_parts(self, mode):
+        assert self.b.bound == mode, "the handle forms the %s bound, not the %s one" % (self.b.bound, mode)
+        return self.b.elbo()
+
     def read(self, name):
         b = self.b
         if name == "Sigma":
@@ -246,9 +295,10 @@ class HandleLDS(object):
         return b.get_state((name,))[name]
 
 
-def lds_trace(m, iters, missing):
+def lds_trace(m, iters, missing, bounds=()):
     """Drive m (OracleLDS or HandleLDS) through `iters` passes of the example's loop; yields ((iteration, stage, name), array)
-    after every stage for every quantity the envelope compares."""
+    after every stage for every quantity the envelope compares, and after each pass ((iteration, "bound", mode), parts [N, 6])
+    for every mode in `bounds` (an oracle forms both on one state; a handle forms the one it was set to)."""
     wishart = m.noise == "wishart"
     for it in range(iters):
         m.sweep("forward")
@@ -269,6 +319,8 @@ def lds_trace(m, iters, missing):
         names = ["A_colvar", "C_colvar"] + (["Q_v", "Q_w", "R_v", "R_w", "A_cov", "C_cov"] if wishart else ["Q_b", "R_b"])
         for nm in names:
             yield (it, "update_R", nm), np.array(m.read(nm))
+        for mode in bounds:
+            yield (it, "bound", mode), np.array(m.elbo_parts(mode))
 
 
 def _alone(c, n, Tn):
@@ -290,9 +342,43 @@ def _cut(key, arr, rows, T):
     return arr
 
 
-@functools.lru_cache(maxsize=None)
+def is_bound(key):
+    return key[1] == "bound"
+
+
+def _problems(c):
+    """[(rows, T, Y, st0)]: the whole batch of a case, or each replicate alone where the replicates have lengths of their own"""
+    if c.get("lengths"):
+        return [(n, Tn) + _alone(c, n, Tn) for n, Tn in enumerate(c["lengths"])]
+    return [(None, c["Y"].shape[1], c["Y"], c["st0"])]
+
+
+def lds_float64_bound(name):
+    """[{(iteration, "bound", mode): parts [N, 6]}] of a fresh run of the float64 oracle, one dict per entry of
+    lds_reference(name).  Not cached: tests/test_extended_ref_cpu.py runs it with parts of the oracle replaced by mutants."""
+    c = lds_case(name)
+    missing = bool(np.isnan(c["Y"]).any())
+    out = []
+    for rows, T, Y, st0 in _problems(c):
+        m64 = OracleLDS(Y.copy(), {k: v.copy() for k, v in st0.items()}, c["pri"])
+        out.append({k: a for k, a in lds_trace(m64, c["iters"], missing, BOUND_MODES) if is_bound(k)})
+    return out
+
+
 def lds_reference(name):
-    """[(rows, T, n, ext, e64, recurrences, run)] for a case: one entry for the whole batch, or one per replicate when the
+    """[(rows, T, n, ext, e64, recurrences, run)] for a case (see _lds_reference)."""
+    return _lds_reference(name)[0]
+
+
+def lds_bound_reference(name):
+    """[{(iteration, "bound", mode): (ext [N, 6] long double, e64 [N, 6], the same relative to each part itself)}], one dict
+    per entry of lds_reference(name), from the same two runs."""
+    return _lds_reference(name)[1]
+
+
+@functools.lru_cache(maxsize=None)
+def _lds_reference(name):
+    """([(rows, T, n, ext, e64, recurrences, run)], [bound records]) for a case: one entry for the whole batch, or one per replicate when the
     replicates have lengths of their own.  ext: {key: long-double array}; e64: {key: distance of the float64 oracle from it};
     recurrences: per iteration (F, B) [N, D, D] of the extended run; run: the extended OracleLDS as the last stage left it.
     Computed once per process, never modified."""
@@ -300,22 +386,23 @@ def lds_reference(name):
     c = lds_case(name)
     D, K = c["st0"]["A_mean"].shape[1], c["Y"].shape[2]
     missing = bool(np.isnan(c["Y"]).any())
-    if c.get("lengths"):
-        parts = [(n, Tn) + _alone(c, n, Tn) for n, Tn in enumerate(c["lengths"])]
-    else:
-        parts = [(None, c["Y"].shape[1], c["Y"], c["st0"])]
-    runs = []
-    for rows, T, Y, st0 in parts:
+    runs, bounds = [], []
+    for rows, T, Y, st0 in _problems(c):
         m64 = OracleLDS(Y.copy(), {k: v.copy() for k, v in st0.items()}, c["pri"])
         mx = OracleLDS(to_long(Y), to_long(st0), to_long(c["pri"]))
-        ext, e64 = {}, {}
-        for (k64, a64), (kx, ax) in zip(lds_trace(m64, c["iters"], missing), lds_trace(mx, c["iters"], missing)):
+        ext, e64, bnd = {}, {}, {}
+        for (k64, a64), (kx, ax) in zip(lds_trace(m64, c["iters"], missing, BOUND_MODES), lds_trace(mx, c["iters"], missing, BOUND_MODES)):
             assert k64 == kx and ax.dtype == LD, (k64, kx, ax.dtype)
+            if is_bound(kx):
+                ax.setflags(write=False)
+                bnd[kx] = (ax,) + bound_errors(a64, ax)
+                continue
             ext[kx] = _cut(kx, ax, None, T)
             e64[kx] = rel(_cut(k64, a64, None, T), ext[kx])
             ext[kx].setflags(write=False)
         runs.append((rows, T, max(D, K, T), ext, e64, mx.recurrences, mx))
-    return runs
+        bounds.append(bnd)
+    return runs, bounds
 
 
 def compare_with_reference(name, handle_trace):
@@ -323,12 +410,28 @@ def compare_with_reference(name, handle_trace):
     rows_out = []
     runs = lds_reference(name)
     for key, arr in handle_trace:
+        if is_bound(key):
+            continue
         for rows, T, n, ext, e64, _, _ in runs:
             got = _cut(key, arr, rows, T)
             assert np.all(np.isfinite(got)), "%s: non-finite values in %r" % (name, key)
             e_gpu = rel(got, ext[key])
             rows_out.append((rows, key, e64[key], e_gpu, e_gpu / yardstick(e64[key], n)))
     return rows_out
+
+
+def compare_bound_with_reference(name, handle_trace):
+    """The bound keys of a handle's trace against lds_bound_reference(name): [(key, replicate, part index, e64, e_gpu,
+    e_gpu / yardstick, error relative to the part itself)]."""
+    out = []
+    for key, arr in handle_trace:
+        if not is_bound(key):
+            continue
+        for (rows, T, n, _, _, _, _), bnd in zip(lds_reference(name), lds_bound_reference(name)):
+            ext, e64, _ = bnd[key]
+            got = arr if rows is None else arr[rows:rows + 1]       # (a non-finite part gives a NaN ratio, which no bound admits)
+            out += [(key, row[0] if rows is None else rows) + row[1:] for row in compare_bound(got, ext, e64, n)]
+    return out
 
 
 # ----------------------------------------------------------------------------------------------------------------------------
@@ -374,9 +477,34 @@ def power_norm(M, J, which):
 
 
 # ----------------------------------------------------------------------------------------------------------------------------
+# the arguments the bounds give digamma and gammaln (and the edges of the kernels' digamma around them)
+# ----------------------------------------------------------------------------------------------------------------------------
+DIGAMMA_ROOT = 1.4616321449683623
+
+
+def special_grid():
+    """float64 [<= 256]: 1e-8, the Gamma priors' 1e-3 and 1e-3 + k / 2 (a0 + T / 2), the Wishart arguments v - i / 2 down to 0.5,
+    the root of digamma, 9.999 / 10 / 10.001 where the kernels go over to the series, half-integers up to 5e3, 7.5e4, 1e5, 1e8,
+    and negative non-integers on both sides of -64, below which the kernels use the reflection formula."""
+    g = [1e-8, 1e-3, 0.5, 1.0, 1.5, 2.0, DIGAMMA_ROOT, 9.999, 10.0, 10.001]
+    g += [1e-3 + 0.5 * k for k in range(1, 73)]
+    g += [k + 0.5 for k in range(41)] + [float(k) for k in range(3, 41)]
+    g += [float(int(1.09 ** k)) + 0.5 for k in range(44, 99)] + [4999.5, 5000.0]
+    g += [7.5e4, 1e5, 1e8]
+    g += [-0.5, -63.5, -64.5, -1000.25]
+    g = np.array(sorted(set(g)))
+    assert g.size <= 256
+    return g
+
+
+# ----------------------------------------------------------------------------------------------------------------------------
 # VB-PCA with missing data
 # ----------------------------------------------------------------------------------------------------------------------------
 PCA_CASES = [(300, 20, 4), (77, 33, 17), (17, 250, 31), (600, 250, 16)]
+# beta_a0 + d N / 2 = 0.501 < 10 at the smallest shape a handle accepts: the recurrence branch of the host's digamma (and the
+# lower bound of a graph none of whose data is observed: pca_problem always hides entry (0, 0))
+PCA_SMALL = (1, 1, 1)
+PCA_BOUND_CASES = PCA_CASES + [PCA_SMALL]
 PCA_NAMES = ("W_mean", "W_var", "Z", "Z_cov", "X", "Mu_mean", "Mu_var", "beta_a", "beta_b")
 
 
@@ -397,8 +525,19 @@ class OraclePCA(object):
     def update_Beta(self): P.update_Beta(self.st, self.pri)
     def get_state(self): return self.st
 
+    def elbo_parts(self, mode):
+        return P.elbo_parts(self.st, self.pri) if mode == "reference" else XR.pca_elbo_parts_exact(self.st, self.pri)
 
-def pca_trace(m, N, iters=2, stage_reads=True):
+
+def pca_handle_parts(b):
+    """elbo_parts(mode) for a PCABatch, as OraclePCA has it"""
+    def parts(mode):
+        assert b.bound == mode, "the handle forms the %s bound, not the %s one" % (b.bound, mode)
+        return b.elbo()
+    return parts
+
+
+def pca_trace(m, N, iters=2, stage_reads=True, bounds=(), parts=None):
     """The stages of tests/test_pca_gpu.py: test_stagewise_vs_oracle on m (OraclePCA or a PCABatch).  stage_reads=False reads
     only at the end of each iteration: a read between update_Z and update_X(1, N) makes a handle carry the Z update out on its
     own, and the fused sweep over the rows (pyvb_amd/csrc/k_pca.hip: PYVB_PCA_SWEEP = columns / pairs) is then never run."""
@@ -420,19 +559,35 @@ def pca_trace(m, N, iters=2, stage_reads=True):
         g = m.get_state()
         for nm in PCA_NAMES:
             yield (it, "update_Beta", nm), np.array(g[nm])
+        for mode in bounds:     # the parts [5] of the bound after the iteration (parts: pca_handle_parts(m) for a handle)
+            yield (it, "bound", mode), np.array((parts or m.elbo_parts)(mode))
+
+
+def pca_reference(N, d, q):
+    """(n, ext, e64, extended state) as lds_reference."""
+    return _pca_reference(N, d, q)[:4]
+
+
+def pca_bound_reference(N, d, q):
+    """{(iteration, "bound", mode): (ext [1, 5], e64 [1, 5], the same relative to each part itself)} as lds_bound_reference."""
+    return _pca_reference(N, d, q)[4]
 
 
 @functools.lru_cache(maxsize=None)
-def pca_reference(N, d, q):
-    """(n, ext, e64, extended state) as lds_reference."""
+def _pca_reference(N, d, q):
     require_extended()
     init, pri = pca_problem(N, d, q)
     m64 = OraclePCA(init, pri, N, d, q)
     mx = OraclePCA(to_long(init), to_long(pri), N, d, q)
-    ext, e64 = {}, {}
-    for (k64, a64), (kx, ax) in zip(pca_trace(m64, N), pca_trace(mx, N)):
+    ext, e64, bnd = {}, {}, {}
+    for (k64, a64), (kx, ax) in zip(pca_trace(m64, N, bounds=BOUND_MODES), pca_trace(mx, N, bounds=BOUND_MODES)):
         assert k64 == kx and ax.dtype == LD, (k64, kx, ax.dtype)
+        if is_bound(kx):
+            ax = ax[None]
+            ax.setflags(write=False)
+            bnd[kx] = (ax,) + bound_errors(a64, ax)
+            continue
         ext[kx] = ax
         e64[kx] = rel(a64, ax)
         ax.setflags(write=False)
-    return max(d, q, N), ext, e64, mx.st
+    return max(d, q, N), ext, e64, mx.st, bnd
