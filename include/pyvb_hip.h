@@ -101,6 +101,36 @@ int pyvb_lds_destroy(pyvb_lds* h);
 int pyvb_lds_create_lengths(pyvb_lds** out, int device, int N, int T, int D, int K, int noise_kind, const int* lengths);
 int pyvb_lds_get_lengths(pyvb_lds* h, int* lengths);
 
+/* Several time series, one model.  A CHAIN is one replicate row (one series of T_n nodes); a MODEL is a run of consecutive
+ * replicates that share the nodes As, Cs, Q, R: the graph of Linear_Dynamic_System.py with `As, A, Cs, C, Q, R` built once and
+ * the loop of :58-66 run once per series, each with its own X_0.  model[N] gives the model of every replicate: it starts at 0,
+ * never decreases and rises in steps of 0 or 1.  model == NULL is pyvb_lds_create_lengths (every replicate a model of its own);
+ * lengths == NULL gives every chain T nodes.  pyvb_lds_get_models reads the ids back (0 .. N-1 on every other handle).
+ *   - hstack, Gamma and DiagonalGamma sum over their children whoever they belong to (nodes_todo.py:43-62, :125-128,
+ *     :183-186): before the columns and the noise are updated, the sufficient statistics of the chains of a model are summed
+ *     (k_tie.hip).  qa counts the children of the whole model: Q has sum (T_n - 1), R has sum T_n (pyvb_lds_set_priors).
+ *     Every update entry -- sweep, update_x, update_columns, update_A/C/Q/R, update_Y, iterate -- does for every model what
+ *     the reference's node updates do on that graph.
+ *   - Arrays stay [N][..].  X, Y, the posterior classes and the outputs are per chain.  The parameters are stored in every row
+ *     of a model and are bitwise equal there, as are qld_A/C and lnd_A/C.  pyvb_lds_set_state takes A_mean, A_colvar, C_mean,
+ *     C_colvar, Q_b, R_b from the row of a model's FIRST replicate and copies them to its other rows; what the caller put
+ *     there is ignored.
+ *   - Lower bound, both modes: the rows of pyvb_lds_get_elbo of a model add up to the six parts of its graph.  L_A, L_C, L_Q,
+ *     L_R are booked on the model's first row and are 0.0 on its other rows.  L_X and L_Y of a row hold the terms of its own
+ *     X_t and Y_t, except -tr(<Q> residual) and -tr(<R> residual), which are sums over the model and are booked once, on the
+ *     first row; how L_X and L_Y split between the rows of a model is not contractual.  Totals, history, all-reduce: as before.
+ *   - pyvb_lds_set_active: a mask that switches off part of a model is PYVB_E_ARG (the message names the model).
+ *   - pyvb_lds_iterate_until on a handle with a model of more than one chain is PYVB_E_UNSUPPORTED before any launch:
+ *     convergence per model is a follow-up.
+ *   - Composes with chain lengths, known entries of A / C, outputs with NaN (where all chains have T nodes), both bound modes,
+ *     every time split, status, communicators (a model never spans ranks: a rank's handle holds whole models).
+ * PYVB_E_ARG when model[] is not of that form (the message names the first offending replicate).  PYVB_E_UNSUPPORTED when some
+ * model has more than one chain and the noise is Wishart or max(D, K) > 64.  Both before any HIP call.  A handle whose models
+ * are all single replicates is bitwise a pyvb_lds_create_lengths handle. */
+int pyvb_lds_create_tied(pyvb_lds** out, int device, int N, int T, int D, int K, int noise_kind,
+                         const int* lengths, const int* model);
+int pyvb_lds_get_models(pyvb_lds* h, int* model);
+
 /* Constant parents (node.py:279-311), shared by all replicates:
  *   x0_mean[D], x0_prec[D][D]                     Gaussian(q, pmu, pprec) for X_0  (:58)
  *   A_prior_mean[D][D] (row,col), A_prior_prec[D][D] (column i, diagonal entry k)   (:47)

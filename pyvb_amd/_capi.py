@@ -36,6 +36,8 @@ SIGNATURES = {
     "pyvb_lds_create": (ctypes.c_int, [ctypes.POINTER(_h)] + [ctypes.c_int] * 6),
     "pyvb_lds_create_lengths": (ctypes.c_int, [ctypes.POINTER(_h)] + [ctypes.c_int] * 6 + [_ip]),
     "pyvb_lds_get_lengths": (ctypes.c_int, [_h, _ip]),
+    "pyvb_lds_create_tied": (ctypes.c_int, [ctypes.POINTER(_h)] + [ctypes.c_int] * 6 + [_ip, _ip]),
+    "pyvb_lds_get_models": (ctypes.c_int, [_h, _ip]),
     "pyvb_lds_destroy": (ctypes.c_int, [_h]),
     "pyvb_lds_set_priors": (ctypes.c_int, [_h] + [_dp] * 10),
     "pyvb_lds_set_wishart_priors": (ctypes.c_int, [_h, ctypes.c_double, _dp, ctypes.c_double, _dp]),

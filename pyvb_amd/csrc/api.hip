@@ -51,7 +51,7 @@ void pyvb_timing_resolve(pyvb_lds* h) {
 extern "C" {
 
 const char* pyvb_last_error(void) { return g_err; }
-int pyvb_version(void) { return 101; }
+int pyvb_version(void) { return 102; }
 
 int pyvb_device_count(int* count) {
     ARGCHK(count, "count is NULL");
@@ -225,6 +225,55 @@ int pyvb_lds_create_lengths(pyvb_lds** out, int device, int N, int T, int D, int
     return PYVB_OK;
 }
 
+int pyvb_lds_create_tied(pyvb_lds** out, int device, int N, int T, int D, int K, int noise_kind, const int* lengths, const int* model) {
+    if (!model) return pyvb_lds_create_lengths(out, device, N, T, D, K, noise_kind, lengths);
+    ARGCHK(out, "out is NULL");
+    ARGCHK(N >= 1, "N must be >= 1");
+    // the models: checked and, where a tied model is not served, refused before the first HIP call
+    bool tied = false;
+    for (int n = 0; n < N; ++n) {
+        const int prev = n ? model[n - 1] : 0;
+        if (n == 0 ? model[0] != 0 : (model[n] != prev && model[n] != prev + 1)) {
+            pyvb_set_error("replicate %d has model %d after %d: model ids start at 0, never decrease and rise in steps of 0 or 1 "
+                           "(a model is a run of consecutive replicates)", n, model[n], n ? prev : -1);
+            return PYVB_E_ARG;
+        }
+        tied = tied || (n && model[n] == prev);
+    }
+    if (tied && noise_kind == PYVB_NOISE_WISHART) {
+        pyvb_set_error("chains that share A, C, Q, R are served with DiagonalGamma and Gamma noise only, not with Wishart noise (k_wishart.hip)");
+        return PYVB_E_UNSUPPORTED;
+    }
+    if (tied && (D > 64 || K > 64)) {
+        pyvb_set_error("chains that share A, C, Q, R are served for max(D, K) <= 64 only, not in the 128-wide class (k_big.hip): D = %d, K = %d", D, K);
+        return PYVB_E_UNSUPPORTED;
+    }
+    int rc = pyvb_lds_create_lengths(out, device, N, T, D, K, noise_kind, lengths);
+    if (rc != PYVB_OK || !tied) return rc;       // models of one replicate each: a pyvb_lds_create_lengths handle
+    pyvb_lds* h = *out;
+    *out = nullptr;
+    h->M = model[N - 1] + 1;
+    h->model_host = (int*)malloc((size_t)N * sizeof(int));
+    memcpy(h->model_host, model, (size_t)N * sizeof(int));
+    std::vector<int> mstart((size_t)h->M + 1, N);
+    std::vector<unsigned char> first((size_t)N, 0);
+    for (int n = N - 1; n >= 0; --n) mstart[model[n]] = n;
+    for (int m = 0; m < h->M; ++m) first[mstart[m]] = 1;
+    CREATE_TRY(h->mem.alloc((void**)&h->mstart, mstart.size() * sizeof(int)), pyvb_lds_destroy, h);
+    CREATE_TRY(h->mem.alloc((void**)&h->first, (size_t)N), pyvb_lds_destroy, h);
+    CREATE_TRYHIP(hipMemcpy(h->mstart, mstart.data(), mstart.size() * sizeof(int), hipMemcpyHostToDevice), pyvb_lds_destroy, h);
+    CREATE_TRYHIP(hipMemcpy(h->first, first.data(), (size_t)N, hipMemcpyHostToDevice), pyvb_lds_destroy, h);
+    *out = h;
+    return PYVB_OK;
+}
+
+int pyvb_lds_get_models(pyvb_lds* h, int* model) {
+    ARGCHK(h, "handle is NULL");
+    ARGCHK(model, "model is NULL");
+    for (int n = 0; n < h->N; ++n) model[n] = h->model_host ? h->model_host[n] : n;
+    return PYVB_OK;
+}
+
 int pyvb_lds_destroy(pyvb_lds* h) {
     if (!h) return PYVB_OK;
     (void)hipSetDevice(h->device);
@@ -237,7 +286,7 @@ int pyvb_lds_destroy(pyvb_lds* h) {
     if (h->running_host) (void)hipHostFree(h->running_host);
     if (h->side) (void)hipStreamDestroy(h->side);
     h->mem.release_all();
-    free(h->active_host); free(h->conv_host); free(h->status_host); free(h->reported); free(h->len_host);
+    free(h->active_host); free(h->conv_host); free(h->status_host); free(h->reported); free(h->len_host); free(h->model_host);
     if (h->pool) {
         for (int i = 0; i < PYVB_EVENT_POOL; ++i) { if (h->pool[i].e0) (void)hipEventDestroy(h->pool[i].e0); if (h->pool[i].e1) (void)hipEventDestroy(h->pool[i].e1); }
         free(h->pool);
@@ -338,12 +387,18 @@ int pyvb_lds_set_priors(pyvb_lds* h, const double* x0_mean, const double* x0_pre
         // qa is fixed by the graph: update_a, nodes_todo.py:125-128 (Gamma: +0.5*child.shape[0] per child)
         // and :183-186 (DiagonalGamma: +0.5 per child); Q has T-1 children X_1.., R has T children Y_t
         std::vector<double> qa((size_t)N * D), ra((size_t)N * K);
+        // the children of replicate n's Q and R: its own chain's, or those of every chain of its model (pyvb_lds_create_tied)
+        std::vector<long> mq((size_t)N, 0), mr((size_t)N, 0);      // per model id (a plain handle: id = n)
         for (int n = 0; n < N; ++n) {
-            const int Tn = h->len_host ? h->len_host[n] : T;       // the children of replicate n's own Q and R
+            const int Tn = h->len_host ? h->len_host[n] : T, m = h->model_host ? h->model_host[n] : n;
+            mq[m] += Tn - 1; mr[m] += Tn;
+        }
+        for (int n = 0; n < N; ++n) {
+            const long nq = mq[h->model_host ? h->model_host[n] : n], nr = mr[h->model_host ? h->model_host[n] : n];
             for (int k = 0; k < D; ++k)
-                qa[(size_t)n * D + k] = (h->noise == PYVB_NOISE_GAMMA) ? Q_a0[0] + 0.5 * D * (Tn - 1) : Q_a0[k] + 0.5 * (Tn - 1);
+                qa[(size_t)n * D + k] = (h->noise == PYVB_NOISE_GAMMA) ? Q_a0[0] + 0.5 * D * nq : Q_a0[k] + 0.5 * nq;
             for (int k = 0; k < K; ++k)
-                ra[(size_t)n * K + k] = (h->noise == PYVB_NOISE_GAMMA) ? R_a0[0] + 0.5 * K * Tn : R_a0[k] + 0.5 * Tn;
+                ra[(size_t)n * K + k] = (h->noise == PYVB_NOISE_GAMMA) ? R_a0[0] + 0.5 * K * nr : R_a0[k] + 0.5 * nr;
         }
         if ((rc = h2d(h, h->Q_a, qa.data(), qa.size()))) return rc;
         if ((rc = h2d(h, h->R_a, ra.data(), ra.size()))) return rc;
@@ -468,6 +523,15 @@ int pyvb_lds_set_column_observations(pyvb_lds* h, const double* A_obs, const dou
 }
 
 static int ensure_expect(pyvb_lds* h);
+// sum_t <y^2> per chain, then summed over the chains of every model (k_tie.hip: once per production, it is in place)
+static int syy(pyvb_lds* h) {
+    const int rc = launch_syy(h);
+    return rc ? rc : launch_tie(h, h->Syy, h->K);
+}
+static int syy_missing(pyvb_lds* h) {
+    const int rc = launch_syy_missing(h);
+    return rc ? rc : launch_tie(h, h->Syy, h->K);
+}
 // Wishart noise, after the means of the outputs changed: sum_t qmu qmu^T, and the entropy terms of the rows that are not
 // fully observed (diag_cov: they still carry their diagonal initial covariances, whose sum is formed here too)
 static int outputs_changed_dense(pyvb_lds* h, int diag_cov) {
@@ -515,11 +579,11 @@ int pyvb_lds_set_observations(pyvb_lds* h, const double* Y) {
         h->has_missing = true;
         // rows with NaN start as N(0, I) until pyvb_lds_set_output_state says otherwise
         if ((rc = launch_missing_init(h, nullptr, nullptr))) return rc;
-        if ((rc = h->dense ? outputs_changed_dense(h, 1) : launch_syy_missing(h))) return rc;
+        if ((rc = h->dense ? outputs_changed_dense(h, 1) : syy_missing(h))) return rc;
     } else {
         h->has_missing = false;
         if ((rc = h2d(h, h->Y, Y, n))) return rc;
-        if ((rc = launch_syy(h))) return rc;
+        if ((rc = syy(h))) return rc;
         if (h->dense && (rc = launch_syy_full(h))) return rc;
     }
     HIPCHK(hipStreamSynchronize(h->stream));
@@ -540,7 +604,7 @@ int pyvb_lds_set_output_state(pyvb_lds* h, const double* Yq, const double* Yrowv
     double* dv = h->X[1 - h->st.cur];      // [N][T][DP] >= [N][T]
     int rc;
     if ((rc = h2d(h, dq, Yq, n)) || (rc = h2d(h, dv, Yrowvar, (size_t)h->N * h->T)) ||
-        (rc = launch_missing_init(h, dq, dv)) || (rc = h->dense ? outputs_changed_dense(h, 1) : launch_syy_missing(h))) {
+        (rc = launch_missing_init(h, dq, dv)) || (rc = h->dense ? outputs_changed_dense(h, 1) : syy_missing(h))) {
         if (tmp) { (void)hipStreamSynchronize(h->stream); (void)hipFree(tmp); }
         return rc;
     }
@@ -580,7 +644,7 @@ int pyvb_lds_update_Y(pyvb_lds* h) {
         if ((rc = outputs_changed_dense(h, 0))) return rc;
     } else {
         if ((rc = launch_impute(h))) return rc;
-        if ((rc = launch_syy_missing(h))) return rc;
+        if ((rc = syy_missing(h))) return rc;
     }
     h->st.outputs_changed();
     return PYVB_OK;
@@ -596,12 +660,24 @@ int pyvb_lds_set_state(pyvb_lds* h, const double* X, const double* A_mean, const
         if ((rc = h2d(h, h->X[1 - h->st.cur], X, N * T * D))) return rc;
         if ((rc = launch_permute(h, h->X[1 - h->st.cur], h->X[h->st.cur], 1))) return rc;
     }
-    if ((rc = h2d(h, h->A_mean, A_mean, N * D * D))) return rc;
-    if ((rc = h2d(h, h->A_var, A_colvar, N * D * D))) return rc;
-    if ((rc = h2d(h, h->C_mean, C_mean, N * K * D))) return rc;
-    if ((rc = h2d(h, h->C_var, C_colvar, N * D * K))) return rc;
-    if ((rc = h2d(h, h->Q_b, Q_b, N * D))) return rc;
-    if ((rc = h2d(h, h->R_b, R_b, N * K))) return rc;
+    // Chains that share A, C, Q, R: the row of a model's first replicate is the model's state and goes to all its rows
+    std::vector<double> tied[6];        // (staging; alive until the synchronisation below)
+    auto model_rows = [&](int slot, const double* src, size_t per) -> const double* {
+        if (!src || !h->model_host) return src;
+        std::vector<double>& v = tied[slot];
+        v.resize(N * per);
+        for (size_t n = 0, f = 0; n < N; ++n) {
+            if (n && h->model_host[n] != h->model_host[n - 1]) f = n;
+            memcpy(v.data() + n * per, src + f * per, per * sizeof(double));
+        }
+        return v.data();
+    };
+    if ((rc = h2d(h, h->A_mean, model_rows(0, A_mean, D * D), N * D * D))) return rc;
+    if ((rc = h2d(h, h->A_var, model_rows(1, A_colvar, D * D), N * D * D))) return rc;
+    if ((rc = h2d(h, h->C_mean, model_rows(2, C_mean, K * D), N * K * D))) return rc;
+    if ((rc = h2d(h, h->C_var, model_rows(3, C_colvar, D * K), N * D * K))) return rc;
+    if ((rc = h2d(h, h->Q_b, model_rows(4, Q_b, D), N * D))) return rc;
+    if ((rc = h2d(h, h->R_b, model_rows(5, R_b, K), N * K))) return rc;
     const bool covs = h->dense && (A_colvar || C_colvar);       // diagonal initial covariances
     if (covs && (rc = launch_colvar_to_cov(h))) return rc;
     HIPCHK(hipStreamSynchronize(h->stream));
@@ -788,6 +864,7 @@ static int ensure_stats(pyvb_lds* h) {
     int rc = launch_stats(h, !st.sxx_valid);
     if (rc) return rc;
     if ((rc = launch_moments(h, st.sxx_valid))) return rc;
+    if ((rc = launch_tie(h, h->mom, (size_t)3 * h->D * h->D + (size_t)h->K * h->D + h->D))) return rc;        // chains that share A, C, Q, R: the moments of a model
     st.stats_valid = true;
     return PYVB_OK;
 }
@@ -960,6 +1037,11 @@ int pyvb_lds_iterate_until(pyvb_lds* h, int max_iters, double tol, int check_eve
     ARGCHK(check_every >= 1, "check_every must be >= 1");
     ARGCHK(tol == tol, "tol is NaN");
     ARGCHK(iters_run, "iters_run is NULL");
+    if (h->model_host) {
+        pyvb_set_error("pyvb_lds_iterate_until is not served on a handle with a model of more than one chain (pyvb_lds_create_tied): "
+                       "the stopping test is per replicate, convergence per model is a follow-up");
+        return PYVB_E_UNSUPPORTED;
+    }
     ENTER(h);
     *iters_run = 0;
     int rc, it = 0;
@@ -1100,6 +1182,13 @@ int pyvb_lds_set_active(pyvb_lds* h, const unsigned char* active) {
         if (active[n] && !h->active_host[n]) {
             pyvb_set_error("replicate %d is switched off and cannot be switched on again: the mask can only shrink "
                            "(the validity tracking of gains and statistics is per handle)", n);
+            return PYVB_E_ARG;
+        }
+    for (int n = 1; h->model_host && n < h->N; ++n)
+        if (h->model_host[n] == h->model_host[n - 1] && (active[n] != 0) != (active[n - 1] != 0)) {
+            pyvb_set_error("the mask switches off part of model %d (replicate %d is %s, replicate %d is %s): the chains of a model "
+                           "share A, C, Q, R and are switched off together", h->model_host[n], n - 1, active[n - 1] ? "on" : "off",
+                           n, active[n] ? "on" : "off");
             return PYVB_E_ARG;
         }
     ENTER(h);

@@ -133,6 +133,10 @@ struct pyvb_lds {
     // ---- per-replicate chain lengths (pyvb_lds_create_lengths): null on a handle whose chains all have T nodes
     int *len;                       // device, [N]: T_n.  T stays the row stride of every [N][T][..] buffer; rows t >= T_n are padding
     int *len_host;                  // its host copy (setters and getters: which rows are padding)
+    // ---- several chains, one model (pyvb_lds_create_tied, k_tie.hip): all null / 0 on a handle whose models are single replicates
+    int *mstart; int M;             // device, [M + 1]: model m is replicates mstart[m] .. mstart[m + 1] - 1
+    unsigned char *first;           // device, [N]: 1 = the first replicate of its model, where k_elbo books the shared nodes' terms
+    int *model_host;                // [N] the model of every replicate
     int *status_host, *reported;    // [N] staging of a read of status; [N] what the most recent failed sync reported and cleared
     LdsState st;                    // what is current on the device (host.h); written by the events of api.hip only
     DeviceBuffers mem;              // every device allocation of this handle
@@ -175,6 +179,7 @@ int launch_carry(pyvb_lds* h, const double* src, double* dst, size_t per);     /
 int launch_stats(pyvb_lds* h, bool with_sxx);   // with_sxx = false: Sxx comes from the backward sweep (h->sxx)
 int launch_moments(pyvb_lds* h, bool sxx_from_sweep);
 int launch_observe(pyvb_lds* h);
+int launch_tie(pyvb_lds* h, double* buf, size_t per);      // k_tie.hip: sum rows of [N][per] over the chains of every model, in place
 int launch_cols(pyvb_lds* h, int which, int c0, int c1, int fuse = 0);   // which: 0 = A, 1 = C, 2 = both; columns [c0, c1); fuse: see k_cols.hip
 int launch_resid(pyvb_lds* h, int which);     // 0 = Q, 1 = R
 int launch_noise(pyvb_lds* h, int which);

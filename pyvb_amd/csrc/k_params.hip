@@ -107,6 +107,9 @@ __global__ void __launch_bounds__(64 * NW) k_elbo(ParamArgs a) {
     const double* x0 = a.X + (size_t)n * T * a.L.DP;
     const int TL = a.len ? a.len[n] : T;              // nodes of this replicate's chain: Q has TL - 1 children, R has TL
     const bool exact = a.bound == PYVB_BOUND_EXACT;
+    // Chains that share A, C, Q, R (k_tie.hip): the terms of the shared nodes, and the residual traces, which are sums over the
+    // whole model, are booked on the model's first replicate; the others keep the terms of their own X_t and Y_t.
+    const bool first = !a.first || a.first[n];
     // the entropy of the X_t: quirk Q1's q_ln_det (reference) or ln det Sigma (exact)
     const double* qx = (exact ? a.lnd_x : a.qld_x) + (size_t)n * 3;
     // --- noise expectations
@@ -125,8 +128,8 @@ __global__ void __launch_bounds__(64 * NW) k_elbo(ParamArgs a) {
     }
     // pass_down_lndet: ln det E[Lambda] (quirk Q2) or E[ln det Lambda] (exact)
     const double lndQ = blk_sum<NW>(lnq, red), lndR = blk_sum<NW>(lnr, red);
-    const double trQ = blk_sum<NW>(rq, red), trR = blk_sum<NW>(rr, red);
-    const double LQ = blk_sum<NW>(lq, red), LR = blk_sum<NW>(lr, red);
+    const double trQ = first ? blk_sum<NW>(rq, red) : 0.0, trR = first ? blk_sum<NW>(rr, red) : 0.0;
+    const double LQ = first ? blk_sum<NW>(lq, red) : 0.0, LR = first ? blk_sum<NW>(lr, red) : 0.0;
     // --- X_0 against its Constant parents
     double e0 = 0.0;
     if (lane < D) {
@@ -151,7 +154,7 @@ __global__ void __launch_bounds__(64 * NW) k_elbo(ParamArgs a) {
     // covariance of the missing part (:150, with the reference's sign of the 2 pi term), all -> no term.
     // The exact bound takes ln det qcov for the first and the entropy of the missing part for the second.
     double la = 0.0, lc = 0.0;
-    if (lane < D) {
+    if (lane < D && first) {
         const int i = lane;   // column i
         auto column = [&](int rows, const double* pp, const double* pm, const double* M, const double* V,
                           const double* obs, double qld, double lndet) {
@@ -194,7 +197,7 @@ __global__ void __launch_bounds__(64 * NW) k_elbo(ParamArgs a) {
         lc = column(K, a.pri.C_pp, a.pri.C_pm, a.C_mean + (size_t)n * K * D, a.C_var + (size_t)n * D * K, a.pri.C_obs,
                     (exact ? a.lnd_C : a.qld_C)[(size_t)n * D + i], a.pri.C_pld[i]);
     }
-    const double LA = blk_sum<NW>(la, red), LC = blk_sum<NW>(lc, red);
+    const double LA = first ? blk_sum<NW>(la, red) : 0.0, LC = first ? blk_sum<NW>(lc, red) : 0.0;
     if (lane == 0) {
         double* o = a.elbo + (size_t)n * 6;
         o[0] = LX; o[1] = LY; o[2] = LA; o[3] = LC; o[4] = LQ; o[5] = LR;
@@ -245,7 +248,7 @@ ParamArgs make_args(pyvb_lds* h) {
     a.lnd_A = h->lnd_A; a.lnd_C = h->lnd_C; a.lnd_x = h->lnd_x; a.YentX = h->has_missing ? h->YentX : nullptr; a.bound = h->bound;
     a.N = h->N; a.T = h->T; a.D = h->D; a.K = h->K; a.noise = h->noise; a.L = h->L; a.c0 = 0; a.c1 = h->D; a.which0 = 0; a.fuse = 0; a.sxx = nullptr; a.W = 1;
     a.active = h->active;
-    a.len = h->len; a.Lw = 0;
+    a.len = h->len; a.Lw = 0; a.first = h->first;
     return a;
 }
 

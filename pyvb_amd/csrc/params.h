@@ -27,6 +27,7 @@ struct ParamArgs {
     int which0;             // blockIdx.y + which0 selects the matrix / noise node (0: A, Q; 1: C, R)
     Layout L;
     const int* len;         // [N] chain length T_n of each replicate (pyvb_lds_create_lengths), or null: T.  T stays the row stride of X
+    const unsigned char* first;     // k_elbo: [N] 1 = first replicate of its model (pyvb_lds_create_tied), or null: every one is
     int Lw;                 // k_moments: interior nodes per part of sxx, cut from the handle's T as k_sweep cuts them
 };
 

@@ -1,6 +1,8 @@
 """LDSBatch: N independent replicates of the linear-dynamical-system graph of the
 reference's examples/Linear_Dynamic_System.py:46-66, resident on one MI355X.
 
+Consecutive replicates can share A, C, Q, R (models=, from_trials): several time series, one model.
+
 Thin Python over the C ABI (include/pyvb_hip.h); every method is one or a few
 kernel launches.  The node classes in pyvb_amd.nodes bind to an LDSBatch with
 N = 1; bench.py and the parity tests drive it directly.
@@ -51,16 +53,30 @@ def pad_series(series):
 class LDSBatch(object):
     ELBO_PARTS = ("X", "Y", "A", "C", "Q", "R")
 
-    def __init__(self, N, T, D, K, noise="diagonal_gamma", device=0, lengths=None):
+    def __init__(self, N, T, D, K, noise="diagonal_gamma", device=0, lengths=None, models=None):
         """lengths: int [N], the chain length T_n of each replicate, 2 <= T_n <= T (pyvb_lds_create_lengths); None: all T.
         Arrays stay [N, T, ...]; rows t >= T_n of replicate n are padding: setters accept anything there, getters return
-        0.0 in X and in the outputs."""
+        0.0 in X and in the outputs.
+        models: int [N], the model of each replicate (pyvb_lds_create_tied): consecutive replicates with the same id are the
+        chains of one model and share A, C, Q, R -- several time series, one model.  Ids start at 0 and rise in steps of 0 or
+        1.  None: every replicate is a model of its own.  Parameter arrays stay [N, ...]; set_state takes a model's
+        parameters from the row of its first replicate, getters return them in every row of the model."""
         if noise not in _NOISE:
             raise NotImplementedError("noise precision %r has no HIP path (DiagonalGamma, Gamma and Wishart do)" % (noise,))
         self.N, self.T, self.D, self.K, self.noise, self.device = int(N), int(T), int(D), int(K), noise, int(device)
         self.bound = "reference"
         h = C.ctypes.c_void_p()
-        if lengths is None:
+        if models is not None:
+            ln = None if lengths is None else np.ascontiguousarray(lengths, dtype=np.int32)
+            md = np.ascontiguousarray(models, dtype=np.int32)
+            for nm, a in (("lengths", ln), ("models", md)):
+                if a is not None and a.shape != (self.N,):
+                    raise AssertionError("%s has shape %s, expected (%d,)" % (nm, a.shape, self.N))
+            C.check(C.lib.pyvb_lds_create_tied(C.ctypes.byref(h), self.device, self.N, self.T, self.D, self.K, _NOISE[noise],
+                                               None if ln is None else ln.ctypes.data_as(C._ip), md.ctypes.data_as(C._ip)))
+            self.lengths = np.empty(self.N, dtype=np.int32)
+            C.check(C.lib.pyvb_lds_get_lengths(h, self.lengths.ctypes.data_as(C._ip)))
+        elif lengths is None:
             C.check(C.lib.pyvb_lds_create(C.ctypes.byref(h), self.device, self.N, self.T, self.D, self.K, _NOISE[noise]))
             self.lengths = np.full(self.N, self.T, dtype=np.int32)
         else:
@@ -71,6 +87,8 @@ class LDSBatch(object):
                                                   ln.ctypes.data_as(C._ip)))
             self.lengths = np.empty(self.N, dtype=np.int32)
             C.check(C.lib.pyvb_lds_get_lengths(h, self.lengths.ctypes.data_as(C._ip)))
+        self.models = np.empty(self.N, dtype=np.int32)
+        C.check(C.lib.pyvb_lds_get_models(h, self.models.ctypes.data_as(C._ip)))
         self._h = h
 
     # -- lifetime ---------------------------------------------------------------------------
@@ -384,10 +402,21 @@ class LDSBatch(object):
         return cls.from_problem(Y, st0, pri, device, lengths=lengths)
 
     @classmethod
-    def from_problem(cls, Y, st0, pri, device=0, lengths=None):
+    def from_trials(cls, trials, pri, device=0):
+        """One model fitted to several recorded series (trials, sessions, subjects): trials is a list with one entry per model,
+        each a list of (Y_n[T_n, K], st0_n) as from_series takes them.  The chains of a model share A, C, Q, R; their
+        initial parameters are those of the model's first entry, every chain keeps its own initial states (pad_series)."""
+        if not trials or any(len(t) == 0 for t in trials):
+            raise ValueError("every model needs at least one series")
+        Y, st0, lengths = pad_series([s for t in trials for s in t])
+        models = np.repeat(np.arange(len(trials), dtype=np.int32), [len(t) for t in trials])
+        return cls.from_problem(Y, st0, pri, device, lengths=lengths, models=models)
+
+    @classmethod
+    def from_problem(cls, Y, st0, pri, device=0, lengths=None, models=None):
         N, T, K = Y.shape
         D = st0["A_mean"].shape[1]
-        b = cls(N, T, D, K, pri.get("noise", "diagonal_gamma"), device, lengths=lengths)
+        b = cls(N, T, D, K, pri.get("noise", "diagonal_gamma"), device, lengths=lengths, models=models)
         b.set_priors(pri)
         b.set_observations(Y)
         if "Yq" in st0 and b.has_missing_outputs(Y):
