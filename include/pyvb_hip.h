@@ -367,6 +367,17 @@ int pyvb_pca_elbo(pyvb_pca* h, double parts[5]);
 /* niters passes of Network.learn's loop body (network.py:46-49) in the crawl order of fetch_network:
  * W columns, Z_0.., X_0, Mu, X_1.., Beta, lower bound */
 int pyvb_pca_iterate(pyvb_pca* h, int niters);
+/* Which kernel serves the sweep of an iteration -- the Z update and the X update of all rows (or all but row 0) in one pass over
+ * X -- where the imputed entries may be left unstored.  pyvb_pca_create picks the kind: PAIRS for d > 192 from 512 rows per
+ * compute unit on, COLUMNS otherwise.  The setter lets a test or an A/B run put a chosen kernel on a small handle; it may be
+ * called between any two calls and touches nothing on the device.  q > 16, rows not yet pinned, partial ranges and an incoming
+ * unstored range the pass cannot take in are written back whatever the kind.  Results do not depend on the kind beyond rounding.
+ * An unknown kind: PYVB_E_ARG. */
+#define PYVB_PCA_SWEEP_STORE   0   /* the imputed entries are written back (k_pca_pass12) */
+#define PYVB_PCA_SWEEP_COLUMNS 1   /* left unstored, column-owning sweep (k_pca_pass12<.., LAZY>) */
+#define PYVB_PCA_SWEEP_PAIRS   2   /* left unstored, pair-owning sweep (k_pca_pairs) */
+int pyvb_pca_get_sweep(pyvb_pca* h, int* kind);
+int pyvb_pca_set_sweep(pyvb_pca* h, int kind);
 int pyvb_pca_sync(pyvb_pca* h);
 int pyvb_pca_comm_init(pyvb_pca* h, const char id[128], int rank, int world);
 int pyvb_pca_comm_init_host(pyvb_pca* h, pyvb_host_allreduce_fn fn, void* user, int rank, int world);

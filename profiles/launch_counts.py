@@ -61,9 +61,9 @@ def pca_sequence():
     sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests", "golden"))
     import make_golden as G
     for sweep, N in (("columns", 3000), ("pairs", 3000)):
-        os.environ["PYVB_PCA_SWEEP"] = sweep
         init, pri = G.pca_problem(N, 250, 16, seed=77)
         b = PCABatch.from_problem(init, pri)
+        b.set_sweep(sweep)
         b.iterate(3); b.update_W(); b.update_Z(); b.update_X(0, 1); b.update_Mu(); b.update_X(1, N); b.update_Beta(); b.elbo()
         b.iterate(1); b.update_X(100, 900); b.iterate(1); b.get_state()
         b.update_Z(); b.update_X(0, N); b.update_X0(); b.update_Mu(); b.iterate(2); b.elbo()

@@ -16,6 +16,6 @@ for C in FETCH_SIZE WRITE_SIZE; do
 done
 python3 $ROOT/profiles/traffic_summary.py $OUT/pcatr k_pca_pass12 k_pca_pass1 k_pca_pass2 k_pca_small k_pca_reduce > $OUT/traffic_pca_pmc.json
 python3 $ROOT/profiles/generic_probe.py > $OUT/generic_probe.txt 2>&1
-PYVB_TAPE_STATS=1 python3 $ROOT/profiles/generic_lds_probe.py 2>&1 | grep "19550\|ms per\|queued run" > $OUT/generic_lds_probe.txt
+python3 $ROOT/profiles/generic_lds_probe.py 2>&1 | grep "ms per\|queued run" > $OUT/generic_lds_probe.txt
 python3 $ROOT/profiles/tape_record_cost.py > $OUT/tape_record_cost.txt 2>&1
 python3 $ROOT/profiles/fuzz_generic.py > $OUT/fuzz_generic.txt 2>&1 || true

@@ -17,6 +17,8 @@ NOISE_DIAGONAL_GAMMA, NOISE_GAMMA, NOISE_WISHART = 0, 1, 2
 FORWARD, BACKWARD = 0, 1
 BOUND_REFERENCE, BOUND_EXACT = 0, 1
 BOUND_MODES = {"reference": BOUND_REFERENCE, "exact": BOUND_EXACT}
+PCA_SWEEP_STORE, PCA_SWEEP_COLUMNS, PCA_SWEEP_PAIRS = 0, 1, 2
+PCA_SWEEPS = {"store": PCA_SWEEP_STORE, "columns": PCA_SWEEP_COLUMNS, "pairs": PCA_SWEEP_PAIRS}
 FAIL_STATES, FAIL_COLUMNS, FAIL_NOISE = 1, 2, 4      # PYVB_FAIL_*: bits of pyvb_lds_get_status
 K_PREP, K_SWEEP_FWD, K_STATS, K_PARAMS, K_STEP, K_SWEEP_BWD, K_ELBO, K_GY = range(8)
 
@@ -114,6 +116,8 @@ SIGNATURES = {
     "pyvb_pca_update_Beta": (ctypes.c_int, [_h]),
     "pyvb_pca_elbo": (ctypes.c_int, [_h, _dp]),
     "pyvb_pca_iterate": (ctypes.c_int, [_h, ctypes.c_int]),
+    "pyvb_pca_get_sweep": (ctypes.c_int, [_h, _ip]),
+    "pyvb_pca_set_sweep": (ctypes.c_int, [_h, ctypes.c_int]),
     "pyvb_pca_sync": (ctypes.c_int, [_h]),
     "pyvb_pca_comm_init": (ctypes.c_int, [_h, ctypes.c_char_p, ctypes.c_int, ctypes.c_int]),
     "pyvb_pca_comm_init_host": (ctypes.c_int, [_h, HOST_ALLREDUCE, ctypes.c_void_p, ctypes.c_int, ctypes.c_int]),

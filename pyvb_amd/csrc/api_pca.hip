@@ -1,8 +1,6 @@
 // Host side of the VB-PCA path: handle, copies, dependency tracking, the all-reduce of the statistics.
 #include "pca.h"
 #include <cmath>
-#include <cstdio>
-#include <cstdlib>
 #include <cstring>
 #include <vector>
 
@@ -54,7 +52,6 @@ int pyvb_pca_create(pyvb_pca** out, int device, long N, int d, int q, long N_tot
         int ncu = 0;
         if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && ncu > 0) nchunk = ncu;
     }
-    { const char* e = getenv("PYVB_PCA_CHUNKS"); if (e && atol(e) > 0) nchunk = atol(e); }      // (experiments)
     const long ntile = (N + 15) / 16;
     if (nchunk > ntile) nchunk = ntile;
     if (nchunk < 1) nchunk = 1;
@@ -77,7 +74,6 @@ int pyvb_pca_create(pyvb_pca** out, int device, long N, int d, int q, long N_tot
     TRY(alloc_d(&h->Mu_mean, d)); TRY(alloc_d(&h->Mu_var, d)); TRY(alloc_d(&h->Z_cov, (size_t)q * q)); TRY(alloc_d(&h->qld_W, q)); TRY(alloc_d(&h->lnd_W, q));
     TRY(alloc_d(&h->W_pm, (size_t)d * q)); TRY(alloc_d(&h->W_pp, (size_t)q * d)); TRY(alloc_d(&h->Mu_pm, d)); TRY(alloc_d(&h->Mu_pp, d));
     TRY(alloc_d(&h->W_x, (size_t)d * q)); TRY(alloc_d(&h->Mu_x, d));
-    { const char* e = getenv("PYVB_PCA_WRITEBACK"); h->lazy_ok = !(e && e[0] == '1'); }
     {   // k_pca_pairs: one workgroup per CU, the rows dealt out in multiples of 16
         int ncu = 0;
         TRYHIP(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device));
@@ -88,14 +84,11 @@ int pyvb_pca_create(pyvb_pca** out, int device, long N, int d, int q, long N_tot
         long ncB = (N + rowsB - 1) / rowsB;
         if (ncB > nchunk) { ncB = nchunk; rowsB = ((N + ncB - 1) / ncB + 15) & ~15L; ncB = (N + rowsB - 1) / rowsB; }
         h->nchunkB = (int)ncB; h->chunk_rowsB = rowsB;
-        // which kernel the lazy sweep is (k_pca.hip): PYVB_PCA_SWEEP = columns (k_pca_pass12<.., LAZY>) / pairs (k_pca_pairs);
-        // unset: pairs where a CU's share is long enough to stream (measured at 10^6 x 256: 0.95 against 0.97 ms per
-        // iteration), columns otherwise
-        const char* e = getenv("PYVB_PCA_SWEEP");
-        if (e && e[0] == 'p') h->pairs = true;
-        else if (e && e[0] == 'c') h->pairs = false;
-        else h->pairs = h->DT >= 13 && N >= 512L * ncu;
-        if (h->pairs) TRY(pca_prepare_pairs());
+        // which kernel the lazy sweep is (k_pca.hip): pairs (k_pca_pairs) where a CU's share is long enough to stream (measured
+        // at 10^6 x 256: 0.95 against 0.97 ms per iteration), columns (k_pca_pass12<.., LAZY>) otherwise; pyvb_pca_set_sweep
+        // changes it
+        h->sweep = (h->DT >= 13 && N >= 512L * ncu) ? PYVB_PCA_SWEEP_PAIRS : PYVB_PCA_SWEEP_COLUMNS;
+        if (h->sweep == PYVB_PCA_SWEEP_PAIRS) { TRY(pca_prepare_pairs()); h->pairs_ready = true; }
     }
     TRY(alloc_d(&h->scal, PS_COUNT));
     TRY(alloc_d(&h->Gz, (size_t)h->QT * (DP / 4) * 64)); TRY(alloc_d(&h->g0, QP));
@@ -149,9 +142,9 @@ static PcaSweepPlan plan_sweep(const pyvb_pca* h, long lo_upd, long hi_upd) {
     p.lo_upd = lo_upd; p.hi_upd = hi_upd;
     p.with_z = st.z_pending;
     p.keep_z0 = st.z0_done;
-    p.lazy = p.with_z && h->lazy_ok && h->QT == 1 && !h->Xdata && lo_upd <= 1 && hi_upd == h->N && hi_upd > lo_upd
+    p.lazy = p.with_z && h->sweep != PYVB_PCA_SWEEP_STORE && h->QT == 1 && !h->Xdata && lo_upd <= 1 && hi_upd == h->N && hi_upd > lo_upd
              && (!st.xlazy || (lo_upd <= st.vlo && st.vhi <= hi_upd));
-    p.pairs = p.lazy && h->pairs;
+    p.pairs = p.lazy && h->sweep == PYVB_PCA_SWEEP_PAIRS;
     p.materialize = st.xlazy && !p.lazy;
     p.vin_lo = st.xlazy ? st.vlo : 0; p.vin_hi = st.xlazy ? st.vhi : 0;
     p.part_chunks = p.pairs ? h->nchunkB : h->nchunk;
@@ -372,6 +365,27 @@ int pyvb_pca_set_bound_mode(pyvb_pca* h, int mode) {
     ARGCHK(mode == PYVB_BOUND_REFERENCE || mode == PYVB_BOUND_EXACT, "mode must be PYVB_BOUND_REFERENCE or PYVB_BOUND_EXACT");
     HIPCHK(hipStreamSynchronize(h->stream));
     h->bound = mode;
+    return PYVB_OK;
+}
+
+int pyvb_pca_get_sweep(pyvb_pca* h, int* kind) {
+    ARGCHK(h, "handle is NULL");
+    ARGCHK(kind, "kind is NULL");
+    *kind = h->sweep;
+    return PYVB_OK;
+}
+
+// Nothing on the device changes: entries an earlier lazy sweep left unstored are taken in or stored by the next pass, whichever
+// kernel that is (plan_sweep, x_read), and the partials are read by the partition of the sweep that wrote them (PcaState: part_chunks).
+int pyvb_pca_set_sweep(pyvb_pca* h, int kind) {
+    ENTER(h);
+    ARGCHK(kind == PYVB_PCA_SWEEP_STORE || kind == PYVB_PCA_SWEEP_COLUMNS || kind == PYVB_PCA_SWEEP_PAIRS, "kind must be one of PYVB_PCA_SWEEP_*");
+    if (kind == PYVB_PCA_SWEEP_PAIRS && !h->pairs_ready) {
+        int rc = pca_prepare_pairs();
+        if (rc) return rc;
+        h->pairs_ready = true;
+    }
+    h->sweep = kind;
     return PYVB_OK;
 }
 

@@ -24,22 +24,14 @@
 // sweeps as the products <Q><A>, <R><C>), though not together with known entries or outputs that hold NaN.
 #include "params.h"
 #include "gj.h"
-#include <cstdio>
-#include <cstdlib>
 
 #define MFMA(a, b, c) __builtin_amdgcn_mfma_f64_16x16x4f64((a), (b), (c), 0, 0, 0)
 #define BDP 128     // padded dimension
 #define BDT 8       // 16-row tiles
 #define BDS 32      // k-steps of 4
-#ifdef BLD_OVERRIDE
-#define BLD BLD_OVERRIDE
-#else
 #define BLD 130     // row stride of the LDS work matrix (A-operand reads conflict free)
-#endif
-#ifndef CHAIN_RUN
 #define CHAIN_RUN 32    // dependent MFMAs on one accumulator before the next accumulator takes its turn (k_gy_big, k_sweep_big);
                         // runs of 16 or 8 measured the same as whole chains (lds_d128: 49.9 / 49.9 / 49.7 ms)
-#endif
 
 // ======================================================================================================================
 // sweep
@@ -192,13 +184,6 @@ __global__ void __launch_bounds__(512 / NTW) k_sweep_big(BigSweepArgs a) {
     double* vs = xs + BDP;                          // [128] boundary scratch
     const int n = blockIdx.x, tid = threadIdx.x, w = tid >> 6, lane = tid & 63, c = lane & 15, q = lane >> 4;
     if (!a.active[n]) return;
-#ifdef BIG_CLOCK        // (profiles/build_variant.sh k_big clock "-DBIG_CLOCK": the chip's clock while this kernel runs, from its two time counters)
-    const unsigned long long ck_c0 = __builtin_amdgcn_s_memtime(), ck_r0 = __builtin_amdgcn_s_memrealtime();
-    struct ClockReport { unsigned long long c0, r0; int on, mode; __device__ ~ClockReport() {
-        if (on) { const unsigned long long dc = __builtin_amdgcn_s_memtime() - c0, dr = __builtin_amdgcn_s_memrealtime() - r0;
-                  printf("k_sweep_big<%d>: %.1f us, %.3f GHz\n", mode, dr / 100.0, dc / (dr * 10.0)); } } }
-        ck_report{ck_c0, ck_r0, blockIdx.x == 300 && blockIdx.y == 0 && threadIdx.x == 0, MODE};
-#endif
     const int part = blockIdx.y;            // the time axis is dealt out to a.W workgroups per replicate when there are few replicates (k_sweep.hip: SPLIT)
     const int T = a.T, D = a.D, K = a.K;
     const bool fwd = (a.dir == 0);
@@ -599,22 +584,13 @@ struct BigPrepArgs {
 // taken in turn at twice that), its 32 B operands fetched while the chain before it runs.  (Operands fetched where they were
 // used, eight accumulators in turn: 620 cycles per MFMA with operands in global memory, 170 with both in LDS -- cycle stamps.)
 // b_at should walk memory along j for neighbouring lanes (row-major B): its loads are 16 lanes x 8 contiguous bytes.
-#ifdef PREP_STAMP
-#define MMSTAMP(i) do { if (mst) { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); mst[i] += t_ - mt; mt = t_; } } while (0)
-#else
-#define MMSTAMP(i) do { } while (0)
-#endif
 template <class FA, class FB, class FS>
-__device__ __forceinline__ void mm128(int wave, int lane, FA a_at, FB b_at, FS store, unsigned long long* mst = nullptr) {
+__device__ __forceinline__ void mm128(int wave, int lane, FA a_at, FB b_at, FS store) {
     const int r = lane & 15, q = lane >> 4;
-#ifdef PREP_STAMP
-    unsigned long long mt = __builtin_amdgcn_s_memtime();
-#endif
     for (int m = wave; m < BDT; m += 4) {
         double av[BDS], bA[BDS], bB[BDS];
 #pragma unroll
         for (int s = 0; s < BDS; ++s) av[s] = a_at(16 * m + r, 4 * s + q);
-        MMSTAMP(0);
         auto fetch = [&](double (&bv)[BDS], int nn) {
             const int nc = nn < BDT ? nn : BDT - 1;
 #pragma unroll
@@ -622,21 +598,10 @@ __device__ __forceinline__ void mm128(int wave, int lane, FA a_at, FB b_at, FS s
         };
         auto chain = [&](const double (&bv)[BDS], int nn) {
             d4 acc = d4{0.0, 0.0, 0.0, 0.0};
-            MMSTAMP(1);
-#if defined(MM_WAIT)
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#elif defined(MM_FENCE)
-            asm volatile("" ::: "memory");
-#endif
 #pragma unroll
             for (int s = 0; s < BDS; ++s) acc = MFMA(av[s], bv[s], acc);
-#ifdef PREP_STAMP
-            if (mst) { asm volatile("s_nop 15\n\ts_nop 15" ::: "memory"); }
-#endif
-            MMSTAMP(2);
 #pragma unroll
             for (int e = 0; e < 4; ++e) store(16 * m + 4 * e + q, 16 * nn + r, acc[e]);
-            MMSTAMP(3);
         };
         fetch(bA, 0);
 #pragma unroll 1
@@ -749,12 +714,6 @@ __device__ __forceinline__ int warmup128(double* W, int tid, double* red) {
 #define STAGE_LOOP _Pragma("unroll 8") for (int u_ = 0, idx = threadIdx.x; u_ < BDP * BDP / 256; ++u_, idx += 256)
 __global__ void __launch_bounds__(256) k_prep_big(BigPrepArgs a) {
     extern __shared__ double lds[];
-#ifdef PREP_STAMP       // (profiles/build_variant.sh k_big pstamp "-DPREP_STAMP": where a workgroup's time goes, shader-clock ticks)
-    unsigned long long ps_t = __builtin_amdgcn_s_memtime(), ps_acc[6] = {0, 0, 0, 0, 0, 0}, ps_mm[4] = {0, 0, 0, 0}, ps_t0 = 0;
-#define PSTAMP(i) do { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); ps_acc[i] += t_ - ps_t; ps_t = t_; } while (0)
-#else
-#define PSTAMP(i) do { } while (0)
-#endif
     double* Pm = lds;                       // [128][BLD]
     double* qbar = Pm + BDP * BLD;          // [128]
     double* rbar = qbar + BDP;
@@ -803,22 +762,12 @@ __global__ void __launch_bounds__(256) k_prep_big(BigPrepArgs a) {
     double* S2 = S1 + BDP * BDP;
     STAGE_LOOP { const int k = idx >> 7, j = idx & 127; Pm[k * BLD + j] = C_at(k, j); }
     __syncthreads();
-#ifdef PREP_STAMP
-    ps_t0 = __builtin_amdgcn_s_memtime();
-#endif
     if (dense)      // <C>^T (E[R]<C>): the second operand straight from the array (the rare, untuned case)
         mm128(wave, lane, [&](int i, int k) { return Pm[k * BLD + i]; }, [&](int k, int j) { return RC_at(k, j); },
               [&](int i, int j, double v) { S1[(size_t)i * BDP + j] = (i < D && j < D) ? v + (i == j ? rowp[i] : 0.0) : 0.0; });
     else
     mm128(wave, lane, [&](int i, int k) { return Pm[k * BLD + i] * rbar[k]; }, [&](int k, int j) { return Pm[k * BLD + j]; },
-          [&](int i, int j, double v) { S1[(size_t)i * BDP + j] = (i < D && j < D) ? v + (i == j ? rowp[i] : 0.0) : 0.0; }
-#if defined(PREP_STAMP) && !defined(PREP_STAMP_NOMM)
-          , ps_mm
-#endif
-          );
-#ifdef PREP_STAMP
-    ps_t = __builtin_amdgcn_s_memtime(); ps_acc[5] += ps_t - ps_t0;
-#endif
+          [&](int i, int j, double v) { S1[(size_t)i * BDP + j] = (i < D && j < D) ? v + (i == j ? rowp[i] : 0.0) : 0.0; });
     __syncthreads();
     STAGE_LOOP { const int k = idx >> 7, j = idx & 127; Pm[k * BLD + j] = A_at(k, j); }
     __syncthreads();
@@ -833,7 +782,6 @@ __global__ void __launch_bounds__(256) k_prep_big(BigPrepArgs a) {
     STAGE_LOOP Pm[(idx >> 7) * BLD + (idx & 127)] = S1[idx] + S2[idx];
     __syncthreads();
 
-    PSTAMP(0);
     // the three posterior precisions (gaussian.py:117), inverted one after the other (qcov, :118-119; q_ln_det, :120)
     const int ta = tid >> 4, tb = tid & 15;
     for (int cc = 0; cc < 3; ++cc) {
@@ -857,9 +805,7 @@ __global__ void __launch_bounds__(256) k_prep_big(BigPrepArgs a) {
                 v[ra][cb] = x + pad;
             }
         __syncthreads();
-        PSTAMP(1);
         gj_wg128(v, D, tid, gjrc, pivs);
-        PSTAMP(2);
         if (tid < 64) {
             double lp = 0.0;
             for (int k = tid; k < D; k += 64) {
@@ -908,7 +854,6 @@ __global__ void __launch_bounds__(256) k_prep_big(BigPrepArgs a) {
         }
         __syncthreads();
     }
-    PSTAMP(1);
     if (tid < BDP) {
         g[L.oqr + tid] = qbar[tid]; g[L.oqr + BDP + tid] = rbar[tid];
         double s = 0.0;        // L0 m0: the Constant mean parent of X_0 through its Constant precision
@@ -927,7 +872,6 @@ __global__ void __launch_bounds__(256) k_prep_big(BigPrepArgs a) {
     mm128(wave, lane, [&](int l, int k) { return dense ? RC_at(l, k) : C_at(l, k) * rbar[l]; }, [&](int k, int j) { return Pm[j * BLD + k]; },
           [&](int l, int j, double v) { g[L.oGp + pos_perm(j, l, BDS)] = (j < D && l < K) ? v : 0.0; });
     __syncthreads();
-    PSTAMP(3);
     // warm-up lengths: powers of F, and of B^T (inf-norm of powers of B^T = 1-norm of powers of B)
     STAGE_LOOP Pm[(idx >> 7) * BLD + (idx & 127)] = S1[idx];
     __syncthreads();
@@ -941,14 +885,6 @@ __global__ void __launch_bounds__(256) k_prep_big(BigPrepArgs a) {
     __syncthreads();
     Jw = warmup128(Pm, tid, rowp);
     if (tid == 0) a.warm[n * 2 + 1] = Jw;
-#ifdef PREP_STAMP
-    PSTAMP(4);
-    if (blockIdx.x == 100 && tid == 0)
-        printf("first product: from the staged operands to its last store %llu (A operands %llu | B operands, waits %llu | 16 chains of 32 MFMAs %llu | stores %llu)\n", ps_acc[5], ps_mm[0], ps_mm[1], ps_mm[2], ps_mm[3]);
-    if (blockIdx.x == 100 && tid == 0)
-        printf("k_prep_big: moments (2 products) %llu | tiles in and out of the three inversions %llu | the three inversions %llu | gains (3 products) %llu | warm-up bounds (10 squarings) %llu\n",
-               ps_acc[0], ps_acc[1], ps_acc[2], ps_acc[3], ps_acc[4]);
-#endif
 }
 
 static constexpr size_t PREP_BIG_LDS = ((size_t)BDP * BLD + 4 * BDP + 2 * GJB_BUF + BDP) * sizeof(double);
@@ -992,12 +928,6 @@ int launch_prep_big(pyvb_lds* h) {
 #define CBP 17      // row stride of a wavefront's panel
 __global__ void __launch_bounds__(256) k_cols_big(ParamArgs a) {
     extern __shared__ double lds[];
-#ifdef COLS_STAMP       // (profiles/build_variant.sh k_big cstamp "-DCOLS_STAMP": where a workgroup's time goes, shader-clock ticks)
-    unsigned long long cs_t = __builtin_amdgcn_s_memtime(), cs_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#define CSTAMP(i) do { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); cs_acc[i] += t_ - cs_t; cs_t = t_; } while (0)
-#else
-#define CSTAMP(i) do { } while (0)
-#endif
     double* Gl = lds;                       // [128][128] zero padded, zero diagonal
     double* plp = Gl + BDP * BDP;           // [4 wavefronts][128 columns] sums of log precision
     double* pkn = plp + 4 * BDP;            // [4][128] numbers of known entries
@@ -1027,7 +957,6 @@ __global__ void __launch_bounds__(256) k_cols_big(ParamArgs a) {
     if (tid < BDP) gd[tid] = tid < D ? G[(size_t)tid * D + tid] : 0.0;
     for (int idx = tid; idx < 8 * BDP; idx += 256) plp[idx] = 0.0;          // plp and pkn: a wavefront without rows leaves zeros
     __syncthreads();
-    CSTAMP(0);
     const bool work = 32 * wave < rows;     // this wavefront has rows at all (K may be small)
     const int nbl = (D + 15) >> 4;          // column blocks in use
     // this lane's eight rows: (mm, e) -> 32 wave + 16 mm + 4 e + q
@@ -1139,7 +1068,6 @@ __global__ void __launch_bounds__(256) k_cols_big(ParamArgs a) {
     };
     if (work) {
         full_product();
-        CSTAMP(1);
         // ---- the pass, block by block
         const int I0 = a.c0 >> 4, I1 = (a.c1 + 15) >> 4;
         // what a block needs from memory (its entries of the matrix, of H, of the column priors, the known values) is requested
@@ -1202,7 +1130,6 @@ __global__ void __launch_bounds__(256) k_cols_big(ParamArgs a) {
             lps += __shfl_xor(lps, 16, 64); lps += __shfl_xor(lps, 32, 64);
             nks += __shfl_xor(nks, 16, 64); nks += __shfl_xor(nks, 32, 64);
             if (q == 0 && incol) { plp[wave * BDP + col] = lps; pkn[wave * BDP + col] = nks; }
-            CSTAMP(2);
             const double* gcol = Gl + (size_t)(16 * I) * BDP;       // row 16 I + j: column (col) in even rows, (col ^ 16) in odd ones
             const int j0 = (a.c0 > 16 * I) ? a.c0 - 16 * I : 0;
             int j1 = a.c1 - 16 * I; if (j1 > 16) j1 = 16; if (j1 > D - 16 * I) j1 = D - 16 * I;
@@ -1234,7 +1161,6 @@ __global__ void __launch_bounds__(256) k_cols_big(ParamArgs a) {
 #pragma unroll
                     for (int e = 0; e < 4; ++e) Sc[mm][e] = __builtin_fma(db[mm][e], gjc, Sc[mm][e]);
             }
-            CSTAMP(3);
             d4 dp[2];
 #pragma unroll
             for (int mm = 0; mm < 2; ++mm) dp[mm] = Mc[mm] - Mo[mm];
@@ -1254,7 +1180,6 @@ __global__ void __launch_bounds__(256) k_cols_big(ParamArgs a) {
             load_raw(I + 1 < nbl ? I + 1 : I);
             __builtin_amdgcn_sched_barrier(0);
             rank16(dp, I, I, I + 1);        // the blocks still to come
-            CSTAMP(4);
         }
     }
     __syncthreads();
@@ -1267,9 +1192,7 @@ __global__ void __launch_bounds__(256) k_cols_big(ParamArgs a) {
         // res[k] = 1/2 own[k] + 1/2 (sum_ij M[k,i] G[i,j] M[k,j] + sum_i var_i[k] G[i,i]) - sum_i H[k,i] M[k,i]   (node.py:260-271)
         // S is formed afresh from the new matrix (behind the barrier above: this wavefront's own stores): the same sums whether the
         // columns were updated in this launch or in one before it
-        CSTAMP(5);
         if (work && a.c0 < a.c1) full_product();
-        CSTAMP(6);
         double rr[2][4];
 #pragma unroll
         for (int mm = 0; mm < 2; ++mm)
@@ -1321,12 +1244,6 @@ __global__ void __launch_bounds__(256) k_cols_big(ParamArgs a) {
             }
         }
     }
-#ifdef COLS_STAMP
-    CSTAMP(7);
-    if (blockIdx.x == 100 && tid == 0)
-        printf("k_cols_big which %d: G to LDS %llu | M G_off %llu | block setup (loads, 1/x, log) %llu | 16 columns %llu | panel update %llu | to the barrier %llu | M G_off again %llu | residual %llu\n",
-               WHICH, cs_acc[0], cs_acc[1], cs_acc[2], cs_acc[3], cs_acc[4], cs_acc[5], cs_acc[6], cs_acc[7]);
-#endif
 }
 
 static constexpr size_t COLS_BIG_LDS = ((size_t)BDP * BDP + 9 * BDP + 8 + 4 * 32 * CBP) * sizeof(double);

@@ -12,7 +12,6 @@
 // X^T Z, so the statistics take it straight from registers.
 // Small single-workgroup kernels do the q x q / d-vector work (W columns, Sigma_z, Mu, Beta, lower bound).
 #include "pca.h"
-#include <cstdlib>
 #include <type_traits>
 
 #define MFMA(a, b, c) __builtin_amdgcn_mfma_f64_16x16x4f64((a), (b), (c), 0, 0, 0)
@@ -111,9 +110,7 @@ __global__ void __launch_bounds__(256) k_pca_pass1(PcaArgs a) {
 // wavefronts launched ~1000 chunks apart, 128 B per row each).  About 100 registers: four wavefronts per SIMD.
 // ---------------------------------------------------------------------------------------------------
 #define P2T 2           // tiles per wavefront
-#ifndef P2_OCC
 #define P2_OCC (QT == 1 ? (PIN ? 3 : 4) : 2)     // workgroups per CU the register budget is set for
-#endif
 // PIN: some rows still carry their initial mean at all entries and take their observations at their first update
 // (pyvb_pca_set_unpinned_rows); its own instantiation, so that the usual one keeps its register budget
 template <int QT, bool PIN>
@@ -205,14 +202,9 @@ __global__ void __launch_bounds__(256, P2_OCC) k_pca_pass2(PcaArgs a) {
             }
             // whole rows go back, known entries with their own bits: full-line writes (a masked 8-byte store is a
             // read-modify-write at the memory side, measured 0.3 ms slower per pass)
-#ifndef P2_GROUP
 #define P2_GROUP 2
-#endif
-            bool st = rowupd;
-            if (P2_GROUP > 0) {
-                const unsigned long long b = __ballot(any);
-                st = ((b >> (lane & ~(P2_GROUP - 1))) & ((1ull << P2_GROUP) - 1)) != 0;
-            }
+            const unsigned long long b = __ballot(any);
+            const bool st = ((b >> (lane & ~(P2_GROUP - 1))) & ((1ull << P2_GROUP) - 1)) != 0;
             if (st) *reinterpret_cast<d2*>(Xc + xoff[r]) = v;
 #pragma unroll
             for (int p = 0; p < P2T; ++p) {
@@ -296,15 +288,6 @@ __global__ void __launch_bounds__(256, P2_OCC) k_pca_pass2(PcaArgs a) {
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 #define P12_XS 36       // row stride (doubles) of the transposition buffer: 32 columns + pad, 32-byte aligned rows
-// -DP12_STAMP (profiles/pca_stamps.py builds it as a variant library): wavefronts 0 and 4 of every workgroup add up, stage by
-// stage, the time they spend (s_memtime ticks: core clock on this part) -- [s0, s1, wait at barrier A, s2, stage 3, stage 4 + fetch, wait at
-// barrier B, whole kernel, steps]; pyvb_pca_debug_stamps copies the table out.  Not in the shipped library.
-#ifdef P12_STAMP
-__device__ unsigned long long g_p12_stamp[4096 * 2 * 12];
-#define STAMP(i) do { const unsigned long long _t = __builtin_amdgcn_s_memtime(); st_acc[i] += _t - st_last; st_last = _t; } while (0)
-#else
-#define STAMP(i) do { } while (0)
-#endif
 // LAZY (round 4): the imputed entries are NOT written back.  They are a function of what is stored anyway -- x_nk = (<W> z_n + <Mu>)_k
 // with the z_n this sweep stores and the parameters it runs with -- so the next sweep recomputes them where it reads the row
 // (stage 0 below: the row's previous z from Z, the previous parameters from W_x / Mu_x, the same transposed product as stage 3,
@@ -432,10 +415,6 @@ __global__ void __launch_bounds__(512) k_pca_pass12(PcaArgs a) {
 #pragma unroll
         for (int rt = 0; rt < RT; ++rt) zfetch(16u * rt < nrows ? 16u * rt : 0u, zq[rt]);
     }
-#ifdef P12_STAMP
-    unsigned long long st_acc[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, st_last = __builtin_amdgcn_s_memtime();
-    const unsigned long long st_begin = st_last;
-#endif
     // A step takes RT tiles through the four stages between two barriers.  Measured with cycle stamps per tile (one tile per step, d = 256,
     // q = 16): stage 1 560, stage 2 790 (four of the eight wavefronts), stage 3 1900-2300, stage 4 1100-1500 cycles, against 3 x 1024
     // for the 48 MFMAs the two wavefronts of a SIMD issue: the sweep runs at the pace of its dependent chains (MFMA -> select -> LDS
@@ -530,7 +509,6 @@ __global__ void __launch_bounds__(512) k_pca_pass12(PcaArgs a) {
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        STAMP(4);
 #pragma unroll
         for (int rt = 0; rt < RT; ++rt) {
             const unsigned n0 = nbase + 16 * rt;
@@ -569,7 +547,6 @@ __global__ void __launch_bounds__(512) k_pca_pass12(PcaArgs a) {
                     }
             }
         }
-        STAMP(5);
     };
     // prologue: Z of the first step
     if (LAZY) s0(0u, std::integral_constant<int, 0>{});
@@ -577,22 +554,16 @@ __global__ void __launch_bounds__(512) k_pca_pass12(PcaArgs a) {
     lds_barrier();
     s2(0u, 0);
     lds_barrier();
-    STAMP(9);
     int zsel = 0;
     for (unsigned base = 0; base < nrows; base += 16 * PF) {
         {   // step at base (register sets 0..RT-1); the next one, if any, at base + 16 RT (sets RT..)
             const bool more = base + 16 * RT < nrows;
             if (LAZY && more) s0(base + 16 * RT, std::integral_constant<int, RT>{});
-            STAMP(0);
             if (more) s1(base + 16 * RT, std::integral_constant<int, RT>{});
-            STAMP(1);
             lds_barrier();
-            STAMP(2);
             if (more) s2(base + 16 * RT, zsel ^ 1);
-            STAMP(3);
             back(base, std::integral_constant<int, 0>{}, zsel);
             lds_barrier();
-            STAMP(6);
             zsel ^= 1;
             if (!more) break;
         }
@@ -600,28 +571,15 @@ __global__ void __launch_bounds__(512) k_pca_pass12(PcaArgs a) {
             const unsigned b2 = base + 16 * RT;
             const bool more = b2 + 16 * RT < nrows;
             if (LAZY && more) s0(b2 + 16 * RT, std::integral_constant<int, 0>{});
-            STAMP(0);
             if (more) s1(b2 + 16 * RT, std::integral_constant<int, 0>{});
-            STAMP(1);
             lds_barrier();
-            STAMP(2);
             if (more) s2(b2 + 16 * RT, zsel ^ 1);
-            STAMP(3);
             back(b2, std::integral_constant<int, RT>{}, zsel);
             lds_barrier();
-            STAMP(6);
             zsel ^= 1;
             if (!more) break;
         }
     }
-#ifdef P12_STAMP
-    if ((wave == 0 || wave == 4) && lane == 0 && blockIdx.x < 4096) {
-        unsigned long long* o = g_p12_stamp + ((size_t)blockIdx.x * 2 + (wave ? 1 : 0)) * 12;
-        for (int i = 0; i < 10; ++i) o[i] = st_acc[i];
-        o[10] = __builtin_amdgcn_s_memtime() - st_begin;
-        o[11] = (nrows + 16 * RT - 1) / (16 * RT);
-    }
-#endif
     // ---- partial sums of this chunk, laid out as k_pca_pass2's
     double* P = a.part + (size_t)blockIdx.x * (a.SL.total + a.DT);
 #pragma unroll
@@ -692,9 +650,6 @@ __device__ __forceinline__ void wave_lds_sync() {
     asm volatile("" ::: "memory");
 }
 #define PP_NW 8
-#ifndef PP_ROT
-#define PP_ROT 0
-#endif
 // FULL: all 16 column tiles exist (d > 240): no bounds tests on them, so that a tile's phase is one basic block for the scheduler
 template <bool FULL>
 __global__ void __launch_bounds__(64 * PP_NW) k_pca_pairs(PcaArgs a) {
@@ -715,10 +670,6 @@ __global__ void __launch_bounds__(64 * PP_NW) k_pca_pairs(PcaArgs a) {
     double* const xch = g0L + 32 + (size_t)PP_NW * (16 * P12_XS);               // [wave][4][64] the partial of Z a wavefront hands to its partner
     int* const flags = reinterpret_cast<int*>(xch + (size_t)PP_NW * 256);        // [wave][2]: tiles whose partial is ready / whose partner partial has been read
     if (tid < 2 * PP_NW) flags[tid] = 0;
-#ifdef P12_STAMP
-    const unsigned long long st_t0 = __builtin_amdgcn_s_memtime(), st_r0 = __builtin_amdgcn_s_memrealtime();
-    unsigned long long st_acc[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, st_last = st_t0;
-#endif
     for (int i = tid; i < DT * 256; i += 64 * PP_NW) {
         gzL[i] = a.Gz[i];
         const int j = i >> 8, s4 = (i >> 6) & 3, ln = i & 63, cc = ln & 15, qq = ln >> 4;
@@ -757,12 +708,8 @@ __global__ void __launch_bounds__(64 * PP_NW) k_pca_pairs(PcaArgs a) {
 
     // ---- the stream of X: position pos of a tile = block pos % 8 (0..7 phase A, 8..15 phase C); the set of position pos is pos % 4
     d4 rx[RING][2]; unsigned rm[RING][2];
-    // workgroup b walks its chunk from tile (rot) on, round: the chunks lie a fixed 8 MB apart, and 256 workgroups in step at that
-    // stride would keep asking the same few HBM channels
-    const unsigned rot = ntiles ? (unsigned)((blockIdx.x * PP_ROT) % ntiles) : 0u;
-    auto TI = [&](unsigned tl) { const unsigned u = tl + rot; return u >= ntiles ? u - ntiles : u; };
     auto fetch = [&](d4 (&x)[2], unsigned (&m)[2], unsigned tile, int b) {
-        const unsigned rw = 16u * TI(tile) + c;
+        const unsigned rw = 16u * tile + c;
         const unsigned row = rw < nrows ? rw : nrows - 1;
 #pragma unroll
         for (int jj = 0; jj < 2; ++jj) {
@@ -773,7 +720,7 @@ __global__ void __launch_bounds__(64 * PP_NW) k_pca_pairs(PcaArgs a) {
         }
     };
     auto zfetch = [&](double (&z)[QS], unsigned tile) {
-        const unsigned rw = 16u * TI(tile) + c;
+        const unsigned rw = 16u * tile + c;
         const unsigned row = rw < nrows ? rw : nrows - 1;
 #pragma unroll
         for (int s4 = 0; s4 < QS; ++s4) z[s4] = Zc[(size_t)row * QP + 4 * s4 + qk];
@@ -789,7 +736,7 @@ __global__ void __launch_bounds__(64 * PP_NW) k_pca_pairs(PcaArgs a) {
         for (int u = 0; u < AHEAD; ++u) fetch(rx[u], rm[u], t, u);
     }
     for (; t < ntiles; t += PP_NW / 2) {
-        const unsigned n0 = 16u * TI(t), rowl = n0 + c;
+        const unsigned n0 = 16u * t, rowl = n0 + c;
         const unsigned tnext = (t + PP_NW / 2 < ntiles) ? t + PP_NW / 2 : t;
         const bool rowv = rowl >= vlo && rowl < vhi;
         const bool rowupd = rowl < nrows && rowl >= lo && rowl < hi;
@@ -882,13 +829,11 @@ __global__ void __launch_bounds__(64 * PP_NW) k_pca_pairs(PcaArgs a) {
             if (pos == NB - 1) {
                 // ---- the pair's hand-over: my partial into my slot (once the partner has read the one before), flag up; the partner's
                 ++seq;
-                STAMP(0);
                 while (__hip_atomic_load(&flags[2 * (wave ^ 1) + 1], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) < seq - 1) __builtin_amdgcn_s_sleep(1);
 #pragma unroll
                 for (int r = 0; r < 4; ++r) xch[(size_t)wave * 256 + r * 64 + lane] = zacc[r];
                 __hip_atomic_store(&flags[2 * wave], seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
                 while (__hip_atomic_load(&flags[2 * (wave ^ 1)], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) < seq) __builtin_amdgcn_s_sleep(1);
-                STAMP(1);
                 d4 other;
 #pragma unroll
                 for (int r = 0; r < 4; ++r) other[r] = xch[(size_t)(wave ^ 1) * 256 + r * 64 + lane];
@@ -916,18 +861,9 @@ __global__ void __launch_bounds__(64 * PP_NW) k_pca_pairs(PcaArgs a) {
 #pragma unroll
                 for (int s4 = 0; s4 < QS; ++s4) za[s4] = zTw[(4 * s4 + qk) * 17 + c];
                 wave_lds_sync();                        // (z transposed shares its place with the 32-column piece of phase C)
-                STAMP(2);
             }
         }
-        STAMP(3);
     }
-#ifdef P12_STAMP
-    if (lane == 0 && wave < 2) {        // phase A | the wait for the partner | phase B | phase C | - | whole kernel in shader ticks, in 100 MHz ticks | tiles
-        unsigned long long* o = g_p12_stamp + ((size_t)blockIdx.x * 2 + wave) * 12;
-        for (int i = 0; i < 4; ++i) o[i] = st_acc[i];
-        o[10] = __builtin_amdgcn_s_memtime() - st_t0; o[9] = __builtin_amdgcn_s_memrealtime() - st_r0; o[11] = (unsigned long long)seq;
-    }
-#endif
     // ---- the wavefronts' sums into one per workgroup, in wavefront order (LDS: the tables are done with)
     __syncthreads();
     double* const red = ldsr;           // [Sxz 256 x 16 | sx 256 | Szz 16 x 16 | sz 16 | sxx]
@@ -1400,14 +1336,7 @@ template <int... MODES>
 __global__ void __launch_bounds__(256) k_pca_small(PcaArgs a) {
     __shared__ double sm[64 * 64 + 64 * 64 + 64 + 1088], red[4], wst[256 * 32];     // wst: <W> [d][q] staged by wtw_lds
     int first = 1;
-#ifdef SMALL_STAMP      // (bash profiles/build_pca_variant.sh sstamp "-DSMALL_STAMP": where the single-workgroup steps spend their microseconds)
-    unsigned long long st = __builtin_amdgcn_s_memrealtime();
-    ((first ? (void)(first = 0) : (__threadfence(), __syncthreads()), pca_small_body<MODES>(a, sm, red, wst), __syncthreads(),
-      (threadIdx.x == 0 ? (void)printf("small mode %d: %.2f us\n", MODES, (__builtin_amdgcn_s_memrealtime() - st) / 100.0) : (void)0),
-      st = __builtin_amdgcn_s_memrealtime()), ...);
-#else
     ((first ? (void)(first = 0) : (__threadfence(), __syncthreads()), pca_small_body<MODES>(a, sm, red, wst)), ...);
-#endif
 }
 
 // q_ln_det (gaussian.py:120, quirk Q1) of every X_n that has no observed entry -- a latent node with qprec = I / var_n --
@@ -1526,14 +1455,6 @@ int pca_launch_sweep(pyvb_pca* h, const PcaSweepPlan& p) {
     HIPCHK(hipGetLastError());
     return PYVB_OK;
 }
-
-#ifdef P12_STAMP
-extern "C" int pyvb_pca_debug_stamps(unsigned long long* out, int nblocks) {
-    HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpyFromSymbol(out, HIP_SYMBOL(g_p12_stamp), (size_t)nblocks * 2 * 12 * sizeof(unsigned long long)));
-    return PYVB_OK;
-}
-#endif
 
 int pca_launch_rowqld(pyvb_pca* h, double* out, int logdet) {
     PcaArgs a = pca_args(h);

@@ -40,12 +40,8 @@ struct StatsSplit {
     static constexpr int MB0 = NA / DT;                 // wave 1 needs y row tiles [MB0, KT)
 };
 
-#ifndef STATS_OCC
 #define STATS_OCC 2      // two wavefronts per SIMD run the fp64 matrix pipe faster than one (profiles/r01/microbench_f64.txt)
-#endif
-#ifndef STATS_PF
 #define STATS_PF 1      // k-steps per half of the operand ring (registers: 2 * PF * 10 doubles next to 168 of accumulators)
-#endif
 
 template <int DT, int KT, bool XX>
 __global__ void __launch_bounds__(128, STATS_OCC) k_stats(StatsArgs a) {

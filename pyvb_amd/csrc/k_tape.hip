@@ -8,16 +8,12 @@
 #include "common.h"
 #include "digamma.h"         // digamma_pos: U_DIGAMMA
 #include "tape_plan.h"          // tape.h: opcodes, record layout, the window form
-#include <cstdio>
-#include <cstdlib>
 
 #define TAPE_CTHREADS (64 * TAPE_BUNDLE)
 
 struct TapeArgs { double* arena; size_t arena_n; const int* ops; int nops; int* status; };
 
-#ifndef TAPE_THREADS
 #define TAPE_THREADS 256    // (one wavefront, 64, measured the same on the node-sized matrices of this path: the barrier per record is not what a record costs)
-#endif
 
 // `count` records starting at `recs` (global memory, or a chunk staged in LDS), interpreted by the calling workgroup.
 // WIN: every operand of every record lies in the workgroup's LDS window `win` (the offsets are window positions, tagged
@@ -354,9 +350,6 @@ static int tape_upload_windows(pyvb_graph* g, int id, const std::vector<int>& bl
     TapeWindows& W = g->tapes[id].win;
     W.drop();
     const TapePlan P = tape_plan(T.host, blocks, launches, g->arena_n);
-    if (getenv("PYVB_TAPE_STATS") && !P.blocks.empty())
-        fprintf(stderr, "tape %d: %zu records in %zu blocks -> %zu windows (%d in LDS, %ld doubles; %d bundled: %ld slots = %ld bundles), %ld device records\n",
-                id, T.host.size() / 8, P.blocks.size() / 2, P.windows.size(), P.lds_windows, P.lds_doubles, P.bundled_windows, P.slots, P.bundles, (long)(P.cops.size() / 8));
     if (!P.in_lds) return PYVB_OK;
     int rc = tape_put(W.buf, &W.ops, P.cops.data(), P.cops.size());
     if (rc == PYVB_OK) rc = tape_put(W.buf, &W.blocks, P.blocks.data(), P.blocks.size());

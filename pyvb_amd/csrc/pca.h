@@ -58,8 +58,9 @@ struct pyvb_pca {
     PcaState st;                         // what is current on the device (host.h); written by api_pca.hip only
     DeviceBuffers mem;                   // every device allocation of this handle
     double *W_x, *Mu_x;                  // [d][q], [d]: the parameters the last lazy sweep imputed with
-    bool lazy_ok;                        // PYVB_PCA_WRITEBACK=1 in the environment at creation turns the lazy sweep off (A/B measurements)
-    bool pairs;                          // the lazy sweep is k_pca_pairs, not k_pca_pass12<.., LAZY>: chosen at creation (api_pca.hip, PYVB_PCA_SWEEP)
+    int sweep;                           // PYVB_PCA_SWEEP_*: what serves the full-range sweep where it may be lazy (api_pca.hip: plan_sweep);
+                                         // chosen at creation by size, changed by pyvb_pca_set_sweep only
+    bool pairs_ready;                    // pca_prepare_pairs() has been called for this handle's device
     int nchunkB; long chunk_rowsB;       // k_pca_pairs' partition of the rows: a workgroup per CU
     pyvb_comm* comm; int rank, world;
 };

@@ -32,9 +32,7 @@ enum {
 #define TAPE_CHUNK 512          // records staged at a time
 #define TAPE_LDS_CAP 12288      // doubles of arena a block may keep in LDS (96 KB)
 #define TAPE_MAX_SEGS 4096
-#ifndef TAPE_BUNDLE
 #define TAPE_BUNDLE 8           // records per bundle = wavefronts of a k_tape_cached workgroup
-#endif
 #define TAPE_BUNDLE_MAX 2048    // records scheduled together (the dependency search is quadratic)
 
 // The window form as the device reads it.  Block table: {first window, number of windows} per block, two ints.

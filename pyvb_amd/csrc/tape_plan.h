@@ -70,7 +70,7 @@ struct TapePlan {
     std::vector<TapeSegment> segs;
     std::vector<size_t> lds_bytes;      // per launch: dynamic LDS of its workgroups (window, padding, TAPE_CHUNK staged records)
     std::vector<int> width;             // per launch: records of a bundle = wavefronts of a workgroup
-    int lds_windows = 0, bundled_windows = 0;           // what PYVB_TAPE_STATS prints
+    int lds_windows = 0, bundled_windows = 0;           // counts of the plan, for who asks the planner (tests/c/tape_plan_driver.cpp); the library does not read them
     long lds_doubles = 0, slots = 0, bundles = 0;
 };
 

@@ -110,6 +110,20 @@ class PCABatch(object):
         C.check(C.lib.pyvb_pca_set_bound_mode(self._h, C.BOUND_MODES[mode]))
         self.bound = mode
 
+    @property
+    def sweep(self):
+        """Which kernel serves the full-range sweep: "store", "columns" or "pairs" (pyvb_pca_get_sweep)."""
+        k = C.ctypes.c_int(0)
+        C.check(C.lib.pyvb_pca_get_sweep(self._h, C.ctypes.byref(k)))
+        return {v: n for n, v in C.PCA_SWEEPS.items()}[k.value]
+
+    def set_sweep(self, kind):
+        """Put a chosen sweep kernel on this handle, by name or by its PYVB_PCA_SWEEP_* number; creation picks one by size,
+        this is for tests and A/B runs (results do not depend on it beyond rounding)."""
+        if isinstance(kind, str) and kind not in C.PCA_SWEEPS:
+            raise ValueError("sweep must be 'store', 'columns' or 'pairs', not %r" % (kind,))
+        C.check(C.lib.pyvb_pca_set_sweep(self._h, int(C.PCA_SWEEPS.get(kind, kind))))
+
     def update_W(self):
         C.check(C.lib.pyvb_pca_update_W(self._h))
 

@@ -540,7 +540,7 @@ def pca_handle_parts(b):
 def pca_trace(m, N, iters=2, stage_reads=True, bounds=(), parts=None):
     """The stages of tests/test_pca_gpu.py: test_stagewise_vs_oracle on m (OraclePCA or a PCABatch).  stage_reads=False reads
     only at the end of each iteration: a read between update_Z and update_X(1, N) makes a handle carry the Z update out on its
-    own, and the fused sweep over the rows (pyvb_amd/csrc/k_pca.hip: PYVB_PCA_SWEEP = columns / pairs) is then never run."""
+    own, and the fused sweep over the rows (pyvb_amd/csrc/k_pca.hip: the "columns" / "pairs" kinds of PCABatch.set_sweep) is then never run."""
     for it in range(iters):
         m.update_W()
         if stage_reads:

@@ -47,6 +47,29 @@ def test_library_has_no_unresolved_symbols_of_its_own():
     assert not bad, bad
 
 
+def test_library_reads_no_environment_and_prints_nothing():
+    """What a handle does is decided by its arguments and setters alone: the library imports neither a reader of the process
+    environment nor a stdio output function (vsnprintf, for pyvb_last_error, writes into memory)."""
+    import subprocess
+    from pyvb_amd import _capi
+    out = subprocess.run(["nm", "-D", "--undefined-only", _capi.LIB_PATH], capture_output=True, text=True, check=True).stdout
+    imported = {l.split()[-1].split("@")[0] for l in out.splitlines() if l.split()}
+    assert "hipMalloc" in imported            # nm did list the imports
+    bad = sorted(imported & {"getenv", "secure_getenv", "printf", "fprintf", "puts", "fputs", "fwrite"})
+    assert not bad, bad
+
+
+def test_pca_sweep_entry_points_check_their_handle_without_gpu():
+    from pyvb_amd import _capi
+    assert _capi.lib.pyvb_version() >= 103
+    assert (_capi.PCA_SWEEP_STORE, _capi.PCA_SWEEP_COLUMNS, _capi.PCA_SWEEP_PAIRS) == (0, 1, 2)
+    k = ctypes.c_int(-1)
+    assert _capi.lib.pyvb_pca_set_sweep(None, _capi.PCA_SWEEP_COLUMNS) == _capi.E_ARG
+    assert b"handle is NULL" in _capi.lib.pyvb_last_error()
+    assert _capi.lib.pyvb_pca_get_sweep(None, ctypes.byref(k)) == _capi.E_ARG
+    assert k.value == -1
+
+
 def test_shipped_library_is_the_build_of_the_sources_beside_it():
     """The .so is not in git (it travels with the push): its embedded source hash must equal the hash of pyvb_amd/csrc as
     it stands, so a stale library cannot pass for the sources."""

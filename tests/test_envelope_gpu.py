@@ -102,18 +102,18 @@ def test_warmup_lengths_are_sufficient_and_not_wasteful(name):
 
 @pytest.mark.parametrize("N,d,q,sweep", [(300, 20, 4, None), (77, 33, 17, None), (17, 250, 31, None),
                                          (600, 250, 16, "columns"), (600, 250, 16, "pairs")])
-def test_pca_envelope(N, d, q, sweep, monkeypatch):
+def test_pca_envelope(N, d, q, sweep):
     """Stage by stage as tests/test_pca_gpu.py: test_stagewise_vs_oracle; where the sweep kernel is chosen, also with reads at the
     end of each iteration only, which is what lets the fused sweep over the rows run (extended_ref.pca_trace)."""
     from pyvb_amd.pca import PCABatch
-    if sweep is not None:
-        monkeypatch.setenv("PYVB_PCA_SWEEP", sweep)
     n, ext, e64, _ = E.pca_reference(N, d, q)
     assert max(e64.values()) <= E.CAP
     init, pri = E.pca_problem(N, d, q)
     over = []
     for stage_reads in ([True] if sweep is None else [True, False]):
         b = PCABatch.from_problem(init, pri)
+        if sweep is not None:
+            b.set_sweep(sweep)
         rows = []
         for key, arr in E.pca_trace(b, N, stage_reads=stage_reads):
             assert np.all(np.isfinite(arr)), key
@@ -151,17 +151,17 @@ def test_lds_bound_envelope(name, mode):
 @pytest.mark.parametrize("mode", E.BOUND_MODES)
 @pytest.mark.parametrize("N,d,q,sweep", [(300, 20, 4, None), (77, 33, 17, None), (17, 250, 31, None),
                                          (600, 250, 16, "columns"), (600, 250, 16, "pairs"), E.PCA_SMALL + (None,)])
-def test_pca_bound_envelope(N, d, q, sweep, mode, monkeypatch):
+def test_pca_bound_envelope(N, d, q, sweep, mode):
     """The five parts of the VB-PCA bound after each iteration.  Where the sweep kernel is chosen the handle is read at the end of
     an iteration only, so that the chosen sweep runs (test_pca_envelope); the 1 x 1 x 1 handle has beta_a = 0.501, which takes
     the host's digamma through its recurrence."""
     from pyvb_amd.pca import PCABatch
-    if sweep is not None:
-        monkeypatch.setenv("PYVB_PCA_SWEEP", sweep)
     n = E.pca_reference(N, d, q)[0]
     ref = E.pca_bound_reference(N, d, q)
     init, pri = E.pca_problem(N, d, q)
     b = PCABatch.from_problem(init, pri)
+    if sweep is not None:
+        b.set_sweep(sweep)
     if mode != "reference":
         b.set_bound_mode(mode)
     rows = []

@@ -57,14 +57,14 @@ def test_golden_fixtures(path):
 
 @pytest.mark.parametrize("sweep", ["pairs"])
 @pytest.mark.parametrize("path", [f for f in FILES if "default_init" not in f], ids=lambda p: os.path.basename(p)[4:-4])
-def test_golden_fixtures_through_the_pair_owning_sweep(path, sweep, monkeypatch):
-    """k_pca_pairs (a pair of wavefronts owns whole rows, half the columns each), chosen with PYVB_PCA_SWEEP at handle creation
-    (pyvb_amd/csrc/k_pca.hip) for problems the size rule would give to the column-owning sweep: it has to give the reference's
+def test_golden_fixtures_through_the_pair_owning_sweep(path, sweep):
+    """k_pca_pairs (a pair of wavefronts owns whole rows, half the columns each), put on the new handle with set_sweep
+    (pyvb_pca_set_sweep) for problems the size rule would give to the column-owning sweep: it has to give the reference's
     numbers all the same."""
     from pyvb_amd.pca import PCABatch
-    monkeypatch.setenv("PYVB_PCA_SWEEP", sweep)
     N, d, q, init, pri, z = _load(path)
     b = PCABatch.from_problem(init, pri)
+    b.set_sweep(sweep)
     for it in range(1, int(max(z["iters"])) + 1):
         b.iterate(1)
         if it in z["iters"]:
@@ -79,11 +79,11 @@ def test_golden_fixtures_through_the_pair_owning_sweep(path, sweep, monkeypatch)
 
 
 @pytest.mark.parametrize("sweep", ["columns", "pairs"])
-def test_imputed_entries_are_recomputed_not_stored(sweep, monkeypatch):
+def test_imputed_entries_are_recomputed_not_stored(sweep):
     """Round 4: the sweep of an iteration leaves the imputed entries of X unstored (they are <W> z_n + <Mu> of what IS stored; the
     next sweep recomputes them, pyvb_pca_get_state and every other reader has them put into X first: pca_materialize_x).  A run
     that is interrupted by a read of the state and by an evaluation of the bound ends bitwise where an uninterrupted one
-    ends, and both agree with a handle that stores the entries (PYVB_PCA_WRITEBACK=1) to rounding.  (Partial row updates and
+    ends, and both agree with a handle that stores the entries (set_sweep("store")) to rounding.  (Partial row updates and
     Z updates in between, without a read: test_lazy_state_transitions_without_a_read.)"""
     import importlib.util
     spec = importlib.util.spec_from_file_location("make_golden", os.path.join(HERE, "golden", "make_golden.py"))
@@ -91,9 +91,9 @@ def test_imputed_entries_are_recomputed_not_stored(sweep, monkeypatch):
     from pyvb_amd.pca import PCABatch
     N, d, q = 3000, 250, 16
     init, pri = G.pca_problem(N, d, q, seed=77)
-    monkeypatch.setenv("PYVB_PCA_SWEEP", sweep)
-    a = PCABatch.from_problem(init, pri); a.iterate(5); sa = a.get_state(); ea = a.elbo(); a.close()
+    a = PCABatch.from_problem(init, pri); a.set_sweep(sweep); a.iterate(5); sa = a.get_state(); ea = a.elbo(); a.close()
     b = PCABatch.from_problem(init, pri)
+    b.set_sweep(sweep)
     b.iterate(2)
     mid = b.get_state()                                 # materialises X
     assert np.isfinite(mid["X"]).all()
@@ -104,8 +104,7 @@ def test_imputed_entries_are_recomputed_not_stored(sweep, monkeypatch):
     for k in ("X", "Z", "W_mean", "Mu_mean", "beta_b"):
         assert np.array_equal(sa[k], sb[k]), k
     assert np.array_equal(ea, eb)
-    monkeypatch.setenv("PYVB_PCA_WRITEBACK", "1")
-    c = PCABatch.from_problem(init, pri); c.iterate(5); sc = c.get_state(); ec = c.elbo(); c.close()
+    c = PCABatch.from_problem(init, pri); c.set_sweep("store"); c.iterate(5); sc = c.get_state(); ec = c.elbo(); c.close()
     for k in ("X", "Z", "W_mean", "Mu_mean"):
         _close(sa[k], sc[k], "lazy vs stored: " + k)
     assert np.all(np.abs(ea - ec) <= 1e-10 * np.abs(ec).sum())
@@ -117,7 +116,7 @@ def test_imputed_entries_are_recomputed_not_stored(sweep, monkeypatch):
     assert np.all(np.abs(ea - ref) <= RTOL * np.abs(ref).sum())
 
 
-def test_the_sweep_a_long_problem_gets_by_default_with_fewer_than_sixteen_latents(monkeypatch):
+def test_the_sweep_a_long_problem_gets_by_default_with_fewer_than_sixteen_latents():
     """From 512 rows per CU on (and d > 192) a handle takes the pair-owning sweep without being asked (api_pca.hip); here with q = 7
     and d = 250 -- padded latent indices and a padded column tile in the kernel that otherwise only meets q = 16 at that size --
     against the oracle and against the column-owning sweep on the same problem."""
@@ -127,10 +126,10 @@ def test_the_sweep_a_long_problem_gets_by_default_with_fewer_than_sixteen_latent
     from pyvb_amd.pca import PCABatch
     N, d, q = 140000, 250, 7
     init, pri = G.pca_problem(N, d, q, seed=5)
-    monkeypatch.delenv("PYVB_PCA_SWEEP", raising=False)
-    a = PCABatch.from_problem(init, pri); a.iterate(3); sa = a.get_state(); ea = a.elbo(); a.close()
-    monkeypatch.setenv("PYVB_PCA_SWEEP", "columns")
-    c = PCABatch.from_problem(init, pri); c.iterate(3); sc = c.get_state(); ec = c.elbo(); c.close()
+    a = PCABatch.from_problem(init, pri)
+    assert a.sweep == "pairs"
+    a.iterate(3); sa = a.get_state(); ea = a.elbo(); a.close()
+    c = PCABatch.from_problem(init, pri); c.set_sweep("columns"); c.iterate(3); sc = c.get_state(); ec = c.elbo(); c.close()
     st = P.make_state(init, pri, N, d, q)
     for _ in range(3):
         ref = P.iterate(st, pri)
@@ -142,7 +141,7 @@ def test_the_sweep_a_long_problem_gets_by_default_with_fewer_than_sixteen_latent
 
 @pytest.mark.parametrize("case", ["a", "b", "c"])
 @pytest.mark.parametrize("sweep", ["columns", "pairs"])
-def test_lazy_state_transitions_without_a_read(sweep, case, monkeypatch):
+def test_lazy_state_transitions_without_a_read(sweep, case):
     """Stage-wise calls that meet a handle whose imputed entries are not in X, with NO read in between: whatever reads rows of X
     outside a sweep (the X_0 step reads row 0) must have them stored first.  One get_state() + elbo() at the end, against the same
     calls on the oracle.  q <= 16, no pinned rows, entries of row 0 missing (pca_problem masks at random; asserted)."""
@@ -154,9 +153,9 @@ def test_lazy_state_transitions_without_a_read(sweep, case, monkeypatch):
     init, pri = G.pca_problem(N, d, q, seed=4242)
     obs0 = np.asarray(init["obs"], dtype=bool)[0]
     assert (~obs0).any() and obs0.any(), "row 0 must be partially observed"
-    monkeypatch.setenv("PYVB_PCA_SWEEP", sweep)
     st = P.make_state(init, pri, N, d, q)
     b = PCABatch.from_problem(init, pri)
+    b.set_sweep(sweep)
 
     def iterate(k):
         for _ in range(k):
@@ -181,6 +180,76 @@ def test_lazy_state_transitions_without_a_read(sweep, case, monkeypatch):
     ref, got = P.elbo_parts(st, pri), b.elbo()
     assert np.all(np.abs(got - ref) <= RTOL * np.abs(ref).sum()), (got, ref)
     b.close()
+
+
+def test_sweep_choice_ignores_the_environment(monkeypatch):
+    """The library reads no environment: with the two variables that used to choose the sweep set, a new handle has the kind its
+    size gives it and computes bitwise what a handle made without them computes.  The kind is changed by set_sweep alone, which
+    refuses kinds it does not know."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("make_golden", os.path.join(HERE, "golden", "make_golden.py"))
+    G = importlib.util.module_from_spec(spec); spec.loader.exec_module(G)
+    from pyvb_amd import _capi
+    from pyvb_amd.pca import PCABatch
+    N, d, q = 600, 250, 16
+    init, pri = G.pca_problem(N, d, q, seed=4242)
+    monkeypatch.delenv("PYVB_PCA_SWEEP", raising=False)
+    monkeypatch.delenv("PYVB_PCA_WRITEBACK", raising=False)
+    a = PCABatch.from_problem(init, pri)
+    assert a.sweep == "columns"
+    a.iterate(3); sa = a.get_state(); ea = a.elbo(); a.close()
+    monkeypatch.setenv("PYVB_PCA_SWEEP", "pairs")
+    monkeypatch.setenv("PYVB_PCA_WRITEBACK", "1")
+    b = PCABatch.from_problem(init, pri)
+    assert b.sweep == "columns"
+    b.iterate(3); sb = b.get_state(); eb = b.elbo()
+    for k in sa:
+        assert np.array_equal(sa[k], sb[k]), k
+    assert np.array_equal(ea, eb)
+    for kind in (-1, 3, 7):
+        with pytest.raises(_capi.PyvbHipError) as err:
+            b.set_sweep(kind)
+        assert err.value.code == _capi.E_ARG
+        assert b.sweep == "columns"
+    with pytest.raises(ValueError):
+        b.set_sweep("rows")
+    b.close()
+
+
+@pytest.mark.parametrize("N,d,q", [(600, 250, 16), (330, 200, 5)])
+def test_sweep_can_change_between_iterations(N, d, q):
+    """pyvb_pca_set_sweep between iterations, with no read in between: columns -> pairs -> store -> pairs -> columns, an iteration
+    under each, so that every kernel meets the unstored entries (or the stored ones) and the partials' partition another one left.
+    d = 250 is k_pca_pairs<FULL>; d = 200, q = 5 the other instantiation (13 column tiles, padded latent indices).  One read at
+    the end, against five iterations of the oracle and against a handle that stays with the column-owning sweep; tolerances of
+    test_imputed_entries_are_recomputed_not_stored, which compares the same paths."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("make_golden", os.path.join(HERE, "golden", "make_golden.py"))
+    G = importlib.util.module_from_spec(spec); spec.loader.exec_module(G)
+    from pyvb_amd.pca import PCABatch
+    init, pri = G.pca_problem(N, d, q, seed=31 + d)
+    b = PCABatch.from_problem(init, pri)
+    for kind in ("columns", "pairs", "store", "pairs", "columns"):
+        b.set_sweep(kind)
+        assert b.sweep == kind
+        b.iterate(1)
+    sb = b.get_state(); eb = b.elbo(); b.close()
+    c = PCABatch.from_problem(init, pri)
+    assert c.sweep == "columns"
+    c.iterate(5); sc = c.get_state(); ec = c.elbo(); c.close()
+    st = P.make_state(init, pri, N, d, q)
+    for _ in range(5):
+        ref = P.iterate(st, pri)
+    keys = ("W_mean", "W_var", "Z", "Z_cov", "X", "Mu_mean", "Mu_var", "beta_a", "beta_b")
+    rel = lambda a, b: np.abs(np.asarray(a, dtype=float) - b).max() / np.abs(b).max()
+    print("switched sweeps (%d, %d, %d): worst rel err vs oracle %.2e, vs the column-owning sweep %.2e; bound vs oracle %.2e, vs columns %.2e of sum |parts|"
+          % (N, d, q, max(rel(sb[k], st[k]) for k in keys), max(rel(sb[k], sc[k]) for k in keys),
+             np.abs(eb - ref).max() / np.abs(ref).sum(), np.abs(eb - ec).max() / np.abs(ec).sum()))
+    for k in keys:
+        _close(sb[k], st[k], "switched sweeps vs oracle: " + k)
+        _close(sb[k], sc[k], "switched sweeps vs the column-owning sweep: " + k)
+    assert np.all(np.abs(eb - ref) <= RTOL * np.abs(ref).sum()), (eb, ref)
+    assert np.all(np.abs(eb - ec) <= 1e-10 * np.abs(ec).sum()), (eb, ec)
 
 
 @pytest.mark.parametrize("N,d,q", [(300, 20, 4), (1000, 64, 16), (77, 33, 17), (5000, 256, 16), (16, 3, 1), (17, 250, 31)])
