@@ -120,8 +120,8 @@ int pyvb_lds_get_lengths(pyvb_lds* h, int* lengths);
  *     X_t and Y_t, except -tr(<Q> residual) and -tr(<R> residual), which are sums over the model and are booked once, on the
  *     first row; how L_X and L_Y split between the rows of a model is not contractual.  Totals, history, all-reduce: as before.
  *   - pyvb_lds_set_active: a mask that switches off part of a model is PYVB_E_ARG (the message names the model).
- *   - pyvb_lds_iterate_until on a handle with a model of more than one chain is PYVB_E_UNSUPPORTED before any launch:
- *     convergence per model is a follow-up.
+ *   - pyvb_lds_iterate_until, whose test is per replicate, still refuses a handle with a model of more than one chain with
+ *     PYVB_E_UNSUPPORTED before any launch: convergence per model is pyvb_lds_iterate_until_model (below).
  *   - Composes with chain lengths, known entries of A / C, outputs with NaN (where all chains have T nodes), both bound modes,
  *     every time split, status, communicators (a model never spans ranks: a rank's handle holds whole models).
  * PYVB_E_ARG when model[] is not of that form (the message names the first offending replicate).  PYVB_E_UNSUPPORTED when some
@@ -279,6 +279,28 @@ int pyvb_lds_get_active(pyvb_lds* h, unsigned char* active);
  * bound), VB-PCA (one model, nothing per replicate). */
 int pyvb_lds_iterate_until(pyvb_lds* h, int max_iters, double tol, int check_every, int* iters_run);
 int pyvb_lds_get_convergence(pyvb_lds* h, int* iters, unsigned char* converged, double* llb);
+
+/* Every MODEL converging on its own: the same test applied to the bound of a model's graph (pyvb_lds_create_tied).  The chains
+ * of a model share A, C, Q, R, so they stop together.
+ *   pyvb_lds_iterate_until_model   pyvb_lds_iterate_until's loop, arguments, checks, return and collective stop; what differs is
+ *                        the quantity tested.  For every running model m: old_m = -inf when the call starts; after iteration i,
+ *                        llb_m = the sum over the model's rows of their six parts (each part summed over the rows in ascending
+ *                        order, then the six added left to right); llb_m - old_m < tol and llb_m finite: converged at i, otherwise
+ *                        old_m = llb_m.  The first iteration of a call stops nobody, a decrease stops a model (quirk Q9), a bound
+ *                        that is not finite never does.  Every chain of a converged model is frozen exactly as
+ *                        pyvb_lds_iterate_until freezes a replicate -- for the life of the handle, still counted: the totals, the
+ *                        history and the all-reduce hold the model at its final bound.  The per-replicate bookkeeping holds the
+ *                        model's values on every one of its chains: pyvb_lds_get_convergence returns them replicated per chain.
+ *                        Served on every handle pyvb_lds_iterate_until serves, where every replicate is a model of its own and
+ *                        this entry does bitwise what that one does, and on handles with tied models; composes with chain lengths,
+ *                        both bound modes, the activity mask (a mask never splits a model), every time split, outputs with NaN
+ *                        (equal lengths) and communicators (a model never spans ranks; the seventh double counts running chains,
+ *                        0 exactly when no model runs).
+ *   pyvb_lds_get_model_convergence   iters[M], converged[M], llb[M], one entry per model (read from its first row), M = the
+ *                        number of models (pyvb_lds_get_models; M = N on a handle without tied models).  Any pointer may be NULL.
+ * Not built: thawing a converged model, models that span ranks. */
+int pyvb_lds_iterate_until_model(pyvb_lds* h, int max_iters, double tol, int check_every, int* iters_run);
+int pyvb_lds_get_model_convergence(pyvb_lds* h, int* iters, unsigned char* converged, double* llb);
 
 /* HIP-event timing of the kernels on the handle's stream (for bench.py's roofline figures). */
 int pyvb_lds_timing_enable(pyvb_lds* h, int on);

@@ -78,6 +78,8 @@ SIGNATURES = {
     "pyvb_lds_get_active": (ctypes.c_int, [_h, _ucp]),
     "pyvb_lds_iterate_until": (ctypes.c_int, [_h, ctypes.c_int, ctypes.c_double, ctypes.c_int, _ip]),
     "pyvb_lds_get_convergence": (ctypes.c_int, [_h, _ip, _ucp, _dp]),
+    "pyvb_lds_iterate_until_model": (ctypes.c_int, [_h, ctypes.c_int, ctypes.c_double, ctypes.c_int, _ip]),
+    "pyvb_lds_get_model_convergence": (ctypes.c_int, [_h, _ip, _ucp, _dp]),
     "pyvb_lds_timing_enable": (ctypes.c_int, [_h, ctypes.c_int]),
     "pyvb_lds_timing_reset": (ctypes.c_int, [_h]),
     "pyvb_lds_timing_get": (ctypes.c_int, [_h, ctypes.c_int, _dp, _ip]),

@@ -51,7 +51,7 @@ void pyvb_timing_resolve(pyvb_lds* h) {
 extern "C" {
 
 const char* pyvb_last_error(void) { return g_err; }
-int pyvb_version(void) { return 103; }
+int pyvb_version(void) { return 104; }
 
 int pyvb_device_count(int* count) {
     ARGCHK(count, "count is NULL");
@@ -1028,18 +1028,19 @@ int pyvb_lds_iterate(pyvb_lds* h, int niters) {
     return PYVB_OK;
 }
 
-// pyvb_lds_iterate with the stopping test of network.py:53 applied by every replicate to itself (k_converge.hip).  The decision of
-// iteration i must be in force before the k_prep of i + 1 reads the mask, so here the bound, the test and the totals run on the
-// main stream, in order, and nothing overlaps the next iteration (has what that costs).
-int pyvb_lds_iterate_until(pyvb_lds* h, int max_iters, double tol, int check_every, int* iters_run) {
+// pyvb_lds_iterate with the stopping test of network.py:53 applied by every replicate to itself (k_converge.hip) or, per_model, by
+// every model to the bound of its graph (k_converge_model.hip).  The decision of iteration i must be in force before the k_prep of
+// i + 1 reads the mask, so here the bound, the test and the totals run on the main stream, in order, and nothing overlaps the next
+// iteration (has what that costs; section 20 the per-model test).
+static int iterate_until(pyvb_lds* h, int max_iters, double tol, int check_every, int* iters_run, bool per_model) {
     ARGCHK(h, "handle is NULL");
     ARGCHK(max_iters >= 0, "max_iters must be >= 0");
     ARGCHK(check_every >= 1, "check_every must be >= 1");
     ARGCHK(tol == tol, "tol is NaN");
     ARGCHK(iters_run, "iters_run is NULL");
-    if (h->model_host) {
+    if (!per_model && h->model_host) {
         pyvb_set_error("pyvb_lds_iterate_until is not served on a handle with a model of more than one chain (pyvb_lds_create_tied): "
-                       "the stopping test is per replicate, convergence per model is a follow-up");
+                       "the stopping test is per replicate, convergence per model is pyvb_lds_iterate_until_model");
         return PYVB_E_UNSUPPORTED;
     }
     ENTER(h);
@@ -1053,7 +1054,7 @@ int pyvb_lds_iterate_until(pyvb_lds* h, int max_iters, double tol, int check_eve
         if (!idle) {
             if ((rc = iterate_updates(h))) return rc;
             if ((rc = h->dense ? launch_elbo_dense(h, h->stream) : launch_elbo(h, h->stream))) return rc;
-            if ((rc = launch_converge(h, tol, it == 0, h->stream))) return rc;
+            if ((rc = per_model ? launch_converge_model(h, tol, it == 0, h->stream) : launch_converge(h, tol, it == 0, h->stream))) return rc;
         }
         double* slot = h->elbo_hist + (size_t)(h->hist_count % PYVB_ELBO_HISTORY) * 8;
         if ((rc = launch_elbo_sum_running(h, slot, h->stream))) return rc;
@@ -1080,6 +1081,14 @@ int pyvb_lds_iterate_until(pyvb_lds* h, int max_iters, double tol, int check_eve
     return PYVB_OK;
 }
 
+int pyvb_lds_iterate_until(pyvb_lds* h, int max_iters, double tol, int check_every, int* iters_run) {
+    return iterate_until(h, max_iters, tol, check_every, iters_run, false);
+}
+
+int pyvb_lds_iterate_until_model(pyvb_lds* h, int max_iters, double tol, int check_every, int* iters_run) {
+    return iterate_until(h, max_iters, tol, check_every, iters_run, true);
+}
+
 int pyvb_lds_get_convergence(pyvb_lds* h, int* iters, unsigned char* converged, double* llb) {
     ENTER(h);
     HIPCHK(hipStreamSynchronize(h->stream));
@@ -1087,6 +1096,26 @@ int pyvb_lds_get_convergence(pyvb_lds* h, int* iters, unsigned char* converged, 
     if (iters) HIPCHK(hipMemcpy(iters, h->conv_iters, (size_t)h->N * sizeof(int), hipMemcpyDeviceToHost));
     if (converged) HIPCHK(hipMemcpy(converged, h->conv, (size_t)h->N, hipMemcpyDeviceToHost));
     if (llb) HIPCHK(hipMemcpy(llb, h->conv_llb, (size_t)h->N * sizeof(double), hipMemcpyDeviceToHost));
+    return PYVB_OK;
+}
+
+// One entry per model, read from the row of its first replicate: every chain of a model holds the model's values.
+int pyvb_lds_get_model_convergence(pyvb_lds* h, int* iters, unsigned char* converged, double* llb) {
+    ARGCHK(h, "handle is NULL");
+    if (!h->model_host) return pyvb_lds_get_convergence(h, iters, converged, llb);      // M = N
+    const size_t N = (size_t)h->N;
+    std::vector<int> it(N);
+    std::vector<unsigned char> cv(N);
+    std::vector<double> lb(N);
+    int rc = pyvb_lds_get_convergence(h, it.data(), cv.data(), lb.data());
+    if (rc) return rc;
+    for (int n = 0, m = 0; n < h->N; ++n) {
+        if (n && h->model_host[n] == h->model_host[n - 1]) continue;
+        if (iters) iters[m] = it[n];
+        if (converged) converged[m] = cv[n];
+        if (llb) llb[m] = lb[n];
+        ++m;
+    }
     return PYVB_OK;
 }
 

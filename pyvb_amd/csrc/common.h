@@ -189,6 +189,9 @@ int launch_elbo_sum(pyvb_lds* h, double* out = nullptr, hipStream_t stream = nul
 // the totals of an iteration with out[6] = the number of replicates still running
 int launch_converge(pyvb_lds* h, double tol, bool first, hipStream_t stream);
 int launch_elbo_sum_running(pyvb_lds* h, double* out, hipStream_t stream);
+// k_converge_model.hip: the same test on the bound of every model (the sum over its chains), the freeze of all chains of the
+// models it stops; on a handle whose models are single replicates it launches k_converge
+int launch_converge_model(pyvb_lds* h, double tol, bool first, hipStream_t stream);
 // k_big.hip
 int launch_prep_big(pyvb_lds* h);
 int big_prepare_kernels();              // once per device, before the first launch: the dynamic-LDS limits of k_prep_big, k_cols_big

@@ -353,6 +353,24 @@ class LDSBatch(object):
         self._check(C.lib.pyvb_lds_get_convergence(self._h, it.ctypes.data_as(C._ip), cv.ctypes.data_as(C._ucp), C.dptr(llb)))
         return it, cv.astype(bool), llb
 
+    def iterate_until_model(self, max_iters, tol=1e-3, check_every=8):
+        """iterate_until() with the stopping test applied by every MODEL to the bound of its graph, the sum of its chains' parts
+        (models=, from_trials): the chains of a model share A, C, Q, R and stop together.  A model that converges is frozen for
+        the life of the handle and stays in the totals at its final bound.  Where every replicate is a model of its own this is
+        iterate_until, bitwise.  Returns the number of iterations launched.  Synchronises."""
+        n = C.ctypes.c_int()
+        self._check(C.lib.pyvb_lds_iterate_until_model(self._h, int(max_iters), float(tol), int(check_every), C.ctypes.byref(n)))
+        return n.value
+
+    def model_convergence(self):
+        """(iters int [M], converged bool [M], llb float [M]), one entry per model: the iterations it has carried out under
+        iterate_until_model, whether it has converged, and the last bound its test saw (NaN before the first).  convergence()
+        returns the same values replicated on every chain of the model."""
+        M = int(self.models[-1]) + 1
+        it, cv, llb = np.zeros(M, dtype=np.int32), np.zeros(M, dtype=np.uint8), np.empty(M)
+        self._check(C.lib.pyvb_lds_get_model_convergence(self._h, it.ctypes.data_as(C._ip), cv.ctypes.data_as(C._ucp), C.dptr(llb)))
+        return it, cv.astype(bool), llb
+
     # -- measurement ------------------------------------------------------------------------
     def timing(self, on=True):
         self._check(C.lib.pyvb_lds_timing_enable(self._h, 1 if on else 0))
