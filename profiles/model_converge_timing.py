@@ -1,5 +1,5 @@
-"""What per-model convergence (pyvb_lds_iterate_until_model, k_converge_model.hip) costs when nobody converges, what it saves once
-models have, and what the new kernel takes per launch: DESIGN.md section 20.
+"""What per-model convergence (pyvb_lds_iterate_until_model, k_converge.hip) costs when nobody converges, what it saves once
+models have, and what the stopping kernel and the totals kernel take per launch: DESIGN.md section 20.
 
     python profiles/model_converge_timing.py [--runs 5] [--steps 10] [--label LABEL] [--out FILE]
     python profiles/model_converge_timing.py --parent [--label parent_run1] [--out FILE]
@@ -19,8 +19,8 @@ inputs), one process, one GPU, `runs` runs of `steps` iterations per variant, th
      iterate_until_model(2, tol), whose second iteration applies the test, and ms per iteration of both entries afterwards.
  (c) --trace: a short sequence for a kernel trace: eight iterations in which nothing stops, then every model but one is switched
      off and iterate_until_model(2, +inf) runs: the first iteration of a call stops nobody, the second stops the one model that
-     runs, so the last launch of k_converge_model is the one in which a model of 8 chains freezes (in it the workgroups of the
-     other models leave at their first instruction).  --summarise prints the durations of k_converge_model from the trace.
+     runs, so the last launch of k_converge is the one in which a model of 8 chains freezes (in it the workgroups of the
+     other models leave at their first instruction).  --summarise prints the durations of k_converge and k_elbo_sum from the trace.
 
 A step that fails ends the run: nothing further is started on the GPU.
 """
@@ -40,7 +40,7 @@ NEVER = -float("inf")
 def summarise(path, say):
     import csv
     rows = sorted(csv.DictReader(open(path)), key=lambda r: int(r["Start_Timestamp"]))
-    for kernel in ("k_converge_model", "k_elbo_sum_running"):
+    for kernel in ("k_converge", "k_elbo_sum"):         # (substrings: no other kernel of the library has either in its name)
         us = [(int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3 for r in rows if kernel in r["Kernel_Name"]]
         if not us:
             say("%s: no launch in the trace" % kernel)

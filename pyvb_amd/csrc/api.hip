@@ -59,26 +59,27 @@ int pyvb_device_count(int* count) {
     return PYVB_OK;
 }
 
-int pyvb_lds_create(pyvb_lds** out, int device, int N, int T, int D, int K, int noise_kind) {
-    return pyvb_lds_create_lengths(out, device, N, T, D, K, noise_kind, nullptr);
-}
-
-int pyvb_lds_create_lengths(pyvb_lds** out, int device, int N, int T, int D, int K, int noise_kind, const int* lengths) {
+// The one creation path; lengths null: every chain has T nodes, model null: every replicate is a model.  Arguments are checked
+// and, where a combination is not served, refused before the first HIP call; *out is written once, when everything exists.
+static int lds_create(pyvb_lds** out, int device, int N, int T, int D, int K, int noise_kind, const int* lengths, const int* model) {
     ARGCHK(out, "out is NULL");
     ARGCHK(N >= 1, "N must be >= 1");
+    bool ragged = false, tied = false;
+    int rc = model ? Replicates::check_models(N, model, &tied) : PYVB_OK;
+    if (rc) return rc;
+    if (tied && noise_kind == PYVB_NOISE_WISHART) {
+        pyvb_set_error("chains that share A, C, Q, R are served with DiagonalGamma and Gamma noise only, not with Wishart noise (k_wishart.hip)");
+        return PYVB_E_UNSUPPORTED;
+    }
+    if (tied && (D > 64 || K > 64)) {
+        pyvb_set_error("chains that share A, C, Q, R are served for max(D, K) <= 64 only, not in the 128-wide class (k_big.hip): D = %d, K = %d", D, K);
+        return PYVB_E_UNSUPPORTED;
+    }
     ARGCHK(T >= 2, "T must be >= 2 (a chain needs X_0 and X_{T-1})");
     ARGCHK(D >= 1 && D <= 128, "latent dimension D must be in 1..128");
     ARGCHK(K >= 1 && K <= 128, "observed dimension K must be in 1..128");
     ARGCHK(noise_kind == PYVB_NOISE_DIAGONAL_GAMMA || noise_kind == PYVB_NOISE_GAMMA || noise_kind == PYVB_NOISE_WISHART, "unknown noise kind");
-    // chain lengths: checked and, where the combination is not served, refused before the first HIP call
-    bool ragged = false;
-    for (int n = 0; lengths && n < N; ++n) {
-        if (lengths[n] < 2 || lengths[n] > T) {
-            pyvb_set_error("replicate %d has length %d: every chain needs 2 <= T_n <= T = %d", n, lengths[n], T);
-            return PYVB_E_ARG;
-        }
-        ragged = ragged || lengths[n] != T;
-    }
+    if (lengths && (rc = Replicates::check_lengths(N, T, lengths, &ragged))) return rc;
     if (ragged && noise_kind == PYVB_NOISE_WISHART) {
         pyvb_set_error("chains of unequal length are served with DiagonalGamma and Gamma noise only, not with Wishart noise (k_wishart.hip)");
         return PYVB_E_UNSUPPORTED;
@@ -96,8 +97,9 @@ int pyvb_lds_create_lengths(pyvb_lds** out, int device, int N, int T, int D, int
     h->L = make_layout(D, K);
     h->big = D > 64 || K > 64;           // the workgroup-per-replicate kernels of k_big.hip
     h->dense = noise_kind == PYVB_NOISE_WISHART;
+    // (lengths that all equal T, models of one replicate each: a plain handle, len / mstart / first stay null)
+    h->rep.init(N, T, ragged ? lengths : nullptr, tied ? model : nullptr);
     const Layout& L = h->L;
-    int rc = PYVB_OK;
 #define TRY(x) CREATE_TRY(x, pyvb_lds_destroy, h)
 #define TRYHIP(x) CREATE_TRYHIP(x, pyvb_lds_destroy, h)
 #define dev_alloc(p, n) h->mem.zeros(p, n)
@@ -168,18 +170,19 @@ int pyvb_lds_create_lengths(pyvb_lds** out, int device, int N, int T, int D, int
     TRY(h->mem.alloc((void**)&h->conv_llb, n * sizeof(double), 0xFF));     // (all-ones bytes = NaN: no test has seen a bound yet)
     TRYHIP(hipHostMalloc((void**)&h->running_host, sizeof(double), hipHostMallocDefault));
     TRYHIP(hipEventCreateWithFlags(&h->ev_check, hipEventDisableTiming));
-    if (ragged) {       // (lengths that all equal T: a plain handle, len stays null)
+    if (ragged) {
         TRY(h->mem.alloc((void**)&h->len, n * sizeof(int)));
-        h->len_host = (int*)malloc(n * sizeof(int));
-        memcpy(h->len_host, lengths, n * sizeof(int));
         TRYHIP(hipMemcpy(h->len, lengths, n * sizeof(int), hipMemcpyHostToDevice));
     }
-    h->active_host = (unsigned char*)malloc(n);
-    memset(h->active_host, 1, n);
-    h->conv_host = (unsigned char*)calloc(n, 1);
-    h->n_active = N;
-    h->status_host = (int*)calloc(n, sizeof(int));
-    h->reported = (int*)calloc(n, sizeof(int));
+    if (tied) {
+        const Replicates& r = h->rep;
+        TRY(h->mem.alloc((void**)&h->mstart, r.model_starts().size() * sizeof(int)));
+        TRY(h->mem.alloc((void**)&h->first, n));
+        TRYHIP(hipMemcpy(h->mstart, r.model_starts().data(), r.model_starts().size() * sizeof(int), hipMemcpyHostToDevice));
+        TRYHIP(hipMemcpy(h->first, r.first_flags().data(), n, hipMemcpyHostToDevice));
+    }
+    h->status_host.assign(n, 0);
+    h->reported.assign(n, 0);
     // priors block: x0_mean D, x0_prec D*D, A_pm D*D, A_pp D*D, C_pm K*D, C_pp D*K, Q_a0 D, Q_b0 D, R_a0 K, R_b0 K
     size_t pn = (size_t)D + 3 * (size_t)D * D + 2 * (size_t)K * D + 2 * (size_t)D + 2 * (size_t)K + (size_t)D * D + (size_t)K * D + 2 * (size_t)D
                 + (size_t)D * D + (size_t)K * K;
@@ -225,52 +228,20 @@ int pyvb_lds_create_lengths(pyvb_lds** out, int device, int N, int T, int D, int
     return PYVB_OK;
 }
 
+int pyvb_lds_create(pyvb_lds** out, int device, int N, int T, int D, int K, int noise_kind) {
+    return lds_create(out, device, N, T, D, K, noise_kind, nullptr, nullptr);
+}
+int pyvb_lds_create_lengths(pyvb_lds** out, int device, int N, int T, int D, int K, int noise_kind, const int* lengths) {
+    return lds_create(out, device, N, T, D, K, noise_kind, lengths, nullptr);
+}
 int pyvb_lds_create_tied(pyvb_lds** out, int device, int N, int T, int D, int K, int noise_kind, const int* lengths, const int* model) {
-    if (!model) return pyvb_lds_create_lengths(out, device, N, T, D, K, noise_kind, lengths);
-    ARGCHK(out, "out is NULL");
-    ARGCHK(N >= 1, "N must be >= 1");
-    // the models: checked and, where a tied model is not served, refused before the first HIP call
-    bool tied = false;
-    for (int n = 0; n < N; ++n) {
-        const int prev = n ? model[n - 1] : 0;
-        if (n == 0 ? model[0] != 0 : (model[n] != prev && model[n] != prev + 1)) {
-            pyvb_set_error("replicate %d has model %d after %d: model ids start at 0, never decrease and rise in steps of 0 or 1 "
-                           "(a model is a run of consecutive replicates)", n, model[n], n ? prev : -1);
-            return PYVB_E_ARG;
-        }
-        tied = tied || (n && model[n] == prev);
-    }
-    if (tied && noise_kind == PYVB_NOISE_WISHART) {
-        pyvb_set_error("chains that share A, C, Q, R are served with DiagonalGamma and Gamma noise only, not with Wishart noise (k_wishart.hip)");
-        return PYVB_E_UNSUPPORTED;
-    }
-    if (tied && (D > 64 || K > 64)) {
-        pyvb_set_error("chains that share A, C, Q, R are served for max(D, K) <= 64 only, not in the 128-wide class (k_big.hip): D = %d, K = %d", D, K);
-        return PYVB_E_UNSUPPORTED;
-    }
-    int rc = pyvb_lds_create_lengths(out, device, N, T, D, K, noise_kind, lengths);
-    if (rc != PYVB_OK || !tied) return rc;       // models of one replicate each: a pyvb_lds_create_lengths handle
-    pyvb_lds* h = *out;
-    *out = nullptr;
-    h->M = model[N - 1] + 1;
-    h->model_host = (int*)malloc((size_t)N * sizeof(int));
-    memcpy(h->model_host, model, (size_t)N * sizeof(int));
-    std::vector<int> mstart((size_t)h->M + 1, N);
-    std::vector<unsigned char> first((size_t)N, 0);
-    for (int n = N - 1; n >= 0; --n) mstart[model[n]] = n;
-    for (int m = 0; m < h->M; ++m) first[mstart[m]] = 1;
-    CREATE_TRY(h->mem.alloc((void**)&h->mstart, mstart.size() * sizeof(int)), pyvb_lds_destroy, h);
-    CREATE_TRY(h->mem.alloc((void**)&h->first, (size_t)N), pyvb_lds_destroy, h);
-    CREATE_TRYHIP(hipMemcpy(h->mstart, mstart.data(), mstart.size() * sizeof(int), hipMemcpyHostToDevice), pyvb_lds_destroy, h);
-    CREATE_TRYHIP(hipMemcpy(h->first, first.data(), (size_t)N, hipMemcpyHostToDevice), pyvb_lds_destroy, h);
-    *out = h;
-    return PYVB_OK;
+    return lds_create(out, device, N, T, D, K, noise_kind, lengths, model);
 }
 
 int pyvb_lds_get_models(pyvb_lds* h, int* model) {
     ARGCHK(h, "handle is NULL");
     ARGCHK(model, "model is NULL");
-    for (int n = 0; n < h->N; ++n) model[n] = h->model_host ? h->model_host[n] : n;
+    for (int n = 0; n < h->N; ++n) model[n] = h->rep.model(n);
     return PYVB_OK;
 }
 
@@ -286,7 +257,6 @@ int pyvb_lds_destroy(pyvb_lds* h) {
     if (h->running_host) (void)hipHostFree(h->running_host);
     if (h->side) (void)hipStreamDestroy(h->side);
     h->mem.release_all();
-    free(h->active_host); free(h->conv_host); free(h->status_host); free(h->reported); free(h->len_host); free(h->model_host);
     if (h->pool) {
         for (int i = 0; i < PYVB_EVENT_POOL; ++i) { if (h->pool[i].e0) (void)hipEventDestroy(h->pool[i].e0); if (h->pool[i].e1) (void)hipEventDestroy(h->pool[i].e1); }
         free(h->pool);
@@ -303,14 +273,14 @@ static int join_elbo(pyvb_lds* h);
 #define ENTER(h) do { ENTER_DEVICE(h); if ((h)->elbo_in_flight) { int _rc = join_elbo(h); if (_rc) return _rc; } } while (0)
 
 // every replicate switched off: the update entries are successful no-ops without a launch
-#define IDLE(h) do { if ((h)->n_active == 0) return PYVB_OK; } while (0)
+#define IDLE(h) do { if ((h)->rep.n_active() == 0) return PYVB_OK; } while (0)
 
 // Rows of switched-off replicates sit out the two ping-pongs of the handle: the X buffers (a sweep reads one and writes the
 // other) and the covariance classes (k_prep writes Sigma_new, adopt_classes swaps).  They stay where they were when the row
 // was switched off, and are copied across here, before a getter reads every row, before a setter or a staging copy uses the
 // other X buffer, and before the mask changes -- never on the update path.
 static int settle_parked(pyvb_lds* h) {
-    if (h->n_active == h->N) return PYVB_OK;
+    if (h->rep.n_active() == h->N) return PYVB_OK;
     int rc;
     if (h->st.x_park != h->st.cur && (rc = launch_carry(h, h->X[h->st.x_park], h->X[h->st.cur], (size_t)h->T * h->L.DP))) return rc;
     if (h->st.cls_parked_other) {
@@ -328,9 +298,9 @@ static int d2h(pyvb_lds* h, double* dst, const double* src, size_t n) { return t
 // A handle with chain lengths: rows t >= T_n of a host array [N][T][per] that a getter has just filled (after the sync) are
 // padding, not nodes; they read as `value` whatever the device buffer holds there.
 static void fill_padding(const pyvb_lds* h, double* a, size_t per, double value) {
-    if (!h->len_host || !a) return;
+    if (!h->rep.ragged() || !a) return;
     for (size_t n = 0; n < (size_t)h->N; ++n)
-        for (size_t i = ((size_t)n * h->T + h->len_host[n]) * per; i < (size_t)(n + 1) * h->T * per; ++i) a[i] = value;
+        for (size_t i = ((size_t)n * h->T + h->rep.length((int)n)) * per; i < (size_t)(n + 1) * h->T * per; ++i) a[i] = value;
 }
 
 // ln det of a symmetric positive definite matrix (Constant.lndet, node.py:301-302)
@@ -359,7 +329,7 @@ int pyvb_lds_set_priors(pyvb_lds* h, const double* x0_mean, const double* x0_pre
     ENTER(h);
     ARGCHK(x0_mean && x0_prec && A_pm && A_pp && C_pm && C_pp, "the priors of X_0 and of the columns are required");
     ARGCHK(h->dense || (Q_a0 && Q_b0 && R_a0 && R_b0), "the Gamma priors of Q and R are required");
-    const int D = h->D, K = h->K, T = h->T, N = h->N;
+    const int D = h->D, K = h->K, N = h->N;
     for (int i = 0; i < D * D; ++i) ARGCHK(A_pp[i] > 0.0, "A_prior_prec must be positive");
     for (int i = 0; i < D * K; ++i) ARGCHK(C_pp[i] > 0.0, "C_prior_prec must be positive");
     if (host_lndet(x0_prec, D, &h->pri.x0_lndet) != PYVB_OK) { pyvb_set_error("x0_prec is not positive definite"); return PYVB_E_LINALG; }
@@ -388,13 +358,10 @@ int pyvb_lds_set_priors(pyvb_lds* h, const double* x0_mean, const double* x0_pre
         // and :183-186 (DiagonalGamma: +0.5 per child); Q has T-1 children X_1.., R has T children Y_t
         std::vector<double> qa((size_t)N * D), ra((size_t)N * K);
         // the children of replicate n's Q and R: its own chain's, or those of every chain of its model (pyvb_lds_create_tied)
-        std::vector<long> mq((size_t)N, 0), mr((size_t)N, 0);      // per model id (a plain handle: id = n)
+        std::vector<long> cq, cr;
+        h->rep.children(cq, cr);
         for (int n = 0; n < N; ++n) {
-            const int Tn = h->len_host ? h->len_host[n] : T, m = h->model_host ? h->model_host[n] : n;
-            mq[m] += Tn - 1; mr[m] += Tn;
-        }
-        for (int n = 0; n < N; ++n) {
-            const long nq = mq[h->model_host ? h->model_host[n] : n], nr = mr[h->model_host ? h->model_host[n] : n];
+            const long nq = cq[n], nr = cr[n];
             for (int k = 0; k < D; ++k)
                 qa[(size_t)n * D + k] = (h->noise == PYVB_NOISE_GAMMA) ? Q_a0[0] + 0.5 * D * nq : Q_a0[k] + 0.5 * nq;
             for (int k = 0; k < K; ++k)
@@ -545,13 +512,13 @@ int pyvb_lds_set_observations(pyvb_lds* h, const double* Y) {
     ARGCHK(Y, "Y is NULL");
     const size_t n = (size_t)h->N * h->T * h->K;
     bool missing = false;
-    if (h->len_host) {      // padding rows may hold anything, NaN included: they are not outputs of any graph
+    if (h->rep.ragged()) {      // padding rows may hold anything, NaN included: they are not outputs of any graph
         for (int r = 0; r < h->N; ++r) {
             const double* Yr = Y + (size_t)r * h->T * h->K;
-            for (size_t i = 0; i < (size_t)h->len_host[r] * h->K; ++i)
+            for (size_t i = 0; i < (size_t)h->rep.length(r) * h->K; ++i)
                 if (Yr[i] != Yr[i]) {
                     pyvb_set_error("outputs that hold NaN are not served together with chains of unequal length (k_missing.hip): "
-                                   "replicate %d, t = %d of its %d nodes", r, (int)(i / h->K), h->len_host[r]);
+                                   "replicate %d, t = %d of its %d nodes", r, (int)(i / h->K), h->rep.length(r));
                     return PYVB_E_UNSUPPORTED;
                 }
         }
@@ -663,13 +630,10 @@ int pyvb_lds_set_state(pyvb_lds* h, const double* X, const double* A_mean, const
     // Chains that share A, C, Q, R: the row of a model's first replicate is the model's state and goes to all its rows
     std::vector<double> tied[6];        // (staging; alive until the synchronisation below)
     auto model_rows = [&](int slot, const double* src, size_t per) -> const double* {
-        if (!src || !h->model_host) return src;
+        if (!src || !h->rep.tied()) return src;
         std::vector<double>& v = tied[slot];
         v.resize(N * per);
-        for (size_t n = 0, f = 0; n < N; ++n) {
-            if (n && h->model_host[n] != h->model_host[n - 1]) f = n;
-            memcpy(v.data() + n * per, src + f * per, per * sizeof(double));
-        }
+        for (size_t n = 0; n < N; ++n) memcpy(v.data() + n * per, src + (size_t)h->rep.first_of((int)n) * per, per * sizeof(double));
         return v.data();
     };
     if ((rc = h2d(h, h->A_mean, model_rows(0, A_mean, D * D), N * D * D))) return rc;
@@ -744,7 +708,7 @@ int pyvb_lds_get_column_qld(pyvb_lds* h, double* qld_A, double* qld_C) {
 int pyvb_lds_get_lengths(pyvb_lds* h, int* lengths) {
     ARGCHK(h, "handle is NULL");
     ARGCHK(lengths, "lengths is NULL");
-    for (int n = 0; n < h->N; ++n) lengths[n] = h->len_host ? h->len_host[n] : h->T;
+    for (int n = 0; n < h->N; ++n) lengths[n] = h->rep.length(n);
     return PYVB_OK;
 }
 
@@ -843,7 +807,7 @@ static void adopt_classes(pyvb_lds* h) {
     double* t = h->Sigma; h->Sigma = h->Sigma_new; h->Sigma_new = t;
     t = h->qld_x; h->qld_x = h->qld_x_new; h->qld_x_new = t;
     t = h->lnd_x; h->lnd_x = h->lnd_x_new; h->lnd_x_new = t;
-    h->st.classes_adopted(h->n_active < h->N);
+    h->st.classes_adopted(h->rep.n_active() < h->N);
 }
 
 static int ensure_stats(pyvb_lds* h) {
@@ -1007,7 +971,7 @@ int pyvb_lds_iterate(pyvb_lds* h, int niters) {
     int rc;
     // Every replicate switched off: no update is launched, but the (empty) sums still go into the history and through the
     // all-reduce, which the other ranks are waiting in.
-    const bool idle = h->n_active == 0;
+    const bool idle = h->rep.n_active() == 0;
     for (int it = 0; it < niters; ++it) {
         if ((rc = idle ? join_elbo(h) : iterate_updates(h))) return rc;
         // The lower bound (network.py:49) feeds nothing in the next iteration: it is evaluated on the side stream while
@@ -1028,8 +992,8 @@ int pyvb_lds_iterate(pyvb_lds* h, int niters) {
     return PYVB_OK;
 }
 
-// pyvb_lds_iterate with the stopping test of network.py:53 applied by every replicate to itself (k_converge.hip) or, per_model, by
-// every model to the bound of its graph (k_converge_model.hip).  The decision of iteration i must be in force before the k_prep of
+// pyvb_lds_iterate with the stopping test of network.py:53 applied by every replicate to itself or, per_model, by
+// every model to the bound of its graph (k_converge.hip serves both).  The decision of iteration i must be in force before the k_prep of
 // i + 1 reads the mask, so here the bound, the test and the totals run on the main stream, in order, and nothing overlaps the next
 // iteration (has what that costs; section 20 the per-model test).
 static int iterate_until(pyvb_lds* h, int max_iters, double tol, int check_every, int* iters_run, bool per_model) {
@@ -1038,7 +1002,7 @@ static int iterate_until(pyvb_lds* h, int max_iters, double tol, int check_every
     ARGCHK(check_every >= 1, "check_every must be >= 1");
     ARGCHK(tol == tol, "tol is NaN");
     ARGCHK(iters_run, "iters_run is NULL");
-    if (!per_model && h->model_host) {
+    if (!per_model && h->rep.tied()) {
         pyvb_set_error("pyvb_lds_iterate_until is not served on a handle with a model of more than one chain (pyvb_lds_create_tied): "
                        "the stopping test is per replicate, convergence per model is pyvb_lds_iterate_until_model");
         return PYVB_E_UNSUPPORTED;
@@ -1048,16 +1012,16 @@ static int iterate_until(pyvb_lds* h, int max_iters, double tol, int check_every
     int rc, it = 0;
     // Nothing to run on this rank: no update is launched, but with a communicator the totals and the running count (0 here)
     // still go through the all-reduce the other ranks are waiting in, until every rank has stopped.
-    const bool idle = h->n_active == 0;
+    const bool idle = h->rep.n_active() == 0;
     bool done = idle && !h->comm;
     while (!done && it < max_iters) {
         if (!idle) {
             if ((rc = iterate_updates(h))) return rc;
             if ((rc = h->dense ? launch_elbo_dense(h, h->stream) : launch_elbo(h, h->stream))) return rc;
-            if ((rc = per_model ? launch_converge_model(h, tol, it == 0, h->stream) : launch_converge(h, tol, it == 0, h->stream))) return rc;
+            if ((rc = launch_converge(h, tol, it == 0, h->stream))) return rc;
         }
         double* slot = h->elbo_hist + (size_t)(h->hist_count % PYVB_ELBO_HISTORY) * 8;
-        if ((rc = launch_elbo_sum_running(h, slot, h->stream))) return rc;
+        if ((rc = launch_elbo_sum(h, slot, h->stream))) return rc;
         if (h->comm && (rc = pyvb_allreduce_f64(h->comm, slot, 7, h->stream))) return rc;
         h->hist_count += 1;
         it += 1;
@@ -1072,12 +1036,12 @@ static int iterate_until(pyvb_lds* h, int max_iters, double tol, int check_every
     *iters_run = it;
     HIPCHK(hipStreamSynchronize(h->stream));
     HIPCHK(hipStreamSynchronize(h->side));
-    // the host mirrors: which replicates the test has frozen, and how many are left for IDLE, settle_parked and adopt_classes.
-    // The rows frozen in this call are identical in both X buffers and both class sets, so x_park / cls_parked_other are
-    // right for them whatever they say.
-    HIPCHK(hipMemcpy(h->conv_host, h->conv, (size_t)h->N, hipMemcpyDeviceToHost));
-    h->n_active = 0;
-    for (int n = 0; n < h->N; ++n) h->n_active += h->active_host[n] && !h->conv_host[n];
+    // the host record: which replicates the test has frozen, and with that how many are left for IDLE, settle_parked and
+    // adopt_classes.  The rows frozen in this call are identical in both X buffers and both class sets, so x_park /
+    // cls_parked_other are right for them whatever they say.
+    std::vector<unsigned char> conv((size_t)h->N);
+    HIPCHK(hipMemcpy(conv.data(), h->conv, conv.size(), hipMemcpyDeviceToHost));
+    h->rep.adopt_conv(conv.data());
     return PYVB_OK;
 }
 
@@ -1102,19 +1066,19 @@ int pyvb_lds_get_convergence(pyvb_lds* h, int* iters, unsigned char* converged, 
 // One entry per model, read from the row of its first replicate: every chain of a model holds the model's values.
 int pyvb_lds_get_model_convergence(pyvb_lds* h, int* iters, unsigned char* converged, double* llb) {
     ARGCHK(h, "handle is NULL");
-    if (!h->model_host) return pyvb_lds_get_convergence(h, iters, converged, llb);      // M = N
+    if (!h->rep.tied()) return pyvb_lds_get_convergence(h, iters, converged, llb);      // M = N
     const size_t N = (size_t)h->N;
     std::vector<int> it(N);
     std::vector<unsigned char> cv(N);
     std::vector<double> lb(N);
     int rc = pyvb_lds_get_convergence(h, it.data(), cv.data(), lb.data());
     if (rc) return rc;
-    for (int n = 0, m = 0; n < h->N; ++n) {
-        if (n && h->model_host[n] == h->model_host[n - 1]) continue;
+    for (int n = 0; n < h->N; ++n) {
+        if (h->rep.first_of(n) != n) continue;
+        const int m = h->rep.model(n);
         if (iters) iters[m] = it[n];
         if (converged) converged[m] = cv[n];
         if (llb) llb[m] = lb[n];
-        ++m;
     }
     return PYVB_OK;
 }
@@ -1166,18 +1130,18 @@ int pyvb_lds_sync(pyvb_lds* h) {
     ENTER(h);
     HIPCHK(hipStreamSynchronize(h->stream));
     HIPCHK(hipStreamSynchronize(h->side));
-    HIPCHK(hipMemcpy(h->status_host, h->status, (size_t)h->N * sizeof(int), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(h->status_host.data(), h->status, (size_t)h->N * sizeof(int), hipMemcpyDeviceToHost));
     int first = -1, failed = 0;
     for (int n = 0; n < h->N; ++n)      // the flags of a replicate that was switched off (because it failed) do not raise again
-        if (h->status_host[n] && h->active_host[n]) { if (first < 0) first = n; ++failed; }
+        if (h->status_host[n] && h->rep.active(n)) { if (first < 0) first = n; ++failed; }
     if (failed) {
-        memcpy(h->reported, h->status_host, (size_t)h->N * sizeof(int));
+        h->reported = h->status_host;
         pyvb_set_error("a posterior precision was not positive definite (numpy.linalg.LinAlgError in the reference): "
                        "first in replicate %d, %d of %d replicates failed (pyvb_lds_get_status)", first, failed, h->N);
         HIPCHK(hipMemset(h->status, 0, (size_t)h->N * sizeof(int)));
         return PYVB_E_LINALG;
     }
-    memset(h->reported, 0, (size_t)h->N * sizeof(int));
+    h->reported.assign((size_t)h->N, 0);
     return PYVB_OK;
 }
 
@@ -1187,47 +1151,31 @@ int pyvb_lds_get_status(pyvb_lds* h, int* status) {
     ENTER(h);
     HIPCHK(hipStreamSynchronize(h->stream));
     HIPCHK(hipStreamSynchronize(h->side));
-    HIPCHK(hipMemcpy(h->status_host, h->status, (size_t)h->N * sizeof(int), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(h->status_host.data(), h->status, (size_t)h->N * sizeof(int), hipMemcpyDeviceToHost));
     for (int n = 0; n < h->N; ++n) status[n] = h->status_host[n] | h->reported[n];
     return PYVB_OK;
 }
 
-// The two device masks from their host mirrors: what the totals count is the caller's mask, what the update kernels run is that
+// The two device masks from the host record: what the totals count is the caller's mask, what the update kernels run is that
 // without the converged replicates (the same bytes until pyvb_lds_iterate_until has stopped one).
 static int upload_masks(pyvb_lds* h) {
-    std::vector<unsigned char> run((size_t)h->N);
-    h->n_active = 0;
-    for (int n = 0; n < h->N; ++n) { run[n] = h->active_host[n] && !h->conv_host[n]; h->n_active += run[n]; }
-    HIPCHK(hipMemcpyAsync(h->counted, h->active_host, (size_t)h->N, hipMemcpyHostToDevice, h->stream));
+    const std::vector<unsigned char> run = h->rep.run_mask();
+    HIPCHK(hipMemcpyAsync(h->counted, h->rep.caller_mask(), (size_t)h->N, hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipMemcpyAsync(h->active, run.data(), (size_t)h->N, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));       // the mirrors may change again as soon as this returns
+    HIPCHK(hipStreamSynchronize(h->stream));       // `run` is about to go out of scope
     return PYVB_OK;
 }
 
 int pyvb_lds_set_active(pyvb_lds* h, const unsigned char* active) {
     ARGCHK(h, "handle is NULL");
     ARGCHK(active, "active is NULL");
-    for (int n = 0; n < h->N; ++n)
-        if (active[n] && !h->active_host[n]) {
-            pyvb_set_error("replicate %d is switched off and cannot be switched on again: the mask can only shrink "
-                           "(the validity tracking of gains and statistics is per handle)", n);
-            return PYVB_E_ARG;
-        }
-    for (int n = 1; h->model_host && n < h->N; ++n)
-        if (h->model_host[n] == h->model_host[n - 1] && (active[n] != 0) != (active[n - 1] != 0)) {
-            pyvb_set_error("the mask switches off part of model %d (replicate %d is %s, replicate %d is %s): the chains of a model "
-                           "share A, C, Q, R and are switched off together", h->model_host[n], n - 1, active[n - 1] ? "on" : "off",
-                           n, active[n] ? "on" : "off");
-            return PYVB_E_ARG;
-        }
-    ENTER(h);
-    int changed = 0;
-    for (int n = 0; n < h->N; ++n) changed += (active[n] != 0) != (h->active_host[n] != 0);
-    if (!changed) return PYVB_OK;
-    // rows switched off earlier move to where the rows switched off now are: the current buffers
-    int rc = settle_parked(h);
+    int rc = h->rep.check_mask(active);
     if (rc) return rc;
-    for (int n = 0; n < h->N; ++n) h->active_host[n] = active[n] ? 1 : 0;
+    ENTER(h);
+    if (!h->rep.mask_differs(active)) return PYVB_OK;
+    // rows switched off earlier move to where the rows switched off now are: the current buffers
+    if ((rc = settle_parked(h))) return rc;
+    h->rep.adopt_mask(active);
     h->st.parked_here();
     return upload_masks(h);
 }
@@ -1235,7 +1183,7 @@ int pyvb_lds_set_active(pyvb_lds* h, const unsigned char* active) {
 int pyvb_lds_get_active(pyvb_lds* h, unsigned char* active) {
     ARGCHK(h, "handle is NULL");
     ARGCHK(active, "active is NULL");
-    memcpy(active, h->active_host, (size_t)h->N);
+    memcpy(active, h->rep.caller_mask(), (size_t)h->N);
     return PYVB_OK;
 }
 

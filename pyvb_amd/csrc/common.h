@@ -2,6 +2,7 @@
 #pragma once
 #include <cstdint>
 #include "host.h"
+#include "replicates.h"
 
 struct pyvb_comm;
 typedef double d4 __attribute__((ext_vector_type(4)));
@@ -114,30 +115,27 @@ struct pyvb_lds {
     double *sxx;                    // [N][W][DP][DP] interior sum of mu mu^T from the backward sweep
     double *mom;                    // [N][3 D^2 + K D + D] second moments (k_moments)
     double *resQ, *resR;            // [N][D], [N][K]
-    double *elbo, *elbo_sum;        // [N][6], [6]
+    double *elbo, *elbo_sum;        // [N][6], [8]: the six parts, then the number of replicates still running (k_elbo_sum)
     int *status;                    // device, [N]: PYVB_FAIL_* bits of the replicates whose factorisations met a non-positive pivot
-    // ---- per-replicate bookkeeping: the activity mask (it can only shrink) and the flags the last failed pyvb_lds_sync reported
+    // ---- per-replicate bookkeeping.  What replicate n is -- chain length, model, switched off, converged -- lives on the host in
+    // `rep` (replicates.h); the device arrays below are what the kernels read of it.
+    Replicates rep;
     unsigned char *active;          // device, [N]: 0 = switched off or converged; every update kernel leaves such a replicate's rows alone
-    unsigned char *active_host;     // the caller's mask on the host (set_active is stream ordered, the mirror is what the host logic reads)
-    int n_active;                   // replicates the update kernels run: switched on and not converged
     // ---- per-replicate convergence (pyvb_lds_iterate_until, k_converge.hip).  `active` above is the mask the update kernels run:
-    // the caller's mask without the converged replicates.  `counted` is the mask the totals count: the caller's mask alone
-    // (active_host mirrors it).  The two are equal until a replicate converges.
+    // the caller's mask without the converged replicates (rep.run_mask()).  `counted` is the mask the totals count: the caller's
+    // mask alone (rep.caller_mask()).  The two are equal until a replicate converges.
     unsigned char *counted;         // device, [N]
-    unsigned char *conv;            // device, [N]: 1 = converged, frozen for the life of the handle
-    unsigned char *conv_host;       // its host mirror, reconciled when pyvb_lds_iterate_until returns
+    unsigned char *conv;            // device, [N]: 1 = converged, frozen for the life of the handle (rep adopts it when iterate_until returns)
     int *conv_iters;                // device, [N]: iterations carried out under pyvb_lds_iterate_until
     double *conv_llb;               // device, [N]: the last bound the test saw (the next test's `old`); NaN before the first
     double *running_host;           // pinned, [1]: the number of running replicates (all ranks) as of the last check
     hipEvent_t ev_check;            // that copy has arrived
     // ---- per-replicate chain lengths (pyvb_lds_create_lengths): null on a handle whose chains all have T nodes
     int *len;                       // device, [N]: T_n.  T stays the row stride of every [N][T][..] buffer; rows t >= T_n are padding
-    int *len_host;                  // its host copy (setters and getters: which rows are padding)
-    // ---- several chains, one model (pyvb_lds_create_tied, k_tie.hip): all null / 0 on a handle whose models are single replicates
-    int *mstart; int M;             // device, [M + 1]: model m is replicates mstart[m] .. mstart[m + 1] - 1
+    // ---- several chains, one model (pyvb_lds_create_tied, k_tie.hip): null on a handle whose models are single replicates
+    int *mstart;                    // device, [rep.M() + 1]: model m is replicates mstart[m] .. mstart[m + 1] - 1
     unsigned char *first;           // device, [N]: 1 = the first replicate of its model, where k_elbo books the shared nodes' terms
-    int *model_host;                // [N] the model of every replicate
-    int *status_host, *reported;    // [N] staging of a read of status; [N] what the most recent failed sync reported and cleared
+    std::vector<int> status_host, reported;     // [N] staging of a read of status; [N] what the most recent failed sync reported and cleared
     LdsState st;                    // what is current on the device (host.h); written by the events of api.hip only
     DeviceBuffers mem;              // every device allocation of this handle
     bool timing; KernelTimer timers[PYVB_K_COUNT]; int timing_errors;
@@ -184,14 +182,10 @@ int launch_cols(pyvb_lds* h, int which, int c0, int c1, int fuse = 0);   // whic
 int launch_resid(pyvb_lds* h, int which);     // 0 = Q, 1 = R
 int launch_noise(pyvb_lds* h, int which);
 int launch_elbo(pyvb_lds* h, hipStream_t stream = nullptr);                           // stream: the handle's main one unless given
-int launch_elbo_sum(pyvb_lds* h, double* out = nullptr, hipStream_t stream = nullptr);    // out: h->elbo_sum unless given
-// k_converge.hip: the stopping test of network.py:53 per replicate with the freeze of those it stops (first: old = -inf), and
-// the totals of an iteration with out[6] = the number of replicates still running
+int launch_elbo_sum(pyvb_lds* h, double* out = nullptr, hipStream_t stream = nullptr);    // out: h->elbo_sum unless given; [7], out[6] = replicates still running
+// k_converge.hip: the stopping test of network.py:53 on the bound of every model (on a handle without tied models: of every
+// replicate) with the freeze of the chains it stops (first: old = -inf)
 int launch_converge(pyvb_lds* h, double tol, bool first, hipStream_t stream);
-int launch_elbo_sum_running(pyvb_lds* h, double* out, hipStream_t stream);
-// k_converge_model.hip: the same test on the bound of every model (the sum over its chains), the freeze of all chains of the
-// models it stops; on a handle whose models are single replicates it launches k_converge
-int launch_converge_model(pyvb_lds* h, double tol, bool first, hipStream_t stream);
 // k_big.hip
 int launch_prep_big(pyvb_lds* h);
 int big_prepare_kernels();              // once per device, before the first launch: the dynamic-LDS limits of k_prep_big, k_cols_big

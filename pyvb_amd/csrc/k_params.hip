@@ -204,21 +204,33 @@ __global__ void __launch_bounds__(64 * NW) k_elbo(ParamArgs a) {
     }
 }
 
-// (rows of switched-off replicates keep the parts they had then, for pyvb_lds_get_elbo; the totals leave them out)
-struct SumArgs { const double* elbo; double* out; const unsigned char* active; int N; };
+// The totals of an iteration over the replicates that count: the running ones at their current bound and the converged ones at
+// their final one (rows of switched-off replicates keep the parts they had then, for pyvb_lds_get_elbo; the totals leave them
+// out).  out[6]: how many replicates are still running (it rides through the all-reduce of pyvb_lds_iterate_until with the six
+// parts, so that every rank stops in the same iteration).
+struct SumArgs { const double* elbo; double* out; const unsigned char* counted; const unsigned char* active; int N; };
 __global__ void __launch_bounds__(256) k_elbo_sum(SumArgs a) {
     __shared__ double red[256 * 6];
+    __shared__ int cnt[256];
     const int tid = threadIdx.x;
     double s[6] = {0, 0, 0, 0, 0, 0};
-    for (int n = tid; n < a.N; n += 256)
-        if (a.active[n])
+    int c = 0;
+    for (int n = tid; n < a.N; n += 256) {
+        if (a.counted[n])
             for (int p = 0; p < 6; ++p) s[p] += a.elbo[(size_t)n * 6 + p];
+        c += a.active[n] != 0;
+    }
     for (int p = 0; p < 6; ++p) red[p * 256 + tid] = s[p];
+    cnt[tid] = c;
     __syncthreads();
     if (tid < 6) {
         double t = 0.0;
         for (int i = 0; i < 256; ++i) t += red[tid * 256 + i];
         a.out[tid] = t;
+    } else if (tid == 6) {
+        int t = 0;
+        for (int i = 0; i < 256; ++i) t += cnt[i];
+        a.out[6] = (double)t;
     }
 }
 
@@ -294,7 +306,7 @@ int launch_elbo(pyvb_lds* h, hipStream_t stream) {
 
 int launch_elbo_sum(pyvb_lds* h, double* out, hipStream_t stream) {
     // the mask the totals count: a converged replicate stays in them at its final bound (common.h: counted)
-    SumArgs a; a.elbo = h->elbo; a.out = out ? out : h->elbo_sum; a.active = h->counted; a.N = h->N;
+    SumArgs a; a.elbo = h->elbo; a.out = out ? out : h->elbo_sum; a.counted = h->counted; a.active = h->active; a.N = h->N;
     hipLaunchKernelGGL(k_elbo_sum, dim3(1), dim3(256), 0, stream ? stream : h->stream, a);
     HIPCHK(hipGetLastError());
     return PYVB_OK;

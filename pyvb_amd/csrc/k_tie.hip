@@ -48,8 +48,8 @@ __global__ void __launch_bounds__(256) k_tie(TieArgs a) {
 // buf: h->mom (per = mom_total) or h->Syy (per = K).  Rows start 16-byte aligned exactly when per is even.
 int launch_tie(pyvb_lds* h, double* buf, size_t per) {
     if (!h->mstart) return PYVB_OK;
-    TieArgs a; a.buf = buf; a.mstart = h->mstart; a.active = h->active; a.per = per; a.M = h->M;
-    const unsigned gy = h->M < 65535 ? h->M : 65535;
+    TieArgs a; a.buf = buf; a.mstart = h->mstart; a.active = h->active; a.per = per; a.M = h->rep.M();
+    const unsigned gy = a.M < 65535 ? a.M : 65535;
     TimedLaunch tl(h, PYVB_K_PARAMS);
     if (per % 2 == 0) hipLaunchKernelGGL(k_tie<d2>, dim3((unsigned)((per / 2 + 255) / 256), gy), dim3(256), 0, h->stream, a);
     else hipLaunchKernelGGL(k_tie<double>, dim3((unsigned)((per + 255) / 256), gy), dim3(256), 0, h->stream, a);

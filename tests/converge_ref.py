@@ -70,13 +70,13 @@ def problem(name):
     return Y, st0, pri, (None if lengths is None else np.asarray(lengths, dtype=np.int32))
 
 
-def learn_alone(Yn, st, pri, bound, tol, max_iters, old=-np.inf):
-    """Network.learn's loop (network.py:46-56) on one replicate in the oracle, st updated in place.  Returns (iterations
-    carried out, converged, parts [iterations, 6], the smallest distance of a delta from tol relative to max(1, |llb|))."""
-    step = XR.iterate_exact if bound == "exact" else O.iterate
+def learn(step, tol, max_iters, old=-np.inf):
+    """Network.learn's loop (network.py:46-56) around step(), one iteration of the oracle that returns its six parts.  Returns
+    (iterations carried out, converged, parts [iterations, 6], the smallest distance of a delta from tol relative to
+    max(1, |llb|)).  tests/model_converge_ref.py runs its models through the same loop."""
     trace, margin, converged = [], np.inf, False
     for i in range(max_iters):
-        parts = step(st, pri, Yn)[0]
+        parts = step()
         trace.append(parts)
         llb = parts.sum()
         if i > 0:
@@ -86,6 +86,18 @@ def learn_alone(Yn, st, pri, bound, tol, max_iters, old=-np.inf):
             break
         old = llb
     return len(trace), converged, np.array(trace).reshape(-1, 6), margin
+
+
+def guarded(run, tol, what):
+    """A result of learn() that a test may compare stop iterations with: no delta it met is a rounding matter."""
+    assert run[3] >= GUARD, "%s: a delta of the reference lies %.2e (relative) from tol = %g" % (what, run[3], tol)
+    return run
+
+
+def learn_alone(Yn, st, pri, bound, tol, max_iters, old=-np.inf):
+    """learn() on one replicate in the oracle, st updated in place."""
+    step = XR.iterate_exact if bound == "exact" else O.iterate
+    return learn(lambda: step(st, pri, Yn)[0], tol, max_iters, old)
 
 
 def start_alone(name, n):
@@ -112,8 +124,7 @@ def alone(name, tol=None, max_iters=None):
     out = []
     for n in range(Y.shape[0]):
         Yn, st = start_alone(name, n)
-        iters, converged, trace, margin = learn_alone(Yn, st, pri, c["bound"], tol, max_iters)
-        assert margin >= GUARD, "case %s, replicate %d: a delta of the reference lies %.2e (relative) from tol = %g" % (name, n, margin, tol)
+        iters, converged, trace, margin = guarded(learn_alone(Yn, st, pri, c["bound"], tol, max_iters), tol, "case %s, replicate %d" % (name, n))
         out.append(dict(iters=iters, converged=converged, trace=trace, margin=margin, st=st, Y=Yn))
     return out
 
@@ -130,8 +141,7 @@ def resumed(name, tol, max_iters):
             out.append(dict(r, trace=r["trace"][-1:], moved=False))
             continue
         st = copy.deepcopy(r["st"])
-        iters, converged, trace, margin = learn_alone(r["Y"], st, pri, c["bound"], tol, max_iters)
-        assert margin >= GUARD, "case %s resumed: a delta of the reference lies %.2e (relative) from tol = %g" % (name, margin, tol)
+        iters, converged, trace, margin = guarded(learn_alone(r["Y"], st, pri, c["bound"], tol, max_iters), tol, "case %s resumed" % name)
         out.append(dict(iters=r["iters"] + iters, converged=converged, trace=trace, margin=margin, st=st, Y=r["Y"], moved=True))
     return out
 

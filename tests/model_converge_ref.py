@@ -86,20 +86,8 @@ def parts_fn(bound):
 
 
 def learn_model(chains, pri, Ys, bound, tol, max_iters, update_outputs=False):
-    """Network.learn's loop (network.py:46-56) on one model, its chains updated in place.  Returns (iterations carried out,
-    converged, parts [iterations, 6], the smallest distance of a delta from tol relative to max(1, |llb|))."""
-    trace, margin, converged, old = [], np.inf, False, -np.inf
-    for i in range(max_iters):
-        parts = TR.iterate(chains, pri, Ys, update_outputs=update_outputs, parts_fn=parts_fn(bound))
-        trace.append(parts)
-        llb = parts.sum()
-        if i > 0:
-            margin = min(margin, abs((llb - old) - tol) / max(1.0, abs(llb)))
-        if llb - old < tol:                             # network.py:53 (old = -inf: the first iteration stops nobody)
-            converged = True
-            break
-        old = llb
-    return len(trace), converged, np.array(trace).reshape(-1, 6), margin
+    """converge_ref.learn (Network.learn's loop, network.py:46-56) on one model, its chains updated in place."""
+    return R.learn(lambda: TR.iterate(chains, pri, Ys, update_outputs=update_outputs, parts_fn=parts_fn(bound)), tol, max_iters)
 
 
 @functools.lru_cache(maxsize=None)
@@ -130,8 +118,7 @@ def alone(name, tol=None, max_iters=None):
     pri = problem(name)[2]
     out = []
     for m, (rows, chains, Ys) in enumerate(start(name)):
-        iters, converged, trace, margin = learn_model(chains, pri, Ys, c["bound"], tol, max_iters)
-        assert margin >= GUARD, "case %s, model %d: a delta of the reference lies %.2e (relative) from tol = %g" % (name, m, margin, tol)
+        iters, converged, trace, margin = R.guarded(learn_model(chains, pri, Ys, c["bound"], tol, max_iters), tol, "case %s, model %d" % (name, m))
         out.append(dict(rows=rows, iters=iters, converged=converged, trace=trace, margin=margin, chains=chains, Ys=Ys))
     return out
 
@@ -149,8 +136,8 @@ def resumed(name, first_max_iters, tol, max_iters):
             continue
         chains = copy.deepcopy(r["chains"])
         TR._share(chains)
-        iters, converged, trace, margin = learn_model(chains, pri, r["Ys"], c["bound"], tol, max_iters)
-        assert margin >= GUARD, "case %s resumed, model %d: a delta of the reference lies %.2e (relative) from tol = %g" % (name, m, margin, tol)
+        iters, converged, trace, margin = R.guarded(learn_model(chains, pri, r["Ys"], c["bound"], tol, max_iters), tol,
+                                                    "case %s resumed, model %d" % (name, m))
         out.append(dict(r, iters=r["iters"] + iters, converged=converged, trace=trace, margin=margin, chains=chains, moved=True))
     return out
 

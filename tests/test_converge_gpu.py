@@ -277,3 +277,121 @@ def test_argument_errors():
         assert not it.any() and not cv.any() and np.isnan(llb).all()
     finally:
         b.close()
+
+
+# ---- 9. what a refactor of the stopping loop must not move -------------------------------------------------------------------
+def _small(models=None):
+    """N = 5, T = 12, D = 4, K = 5, DiagonalGamma, chains of 12, 2, 7, 3, 12 nodes (padding zeroed as R.problem does)."""
+    from pyvb_amd import synth
+    from pyvb_amd.lds import LDSBatch
+    lengths = np.array([12, 2, 7, 3, 12], dtype=np.int32)
+    Y, st0, pri = synth.make_problem(12, 4, 5, 5, seed=8500)
+    live = np.arange(12)[None, :] < lengths[:, None]
+    Y = np.where(live[:, :, None], Y, 0.0)
+    st0["X"] = np.where(live[:, :, None], st0["X"], 0.0)
+    return LDSBatch.from_problem(Y, st0, pri, lengths=lengths, models=models)
+
+
+def test_the_three_loops_agree_bitwise_when_nobody_stops():
+    """iterate(6), iterate_until(6, -inf) and iterate_until_model(6, -inf): llb - old < -inf is never true, so nobody stops and
+    the three loops carry out the same six iterations -- the bound on the side stream in one, on the main stream in the others."""
+    ninf = float("-inf")
+    loops = {"iterate": lambda b: b.iterate(6), "until": lambda b: b.iterate_until(6, ninf, 4), "until_model": lambda b: b.iterate_until_model(6, ninf, 4)}
+    for models, names in ((None, ("iterate", "until", "until_model")), (np.array([0, 0, 1, 2, 2], dtype=np.int32), ("iterate", "until_model"))):
+        got = {}
+        for nm in names:
+            b = _small(models)
+            try:
+                ran = loops[nm](b)
+                assert ran in (None, 6), (nm, ran)
+                g = dict(history=b.elbo_history(), total=b.elbo_total(), all=_everything(b, with_elbo=False))
+                g["iters"], g["converged"], g["llb"] = b.convergence()
+                got[nm] = g
+            finally:
+                b.close()
+        base = got["iterate"]
+        assert base["history"].shape == (6, 6) and np.all(np.isfinite(base["history"]))
+        for nm in names[1:]:
+            what = "%s against iterate, models %r" % (nm, models)
+            assert np.array_equal(got[nm]["history"], base["history"]), what
+            assert np.array_equal(got[nm]["total"], base["total"]), what
+            _same_rows(got[nm]["all"], base["all"], slice(None), what)
+            assert list(got[nm]["iters"]) == [6] * 5 and not got[nm]["converged"].any(), what
+            assert np.all(np.isfinite(got[nm]["llb"])), what
+        if "until" in got:      # the last bound the test saw is defined in both
+            assert np.array_equal(got["until"]["llb"], got["until_model"]["llb"])
+
+
+SUM_OFF = (0, 41, 97, 150, 255, 256, 299)       # switched off: row 0 and row 299 among them, a pair that shares a thread (0 and 256)
+
+
+@functools.lru_cache(maxsize=None)
+def _sum_problem():
+    """N = 300 (the smallest N at which some of the 256 threads of the totals kernel add two rows), T = 4, D = 2, K = 2: the
+    problem, the oracle's bound over four iterations, and a tol at which some replicates but not all stop within them.  The
+    oracle runs the batch at once (replicates share no arithmetic); tol is the middle of the widest gap between deltas at which
+    20-80 % of the replicates that are switched on stop."""
+    from oracle import lds_closed_form as O
+    from pyvb_amd import synth
+    N, T, D, K = 300, 4, 2, 2
+    Y, st0, pri = synth.make_problem(T, D, K, N, seed=8600)
+    st = O.expand_state(st0, pri, T)
+    trace = np.array([O.iterate(st, pri, Y) for _ in range(4)])            # [4, N, 6]
+    mask = np.ones(N, dtype=bool); mask[list(SUM_OFF)] = False
+    d = np.diff(trace.sum(2), axis=0)[:, mask]                              # [3, on] the deltas a run with tol = -inf meets
+    cand = np.sort(d.ravel())
+    mid, gap = 0.5 * (cand[1:] + cand[:-1]), np.diff(cand)
+    share = np.array([(d.min(0) < t).mean() for t in mid])
+    ok = (share >= 0.2) & (share <= 0.8)
+    tol = float(mid[ok][np.argmax(gap[ok])])
+    return Y, st0, pri, mask, trace, tol
+
+
+def _kernel_order_total(rows, mask):
+    """The totals as the kernel forms them: thread tid adds rows tid, tid + 256, .. that count, in turn; then the 256 partial
+    sums are added in ascending order."""
+    out = np.zeros(6)
+    for p in range(6):
+        t = np.float64(0.0)
+        for tid in range(256):
+            s = np.float64(0.0)
+            for n in range(tid, len(rows), 256):
+                if mask[n]:
+                    s = s + rows[n, p]
+            t = t + s
+        out[p] = t
+    return out
+
+
+def test_the_totals_are_the_kernel_s_own_sum_order():
+    from pyvb_amd.lds import LDSBatch
+    Y, st0, pri, mask, trace, tol = _sum_problem()
+    # the reference's decisions at this tol, through converge_ref's loop and its guard, asserted before anything is compared
+    runs = []
+    for n in np.nonzero(mask)[0]:
+        rows = iter(trace[:, n])
+        runs.append(R.guarded(R.learn(lambda: next(rows), tol, 4), tol, "totals, replicate %d" % n))
+    stopped = sum(r[1] for r in runs)
+    print("tol %.6g: %d of %d replicates stop within 4 iterations, smallest margin %.2e" % (tol, stopped, len(runs), min(r[3] for r in runs)))
+    assert 0 < stopped < len(runs)
+    for loop in ("until", "iterate"):
+        b = LDSBatch.from_problem(Y, st0, pri)
+        try:
+            b.set_active(mask)
+            if loop == "until":
+                assert b.iterate_until(4, tol, 8) == 4
+                it, cv, _ = b.convergence()
+                assert list(it[mask]) == [r[0] for r in runs] and list(cv[mask]) == [r[1] for r in runs]
+                assert not it[~mask].any() and not cv[~mask].any()
+            else:
+                b.iterate(2)
+            history, total = b.elbo_history(), b.elbo_total()
+            rows = b.elbo()
+            assert np.array_equal(b.active(), mask)
+            want = _kernel_order_total(rows, b.active())
+            print("%s: total %r" % (loop, total))
+            assert np.array_equal(total, want), (loop, total - want)
+            assert np.array_equal(history[-1], want), (loop, history[-1] - want)
+            assert np.array_equal(b.elbo_total(), want), loop
+        finally:
+            b.close()

@@ -11,7 +11,7 @@ Base case: D = 4, K = 5 (no multiple of 16), T = 60, eight chains in models of [
 models -- with ragged lengths that include T_n = 2 and 3.  Both of its runs freeze models in odd and in even iterations.
 
 "Bitwise" is justified as in tests/test_tied_gpu.py: rows share no arithmetic but the fixed-order sums over the chains of a model
-(k_tie.hip, k_converge_model.hip), so two handles of the same shapes, lengths, models and time split run the same instructions in
+(k_tie.hip, k_converge.hip), so two handles of the same shapes, lengths, models and time split run the same instructions in
 the same order on the rows both compute.
 """
 import functools
