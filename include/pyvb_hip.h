@@ -176,6 +176,25 @@ int pyvb_lds_get_outputs(pyvb_lds* h, double* Yq, double* Yvar, double* Yqld);
  * Call after set_state: fully known columns take their value at once, partially known ones at their next update. */
 int pyvb_lds_set_column_observations(pyvb_lds* h, const double* A_obs, const double* C_obs);
 
+/* Automatic relevance determination: Gamma precision parents for the columns of A (which = 0, rows = D) or C (which = 1,
+ * rows = K).  Column i becomes Gaussian(rows, pm_i, alpha_i) with alpha_i = Gamma(rows, a0_i, b0_i) (gaussian.py:55-61;
+ * nodes_todo.py:113-157) in place of its Constant precision: the prior precision of the column is qa_i / qb[n][i] in every row,
+ * qa_i = a0_i + rows / 2 is fixed by the graph, and
+ *   alpha_i.update():  qb[n][i] = b0_i + 1/2 sum_k ((M[k,i] - pm[k,i])^2 + V[i][k])      (known entries: M = value, V = 0).
+ * The lower bound takes rows (ln qa - ln qb) (reference mode, quirk Q2) or rows (psi(qa) - ln qb) (exact mode) as the column's
+ * ln det, and adds the alpha nodes' own terms to part 2 (A) and part 3 (C).
+ *   a0[D], b0[D]: per column, shared by the replicates like every prior.
+ *   qb[N][D]: initial state (the reference draws rand(), nodes_todo.py:119).  On a handle with tied models it is taken from
+ *   each model's first row and copied to its other rows, as pyvb_lds_set_state does.
+ * Call after pyvb_lds_set_priors; a later pyvb_lds_set_priors returns both matrices to Constant parents.
+ * pyvb_lds_iterate, pyvb_lds_iterate_until and pyvb_lds_iterate_until_model on such a handle run forward, backward, A, C, Q, R,
+ * alpha_A, alpha_C, bound.  Switched-off and converged replicates keep their qb.
+ * PYVB_E_UNSUPPORTED: Wishart noise, or max(D, K) > 64.  PYVB_E_ARG: which outside {0, 1}; a non-finite or non-positive a0, b0
+ * or qb (the message names the column, or the replicate and column); get / update for a matrix without hyperpriors. */
+int pyvb_lds_set_column_precisions(pyvb_lds* h, int which, const double* a0, const double* b0, const double* qb);
+int pyvb_lds_get_column_precisions(pyvb_lds* h, int which, double* qa, double* qb);   /* [N][D] each; NULL = skip */
+int pyvb_lds_update_column_precisions(pyvb_lds* h, int which);     /* [al.update() for al in alphas of that matrix] */
+
 /* Explicit posterior state instead of the constructors' random initialisation
  * (gaussian.py:70-72, nodes_todo.py:119,177). */
 int pyvb_lds_set_state(pyvb_lds* h, const double* X, const double* A_mean, const double* A_colvar,

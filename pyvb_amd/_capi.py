@@ -52,6 +52,9 @@ SIGNATURES = {
     "pyvb_lds_update_Y": (ctypes.c_int, [_h]),
     "pyvb_lds_get_outputs": (ctypes.c_int, [_h, _dp, _dp, _dp]),
     "pyvb_lds_set_column_observations": (ctypes.c_int, [_h, _dp, _dp]),
+    "pyvb_lds_set_column_precisions": (ctypes.c_int, [_h, ctypes.c_int, _dp, _dp, _dp]),
+    "pyvb_lds_get_column_precisions": (ctypes.c_int, [_h, ctypes.c_int, _dp, _dp]),
+    "pyvb_lds_update_column_precisions": (ctypes.c_int, [_h, ctypes.c_int]),
     "pyvb_lds_set_state": (ctypes.c_int, [_h] + [_dp] * 7),
     "pyvb_lds_get_state": (ctypes.c_int, [_h] + [_dp] * 9),
     "pyvb_lds_get_posterior_classes": (ctypes.c_int, [_h, _dp, _dp]),

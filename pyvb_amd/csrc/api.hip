@@ -51,7 +51,7 @@ void pyvb_timing_resolve(pyvb_lds* h) {
 extern "C" {
 
 const char* pyvb_last_error(void) { return g_err; }
-int pyvb_version(void) { return 104; }
+int pyvb_version(void) { return 105; }
 
 int pyvb_device_count(int* count) {
     ARGCHK(count, "count is NULL");
@@ -371,8 +371,92 @@ int pyvb_lds_set_priors(pyvb_lds* h, const double* x0_mean, const double* x0_pre
         if ((rc = h2d(h, h->R_a, ra.data(), ra.size()))) return rc;
         HIPCHK(hipStreamSynchronize(h->stream));       // qa, ra are about to go out of scope
     }
+    h->ard[0].on = h->ard[1].on = false;       // the columns have Constant parents again (pyvb_lds_set_column_precisions comes after)
     h->st.parameters_changed();
     return PYVB_OK;
+}
+
+// ---- Gamma parents of the columns of A / C (automatic relevance determination, k_ard.hip) ----
+static int ard_which(const pyvb_lds* h, int which, bool need_on) {
+    ARGCHK(which == 0 || which == 1, "which must be 0 (A) or 1 (C)");
+    if (need_on && !h->ard[which].on) {
+        pyvb_set_error("the columns of %s have Constant precision parents: no hyperpriors were given (pyvb_lds_set_column_precisions)",
+                       which == 0 ? "A" : "C");
+        return PYVB_E_ARG;
+    }
+    return PYVB_OK;
+}
+
+int pyvb_lds_set_column_precisions(pyvb_lds* h, int which, const double* a0, const double* b0, const double* qb) {
+    ARGCHK(h, "handle is NULL");
+    int rc = ard_which(h, which, false);
+    if (rc) return rc;
+    if (h->dense) {
+        pyvb_set_error("Gamma precision parents of the columns are served with DiagonalGamma and Gamma noise only, not with Wishart noise (k_wishart.hip)");
+        return PYVB_E_UNSUPPORTED;
+    }
+    if (h->big) {
+        pyvb_set_error("Gamma precision parents of the columns are served for max(D, K) <= 64 only, not in the 128-wide class (k_big.hip): D = %d, K = %d", h->D, h->K);
+        return PYVB_E_UNSUPPORTED;
+    }
+    ARGCHK(a0 && b0 && qb, "a0, b0 and qb are required");
+    const size_t N = h->N, D = h->D;
+    const int rows = which == 0 ? h->D : h->K;
+    const char* nm = which == 0 ? "A" : "C";
+    for (size_t i = 0; i < D; ++i) {
+        if (!(a0[i] > 0.0 && a0[i] - a0[i] == 0.0)) { pyvb_set_error("a0 of column %d of %s is %g: it must be finite and positive", (int)i, nm, a0[i]); return PYVB_E_ARG; }
+        if (!(b0[i] > 0.0 && b0[i] - b0[i] == 0.0)) { pyvb_set_error("b0 of column %d of %s is %g: it must be finite and positive", (int)i, nm, b0[i]); return PYVB_E_ARG; }
+    }
+    // Chains that share A, C, Q, R: the row of a model's first replicate is the model's state and goes to all its rows
+    std::vector<double> rowsqb(N * D), qa(D);
+    for (size_t n = 0; n < N; ++n) {
+        const double* src = qb + (size_t)h->rep.first_of((int)n) * D;
+        for (size_t i = 0; i < D; ++i) {
+            if (!(src[i] > 0.0 && src[i] - src[i] == 0.0)) {
+                pyvb_set_error("qb of replicate %d, column %d of %s is %g: it must be finite and positive", h->rep.first_of((int)n), (int)i, nm, src[i]);
+                return PYVB_E_ARG;
+            }
+            rowsqb[n * D + i] = src[i];
+        }
+    }
+    for (size_t i = 0; i < D; ++i) qa[i] = a0[i] + 0.5 * rows;      // update_a, nodes_todo.py:125-128: one child of `rows` entries
+    ENTER(h);
+    ArdBuffers& g = h->ard[which];
+    if (!g.qb) {
+        double* blk = nullptr;
+        if ((rc = h->mem.zeros(&blk, 3 * D + 4 * N * D))) return rc;
+        g.a0 = blk; g.b0 = blk + D; g.qa = blk + 2 * D;
+        g.ex = blk + 3 * D; g.ld_ref = g.ex + N * D; g.ld_exact = g.ld_ref + N * D; g.qb = g.ld_exact + N * D;
+    }
+    if ((rc = h2d(h, g.a0, a0, D)) || (rc = h2d(h, g.b0, b0, D)) || (rc = h2d(h, g.qa, qa.data(), D)) || (rc = h2d(h, g.qb, rowsqb.data(), N * D))) return rc;
+    g.on = true;
+    if ((rc = launch_ard(h, which, true))) return rc;       // qa / qb and the two log-determinants of every row, from qb as given
+    HIPCHK(hipStreamSynchronize(h->stream));               // the staging vectors are about to go out of scope
+    // (nothing on the host depends on the column priors: gains, statistics and residuals read the columns, not their parents)
+    return PYVB_OK;
+}
+
+int pyvb_lds_get_column_precisions(pyvb_lds* h, int which, double* qa, double* qb) {
+    ARGCHK(h, "handle is NULL");
+    int rc = ard_which(h, which, true);
+    if (rc) return rc;
+    ENTER(h);
+    const size_t N = h->N, D = h->D;
+    std::vector<double> a(qa ? D : 0);
+    if (qa && (rc = d2h(h, a.data(), h->ard[which].qa, D))) return rc;
+    if ((rc = d2h(h, qb, h->ard[which].qb, N * D))) return rc;
+    if ((rc = pyvb_lds_sync(h))) return rc;
+    for (size_t n = 0; qa && n < N; ++n) memcpy(qa + n * D, a.data(), D * sizeof(double));
+    return PYVB_OK;
+}
+
+int pyvb_lds_update_column_precisions(pyvb_lds* h, int which) {
+    ARGCHK(h, "handle is NULL");
+    int rc = ard_which(h, which, true);
+    if (rc) return rc;
+    ENTER(h);
+    IDLE(h);
+    return launch_ard(h, which, false);
 }
 
 int pyvb_lds_set_wishart_priors(pyvb_lds* h, double Q_v0, const double* Q_w0, double R_v0, const double* R_w0) {
@@ -960,6 +1044,10 @@ static int iterate_updates(pyvb_lds* h) {
         if ((rc = launch_cols(h, 2, 0, h->D, 3))) return rc;       // columns, residuals and noise update in one launch
         h->st.columns_updated(2, false);
         h->st.noise_updated(2);
+        // [al.update() for al in alphas]: they read their own column and feed the next column update only, so they commute with Q
+        // and R.  They sit behind the join_elbo above like k_cols: the bound of the iteration before reads qb and qa / qb.
+        const bool aa = h->ard[0].on, ac = h->ard[1].on;
+        if ((aa || ac) && (rc = launch_ard(h, aa && ac ? 2 : (ac ? 1 : 0), false))) return rc;
     }
     if (h->bound == PYVB_BOUND_EXACT && (rc = ensure_lnd_x(h))) return rc;       // (only before the first complete sweep)
     return PYVB_OK;

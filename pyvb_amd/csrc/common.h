@@ -78,6 +78,14 @@ struct Priors {          // device pointers, shared by all replicates
     double Q_a0_host, R_a0_host, Q_w0_lndet, R_w0_lndet;    // Wishart: v0 and ln det w0 of the two priors
 };
 
+// Gamma parents of the columns of one matrix (pyvb_lds_set_column_precisions, k_ard.hip): allocated by the first call that gives
+// the matrix hyperpriors, never on a handle that makes none.  `on` is what make_args reads; pyvb_lds_set_priors clears it.
+struct ArdBuffers {
+    bool on;
+    double *a0, *b0, *qa;                   // [D] each, shared by the replicates; qa_i = a0_i + rows / 2
+    double *qb, *ex, *ld_ref, *ld_exact;    // [N][D] each: see ColumnPrior (params.h)
+};
+
 struct EventPair;
 struct KernelTimer {
     double total_ms; int launches;
@@ -100,6 +108,7 @@ struct pyvb_lds {
     int bound;                      // PYVB_BOUND_REFERENCE / PYVB_BOUND_EXACT: which lower bound k_elbo / k_elbo_dense form
     Priors pri;
     double *pri_block;
+    ArdBuffers ard[2];              // Gamma parents of the columns of A ([0]) and C ([1]); all null / off unless the caller asked
     // derived
     double *Sigma, *qld_x;          // as of the last X update: [N][3][D][D], [N][3]
     double *Sigma_new, *qld_x_new;  // written by k_prep for the current parameters
@@ -180,6 +189,8 @@ int launch_observe(pyvb_lds* h);
 int launch_tie(pyvb_lds* h, double* buf, size_t per);      // k_tie.hip: sum rows of [N][per] over the chains of every model, in place
 int launch_cols(pyvb_lds* h, int which, int c0, int c1, int fuse = 0);   // which: 0 = A, 1 = C, 2 = both; columns [c0, c1); fuse: see k_cols.hip
 int launch_resid(pyvb_lds* h, int which);     // 0 = Q, 1 = R
+// k_ard.hip: [al.update() for al in alphas] of A (0), C (1) or both (2); derive: form qa / qb and the log-determinants from qb as given
+int launch_ard(pyvb_lds* h, int which, bool derive);
 int launch_noise(pyvb_lds* h, int which);
 int launch_elbo(pyvb_lds* h, hipStream_t stream = nullptr);                           // stream: the handle's main one unless given
 int launch_elbo_sum(pyvb_lds* h, double* out = nullptr, hipStream_t stream = nullptr);    // out: h->elbo_sum unless given; [7], out[6] = replicates still running

@@ -56,7 +56,10 @@ __global__ void __launch_bounds__(64) k_cols(ParamArgs a) {
     double* qld = (WHICH == 0 ? a.qld_A : a.qld_C) + (size_t)n * D;
     double* lnd = (WHICH == 0 ? a.lnd_A : a.lnd_C) + (size_t)n * D;
     const double* pm = WHICH == 0 ? a.pri.A_pm : a.pri.C_pm;    // [row][col]
-    const double* pp = WHICH == 0 ? a.pri.A_pp : a.pri.C_pp;    // [col][row]
+    // prior precision of (column i, this lane's row): pp[i * ppc] (params.h: ColumnPrior; Constant parents: [col][row])
+    const double* pp = (WHICH == 0 ? a.cpA.pp : a.cpC.pp) + (size_t)n * (WHICH == 0 ? a.cpA.pp_n : a.cpC.pp_n);
+    const size_t ppc = WHICH == 0 ? a.cpA.pp_c : a.cpC.pp_c;
+    const int ppr = WHICH == 0 ? a.cpA.pp_r : a.cpC.pp_r;
     const double* obs = WHICH == 0 ? a.pri.A_obs : a.pri.C_obs; // [row][col], NaN = not observed
     const double* mo = a.mom + (size_t)n * mom_total(D, K);
     const double* G = mo + (WHICH == 0 ? MOM_GA(D, K) : MOM_GC(D, K));
@@ -68,6 +71,7 @@ __global__ void __launch_bounds__(64) k_cols(ParamArgs a) {
     const int nb = (D + 15) >> 4;
     const double* Mrow = M + (size_t)lr * D;
     const double* Hrow = H + (size_t)lr * D;
+    pp += (size_t)lr * ppr;
 
     // ---- this lane's row of M into LDS
     for (int b = 0; b < 4; ++b) {
@@ -115,7 +119,7 @@ __global__ void __launch_bounds__(64) k_cols(ParamArgs a) {
 #pragma unroll
             for (int u = 0; u < 16; ++u) {
                 const int i = 16 * b + u;
-                p0[u] = pp[(size_t)(i < D ? i : D - 1) * rows + lr];
+                p0[u] = pp[(size_t)(i < D ? i : D - 1) * ppc];
             }
             load_row16(pm + (size_t)lr * D, 16 * b, D, vec, 0.0, m0);
             load_row16(Hrow, 16 * b, D, vec, 0.0, hk);

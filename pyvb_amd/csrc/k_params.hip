@@ -156,10 +156,11 @@ __global__ void __launch_bounds__(64 * NW) k_elbo(ParamArgs a) {
     double la = 0.0, lc = 0.0;
     if (lane < D && first) {
         const int i = lane;   // column i
-        auto column = [&](int rows, const double* pp, const double* pm, const double* M, const double* V,
-                          const double* obs, double qld, double lndet) {
-            // this lane's rows of pp and V are contiguous, the columns of M, pm and obs are coalesced across lanes
-            const double* ppi = pp + (size_t)i * rows;
+        auto column = [&](int rows, const ColumnPrior& cp, const double* pm, const double* M, const double* V,
+                          const double* obs, double qld) {
+            // this lane's rows of pp (Constant parents) and V are contiguous, the columns of M, pm and obs are coalesced across lanes
+            const double* ppi = cp.pp + (size_t)n * cp.pp_n + (size_t)i * cp.pp_c;
+            const double lndet = cp.pld[(size_t)n * cp.pld_n + i];
             const double* Vi = V + (size_t)i * rows;
             double tr0 = 0.0, tr1 = 0.0, lvar = 0.0;
             int missing = 0;
@@ -168,7 +169,7 @@ __global__ void __launch_bounds__(64 * NW) k_elbo(ParamArgs a) {
 #pragma unroll
                 for (int u = 0; u < 8; ++u) {
                     const int k = k0 + u < rows ? k0 + u : rows - 1;
-                    p[u] = ppi[k]; v[u] = Vi[k];
+                    p[u] = ppi[(size_t)k * cp.pp_r]; v[u] = Vi[k];
                     m[u] = M[(size_t)k * D + i]; m0[u] = pm[(size_t)k * D + i]; ob[u] = obs[(size_t)k * D + i];
                 }
 #pragma unroll
@@ -190,12 +191,14 @@ __global__ void __launch_bounds__(64 * NW) k_elbo(ParamArgs a) {
                 if (exact) r += 0.5 * missing * LN2PI + 0.5 * lvar + 0.5 * missing;
                 else r -= 0.5 * missing * LN2PI - 0.5 * lvar - 0.5 * missing;
             }
+            // the column's Gamma parent, if it has one (k_ard.hip): its own term, the same in both modes (nodes_todo.py:149-157)
+            if (cp.qb) r += gamma_llb(cp.a0[i], cp.b0[i], cp.qa[i], cp.qb[(size_t)n * D + i]);
             return r;
         };
-        la = column(D, a.pri.A_pp, a.pri.A_pm, a.A_mean + (size_t)n * D * D, a.A_var + (size_t)n * D * D, a.pri.A_obs,
-                    (exact ? a.lnd_A : a.qld_A)[(size_t)n * D + i], a.pri.A_pld[i]);
-        lc = column(K, a.pri.C_pp, a.pri.C_pm, a.C_mean + (size_t)n * K * D, a.C_var + (size_t)n * D * K, a.pri.C_obs,
-                    (exact ? a.lnd_C : a.qld_C)[(size_t)n * D + i], a.pri.C_pld[i]);
+        la = column(D, a.cpA, a.pri.A_pm, a.A_mean + (size_t)n * D * D, a.A_var + (size_t)n * D * D, a.pri.A_obs,
+                    (exact ? a.lnd_A : a.qld_A)[(size_t)n * D + i]);
+        lc = column(K, a.cpC, a.pri.C_pm, a.C_mean + (size_t)n * K * D, a.C_var + (size_t)n * D * K, a.pri.C_obs,
+                    (exact ? a.lnd_C : a.qld_C)[(size_t)n * D + i]);
     }
     const double LA = first ? blk_sum<NW>(la, red) : 0.0, LC = first ? blk_sum<NW>(lc, red) : 0.0;
     if (lane == 0) {
@@ -261,6 +264,21 @@ ParamArgs make_args(pyvb_lds* h) {
     a.N = h->N; a.T = h->T; a.D = h->D; a.K = h->K; a.noise = h->noise; a.L = h->L; a.c0 = 0; a.c1 = h->D; a.which0 = 0; a.fuse = 0; a.sxx = nullptr; a.W = 1;
     a.active = h->active;
     a.len = h->len; a.Lw = 0; a.first = h->first;
+    // the prior precisions of the columns (params.h: ColumnPrior): Constant parents, or the Gamma parents of pyvb_lds_set_column_precisions
+    for (int w = 0; w < 2; ++w) {
+        ColumnPrior& cp = w == 0 ? a.cpA : a.cpC;
+        const ArdBuffers& g = h->ard[w];
+        if (g.on) {
+            cp.pp = g.ex; cp.pp_n = h->D; cp.pp_c = 1; cp.pp_r = 0;
+            cp.pld = h->bound == PYVB_BOUND_EXACT ? g.ld_exact : g.ld_ref; cp.pld_n = h->D;
+            cp.a0 = g.a0; cp.b0 = g.b0; cp.qa = g.qa; cp.qb = g.qb; cp.ex = g.ex; cp.ld_ref = g.ld_ref; cp.ld_exact = g.ld_exact;
+        } else {
+            cp.pp = w == 0 ? h->pri.A_pp : h->pri.C_pp; cp.pp_n = 0; cp.pp_c = w == 0 ? h->D : h->K; cp.pp_r = 1;
+            cp.pld = w == 0 ? h->pri.A_pld : h->pri.C_pld; cp.pld_n = 0;
+            cp.a0 = cp.b0 = cp.qa = nullptr; cp.qb = cp.ex = cp.ld_ref = cp.ld_exact = nullptr;
+        }
+    }
+    a.derive = 0;
     return a;
 }
 

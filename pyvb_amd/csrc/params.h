@@ -5,6 +5,21 @@
 
 #define LN2PI 1.8378770664093453
 
+// The prior precision of the columns of one matrix (A or C) as the column kernels read it: a strided view, so that Constant
+// parents (one [D][rows] array shared by the replicates) and Gamma parents (one expectation per replicate and column, the same
+// in every row: automatic relevance determination, k_ard.hip) are the same loads.
+//   precision of row k of column i in replicate n:  pp[n * pp_n + i * pp_c + k * pp_r]
+//   ln det of column i's prior precision:            pld[n * pld_n + i]
+// Constant parents: strides (0, rows, 1) over Priors::A_pp / C_pp and (0) over A_pld / C_pld.  Gamma parents: (D, 1, 0) over the
+// expectations qa / qb and (D) over the log-determinants of the handle's bound mode.
+struct ColumnPrior {
+    const double* pp; int pp_n, pp_c, pp_r;
+    const double* pld; int pld_n;
+    // Gamma parents alpha_i ~ Gamma(a0_i, b0_i) of the columns; all null with Constant parents
+    const double *a0, *b0, *qa;             // [D]; qa_i = a0_i + rows / 2 is fixed by the graph (nodes_todo.py:125-128)
+    double *qb, *ex, *ld_ref, *ld_exact;    // [N][D]: qb, qa / qb, rows (ln qa - ln qb) (quirk Q2), rows (psi(qa) - ln qb)
+};
+
 struct ParamArgs {
     // statistics
     const double* part; int nchunk; const double* Sigma; const double* qld_x; const double* X; const double* Syy;
@@ -29,6 +44,8 @@ struct ParamArgs {
     const int* len;         // [N] chain length T_n of each replicate (pyvb_lds_create_lengths), or null: T.  T stays the row stride of X
     const unsigned char* first;     // k_elbo: [N] 1 = first replicate of its model (pyvb_lds_create_tied), or null: every one is
     int Lw;                 // k_moments: interior nodes per part of sxx, cut from the handle's T as k_sweep cuts them
+    ColumnPrior cpA, cpC;   // k_cols, k_elbo, k_ard: the prior precisions of the columns of A and C
+    int derive;             // k_ard: 1 = qb is given (pyvb_lds_set_column_precisions): form what follows from it, in every row
 };
 
 // layout of the per-replicate moment block written by k_moments (all row-major, no padding)
