@@ -33,6 +33,11 @@ CASES = {
     "wide": dict(T=20, D=33, K=17, N=4, seed=9310, models=(0, 0, 1, 1), bound="reference", tol=None, max_iters=8),
     # the problem of converge_ref's case "nan" (same NaN pattern), its three chains in two models
     "nan": dict(R.CASES["nan"], models=(0, 0, 1), like="nan", tol=5.0, max_iters=30),
+    # models of 5, 1 and 9 chains, a singleton between them: k_converge's sum over the chains of a model runs over more than three,
+    # k_tie through its unrolled body.  tol from the float64 comparator's deltas in exact mode (they fall monotonically): the
+    # singleton meets 1.757, 1.314 in iterations 10, 11, the five chains 1.827, 1.325 in 11, 12, the nine 1.491, 1.279 in 16, 17
+    "sizes_5_1_9": dict(T=12, D=4, K=5, N=15, seed=9322, lengths=(12, 2, 3, 9, 7, 5, 11, 4, 12, 2, 8, 6, 10, 3, 12),
+                        models=(0,) * 5 + (1,) + (2,) * 9, bound="exact", tol=1.4, max_iters=25),
     # converge_ref's case D, every chain a model of its own: the comparator must reproduce converge_ref.learn_alone
     "singletons": dict(R.CASES["D"], models=(0, 1, 2, 3), like="D"),
 }

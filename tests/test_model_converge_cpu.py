@@ -81,6 +81,15 @@ def test_the_base_cases_stop_where_they_were_chosen_to():
     assert abs((r["trace"][1].sum() - r["trace"][0].sum()) + 20.2) < 0.05
 
 
+def test_the_large_models_stop_in_three_different_iterations():
+    """Models of 5, 1 and 9 chains (tests/model_converge_ref.py: sizes_5_1_9): every model stops, each in an iteration of its own,
+    odd and even ones among them."""
+    runs = MR.alone("sizes_5_1_9")
+    assert [len(r["rows"]) for r in runs] == [5, 1, 9] and all(r["converged"] for r in runs)
+    assert [r["iters"] for r in runs] == [12, 11, 17]
+    assert min(r["margin"] for r in runs) >= 10 * MR.GUARD
+
+
 def test_the_other_cases_cover_what_they_are_for():
     wide = MR.alone("wide")
     assert sorted(r["converged"] for r in wide) == [False, True], "the tol of the wide case stops exactly one model"

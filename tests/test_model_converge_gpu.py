@@ -179,6 +179,22 @@ def test_every_model_stops_where_the_reference_would(name):
     assert got["rerun"] == 0                            # nobody left: nothing is launched
 
 
+def test_models_of_five_and_nine_chains_stop_where_the_reference_would():
+    """Models of 5, 1 and 9 chains: the per-model sum of k_converge runs over more chains than any other case gives it (three), and
+    the statistics behind the bound come through the unrolled body of k_tie.  Every model stops in an iteration of its own, and
+    the chains of a model carry its count (_against_comparator)."""
+    name = "sizes_5_1_9"
+    got, runs = _ran(name, 1), MR.alone(name)
+    print("case %s: iters %s converged %s iters_run %d" % (name, got["iters"], got["converged"].astype(int), got["iters_run"]))
+    assert [len(r["rows"]) for r in runs] == [5, 1, 9] and len({r["iters"] for r in runs}) == 3
+    _against_comparator(got, runs, name)
+    for r in runs:
+        assert len(set(got["chain_iters"][r["rows"]])) == 1
+    assert got["iters_run"] == max(r["iters"] for r in runs) and got["converged"].all()
+    _totals_ok(got, runs)
+    assert got["rerun"] == 0
+
+
 # ---- 2. every replicate a model of its own: the per-replicate entry, bitwise --------------------------------------------------
 @pytest.mark.parametrize("plain", [False, True], ids=["singleton_models", "plain_handle"])
 def test_singletons_are_the_per_replicate_entry_bitwise(plain):

@@ -5,6 +5,9 @@
    tolerance tests/test_oracle_golden.py uses for the same quantities (1e-10 relative; observed about 1e-14).
 2. The two C ABI entries exist everywhere they must; the argument checks and the refusals of pyvb_lds_create_tied come before any
    HIP call; models of one replicate each are pyvb_lds_create_lengths.
+3. The cases on which k_tie.hip is held to the accuracy envelope (tied_ref.CASES): the comparator's long-double
+   run is long double throughout, the float64 comparator is within the cap of it on every compared quantity and part, and the
+   envelope comparison catches a chain pooled at a weight of 1 + 1e-10, which the 1e-8 comparison cannot see.
 """
 import ctypes
 import glob
@@ -15,6 +18,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import extended_ref as ER
 import tied_ref as TR
 from conftest import GOLDEN_DIR
 from oracle import lds_closed_form as O
@@ -160,3 +164,142 @@ def test_from_trials_needs_a_series_per_model():
         lds.LDSBatch.from_trials([], synth.default_priors(2, 3))
     with pytest.raises(ValueError):
         lds.LDSBatch.from_trials([[]], synth.default_priors(2, 3))
+
+
+# ---- 3. the envelope cases: the float64 comparator against its long-double run ----------------------------------------------
+@pytest.mark.parametrize("name", sorted(TR.CASES))
+def test_envelope_cases_reach_what_they_are_for(name):
+    T, D, K, sizes, kind, seed = TR.CASES[name]
+    Y, st0, pri, lengths, models = TR.problem(name)
+    assert Y.shape == (sum(sizes), T, K) and [len(r) for r in TR.rows_of(models)] == list(sizes)
+    assert list(lengths[:3]) == [T, 2, 3] and lengths.min() == 2 and lengths.max() == T and pri["noise"] == kind
+    assert not Y[np.arange(T)[None, :] >= lengths[:, None]].any()
+    odd = (3 * D * D + K * D + D) % 2 == 1
+    assert odd == (D % 2 == 1 and K % 2 == 1)
+    want = {"d3k3": (True, True), "d4k4": (False, False), "d33k17": (True, True), "d4k5_13": (False, True)}[name]
+    assert (odd, K % 2 == 1) == want                     # k_tie<double> on (the moment block, Syy)
+
+
+def test_envelope_cases_cover_every_state_of_the_loop():
+    """A model of c chains: (c - 1) // 4 turns of the unrolled body and a tail of (c - 1) % 4."""
+    sizes = sorted({c for case in TR.CASES.values() for c in case[3]})
+    assert sizes == [1, 2, 4, 5, 6, 7, 8, 9, 13]
+    assert {((c - 1) // 4, (c - 1) % 4) for c in sizes if c > 1} == {(0, 1), (0, 3), (1, 0), (1, 1), (1, 2), (1, 3), (2, 0), (3, 0)}
+    assert TR.CASES["d4k4"][3][:3] == (5, 1, 9) and TR.CASES["d4k5_13"][3] == (13,) and TR.CASES["d33k17"][3] == (6,)
+    assert (3 * 33 * 33 + 17 * 33 + 33 + 255) // 256 > 1        # more than one block along the elements
+
+
+def _all_long(st, what):
+    for k, v in st.items():
+        if isinstance(v, np.ndarray) and v.dtype.kind == "f":
+            assert v.dtype == ER.LD, "%s: %s has dtype %s" % (what, k, v.dtype)
+
+
+@pytest.mark.parametrize("name", sorted(TR.CASES))
+def test_long_double_run_is_long_double_throughout(name):
+    ms, tr = TR.trace(name, extended=True)
+    assert len(tr) == TR.ITERS == 2
+    for m, (rows, chains, Ys) in enumerate(ms):
+        for c, st in enumerate(chains):
+            _all_long(st, "%s model %d chain %d" % (name, m, c))
+        _all_long(TR.statistics(chains, Ys)[1], "%s model %d pooled statistics" % (name, m))
+    for snaps in tr:
+        for s in snaps:
+            for k, v in s.items():
+                for a in (v if isinstance(v, list) else v.values() if isinstance(v, dict) else [v]):
+                    assert a.dtype == ER.LD and np.all(np.isfinite(a)), (name, k, a.dtype)
+
+
+@pytest.mark.parametrize("name", sorted(TR.CASES))
+def test_float64_comparator_is_within_the_cap(name):
+    (ms, f64), (_, ext) = TR.trace(name), TR.trace(name, extended=True)
+    worst = (0.0, None)
+    for it in range(TR.ITERS):
+        for m, (rows, chains, Ys) in enumerate(ms):
+            for what, e64, e, ratio in TR.envelope(f64[it][m], f64[it][m], ext[it][m], TR.accumulation_length(chains)):
+                assert e == e64 and ratio <= 1.0
+                assert e64 <= ER.CAP, "%s iteration %d model %d %s: e64 %.3e, cap %.0e" % (name, it + 1, m, what, e64, ER.CAP)
+                worst = max(worst, (e64, "iteration %d model %d %s" % (it + 1, m, what)))
+    print("%s: largest e64 %.2e at %s" % ((name,) + worst))
+
+
+# ---- 4. what the envelope sees and 1e-8 does not -----------------------------------------------------------------------------
+def _plant(monkeypatch, size, change):
+    """tied_ref.statistics with the POOLED statistics of every model of `size` chains changed by change(per, pooled, Ys); what each
+    chain keeps for its own terms of the bound is untouched, as on the device, where k_tie writes only the sum."""
+    clean = TR.statistics
+
+    def statistics(chains, Ys):
+        per, pooled = clean(chains, Ys)
+        if len(chains) == size:
+            pooled = dict(pooled)
+            change(per, pooled, Ys)
+        return per, pooled
+    monkeypatch.setattr(TR, "statistics", statistics)
+
+
+def _syy_of_one_chain_scaled(w):
+    def change(per, pooled, Ys):
+        pooled["Syy"] = pooled["Syy"] + w * per[4]["Syy"]
+    return change
+
+
+def _moments_of_the_last_chain_weighted(w):
+    def change(per, pooled, Ys):
+        for k in pooled:
+            if k != "Syy":
+                pooled[k] = pooled[k] + w * per[-1][k]
+    return change
+
+
+def _without_the_chain_of_length_2(per, pooled, Ys):
+    (c,) = [i for i, Y in enumerate(Ys) if Y.shape[1] == 2]
+    for k in pooled:
+        pooled[k] = pooled[k] - per[c][k]
+
+
+# (case, chains of the model, the change, passes the 1e-8 comparison of tests/test_tied_gpu.py?)
+# The weight 1 + 1e-10 separates the two comparisons as it stands, no other weight was needed: one of nine contributions changed by
+# 1e-10 of itself moves R_b by 5.5e-11 (a) and the states by 3.6e-11 (b) after two iterations -- the residuals are small differences
+# of the large sums, which amplifies the change a little -- 200 times under 1e-8 and 3000 to 5000 times the yardstick
+# max(e64, n 2^-52) = 1.1e-14 (n = 51 nodes), i.e. 200 to 300 times the envelope's bound.
+MUTANTS = {
+    "a_one_chains_Syy_scaled_by_1+1e-10": ("d3k3", 9, _syy_of_one_chain_scaled(1e-10), True),
+    "b_last_chains_moments_at_weight_1+1e-10": ("d3k3", 9, _moments_of_the_last_chain_weighted(1e-10), True),
+    "c_pooled_without_the_chain_of_length_2": ("d4k5_13", 13, _without_the_chain_of_length_2, False),
+}
+
+
+@pytest.mark.parametrize("mutant", sorted(MUTANTS))
+def test_envelope_catches_what_the_parity_tolerance_cannot(mutant, monkeypatch):
+    """The comparisons of test_tied_gpu.py::test_parity_and_envelope applied to the float64 comparator with one error planted in the
+    pooled statistics of one model: (a) and (b) pass the RTOL = 1e-8 comparison and fail the envelope -- the envelope is what catches
+    them; (c) fails both.  The comparator without a mutant passes both (its e is e64, at most the yardstick)."""
+    import test_tied_gpu as G
+    name, size, change, passes_parity = MUTANTS[mutant]
+    Y, st0, pri, lengths, models = TR.problem(name)
+    (m,) = [i for i, c in enumerate(TR.CASES[name][3]) if c == size]
+    (ms, f64), (_, ext) = TR.trace(name), TR.trace(name, extended=True)      # before the mutant is planted
+    n = TR.accumulation_length(ms[m][1])
+    _plant(monkeypatch, size, change)
+    mut = TR.run(TR.build_models(Y, st0, pri, lengths, models, only=[m]), pri)
+
+    def parity(got, it):
+        try:
+            G._parity(got, f64[it][m], "%s iteration %d: " % (mutant, it + 1))
+        except AssertionError as e:
+            return str(e).splitlines()[0]
+        return None
+
+    failed_parity, worst = [], (0.0, None)
+    for it in range(TR.ITERS):
+        assert parity(f64[it][m], it) is None
+        assert max(r[3] for r in TR.envelope(f64[it][m], f64[it][m], ext[it][m], n)) <= 1.0
+        why = parity(mut[it][0], it)
+        if why:
+            failed_parity.append(why)
+        for what, e64, e, ratio in TR.envelope(mut[it][0], f64[it][m], ext[it][m], n):
+            worst = max(worst, (ratio, "iteration %d %s: e64 %.2e, e %.2e" % (it + 1, what, e64, e)))
+    print("%s: envelope e / y up to %.3g (%s); 1e-8 comparison: %s" % (mutant, worst[0], worst[1], failed_parity[:1] or "passes"))
+    assert worst[0] > ER.FACTOR, "mutant %s stays within %g x the yardstick" % (mutant, ER.FACTOR)
+    assert (not failed_parity) == passes_parity, failed_parity

@@ -8,6 +8,10 @@ to RTOL of the sum of their magnitudes and the total to RTOL of itself.
 Shapes: D = 4, K = 5 (no multiple of 16), T = 60, six chains in models of [1, 3, 2] chains -- a singleton beside two tied models;
 one test puts it between them, [3, 1, 2] -- with ragged lengths that include T_n = 2 and 3.
 
+Section 8 holds models of five and more chains (tests/tied_ref.py: CASES, with the argument which case reaches which path of
+k_tie.hip) to the accuracy envelope of DESIGN.md section 17 against the comparator's long-double run, and covers a handle with more
+models than the grid of k_tie has rows.
+
 "Bitwise" is justified as in tests/test_lengths_gpu.py: rows share no arithmetic but the sums of k_tie.hip, which adds the chains
 of a model in ascending replicate order whatever the launch, so two handles of the same shapes, lengths, models and time split run
 the same instructions in the same order.
@@ -21,6 +25,7 @@ import numpy as np
 import pytest
 
 import exact_bound_ref as XR
+import extended_ref as ER
 import tied_ref as TR
 from conftest import GOLDEN_DIR
 from oracle import lds_closed_form as O
@@ -581,3 +586,191 @@ def test_the_same_graph_through_the_node_front_end():
                         + [float(g["Q"].log_lower_bound()), float(g["R"].log_lower_bound())])
         _compare_parts(b.elbo().sum(0), want, "it%d bound" % it)
     b.close()
+
+
+# ---- 8. models of five and more chains: every path of k_tie, at the accuracy envelope ----------------------------------------
+PARAM_ROWS = ("A_mean", "A_colvar", "C_mean", "C_colvar", "Q_a", "Q_b", "R_a", "R_b", "qld_A", "qld_C", "lnd_A", "lnd_C")
+
+
+def _bounds(b):
+    """{mode: parts [N, 6]} of the handle's current state (tests/test_ard_gpu.py: _bounds); the handle is left in reference mode."""
+    out = {}
+    for mode in ("exact", "reference"):
+        b.set_bound_mode(mode)
+        out[mode] = b.elbo()
+    return out
+
+
+def _parameter_rows(b):
+    g = b.get_state()
+    g["qld_A"], g["qld_C"] = b.get_column_qld()
+    ld = b.get_logdets()
+    g["lnd_A"], g["lnd_C"] = ld["A"], ld["C"]
+    return g
+
+
+def _readout(b, rows_of_models):
+    """The handle's counterpart of tied_ref.snapshot, model by model: X per chain over its own length, Sigma on the live classes,
+    the parameters from the model's first row, the parts summed over the model's rows (in long double: the sum is the test's, not
+    the device's).  Asserts what holds by construction: zero padding, bitwise equal parameter rows, the shared nodes' parts on the
+    first row only."""
+    g, parts = _parameter_rows(b), _bounds(b)
+    Sig = b.get_posterior_classes()[0]
+    lens = b.lengths
+    out = []
+    for m, rows in enumerate(rows_of_models):
+        _rows_equal({k: g[k] for k in PARAM_ROWS}, rows, "model %d: " % m)
+        s = {"X": [g["X"][n, :lens[n]] for n in rows], "Sigma": [Sig[n][TR.live_classes(lens[n])] for n in rows]}
+        for n in rows:
+            assert not g["X"][n, lens[n]:].any(), "padding rows of X, replicate %d" % n
+        for k in TR.PARAMS:
+            s[k] = g[k][rows[0]]
+        s["parts"] = {}
+        for mode in TR.BOUNDS:
+            assert np.all(parts[mode][rows[1:], 2:] == 0.0), "model %d, %s: L_A, L_C, L_Q, L_R on rows that are not the first" % (m, mode)
+            assert np.all(parts[mode][rows[0], 2:] != 0.0)
+            s["parts"][mode] = parts[mode][rows].astype(ER.LD).sum(0)
+        out.append(s)
+    return out, parts
+
+
+def _parity(got, want, tag):
+    """A snapshot (tied_ref.snapshot, _readout) against the float64 comparator's at this file's tolerances."""
+    for k in ("X", "Sigma"):
+        for c, (a, w) in enumerate(zip(got[k], want[k])):
+            _close(a, w, "%s%s of chain %d" % (tag, k, c))
+    for k in TR.PARAMS:
+        _close(got[k], want[k], tag + k)
+    for mode in TR.BOUNDS:
+        _compare_parts(np.asarray(got["parts"][mode], dtype=float), np.asarray(want["parts"][mode], dtype=float), tag + mode, mode == "exact")
+
+
+def _envelope(got, s64, sx, n, tag, worst):
+    """The rule of DESIGN.md section 17 on one model (tied_ref.envelope), printed and asserted; worst: {kind: (e64, e_gpu, ratio)},
+    the largest of each over what has been compared, for the summary line."""
+    for what, e64, e_gpu, ratio in TR.envelope(got, s64, sx, n):
+        print("%s%-16s e64 %.2e  e_gpu %.2e  (%.2f y)" % (tag, what, e64, e_gpu, ratio))
+        kind = what.split()[0] if what.split()[0] in TR.BOUNDS else "states"
+        worst[kind] = tuple(max(a, b) for a, b in zip(worst.get(kind, (0.0, 0.0, 0.0)), (e64, e_gpu, ratio)))
+        assert e64 <= ER.CAP, (tag, what, e64)
+        assert ratio <= ER.FACTOR, "%s%s: e_gpu %.3e is %.1f x max(e64 = %.3e, %d 2^-52)" % (tag, what, e_gpu, ratio, e64, n)
+
+
+@pytest.mark.parametrize("name", sorted(TR.CASES))
+def test_parity_and_envelope(name):
+    """After each of two iterations: the states, the covariance classes, the parameters and both bounds of every model against the
+    float64 comparator at RTOL and against its long-double run by e_gpu <= 16 max(e64, n 2^-52), n = max(D, K, sum of the model's
+    T_c) (tied_ref.accumulation_length); e64 is measured here, on the CPU."""
+    Y, st0, pri, lengths, models = TR.problem(name)
+    (ms, f64), (_, ext) = TR.trace(name), TR.trace(name, extended=True)
+    b = _batch(Y, st0, pri, lengths, models)
+    worst = {}
+    try:
+        for it in range(TR.ITERS):
+            b.iterate(1)
+            got, parts = _readout(b, [rows for rows, _, _ in ms])
+            for m, (rows, chains, Ys) in enumerate(ms):
+                tag = "%s iteration %d model %d (%d chains) " % (name, it + 1, m, len(rows))
+                _parity(got[m], f64[it][m], tag)
+                _envelope(got[m], f64[it][m], ext[it][m], TR.accumulation_length(chains), tag, worst)
+            tot, rows_sum = b.elbo_total(), parts["reference"].sum(0)
+            assert np.all(np.abs(tot - rows_sum) <= 1e-12 * np.abs(parts["reference"]).sum(0)), (tot, rows_sum)
+    finally:
+        b.close()
+    for kind in sorted(worst):
+        print("SUMMARY tied %s %s: largest e64 %.2e  e_gpu %.2e  e_gpu / y %.2f" % ((name, kind) + worst[kind]))
+
+
+@pytest.mark.parametrize("name,size", [("d3k3", 9), ("d4k4", 5)], ids=["d3k3-last-of-eight", "d4k4-first-of-four"])
+def test_a_models_sum_does_not_depend_on_its_neighbours(name, size):
+    """k_tie shares nothing between threads: a model alone on a handle (another grid, other block and model indices) gives bitwise
+    the rows it gives among its neighbours -- the 9-chain model that comes last of eight, the 5-chain model that comes first of four."""
+    Y, st0, pri, lengths, models = TR.problem(name)
+    (m,) = [i for i, c in enumerate(TR.CASES[name][3]) if c == size]
+    rows = TR.rows_of(models)[m]
+    among = _batch(Y, st0, pri, lengths, models)
+    alone = _batch(Y[rows], {k: v[rows] for k, v in st0.items()}, pri, lengths[rows], np.zeros(size, dtype=np.int32))
+    try:
+        assert among.get_time_split() == alone.get_time_split() == 1        # (T = 12: no split to choose)
+        among.iterate(2); alone.iterate(2)
+        ea, eb = _everything(among), _everything(alone)
+        for k in ea:
+            assert ea[k][rows].shape == eb[k].shape and np.array_equal(ea[k][rows], eb[k], equal_nan=True), k
+        assert np.all(np.isfinite(eb["X"])) and np.all(np.isfinite(eb["elbo"]))
+    finally:
+        among.close(); alone.close()
+
+
+def test_more_models_than_the_grid_has_rows():
+    """M = 65 537 models: 65 535 of one chain, then one of five chains (model 65 535) and one of two (65 536).  The grid of k_tie
+    has min(M, 65 535) rows, so these two are summed in the second turn of `for (m = blockIdx.y; m < M; m += gridDim.y)`, the five
+    chains through the unrolled body.  D = K = 1 and T = 2, the smallest pyvb_lds_create accepts; all lengths equal: tied, not
+    ragged.
+
+    Device memory, from the allocations of pyvb_lds_create at this shape (DP = KP = 16, W = 1, one statistics chunk), in doubles
+    per replicate: gains 1424, stats 768, trash 512, sxx 256, X (two buffers) and the c_t cache 3 x 32, Sigma and Sigma_new 6,
+    Y 2, and 40 in the parameter, log-determinant, moment, residual and bound rows: 3104 doubles = 24 832 bytes, and 32 bytes of
+    flags and counters.  N = 65 542 replicates: 1.63e9 bytes (1.52 GiB), against 288 GB on the device.  Measured as the free device
+    memory before and after the handle exists: 1.82e9 bytes, the granularity of some fifty separate allocations and the runtime's
+    own buffers included.  Host side: the problem is drawn in 0.11 s, the handle created and filled in 0.17 s, an iteration 9 ms.
+
+    The four models that are compared (0, 65 534 and the two tied ones) are the only ones the comparator runs."""
+    from pyvb_amd.lds import LDSBatch
+    T, Dm, Km = 2, 1, 1
+    sizes = np.array([1] * 65535 + [5, 2])
+    M, N = sizes.size, int(sizes.sum())
+    models = np.repeat(np.arange(M, dtype=np.int32), sizes)
+    Y, st0, pri = synth.make_problem(T, Dm, Km, N, seed=9210)
+    pick = [0, 65534, 65535, 65536]
+    ms = TR.build_models(Y, st0, pri, None, models, only=pick)
+    mx = TR.build_models(ER.to_long(Y), ER.to_long(st0), ER.to_long(pri), None, models, only=pick)
+    assert [len(r) for r, _, _ in ms] == [1, 1, 5, 2] and ms[2][0] == list(range(65535, 65540)) and ms[3][0] == [65540, 65541]
+    f64, ext = TR.run(ms, pri, 1)[0], TR.run(mx, ER.to_long(pri), 1)[0]
+    b = LDSBatch.from_problem(Y, st0, pri, models=models)
+    try:
+        assert (b.N, int(b.models[-1]) + 1) == (N, M) and np.all(b.lengths == T)
+        b.iterate(1)
+        got, parts = _readout(b, [rows for rows, _, _ in ms])
+        worst = {}
+        for i, (rows, chains, Ys) in enumerate(ms):
+            tag = "M = 65537, model %d (%d chains) " % (pick[i], len(rows))
+            _parity(got[i], f64[i], tag)
+            _envelope(got[i], f64[i], ext[i], TR.accumulation_length(chains), tag, worst)
+        g = _parameter_rows(b)
+        for k in PARAM_ROWS:
+            assert g[k].shape[0] == N and np.all(np.isfinite(g[k])), k
+            for rows in (ms[2][0], ms[3][0]):
+                assert np.all(g[k][rows] == g[k][rows[:1]]), k
+        assert np.all(np.isfinite(g["X"])) and np.all(np.isfinite(parts["reference"])) and np.all(np.isfinite(parts["exact"]))
+        first = np.concatenate([[True], np.diff(models) != 0])
+        for mode in TR.BOUNDS:
+            assert np.all(parts[mode][~first, 2:] == 0.0) and np.all(parts[mode][first, 2:] != 0.0)
+        iters, conv, llb = b.model_convergence()
+        assert iters.shape == conv.shape == llb.shape == (M,)
+    finally:
+        b.close()
+    for kind in sorted(worst):
+        print("SUMMARY tied M65537 %s: largest e64 %.2e  e_gpu %.2e  e_gpu / y %.2f" % ((kind,) + worst[kind]))
+
+
+def test_mask_drops_a_model_of_nine_chains():
+    """test_mask_drops_whole_models_only at these sizes: the 9-chain model of the D = K = 3 case switched off -- its rows stay
+    bitwise what they were, every other model is bitwise what it is on a handle that was never masked."""
+    Y, st0, pri, lengths, models = TR.problem("d3k3")
+    rows = TR.rows_of(models)[-1]
+    assert len(rows) == 9
+    mask = np.ones(len(models), dtype=bool); mask[rows] = False
+    b, twin = _batch(Y, st0, pri, lengths, models), _batch(Y, st0, pri, lengths, models)
+    try:
+        b.iterate(1); twin.iterate(1)
+        before = _everything(b)
+        b.set_active(mask)
+        b.iterate(2); twin.iterate(2)
+        after, ref = _everything(b), _everything(twin)
+        _same(after, before, ~mask, "switched-off rows")
+        _same(after, ref, mask, "active rows")
+        assert not np.array_equal(ref["A_mean"][rows], before["A_mean"][rows])      # (the model would have moved)
+        tot = b.elbo_total()
+        assert np.all(np.abs(tot - after["elbo"][mask].sum(0)) <= mask.sum() * 2.0 ** -52 * np.abs(after["elbo"][mask]).sum(0))
+    finally:
+        b.close(); twin.close()
