@@ -15,11 +15,26 @@
 //       sum_{j != i} M[k][j] G[i][j] = P[k][i] - Mold[k][i] G[i][i] + sum_{j<i, j in block} (Mnew - Mold)[k][j] G[i][j],
 // at most 15 multiply-adds per column and lane.  The residuals need diag(M G M^T): the same
 // product once more with the renewed M, then a row-wise dot product.
+//
+// LDS is what bounds how many of these one-wavefront workgroups a CU holds, and the kernel is latency bound, so it is
+// kept at 40 960 B: four workgroups a CU, one wavefront on every SIMD (4 x 40 960 B is exactly the CU's 160 KB, so the
+// four fit only while the kernel allocates no other LDS: not one more __shared__ double).
+// M and the rows of G have no padding (an XOR on
+// the index keeps the MFMA operand reads, the accumulator write and the lane-per-row accesses free of bank conflicts
+// instead; the four reads a block that save the diagonal block and the reads of the log-determinants are not), and the
+// product of a block is written over the rows of G it was formed from; the 16 x 16 diagonal block of G that the chain
+// still needs waits in registers, four entries a lane, and is handed round with v_readlane.
 #include "params.h"
 
 #define MFMA(a, b, c) __builtin_amdgcn_mfma_f64_16x16x4f64((a), (b), (c), 0, 0, 0)
-#define MS 72       // row stride of Mb: A-operand reads and lane-per-row reads are conflict free
-#define GS 68       // row stride of Gb and Sb
+// Mb[MI(col, row)], 64 x 64: lane-per-row accesses of a column are a permutation of 64 consecutive doubles, and the
+// A-operand read of four consecutive columns (quarter q reads column 4 s + q, rows 16 rt + c) falls on four different
+// sixteens of rows
+#define MI(col, row) (((col) << 6) + ((row) ^ (((col) & 3) << 4)))
+// GSb[GI(ii, x)], 16 x 64, holds rows of G (x = column j) and then the block's product and precisions (x = row of M):
+// the B-operand read (lane (c, q) reads row c, column 4 s + q) and the accumulator write (row c, x = 16 rt + 4 r + q)
+// both fall on 64 different doubles
+#define GI(ii, x) (((ii) << 6) + ((x) ^ ((ii) << 2)))
 
 // 16 consecutive entries of this lane's row (row-contiguous per lane); columns >= D read as `fill`
 __device__ __forceinline__ void load_row16(const double* row, int col0, int D, bool vec, double fill, double* out) {
@@ -43,11 +58,15 @@ __device__ __forceinline__ void load_row16(const double* row, int col0, int D, b
     }
 }
 
+// The workgroup is ONE wavefront, and the kernel relies on it: keep_block() and product() read GSb and product() writes its
+// result over the same array with no barrier in between.  Within a wavefront every lane's loads are issued, and their data
+// in registers, before any lane's dependent store; with a second wavefront in the block that order is gone.
 __global__ void __launch_bounds__(64) k_cols(ParamArgs a) {
     const int WHICH = a.which0 + blockIdx.y;
-    __shared__ double Mb[64 * MS];      // Mb[col * MS + row], zero padded to 64 x 64
-    __shared__ double Gb[16 * GS];      // rows 16b .. 16b+15 of G, zero padded: Gb[ii * GS + j] = G[16b+ii][j]
-    __shared__ double Sb[16 * GS];      // Sb[ii * GS + row]: P of the block, then the precisions of column ii
+    __shared__ double Mb[64 * 64];      // Mb[MI(col, row)], zero padded to 64 x 64
+    // rows 16b .. 16b+15 of G, zero padded: GSb[GI(ii, j)] = G[16b+ii][j]; after the product P of the block, GSb[GI(ii, row)],
+    // then the precisions of column ii
+    __shared__ double GSb[16 * 64];
     const int n = blockIdx.x, lane = threadIdx.x, D = a.D, K = a.K, c = lane & 15, q = lane >> 4;
     if (!a.active[n]) return;
     const int rows = WHICH == 0 ? D : K;
@@ -78,7 +97,7 @@ __global__ void __launch_bounds__(64) k_cols(ParamArgs a) {
         double m[16] = {};
         if (b < nb) load_row16(Mrow, 16 * b, D, vec, 0.0, m);
 #pragma unroll
-        for (int u = 0; u < 16; ++u) Mb[(16 * b + u) * MS + lane] = (b < nb && live) ? m[u] : 0.0;
+        for (int u = 0; u < 16; ++u) Mb[MI(16 * b + u, lane)] = (b < nb && live) ? m[u] : 0.0;
     }
     const double lam = live ? (WHICH == 0 ? a.Q_a[(size_t)n * D + lane] / a.Q_b[(size_t)n * D + lane]
                                           : a.R_a[(size_t)n * K + lane] / a.R_b[(size_t)n * K + lane]) : 0.0;
@@ -91,23 +110,29 @@ __global__ void __launch_bounds__(64) k_cols(ParamArgs a) {
             g[u] = G[(size_t)(i < D ? i : D - 1) * D + lc];
         }
 #pragma unroll
-        for (int u = 0; u < 16; ++u) Gb[u * GS + lane] = (16 * b + u < D && lane < D) ? g[u] : 0.0;
+        for (int u = 0; u < 16; ++u) GSb[GI(u, lane)] = (16 * b + u < D && lane < D) ? g[u] : 0.0;
     };
-    auto product = [&]() {              // Sb[ii][k] = sum_j Mb[j][k] Gb[ii][j]
+    // this lane's four entries of the diagonal block of G, before the product takes the place of the rows:
+    // blk[r] = G[16b + (lane >> 2)][16b + 4 (lane & 3) + r], so G[16b+u][16b+v] is blk[v & 3] of lane 4 u + (v >> 2)
+    auto keep_block = [&](int b, double (&blk)[4]) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) blk[r] = GSb[GI(lane >> 2, 16 * b + 4 * (lane & 3) + r)];
+    };
+    auto product = [&]() {              // GSb[ii][k] = sum_j Mb[j][k] GSb[ii][j], in place
         d4 acc[4];
 #pragma unroll
         for (int rt = 0; rt < 4; ++rt) acc[rt] = d4{0.0, 0.0, 0.0, 0.0};
-        // all 16 k-steps whatever D is: Mb and Gb are zero beyond it, and a fixed trip count unrolls
+        // all 16 k-steps whatever D is: Mb and GSb are zero beyond it, and a fixed trip count unrolls
 #pragma unroll 4
         for (int s = 0; s < 16; ++s) {
-            const double bop = Gb[c * GS + 4 * s + q];
+            const double bop = GSb[GI(c, 4 * s + q)];
 #pragma unroll
-            for (int rt = 0; rt < 4; ++rt) acc[rt] = MFMA(Mb[(4 * s + q) * MS + 16 * rt + c], bop, acc[rt]);
+            for (int rt = 0; rt < 4; ++rt) acc[rt] = MFMA(Mb[MI(4 * s + q, 16 * rt + c)], bop, acc[rt]);
         }
 #pragma unroll
         for (int rt = 0; rt < 4; ++rt)
 #pragma unroll
-            for (int r = 0; r < 4; ++r) Sb[c * GS + 16 * rt + 4 * r + q] = acc[rt][r];
+            for (int r = 0; r < 4; ++r) GSb[GI(c, 16 * rt + 4 * r + q)] = acc[rt][r];
     };
 
     // ---- the columns
@@ -125,6 +150,8 @@ __global__ void __launch_bounds__(64) k_cols(ParamArgs a) {
             load_row16(Hrow, 16 * b, D, vec, 0.0, hk);
             load_row16(obs + (size_t)lr * D, 16 * b, D, vec, 0.0, ob);
             __syncthreads();
+            double blk[4];
+            keep_block(b, blk);
             product();
             __syncthreads();
             // everything that does not depend on the columns renewed in this block, so that the chain from
@@ -132,7 +159,7 @@ __global__ void __launch_bounds__(64) k_cols(ParamArgs a) {
             double gd[16], var[16], base[16];
 #pragma unroll
             for (int u = 0; u < 16; ++u) {
-                gd[u] = Gb[u * GS + 16 * b + u];
+                gd[u] = bcast(blk[u & 3], 4 * u + (u >> 2));
                 const double prec = p0[u] + lam * gd[u];                                // qprec  gaussian.py:117
                 var[u] = 1.0 / prec;                                                    // qcov   gaussian.py:118-119
                 base[u] = p0[u] * m0[u] + lam * hk[u];
@@ -145,10 +172,10 @@ __global__ void __launch_bounds__(64) k_cols(ParamArgs a) {
                 const int i = 16 * b + u;
                 dl[u] = 0.0;
                 if (i >= a.c0 && i < a.c1) {            // wave-uniform
-                    const double xo = Mb[i * MS + lane];
-                    double acc = Sb[u * GS + lane] - xo * gd[u];
+                    const double xo = Mb[MI(i, lane)];
+                    double acc = GSb[GI(u, lane)] - xo * gd[u];
 #pragma unroll
-                    for (int v = 0; v < u; ++v) acc += dl[v] * Gb[u * GS + 16 * b + v];
+                    for (int v = 0; v < u; ++v) acc += dl[v] * bcast(blk[v & 3], 4 * u + (v >> 2));
                     double val = (base[u] - lam * acc) * var[u], vr = var[u];           // qmu  gaussian.py:119-123
                     // known entries (Gaussian.observe on a column, LDS_knowns_in_A.py:73-74): conditioning a
                     // diagonal Gaussian on them (gaussian.py:125-134) pins those entries and leaves the others
@@ -159,12 +186,12 @@ __global__ void __launch_bounds__(64) k_cols(ParamArgs a) {
                     mynk = (lane == u) ? nknown : mynk;
                     if (live) {
                         dl[u] = val - xo;
-                        Mb[i * MS + lane] = val;
+                        Mb[MI(i, lane)] = val;
                         V[(size_t)i * rows + lane] = vr;
                     }
-                    Sb[u * GS + lane] = live ? p0[u] : 1.0;
+                    GSb[GI(u, lane)] = live ? p0[u] : 1.0;
                 } else {
-                    Sb[u * GS + lane] = 1.0;
+                    GSb[GI(u, lane)] = 1.0;
                     mynk = (lane == u) ? rows : mynk;   // no q_ln_det for a column that was not updated
                 }
             }
@@ -176,7 +203,7 @@ __global__ void __launch_bounds__(64) k_cols(ParamArgs a) {
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     int e;
-                    mant *= frexp(Sb[c * GS + 16 * q + r], &e);
+                    mant *= frexp(GSb[GI(c, 16 * q + r)], &e);
                     ex += e;
                 }
 #pragma unroll
@@ -203,13 +230,13 @@ __global__ void __launch_bounds__(64) k_cols(ParamArgs a) {
                         if (cc < D) {
                             d4 v;
 #pragma unroll
-                            for (int r = 0; r < 4; ++r) v[r] = Mb[(cc + r) * MS + lane];
+                            for (int r = 0; r < 4; ++r) v[r] = Mb[MI(cc + r, lane)];
                             *reinterpret_cast<d4*>(M + (size_t)lane * D + cc) = v;
                         }
                     } else {
 #pragma unroll
                         for (int r = 0; r < 4; ++r)
-                            if (cc + r < D) M[(size_t)lane * D + cc + r] = Mb[(cc + r) * MS + lane];
+                            if (cc + r < D) M[(size_t)lane * D + cc + r] = Mb[MI(cc + r, lane)];
                     }
                 }
             }
@@ -231,14 +258,16 @@ __global__ void __launch_bounds__(64) k_cols(ParamArgs a) {
                 vv[u] = V[(size_t)(i < D ? i : D - 1) * rows + lr];
             }
             __syncthreads();
+            double blk[4];
+            keep_block(b, blk);
             product();
             __syncthreads();
 #pragma unroll
             for (int u = 0; u < 16; u += 2) {
                 const int i = 16 * b + u;
-                const double x0 = Mb[i * MS + lane], x1 = Mb[(i + 1) * MS + lane];
-                e0 += x0 * Sb[u * GS + lane] + (i < D ? vv[u] * Gb[u * GS + i] : 0.0);
-                e1 += x1 * Sb[(u + 1) * GS + lane] + (i + 1 < D ? vv[u + 1] * Gb[(u + 1) * GS + i + 1] : 0.0);
+                const double x0 = Mb[MI(i, lane)], x1 = Mb[MI(i + 1, lane)];
+                e0 += x0 * GSb[GI(u, lane)] + (i < D ? vv[u] * bcast(blk[u & 3], 4 * u + (u >> 2)) : 0.0);
+                e1 += x1 * GSb[GI(u + 1, lane)] + (i + 1 < D ? vv[u + 1] * bcast(blk[(u + 1) & 3], 4 * (u + 1) + ((u + 1) >> 2)) : 0.0);
                 hm0 += x0 * hk[u];
                 hm1 += x1 * hk[u + 1];
             }
