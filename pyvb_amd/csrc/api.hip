@@ -94,9 +94,9 @@ static int lds_create(pyvb_lds** out, int device, int N, int T, int D, int K, in
     HIPCHK(hipSetDevice(device));
     pyvb_lds* h = new pyvb_lds();       // value-initialised: every pointer null, every flag false
     h->device = device; h->N = N; h->T = T; h->D = D; h->K = K; h->noise = noise_kind;
-    h->L = make_layout(D, K);
-    h->big = D > 64 || K > 64;           // the workgroup-per-replicate kernels of k_big.hip
-    h->dense = noise_kind == PYVB_NOISE_WISHART;
+    const LdsGeometry g = lds_geometry(N, T, D, K, noise_kind);     // geometry.h: the shape class, the chunks, the time split, the extents
+    h->L = g.L; h->big = g.big; h->dense = g.dense;
+    h->nchunk = g.nchunk; h->chunk_len = g.chunk_len; h->W = g.W;
     // (lengths that all equal T, models of one replicate each: a plain handle, len / mstart / first stay null)
     h->rep.init(N, T, ragged ? lengths : nullptr, tied ? model : nullptr);
     const Layout& L = h->L;
@@ -127,38 +127,15 @@ static int lds_create(pyvb_lds** out, int device, int N, int T, int D, int K, in
     TRY(dev_alloc(&h->lnd_A, n * D)); TRY(dev_alloc(&h->lnd_C, n * D));
     TRY(dev_alloc(&h->lnd_x, n * 3)); TRY(dev_alloc(&h->lnd_x_new, n * 3));
     TRY(dev_alloc(&h->gains, n * L.gains_total));
-    TRY(dev_alloc(&h->scratch, h->big ? n * 2 * L.DP * L.DP : n * 2 * D * D));
+    TRY(dev_alloc(&h->scratch, g.scratch));
     TRY(dev_alloc(&h->zeros, 128));
     TRY(dev_alloc(&h->U, n * T * L.DP));                        // the c_t cache between a forward sweep and the backward one behind it
     TRY(h->mem.alloc((void**)&h->warm, n * 2 * sizeof(int)));
-    // time chunks of the statistics kernel: enough wavefronts to fill the chip when N is small
-    int nchunk = (1024 + N - 1) / N;
-    if (nchunk > 32) nchunk = 32;
-    if (nchunk > (T + 15) / 16) nchunk = (T + 15) / 16;
-    if (nchunk < 1) nchunk = 1;
-    int clen = (T + nchunk - 1) / nchunk;
-    clen = (clen + 3) & ~3;
-    nchunk = (T + clen - 1) / clen;
-    h->nchunk = nchunk; h->chunk_len = clen;
-    TRY(dev_alloc(&h->stats, n * nchunk * L.stats_total));
-    TRY(dev_alloc(&h->mom, n * ((size_t)3 * D * D + (size_t)K * D + D)));
-    // The sweeps may split the time axis over W wavefronts per replicate (k_sweep.hip).  A wavefront takes
-    // ceil(part/16) + J steps (J ~ 32 warm-up steps), the chip runs 1024 of them at a time: W minimises
-    // rounds x steps, with parts of at least 64 nodes.  At N >= 1024 that is W = 1.
-    // (The 128-wide class: a part is a workgroup of four wavefronts, one per CU at a time.)
-    h->W = 1;
-    {
-        const long Tint = T - 2, slots = h->big ? 256 : 1024;
-        double best = 1e300;
-        for (int W = 1; W <= 128 && (W == 1 || Tint / W >= 64); ++W) {
-            const long part = (((Tint + W - 1) / W) + 15) & ~15L;
-            const double cost = (double)(((long)N * W + slots - 1) / slots) * (double)((part + 15) / 16 + 32);
-            if (cost < best * 0.97) { best = cost; h->W = W; }      // prefer fewer wavefronts unless clearly better
-        }
-    }
-    TRY(dev_alloc(&h->sxx, h->big ? 8 : n * (size_t)h->W * L.DP * L.DP));        // (the 128-wide sweeps fuse no statistics)
-    if (h->big && h->W > 1) TRY(dev_alloc(&h->U2, n * T * L.DP));
-    TRY(dev_alloc(&h->trash, n * (size_t)(h->big ? h->W : 1) * 512));      // 128-wide class: per (replicate, part of the time axis)
+    TRY(dev_alloc(&h->stats, g.stats));
+    TRY(dev_alloc(&h->mom, g.mom));
+    TRY(dev_alloc(&h->sxx, g.sxx));
+    if (g.U2) TRY(dev_alloc(&h->U2, g.U2));
+    TRY(dev_alloc(&h->trash, g.trash));
     TRY(dev_alloc(&h->resQ, n * D)); TRY(dev_alloc(&h->resR, n * K));
     TRY(dev_alloc(&h->elbo, n * 6)); TRY(dev_alloc(&h->elbo_sum, 8));
     TRY(dev_alloc(&h->elbo_hist, (size_t)PYVB_ELBO_HISTORY * 8));
@@ -183,10 +160,7 @@ static int lds_create(pyvb_lds** out, int device, int N, int T, int D, int K, in
     }
     h->status_host.assign(n, 0);
     h->reported.assign(n, 0);
-    // priors block: x0_mean D, x0_prec D*D, A_pm D*D, A_pp D*D, C_pm K*D, C_pp D*K, Q_a0 D, Q_b0 D, R_a0 K, R_b0 K
-    size_t pn = (size_t)D + 3 * (size_t)D * D + 2 * (size_t)K * D + 2 * (size_t)D + 2 * (size_t)K + (size_t)D * D + (size_t)K * D + 2 * (size_t)D
-                + (size_t)D * D + (size_t)K * K;
-    TRY(dev_alloc(&h->pri_block, pn));
+    TRY(dev_alloc(&h->pri_block, g.priors));       // one block, cut below in the order LdsGeometry.priors lists
     double* p = h->pri_block;
     h->pri.x0_mean = p; p += D; h->pri.x0_prec = p; p += D * D;
     h->pri.A_pm = p; p += D * D; h->pri.A_pp = p; p += D * D;
@@ -204,7 +178,7 @@ static int lds_create(pyvb_lds** out, int device, int N, int T, int D, int K, in
         TRY(dev_alloc(&h->A_cov, n * D * cov_stride(D))); TRY(dev_alloc(&h->C_cov, n * D * cov_stride(K)));
         TRY(dev_alloc(&h->SyyF, n * K * K));
         TRY(dev_alloc(&h->RQ, n * D * D)); TRY(dev_alloc(&h->RR, n * K * K));
-        TRY(dev_alloc(&h->SG, h->big ? n * 2 * 128 * 128 : n * 2 * 64 * 64));
+        TRY(dev_alloc(&h->SG, g.SG));
         TRY(dev_alloc(&h->ldm, n * 2 * D));
     }
     TRYHIP(hipMemset(h->pri.A_obs, 0xFF, ((size_t)D * D + (size_t)K * D) * sizeof(double)));     // all-ones bytes = NaN = nothing observed
@@ -805,17 +779,18 @@ int pyvb_lds_get_time_split(pyvb_lds* h, int* W) {
 
 int pyvb_lds_set_time_split(pyvb_lds* h, int W) {
     ENTER(h);
-    ARGCHK(W >= 1 && W <= 128, "W must be in 1..128");
-    ARGCHK(W == 1 || (h->T - 2) / W >= 16, "parts of fewer than 16 nodes");
+    int rc = check_time_split(h->T, W);
+    if (rc) return rc;
     HIPCHK(hipStreamSynchronize(h->stream));
     if (W != h->W) {
+        const LdsGeometry g = lds_geometry(h->N, h->T, h->D, h->K, h->noise).with_time_split(W);
         double* p = nullptr;
-        int rc = h->mem.zeros(&p, h->big ? 8 : (size_t)h->N * W * h->L.DP * h->L.DP);
+        rc = h->mem.zeros(&p, g.sxx);
         if (rc) { h->mem.release(p); return rc; }
-        if (h->big && W > 1 && !h->U2 && (rc = h->mem.zeros(&h->U2, (size_t)h->N * h->T * h->L.DP))) { h->mem.release(p); return rc; }
-        if (h->big) {
+        if (g.U2 && !h->U2 && (rc = h->mem.zeros(&h->U2, g.U2))) { h->mem.release(p); return rc; }
+        if (h->big) {       // (elsewhere trash does not depend on W)
             double* tr = nullptr;
-            if ((rc = h->mem.zeros(&tr, (size_t)h->N * W * 512))) { h->mem.release(tr); h->mem.release(p); return rc; }
+            if ((rc = h->mem.zeros(&tr, g.trash))) { h->mem.release(tr); h->mem.release(p); return rc; }
             h->mem.release(h->trash);
             h->trash = tr;
         }

@@ -41,28 +41,19 @@ int pyvb_pca_create(pyvb_pca** out, int device, long N, int d, int q, long N_tot
     HIPCHK(hipSetDevice(device));
     pyvb_pca* h = new pyvb_pca();       // value-initialised: every pointer null, every flag false
     h->device = device; h->N = N; h->N_total = N_total; h->row_offset = row_offset; h->d = d; h->q = q;
-    h->DP = (d + 15) & ~15; h->QP = (q + 15) & ~15; h->DT = h->DP / 16; h->QT = h->QP / 16;
-    h->SL = pca_stats_layout(h->DP, h->QP);
     h->world = 1;
-    long nchunk = (16384 + h->DT - 1) / h->DT;      // pass 2 runs nchunk workgroups of ceil(DT / 2) wavefronts, pass 1 nchunk x 4
-    if (h->DT >= 13) {
-        // the sweep's workgroup (seven or eight wavefronts, 120 KB of LDS) has a CU to itself: ONE chunk per CU, so that every
-        // workgroup pays its prologue (operands, first tiles) and its partial sums once -- measured at N = 10^6 x 256:
-        // 1024 chunks (four rounds) 1.040 ms per iteration, 768: 1.028, 512: 1.009, 256: 0.990 (profiles/r04/pca_chunks.txt)
-        int ncu = 0;
-        if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && ncu > 0) nchunk = ncu;
-    }
-    const long ntile = (N + 15) / 16;
-    if (nchunk > ntile) nchunk = ntile;
-    if (nchunk < 1) nchunk = 1;
-    long rows = (N + nchunk - 1) / nchunk;
-    rows = (rows + 15) & ~15L;
-    nchunk = (N + rows - 1) / rows;
-    h->nchunk = (int)nchunk; h->chunk_rows = rows;
     int rc = PYVB_OK;
 #define TRY(x) CREATE_TRY(x, pyvb_pca_destroy, h)
 #define TRYHIP(x) CREATE_TRYHIP(x, pyvb_pca_destroy, h)
 #define alloc_d(p, n) h->mem.zeros(p, n)
+    // The CU count is asked for once.  A query that fails fails the creation, as the partition of k_pca_pairs always required;
+    // a count below 1 leaves nchunk at its default, as the query made for nchunk alone tolerated (geometry.h: pca_geometry).
+    int ncu = 0;
+    TRYHIP(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device));
+    const PcaGeometry g = pca_geometry(N, d, q, ncu);
+    h->DP = g.DP; h->QP = g.QP; h->DT = g.DT; h->QT = g.QT;
+    h->SL = pca_stats_layout(h->DP, h->QP);
+    h->nchunk = g.nchunk; h->chunk_rows = g.chunk_rows; h->nchunkB = g.nchunkB; h->chunk_rowsB = g.chunk_rowsB; h->sweep = g.sweep;
     TRYHIP(hipStreamCreate(&h->stream));
     const size_t n = (size_t)N, DP = h->DP, QP = h->QP;
     TRY(alloc_d(&h->X, n * DP));
@@ -74,22 +65,7 @@ int pyvb_pca_create(pyvb_pca** out, int device, long N, int d, int q, long N_tot
     TRY(alloc_d(&h->Mu_mean, d)); TRY(alloc_d(&h->Mu_var, d)); TRY(alloc_d(&h->Z_cov, (size_t)q * q)); TRY(alloc_d(&h->qld_W, q)); TRY(alloc_d(&h->lnd_W, q));
     TRY(alloc_d(&h->W_pm, (size_t)d * q)); TRY(alloc_d(&h->W_pp, (size_t)q * d)); TRY(alloc_d(&h->Mu_pm, d)); TRY(alloc_d(&h->Mu_pp, d));
     TRY(alloc_d(&h->W_x, (size_t)d * q)); TRY(alloc_d(&h->Mu_x, d));
-    {   // k_pca_pairs: one workgroup per CU, the rows dealt out in multiples of 16
-        int ncu = 0;
-        TRYHIP(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device));
-        if (ncu < 1) ncu = 1;
-        long rowsB = (N + ncu - 1) / ncu;
-        rowsB = (rowsB + 15) & ~15L;
-        if (rowsB < 64) rowsB = 64;
-        long ncB = (N + rowsB - 1) / rowsB;
-        if (ncB > nchunk) { ncB = nchunk; rowsB = ((N + ncB - 1) / ncB + 15) & ~15L; ncB = (N + rowsB - 1) / rowsB; }
-        h->nchunkB = (int)ncB; h->chunk_rowsB = rowsB;
-        // which kernel the lazy sweep is (k_pca.hip): pairs (k_pca_pairs) where a CU's share is long enough to stream (measured
-        // at 10^6 x 256: 0.95 against 0.97 ms per iteration), columns (k_pca_pass12<.., LAZY>) otherwise; pyvb_pca_set_sweep
-        // changes it
-        h->sweep = (h->DT >= 13 && N >= 512L * ncu) ? PYVB_PCA_SWEEP_PAIRS : PYVB_PCA_SWEEP_COLUMNS;
-        if (h->sweep == PYVB_PCA_SWEEP_PAIRS) { TRY(pca_prepare_pairs()); h->pairs_ready = true; }
-    }
+    if (h->sweep == PYVB_PCA_SWEEP_PAIRS) { TRY(pca_prepare_pairs()); h->pairs_ready = true; }
     TRY(alloc_d(&h->scal, PS_COUNT));
     TRY(alloc_d(&h->Gz, (size_t)h->QT * (DP / 4) * 64)); TRY(alloc_d(&h->g0, QP));
     TRY(alloc_d(&h->part, (size_t)h->nchunk * (h->SL.total + h->DT)));
@@ -112,11 +88,10 @@ static int down(pyvb_pca* h, double* dst, const double* src, size_t n) { return 
 // Rows [lo, hi) of X are about to be read outside a sweep: where a lazy sweep left their imputed entries unstored (PcaState:
 // xlazy, [vlo, vhi)), they are put into X first.  Every such reader calls this.
 static int x_read(pyvb_pca* h, long lo, long hi) {
-    PcaState& st = h->st;
-    if (!st.xlazy || !(lo < st.vhi && st.vlo < hi)) return PYVB_OK;
-    int rc = pca_materialize_x(h, st.vlo, st.vhi);
+    if (!h->st.needs_store(lo, hi)) return PYVB_OK;
+    int rc = pca_materialize_x(h, h->st.vlo, h->st.vhi);
     if (rc) return rc;
-    st.xlazy = false;
+    h->st.x_stored();
     return PYVB_OK;
 }
 
@@ -131,25 +106,6 @@ static int resolve_z(pyvb_pca* h) {
     return rc;
 }
 
-// What the next pass over the rows is, for the update of rows [lo_upd, hi_upd) of X: pass 2, or pass 1+2 where a Z update is
-// pending.  The standard sweep of an iteration -- all rows, or all but row 0, which the crawl order updates on its own -- leaves
-// the imputed entries to be recomputed by the next one (lazy); any other range, latent dimensions beyond 16 (the register budget)
-// and rows that still wait for their first update take the write-back, and entries an earlier sweep left unstored that the new
-// range does not cover are stored first.
-static PcaSweepPlan plan_sweep(const pyvb_pca* h, long lo_upd, long hi_upd) {
-    const PcaState& st = h->st;
-    PcaSweepPlan p;
-    p.lo_upd = lo_upd; p.hi_upd = hi_upd;
-    p.with_z = st.z_pending;
-    p.keep_z0 = st.z0_done;
-    p.lazy = p.with_z && h->sweep != PYVB_PCA_SWEEP_STORE && h->QT == 1 && !h->Xdata && lo_upd <= 1 && hi_upd == h->N && hi_upd > lo_upd
-             && (!st.xlazy || (lo_upd <= st.vlo && st.vhi <= hi_upd));
-    p.pairs = p.lazy && h->sweep == PYVB_PCA_SWEEP_PAIRS;
-    p.materialize = st.xlazy && !p.lazy;
-    p.vin_lo = st.xlazy ? st.vlo : 0; p.vin_hi = st.xlazy ? st.vhi : 0;
-    p.part_chunks = p.pairs ? h->nchunkB : h->nchunk;
-    return p;
-}
 
 int pyvb_pca_set_priors(pyvb_pca* h, const double* W_pm, const double* W_pp, const double* Mu_pm, const double* Mu_pp,
                         double beta_a0, double beta_b0) {
@@ -256,7 +212,7 @@ int pyvb_pca_set_initial_variances(pyvb_pca* h, const double* W_var, const doubl
     if ((rc = up(h, h->W_var, W_var, (size_t)h->q * h->d))) return rc;
     if ((rc = up(h, h->Mu_var, Mu_var, h->d))) return rc;
     HIPCHK(hipStreamSynchronize(h->stream));
-    h->st.res_valid = false;
+    h->st.residual_stale();
     return PYVB_OK;
 }
 
@@ -391,18 +347,14 @@ int pyvb_pca_set_sweep(pyvb_pca* h, int kind) {
 
 // ---- dependency tracking: "full" = every sum current, "lin" = at least sum x and sum z ----
 static int full_stats(pyvb_pca* h, long lo_upd, long hi_upd) {
-    PcaState& st = h->st;
-    const PcaSweepPlan p = plan_sweep(h, lo_upd, hi_upd);
+    const PcaPlanInput in = { h->N, h->QT, h->sweep, h->Xdata != nullptr, h->nchunk, h->nchunkB };
+    const PcaSweepPlan p = plan_sweep(h->st, in, lo_upd, hi_upd);
     int rc = pca_launch_sweep(h, p);
-    if (p.with_z) st.z_written();           // the Z update rode along: one sweep over X instead of two
+    h->st.sweep_ran(p, rc == PYVB_OK);
     if (rc) return rc;
-    st.part_chunks = p.part_chunks;
-    if (p.materialize) st.xlazy = false;
-    if (p.lazy) { st.xlazy = true; st.vlo = lo_upd; st.vhi = hi_upd; }
     if ((rc = pca_launch_reduce(h, 0))) return rc;
     if (h->comm && (rc = pyvb_allreduce_f64(h->comm, h->stats, h->SL.total, h->stream))) return rc;
-    st.full_valid = st.lin_valid = true;
-    if (hi_upd > lo_upd) st.res_valid = false;          // rows changed: the cached residual of the last Beta update is stale
+    h->st.stats_reduced(p);
     return PYVB_OK;
 }
 static int ensure_full(pyvb_pca* h) { return h->st.full_valid ? PYVB_OK : full_stats(h, 0, 0); }
@@ -411,7 +363,7 @@ int pyvb_pca_update_W(pyvb_pca* h) {
     ENTER(h);
     int rc = ensure_full(h);
     if (rc) return rc;
-    h->st.res_valid = false;
+    h->st.residual_stale();
     return pca_launch_small(h, PCA_W);
 }
 
@@ -432,7 +384,7 @@ int pyvb_pca_update_Z(pyvb_pca* h) {
     // that follows (k_pca_pass12) -- or by resolve_z() if something asks for them first.
     if (!h->st.lin_valid && (rc = ensure_full(h))) return rc;   // may carry out an earlier pending request
     h->st.z_requested();
-    if ((rc = pca_launch_small(h, PCA_PREPZ))) { h->st.z_pending = false; return rc; }
+    if ((rc = pca_launch_small(h, PCA_PREPZ))) { h->st.z_request_failed(); return rc; }
     if ((rc = exchange_lin(h))) return rc;
     h->st.linear_step();                                        // sum x is unchanged, sum z is the new one
     return PYVB_OK;
@@ -450,7 +402,7 @@ static int x0_step(pyvb_pca* h) {
     if (h->comm && h->row_offset != 0)
         HIPCHK(hipMemsetAsync(v, 0, h->QP * sizeof(double), h->stream));
     if ((rc = pca_launch_small(h, PCA_X0))) return rc;      // a no-op for the data of the other ranks (k_pca.hip checks row_offset)
-    if (h->st.z_pending && h->row_offset == 0) h->st.z0_done = true;     // the kernel has stored z_0 from the row as it was
+    h->st.x0_stepped(h->row_offset == 0);
     if ((rc = exchange_lin(h))) return rc;
     h->st.linear_step();
     return PYVB_OK;
@@ -481,7 +433,7 @@ int pyvb_pca_update_Mu(pyvb_pca* h) {
     ENTER(h);
     int rc;
     if (!h->st.lin_valid && (rc = ensure_full(h))) return rc;
-    h->st.res_valid = false;
+    h->st.residual_stale();
     return pca_launch_small(h, PCA_MU);
 }
 
@@ -490,7 +442,7 @@ int pyvb_pca_update_Beta(pyvb_pca* h) {
     int rc = ensure_full(h);
     if (rc) return rc;
     if ((rc = pca_launch_small(h, PCA_BETA))) return rc;
-    h->st.res_valid = true;     // the residual does not depend on Beta: the lower bound can reuse it
+    h->st.beta_updated();
     return PYVB_OK;
 }
 
@@ -518,17 +470,17 @@ int pyvb_pca_iterate(pyvb_pca* h, int niters) {
             // as the calls of the general path below.
             if ((rc = ensure_full(h))) return rc;                       // update_W
             h->st.z_requested();                                        // update_Z, deferred (lin_valid holds after ensure_full)
-            if ((rc = pca_launch_small(h, PCA_RUN_HEAD))) { h->st.z_pending = false; return rc; }
+            if ((rc = pca_launch_small(h, PCA_RUN_HEAD))) { h->st.z_request_failed(); return rc; }
             h->st.linear_step();
             // the X_0 step reads row 0: a no-op after an iteration of this loop (its sweep left vlo == 1), but not after a
             // stage-wise pyvb_pca_update_X(0, N)
             if ((rc = x_read(h, 0, h->row_offset == 0 ? 1 : 0))) return rc;
             if ((rc = pca_launch_small(h, PCA_RUN_MID))) return rc;     // x0_step, update_Mu
-            h->st.z0_done = h->row_offset == 0;                         // the kernel stored z_0 if this handle holds global row 0
+            h->st.x0_stepped(h->row_offset == 0);                       // the kernel stored z_0 if this handle holds global row 0
             if ((rc = x_rows(h, h->row_offset == 0 ? 1 : 0, h->N))) return rc;
             if ((rc = ensure_full(h))) return rc;                       // N == 1: no row left for x_rows, the sweep still has to run
             if ((rc = pca_launch_small(h, PCA_RUN_TAIL))) return rc;    // update_Beta, elbo
-            h->st.res_valid = true;
+            h->st.beta_updated();
             continue;
         }
         if ((rc = pyvb_pca_update_W(h))) return rc;

@@ -2,72 +2,12 @@
 #pragma once
 #include <cstdint>
 #include "host.h"
+#include "geometry.h"
 #include "replicates.h"
 
 struct pyvb_comm;
 typedef double d4 __attribute__((ext_vector_type(4)));
 typedef double d2 __attribute__((ext_vector_type(2)));
-
-// Per-replicate block of "gains": every matrix the state updates multiply by, written by
-// k_prep once per parameter change and read by the sweep / step kernels.
-//   Sigma_c = posterior covariance of class c (0: X_0, 1: interior, 2: X_{T-1})
-//   F  = Sigma_1 <Q><A>      B  = Sigma_1 <A>^T<Q>     G  = Sigma_1 <C>^T<R>
-// The two boundary nodes are single matrix-vector chains, mu = Sigma_c (sum of the messages), so for them
-// the block holds the pieces instead of products: S0 = Sigma_0, S2 = Sigma_2 ([row][DP]), qr = <Q> diagonal
-// (QR = 64 entries, 128 in the second shape class) then <R> diagonal (QR), w0 = L0 m0 (the Constant parents of X_0).
-// "n"/"p" blocks are laid out as v_mfma_f64_16x16x4 A-operands: element [(m*S+s)*64+lane]
-// = M[16m + (lane&15)][kidx(s, lane>>4)], kidx natural = 4s+q (F, B: they meet states, which come in
-// accumulator order), permuted = 8(s>>1)+2q+(s&1) (G: it meets rows of Y read 16 bytes per lane).
-// (pos_nat / pos_perm below give the position of element (i, j) in such a block.)
-struct Layout {
-    int D, K, DT, KT, DP, KP, DS, KS;
-    int QR;                 // length of each of the two noise diagonals at oqr: 64, or 128 in the second shape class
-    size_t oFn, oBn, oGp;
-    size_t oS0, oS2, oqr, ow0;
-    size_t gains_total;     // doubles per replicate
-    size_t stats_total;     // doubles per replicate per chunk: Sxx[DP][DP], Sx1x[DP][DP], Syx[KP][DP]
-    size_t oSxx, oSx1x, oSyx;
-};
-
-// Internal layout of a state row (X buffers, stride DP): "accumulator order".  Dimension
-// d = 16m + 4r + q sits at 16m + 4q + r, which is where lane group q keeps register r of tile m of a
-// v_mfma_f64_16x16x4 accumulator -- and also its B operand of k-step 4m + r.  A lane therefore moves
-// four contiguous doubles per tile, for the state stores as well as for the neighbour loads.
-__host__ __device__ static inline int xpos(int d) { return (d & ~15) | ((d & 3) << 2) | ((d >> 2) & 3); }
-
-// position of matrix element (i, j) in an MFMA A-operand block with S k-steps
-__host__ __device__ static inline size_t pos_nat(int i, int j, int S) {
-    return ((size_t)((i >> 4) * S + (j >> 2)) * 64) + (j & 3) * 16 + (i & 15);
-}
-__host__ __device__ static inline size_t pos_perm(int i, int j, int S) {
-    int s = 2 * (j >> 3) + (j & 1), q = (j & 7) >> 1;
-    return ((size_t)((i >> 4) * S + s) * 64) + q * 16 + (i & 15);
-}
-
-// column covariances under Wishart noise are stored as the upper 8 x 8 tiles of the matrix (k_wishart.hip: cov_pos)
-__host__ __device__ static inline int cov_tiles(int rows) { const int RT = (rows + 7) >> 3; return RT * (RT + 1) / 2; }
-__host__ __device__ static inline size_t cov_stride(int rows) { return (size_t)cov_tiles(rows) * 64; }
-
-static inline int tiles16(int d) { return d <= 16 ? 1 : (d <= 32 ? 2 : (d <= 64 ? 4 : 8)); }
-
-static inline Layout make_layout(int D, int K) {
-    Layout L;
-    L.D = D; L.K = K;
-    L.DT = tiles16(D); L.KT = tiles16(K);
-    if (L.DT > 4 || L.KT > 4) L.DT = L.KT = 8;      // the second shape class (k_big.hip): both dimensions padded to 128
-    L.QR = L.DT > 4 ? 128 : 64;
-    L.DP = 16 * L.DT; L.KP = 16 * L.KT;
-    L.DS = 4 * L.DT; L.KS = 4 * L.KT;
-    size_t o = 0;
-    size_t dd = (size_t)L.DT * L.DS * 64, dk = (size_t)L.DT * L.KS * 64;
-    L.oFn = o; o += dd; L.oBn = o; o += dd; L.oGp = o; o += dk;
-    size_t tdd = (size_t)L.DP * L.DP, tkd = (size_t)L.KP * L.DP;
-    L.oS0 = o; o += tdd; L.oS2 = o; o += tdd; L.oqr = o; o += 2 * (size_t)L.QR; L.ow0 = o; o += L.DP;
-    L.gains_total = o;
-    L.oSxx = 0; L.oSx1x = tdd; L.oSyx = 2 * tdd;
-    L.stats_total = 2 * tdd + tkd;
-    return L;
-}
 
 struct Priors {          // device pointers, shared by all replicates
     double *x0_mean, *x0_prec, *A_pm, *A_pp, *C_pm, *C_pp, *Q_a0, *Q_b0, *R_a0, *R_b0;

@@ -1,14 +1,16 @@
 // Host-side plumbing shared by the three handle types (pyvb_lds: api.hip, pyvb_pca: api_pca.hip, pyvb_graph: k_tape.hip): argument
-// and error checks, the record of the device buffers a handle owns, copies on a handle's stream -- and the state the two fused
-// handles track on the host about what is current on the device, with the events that change it (a pyvb_graph keeps none: its
-// tapes are planned on the host once, tape_plan.h).  Kernel files read this state; only the API files
-// (through the events below) write it.  DESIGN.md, "What is current: the host-side state of a handle", has the dependency table.
+// and error checks, the record of the device buffers a handle owns, copies on a handle's stream -- and LdsState: what a pyvb_lds
+// tracks on the host about what is current on the device, with the events that change it.  The same for a pyvb_pca, with the
+// planner of its sweeps, is pca_plan.h, included here; a pyvb_graph keeps no such state: its tapes are planned on the host once
+// (tape_plan.h).  What a handle is sized as is geometry.h.  Kernel files read the state; only the API files (through the events)
+// write it.  DESIGN.md, "What is current: the host-side state of a handle", has the dependency table.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstddef>
 #include <cstring>
 #include <vector>
 #include "../../include/pyvb_hip.h"
+#include "pca_plan.h"
 
 void pyvb_set_error(const char* fmt, ...);
 int pyvb_hip_fail(hipError_t e, const char* what, const char* file, int line);
@@ -147,20 +149,4 @@ struct LdsState {
     void parked_here() { x_park = cur; cls_parked_other = false; }      // settled, or the mask changed: parked rows are in the current buffers
 };
 
-// ---- pyvb_pca: what is current ---------------------------------------------------------------------------------------------
-struct PcaState {
-    bool full_valid, lin_valid; // stats: every sum current / at least sum x and sum z current.  Dropped by every setter of data or state;
-                                // full_valid also by the deferred Z update and the X_0 step, which keep only the linear sums current.
-    bool res_valid;             // scal[PS_RES] is the residual of the current W, Z, X, Mu (nothing but Beta updated since)
-    bool z_pending;             // [z.update() for z in Zs] has been requested and its operands (Gz, g0, sum z) are set, but the
-                                // rows of Z are not written yet: the next pass over X does it on its way (k_pca_pass12)
-    bool z0_done;               // while z_pending: Xs[0].update() has run and stored z_0 itself
-    bool xlazy; long vlo, vhi;  // the missing entries of rows [vlo, vhi) are not in X: they stand for <W>_x z_n + <Mu>_x
-                                // (k_pca_pass12<.., LAZY>, k_pca_pairs); k_pca_materialize puts them there
-    int part_chunks;            // chunks of the partial statistics in `part` now (the partition of the sweep that wrote them)
-
-    void inputs_changed() { full_valid = lin_valid = false; res_valid = false; }
-    void z_requested() { z_pending = true; z0_done = false; }
-    void z_written() { z_pending = false; z0_done = false; }
-    void linear_step() { full_valid = false; res_valid = false; }      // lin_valid stays: sum x and sum z were kept current
-};
+// ---- pyvb_pca: what is current, and what the next pass over the rows is: PcaState, PcaSweepPlan and plan_sweep of pca_plan.h

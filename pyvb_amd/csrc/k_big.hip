@@ -212,7 +212,7 @@ __global__ void __launch_bounds__(512 / NTW) k_sweep_big(BigSweepArgs a) {
     const int J = a.warm[n * 2 + a.dir];
     // this workgroup's part of the interior: Lw nodes from interior node ow on (counted from the side the sweep starts at), again
     // cut into 16 segments; all columns but those that reach the chain's first node within J steps warm up from zero
-    const int Lw = a.W > 1 ? ((((Tint + a.W - 1) / a.W) + 15) & ~15) : Tint;
+    const int Lw = a.W > 1 ? split_part_len(T, a.W) : Tint;
     const int ow = part * Lw;
     const int Tw = (Tint - ow < Lw) ? Tint - ow : Lw;
     const int t_first = fwd ? 0 : T - 1, t_last = fwd ? T - 1 : 0;

@@ -25,10 +25,7 @@ __global__ void __launch_bounds__(256) k_moments(ParamArgs a) {
     // parts of sxx this replicate's sweep wrote: a chain shorter than the handle's leaves the parts beyond its last interior
     // node unwritten (k_sweep: Tw <= 0)
     int nparts = a.W;
-    if (a.len) {
-        const int live = TL - 2 <= 0 ? 0 : (a.W == 1 ? 1 : (TL - 2 + a.Lw - 1) / a.Lw);
-        nparts = live < a.W ? live : a.W;
-    }
+    if (a.len) nparts = live_parts_of(a.Lw, a.W, TL - 2);
     for (int idx = tid; idx < D * D; idx += 256) {
         const int i = idx / D, j = idx % D;
         double xx = 0.0, h = 0.0;
@@ -294,7 +291,7 @@ int launch_moments(pyvb_lds* h, bool sxx_from_sweep) {
     ParamArgs a = make_args(h);
     a.sxx = sxx_from_sweep ? h->sxx : nullptr;
     a.W = h->W;
-    a.Lw = h->W > 1 ? ((((h->T - 2 + h->W - 1) / h->W) + 15) & ~15) : h->T - 2;      // as k_sweep cuts the parts
+    a.Lw = part_len(h->T, h->W);
     TimedLaunch tl(h, PYVB_K_PARAMS);
     hipLaunchKernelGGL(k_moments, dim3(h->N), dim3(256), 0, h->stream, a);
     HIPCHK(hipGetLastError());

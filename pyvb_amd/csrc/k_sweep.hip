@@ -134,7 +134,7 @@ __global__ void __launch_bounds__(64) k_sweep(SweepArgs a) {
     // Lw is cut from the handle's T for every replicate (k_moments counts a replicate's parts the same way):
     // a shorter chain fills the first parts and leaves the others without nodes (Tw <= 0).
     const int Tint = TL - 2;
-    const int Lw = SPLIT ? ((((T - 2 + a.W - 1) / a.W) + 15) & ~15) : Tint;
+    const int Lw = SPLIT ? split_part_len(T, a.W) : Tint;
     const int ow = SPLIT ? w * Lw : 0;                       // interior nodes before this part
     const int Tw = (Tint - ow < Lw) ? Tint - ow : Lw;        // interior nodes of this part (<= 0: none)
     const int J = a.warm[n * 2 + a.dir];

@@ -1,6 +1,7 @@
 // Internal definitions of the VB-PCA-with-missing-data path (examples/PCA_missing_data.py of the reference).
 #pragma once
 #include "common.h"
+#include "pca_plan.h"
 
 // Reduced statistics vector (doubles), all sums over the rows n of this rank (then over ranks):
 //   Szz [QP][QP]  sum z_n z_n^T (means only; the shared covariance is added by the consumers)
@@ -55,27 +56,14 @@ struct pyvb_pca {
     int *status;
     PcaStatsLayout SL;
     long n_part_missing, n_none_rows, n_part_rows;   // global counts (from the mask)
-    PcaState st;                         // what is current on the device (host.h); written by api_pca.hip only
+    PcaState st;                         // what is current on the device (pca_plan.h); written by api_pca.hip only
     DeviceBuffers mem;                   // every device allocation of this handle
     double *W_x, *Mu_x;                  // [d][q], [d]: the parameters the last lazy sweep imputed with
-    int sweep;                           // PYVB_PCA_SWEEP_*: what serves the full-range sweep where it may be lazy (api_pca.hip: plan_sweep);
+    int sweep;                           // PYVB_PCA_SWEEP_*: what serves the full-range sweep where it may be lazy (pca_plan.h: plan_sweep);
                                          // chosen at creation by size, changed by pyvb_pca_set_sweep only
     bool pairs_ready;                    // pca_prepare_pairs() has been called for this handle's device
     int nchunkB; long chunk_rowsB;       // k_pca_pairs' partition of the rows: a workgroup per CU
     pyvb_comm* comm; int rank, world;
-};
-
-// What the next pass over the rows is (api_pca.hip: plan_sweep decides, from the requested range and PcaState; the launchers below
-// carry it out and assign nothing on the handle).
-struct PcaSweepPlan {
-    long lo_upd, hi_upd;                 // rows of X to update
-    bool with_z;                         // the deferred Z update rides along (k_pca_pass12 / k_pca_pairs); false: k_pca_pass2 alone
-    bool keep_z0;                        // z_0 was stored by the X_0 step already
-    bool lazy;                           // the imputed entries stay unstored; then the rows [lo_upd, hi_upd) are the new lazy range
-    bool pairs;                          // lazy, by k_pca_pairs on its own partition of the rows
-    bool materialize;                    // rows [vin_lo, vin_hi) hold unstored entries that this pass cannot take in: store them first
-    long vin_lo, vin_hi;                 // the incoming lazy range (empty: none)
-    int part_chunks;                     // chunks of partial statistics the pass leaves in `part`
 };
 
 int pca_launch_small(pyvb_pca* h, int mode);

@@ -648,6 +648,24 @@ def test_time_split_of_the_128_wide_class():
     _stagewise(Y[:, :400], {k: (v[:, :400] if k == "X" else v) for k, v in st0.items()}, pri, iters=1)
 
 
+def test_time_split_of_the_128_wide_class_with_a_part_without_nodes():
+    """T = 51 forced into three parts: 49 interior nodes in parts of 32, so the third workgroup of a replicate owns no node.  Two
+    iterations against the oracle."""
+    T, D, K, N = 51, 100, 70, 2
+    Y, st0, pri = synth.make_problem(T, D, K, N, seed=4243)
+    b = _batch(Y, st0, pri)
+    b.set_time_split(3)
+    assert b.get_time_split() == 3
+    st = O.expand_state(st0, pri, T)
+    for _ in range(2):
+        parts = O.iterate(st, pri, Y)
+        b.iterate(1)
+    _compare_params(b, st, "T = 51, set_time_split(3): ")
+    _close(b.get_state(("X",))["X"], st["X"], "X, T = 51, set_time_split(3)")
+    _close(b.elbo().sum(1), parts.sum(1), "elbo, T = 51, set_time_split(3)")
+    b.close()
+
+
 def test_headline_batch_1024_replicates():
     """BASELINE configs[2] as bench.py runs it: N = 1024 replicates (the library itself chooses one wavefront per
     replicate), T = 10^4, D = K = 64.  Two distinct problems tiled 512 times: replicates 0 and 1 against the oracle,

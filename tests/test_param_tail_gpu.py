@@ -140,8 +140,9 @@ def test_a_tied_handle_of_two_chains():
         a.close(); b.close()
 
 
-def test_time_split_into_three_parts():
-    T, D, K, N = 100, 64, 33, 2
+@pytest.mark.parametrize("T,D,K,N", [(100, 64, 33, 2),
+                                     (51, 33, 17, 2)])      # 49 interior nodes in parts of 32: the third part holds no node
+def test_time_split_into_three_parts(T, D, K, N):
     Y, st0, pri = synth.make_problem(T, D, K, N, seed=7601)
 
     def split(b):
@@ -158,6 +159,20 @@ def test_time_split_into_three_parts():
     P._close(b.elbo().sum(1), parts.sum(1), "elbo after iterate, set_time_split(3)")
     b.close()
     _iterate_equals_staged(Y, st0, pri, prepare=split)
+
+
+def test_default_time_split_matches_the_recorded_table():
+    """The time split a handle picks for itself is the one tests/test_geometry_cpu.py holds geometry.h to: the same literal table
+    (the shapes up to T = 4099; no data is needed to ask)."""
+    from test_geometry_cpu import LDS_TABLE
+    from pyvb_amd.lds import LDSBatch
+    got = {}
+    for (N, T, D, K) in LDS_TABLE:
+        if T <= 4099:
+            b = LDSBatch(N, T, D, K)
+            got[(N, T, D, K)] = b.get_time_split()
+            b.close()
+    assert len(got) == 16 and got == {s: LDS_TABLE[s][1] for s in got}
 
 
 def test_moments_reduced_over_chunks():
