@@ -361,6 +361,20 @@ int pyvb_pca_set_priors(pyvb_pca* h, const double* W_prior_mean, const double* W
                         const double* Mu_prior_mean, const double* Mu_prior_prec, double beta_a0, double beta_b0);
 /* [x.observe(row) for x in Xs] (gaussian.py:74-100): NaN = missing; rows may be fully, partially or not observed */
 int pyvb_pca_set_data(pyvb_pca* h, const double* X);
+/* Automatic relevance determination (Bishop's VB-PCA): column i of W gets the precision parent alpha_i = Gamma(d, a0_i, b0_i) in
+ * place of its Constant one -- Ws = [Gaussian(d, pmu_i, Gamma(d, a0_i, b0_i)) for i in range(q)], which gaussian.py:55-61 accepts.
+ * The column then sees pprec = (qa_i / qb_i) I (gaussian.py:113, nodes_todo.py:140-142), qa_i = a0_i + d / 2 (nodes_todo.py:125-128);
+ * alpha_i.update() is qb_i = b0_i + 1/2 sum_k ((<W>[k][i] - pmu[k][i])^2 + var W[k][i]) (nodes_todo.py:130-138); the column's own
+ * bound term takes 1/2 d (ln qa_i - ln qb_i) (nodes_todo.py:144-147, quirk Q2; PYVB_BOUND_EXACT: 1/2 d (psi(qa_i) - ln qb_i)), and
+ * each alpha_i adds Gamma.log_lower_bound (nodes_todo.py:149-157) to parts[0], the W class.
+ * pyvb_pca_set_column_precisions: a0[q], b0[q] and the initial qb[q] (the reference draws it at random, nodes_todo.py:119), all
+ * finite and positive; call it after pyvb_pca_set_priors, whose W_prior_prec it replaces by qa / qb -- and which, called again,
+ * gives the columns their Constant parents back.  pyvb_pca_iterate then runs [al.update() for al in alphas] in every pass, where
+ * fetch_network puts it (after the Z_n; it commutes with them); stage-wise callers use pyvb_pca_update_column_precisions.
+ * update / get on a handle without hyperpriors, a NULL handle or array, a value that is not finite and positive: PYVB_E_ARG. */
+int pyvb_pca_set_column_precisions(pyvb_pca* h, const double* a0, const double* b0, const double* qb);  /* [q] each */
+int pyvb_pca_get_column_precisions(pyvb_pca* h, double* qa, double* qb);                               /* [q]; NULL = skip */
+int pyvb_pca_update_column_precisions(pyvb_pca* h);            /* [al.update() for al in alphas] */
 /* explicit posterior state; X_missing[N][d] supplies the posterior means of the missing entries only */
 int pyvb_pca_set_state(pyvb_pca* h, const double* X_missing, const double* W_mean, const double* Z, const double* Z_cov,
                        const double* Mu_mean, const double* beta_b);

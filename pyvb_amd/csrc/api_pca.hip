@@ -129,7 +129,66 @@ int pyvb_pca_set_priors(pyvb_pca* h, const double* W_pm, const double* W_pp, con
     HIPCHK(hipMemcpy(h->qld_W, nanq.data(), nanq.size() * sizeof(double), hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(h->lnd_W, nanq.data(), nanq.size() * sizeof(double), hipMemcpyHostToDevice));
     HIPCHK(hipStreamSynchronize(h->stream));
+    h->ard_on = false;      // the columns of W have Constant parents again: W_pp is the caller's (pyvb_pca_set_column_precisions comes after)
     return PYVB_OK;
+}
+
+// ---- Gamma parents of the columns of W (automatic relevance determination; k_pca.hip: PCA_ARD) ----
+// Nothing PcaState tracks depends on W_pp: the statistics are sums over X and Z, the cached residual reads <W>, var(W), Mu and the
+// statistics, the pending Z update reads <W> and var(W).  The prior precisions are read by the next W update and by the bound only,
+// so none of the three entries below raises an event.
+static int ard_required(const pyvb_pca* h) {
+    if (!h->ard_on) {
+        pyvb_set_error("the columns of W have Constant precision parents: no hyperpriors were given (pyvb_pca_set_column_precisions)");
+        return PYVB_E_ARG;
+    }
+    return PYVB_OK;
+}
+
+int pyvb_pca_set_column_precisions(pyvb_pca* h, const double* a0, const double* b0, const double* qb) {
+    ARGCHK(h, "handle is NULL");
+    ARGCHK(a0 && b0 && qb, "a0, b0 and qb are required");
+    const size_t q = (size_t)h->q;
+    for (size_t i = 0; i < q; ++i) {
+        if (!(a0[i] > 0.0 && a0[i] - a0[i] == 0.0)) { pyvb_set_error("a0 of column %d of W is %g: it must be finite and positive", (int)i, a0[i]); return PYVB_E_ARG; }
+        if (!(b0[i] > 0.0 && b0[i] - b0[i] == 0.0)) { pyvb_set_error("b0 of column %d of W is %g: it must be finite and positive", (int)i, b0[i]); return PYVB_E_ARG; }
+        if (!(qb[i] > 0.0 && qb[i] - qb[i] == 0.0)) { pyvb_set_error("qb of column %d of W is %g: it must be finite and positive", (int)i, qb[i]); return PYVB_E_ARG; }
+    }
+    std::vector<double> host(AR_COUNT * q, 0.0);
+    for (size_t i = 0; i < q; ++i) {
+        const double qa = a0[i] + 0.5 * (double)h->d;       // update_a, nodes_todo.py:125-128: one child of d entries
+        host[AR_A0 * q + i] = a0[i]; host[AR_B0 * q + i] = b0[i]; host[AR_QA * q + i] = qa; host[AR_QB * q + i] = qb[i];
+        host[AR_LGAMMA_A0 * q + i] = std::lgamma(a0[i]); host[AR_LGAMMA_QA * q + i] = std::lgamma(qa);
+        host[AR_DIGAMMA_QA * q + i] = digamma_host(qa); host[AR_LN_QA * q + i] = std::log(qa);
+    }
+    ENTER(h);
+    int rc;
+    if (!h->ard && (rc = h->mem.zeros(&h->ard, AR_COUNT * q))) return rc;
+    if ((rc = up(h, h->ard, host.data(), AR_COUNT * q))) return rc;
+    h->ard_on = true;
+    // W_pp = qa / qb and the two log terms from qb as given: the first update_W already sees <alpha>
+    if ((rc = pca_launch_ard(h, true))) { h->ard_on = false; return rc; }
+    HIPCHK(hipStreamSynchronize(h->stream));               // the staging vector is about to go out of scope
+    return PYVB_OK;
+}
+
+int pyvb_pca_get_column_precisions(pyvb_pca* h, double* qa, double* qb) {
+    ARGCHK(h, "handle is NULL");
+    int rc = ard_required(h);
+    if (rc) return rc;
+    ENTER(h);
+    const size_t q = (size_t)h->q;
+    if ((rc = down(h, qa, h->ard + AR_QA * q, q))) return rc;
+    if ((rc = down(h, qb, h->ard + AR_QB * q, q))) return rc;
+    return pyvb_pca_sync(h);
+}
+
+int pyvb_pca_update_column_precisions(pyvb_pca* h) {
+    ARGCHK(h, "handle is NULL");
+    int rc = ard_required(h);
+    if (rc) return rc;
+    ENTER(h);
+    return pca_launch_ard(h, false);
 }
 
 // rows [N][d] on the host -> padded device rows [N][DP]
@@ -458,7 +517,8 @@ int pyvb_pca_elbo(pyvb_pca* h, double parts[5]) {
     return PYVB_OK;
 }
 
-// niters passes of Network.learn's body over the fetched PCA network: crawl order W, Z, X_0, Mu, X_1.., Beta, bound
+// niters passes of Network.learn's body over the fetched PCA network: crawl order W, Z, (the columns' Gamma parents,) X_0, Mu,
+// X_1.., Beta, bound
 int pyvb_pca_iterate(pyvb_pca* h, int niters) {
     ENTER(h);
     ARGCHK(niters >= 0, "niters must be >= 0");
@@ -470,7 +530,9 @@ int pyvb_pca_iterate(pyvb_pca* h, int niters) {
             // as the calls of the general path below.
             if ((rc = ensure_full(h))) return rc;                       // update_W
             h->st.z_requested();                                        // update_Z, deferred (lin_valid holds after ensure_full)
-            if ((rc = pca_launch_small(h, PCA_RUN_HEAD))) { h->st.z_request_failed(); return rc; }
+            // Gamma parents on the columns of W: their update is one more step of the same launch, behind W (it commutes with the Z
+            // update, after which the crawl order has it); a handle without them launches what it always launched
+            if ((rc = pca_launch_small(h, h->ard_on ? PCA_RUN_HEAD_ARD : PCA_RUN_HEAD))) { h->st.z_request_failed(); return rc; }
             h->st.linear_step();
             // the X_0 step reads row 0: a no-op after an iteration of this loop (its sweep left vlo == 1), but not after a
             // stage-wise pyvb_pca_update_X(0, N)
@@ -484,6 +546,7 @@ int pyvb_pca_iterate(pyvb_pca* h, int niters) {
             continue;
         }
         if ((rc = pyvb_pca_update_W(h))) return rc;
+        if (h->ard_on && (rc = pca_launch_ard(h, false))) return rc;    // local, not a collective: W is the same on every rank, so alpha is too
         if ((rc = pyvb_pca_update_Z(h))) return rc;
         const long first = h->row_offset == 0 ? 1 : 0;         // global row 0 lives on the rank with offset 0
         if ((rc = x0_step(h))) return rc;                       // every rank: the exchange is collective

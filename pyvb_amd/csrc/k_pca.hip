@@ -21,7 +21,7 @@ struct PcaArgs {
     double* X; const unsigned char* M; double* xvar; const int* nmiss; double* Z;
     const double* Xdata; unsigned char* pinned;     // null unless some rows have not been conditioned on their observations yet
     double *W_mean, *W_var, *Mu_mean, *Mu_var, *Z_cov, *qld_W, *lnd_W;
-    const double *W_pm, *W_pp, *Mu_pm, *Mu_pp;
+    const double* W_pm; double* W_pp; const double *Mu_pm, *Mu_pp;     // W_pp is written by PCA_ARD only
     double* scal; double* Gz; double* g0; double* sx_local;
     double* part; double* stats; double* aux; double* aux_tail; double* elbo; int* status;     // aux_tail: the [sum z | delta of sum x] vector
     long N, N_total, chunk_rows, lo_upd, hi_upd, n_part_missing, n_none_rows, row_offset;
@@ -36,6 +36,9 @@ struct PcaArgs {
     double *W_x, *Mu_x; long vin_lo, vin_hi;
     int save_wx;        // k_pca_rowvar: copy W_mean, Mu_mean to W_x, Mu_x (the sweep before it imputed with them and stored nothing)
     PcaStatsLayout SL;
+    // Gamma precision parents of the columns of W (pca.h: AR_*, [AR_COUNT][q]); null on a handle without them
+    double* ard;
+    int ard_derive;     // PCA_ARD: qb is the caller's (pyvb_pca_set_column_precisions): form only what follows from it
 };
 
 __device__ __forceinline__ double wsum(double v) {
@@ -1163,6 +1166,65 @@ __device__ __forceinline__ void pca_small_body(const PcaArgs& a, double* sm, dou
             a.qld_W[tid] = 0.5 / hl;                // gaussian.py:120 (quirk Q1)
             a.lnd_W[tid] = -2.0 * hl;               // ln det qcov (exact bound)
         }
+    } else if constexpr (MODE == PCA_ARD) {
+        // [al.update() for al in alphas]: column i of W has the precision parent Gamma(d, a0_i, b0_i) (gaussian.py:55-61); its one
+        // child has d entries, so qa_i = a0_i + d / 2 is fixed (nodes_todo.py:125-128) and
+        //   qb_i = b0_i + 1/2 sum_k ((<W>[k][i] - pm[k][i])^2 + var(W[k][i]))                       (nodes_todo.py:130-138, traces).
+        // thread = row k; per block of 16 columns the terms go through pv, PCA_W's LDS columns (all their loads are issued before
+        // the first sum), and the sum over the rows is PCA_W's: wsum, then the four wavefront partials added left to right
+        double* ar = a.ard;
+        double* ex = sm;                                    // [32] <alpha_i> = qa_i / qb_i
+        double* pv = sm + 32 * 32;                          // [16][256]
+        double* lred = pv + 2 * 16 * 256;                   // [4][32]
+        const int k = tid;
+        // the column's constants (and the caller's qb) are asked for before the rows: one trip to L2 for both
+        double b0q = 1.0, qa = 1.0, lqa = 0.0, dga = 0.0;
+        if (tid < q) {
+            b0q = ar[(a.ard_derive ? AR_QB : AR_B0) * q + tid]; qa = ar[AR_QA * q + tid];
+            lqa = ar[AR_LN_QA * q + tid]; dga = ar[AR_DIGAMMA_QA * q + tid];
+        }
+        if (!a.ard_derive) {
+            for (int i0 = 0; i0 < q; i0 += 16) {
+#pragma unroll
+                for (int ii = 0; ii < 16; ++ii) {
+                    const int i = i0 + ii;
+                    if (i < q && k < d) {
+                        const double dw = a.W_mean[(size_t)k * q + i] - a.W_pm[(size_t)k * q + i];
+                        pv[ii * 256 + tid] = dw * dw + a.W_var[(size_t)i * d + k];
+                    }
+                }
+                // four columns at a time: their wsum chains are independent and interleave (a chain is six dependent cross-lane
+                // steps, which a wavefront alone on its SIMD cannot hide); each chain is wsum's, step for step
+                for (int ii = 0; ii < 16 && i0 + ii < q; ii += 4) {
+                    double v[4];
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) v[j] = (k < d && i0 + ii + j < q) ? pv[(ii + j) * 256 + tid] : 0.0;
+#pragma unroll
+                    for (int o = 32; o > 0; o >>= 1)
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) v[j] += __shfl_xor(v[j], o, 64);
+                    if ((tid & 63) == 0)
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) lred[(tid >> 6) * 32 + i0 + ii + j] = v[j];     // (columns >= q: zeros nobody reads)
+                }
+            }
+            __syncthreads();
+        }
+        if (tid < q) {
+            double qb = b0q;
+            if (!a.ard_derive) {
+                qb = b0q + 0.5 * (((lred[tid] + lred[32 + tid]) + lred[64 + tid]) + lred[96 + tid]);
+                ar[AR_QB * q + tid] = qb;
+            }
+            const double lqb = log(qb);
+            ar[AR_LN_REF * q + tid] = lqa - lqb;            // Gamma.pass_down_lndet / d (nodes_todo.py:147, quirk Q2)
+            ar[AR_LN_EXACT * q + tid] = dga - lqb;          // E ln alpha_i
+            ex[tid] = qa / qb;
+        }
+        __syncthreads();
+        // what the next w_i.update() and the bound read as the column's prior precision: pprec = (qa_i / qb_i) I (gaussian.py:113)
+        if (k < d)
+            for (int i = 0; i < q; ++i) a.W_pp[(size_t)i * d + k] = ex[i];
     } else if constexpr (MODE == PCA_PREPZ) {
         // posterior of the Z_n: precision I + beta <W^T W>, shared by all n; Gz = beta Sigma_z <W>^T
         double* P = sm; double* Sg = sm + 64 * 64;
@@ -1313,6 +1375,17 @@ __device__ __forceinline__ void pca_small_body(const PcaArgs& a, double* sm, dou
             }
         }
         if (tid < q) lw += 0.5 * (exact ? a.lnd_W : a.qld_W)[tid] + 0.5 * d;        // (- d/2 ln 2 pi of the prior term + d/2 ln 2 pi of the entropy cancel)
+        if (a.ard && tid < q) {
+            // Gamma parents of the columns: W_pp[i][.] = qa_i / qb_i, so the sum above took 1/2 d ln (qa_i / qb_i) as the column's
+            // 1/2 pass_down_lndet (quirk Q2; the same value up to rounding); the exact bound has 1/2 d E[ln alpha_i] there.
+            // Then Gamma.log_lower_bound of alpha_i itself (nodes_todo.py:149-157), booked with the W class.
+            const double* ar = a.ard;
+            const double a0 = ar[AR_A0 * q + tid], b0 = ar[AR_B0 * q + tid], aqa = ar[AR_QA * q + tid], aqb = ar[AR_QB * q + tid];
+            const double Elnx = ar[AR_LN_EXACT * q + tid], ex = aqa / aqb;
+            if (exact) lw += 0.5 * d * (Elnx - ar[AR_LN_REF * q + tid]);
+            lw += (a0 - 1.0) * Elnx - ar[AR_LGAMMA_A0 * q + tid] + a0 * log(b0) - b0 * ex;
+            lw -= (aqa - 1.0) * Elnx - ar[AR_LGAMMA_QA * q + tid] + aqa * log(aqb) - aqb * ex;
+        }
         const double LW = bsum(lw, red);
         double lm = 0.0;
         if (tid < d) {
@@ -1363,6 +1436,7 @@ static PcaArgs pca_args(pyvb_pca* h) {
     a.res_cached = h->st.res_valid ? 1 : 0;
     a.keep_z0 = 0; a.z_deferred = 0; a.x0_prep = 0;
     a.W_x = h->W_x; a.Mu_x = h->Mu_x; a.vin_lo = a.vin_hi = 0; a.save_wx = 0;
+    a.ard = h->ard_on ? h->ard : nullptr; a.ard_derive = 0;
     return a;
 }
 
@@ -1377,11 +1451,23 @@ int pca_launch_small(pyvb_pca* h, int mode) {
         PCA_SMALL(PCA_ELBO, PCA_ELBO); PCA_SMALL(PCA_X0, PCA_X0); PCA_SMALL(PCA_APPLY, PCA_APPLY);
         // runs of pyvb_pca_iterate without a communicator (with one, an all-reduce sits between the steps)
         PCA_SMALL(PCA_RUN_HEAD, PCA_W, PCA_PREPZ, PCA_APPLY);
+        // the same with Gamma parents on the columns of W: their update commutes with the Z update (it reads its own column of
+        // <W>, var(W) and the prior mean, and feeds the next W update and the bound only) and runs right behind W
+        PCA_SMALL(PCA_RUN_HEAD_ARD, PCA_W, PCA_ARD, PCA_PREPZ, PCA_APPLY);
         PCA_SMALL(PCA_RUN_MID, PCA_X0, PCA_APPLY, PCA_MU);
         PCA_SMALL(PCA_RUN_TAIL, PCA_BETA, PCA_ELBO);
 #undef PCA_SMALL
         default: pyvb_set_error("no such small kernel"); return PYVB_E_ARG;
     }
+    HIPCHK(hipGetLastError());
+    return PYVB_OK;
+}
+
+// [al.update() for al in alphas] alone; derive: from qb as the caller gave it (pyvb_pca_set_column_precisions)
+int pca_launch_ard(pyvb_pca* h, bool derive) {
+    PcaArgs a = pca_args(h); a.mode = PCA_ARD; a.ard_derive = derive ? 1 : 0;
+    if (!a.ard) { pyvb_set_error("no Gamma parents on the columns of W"); return PYVB_E_ARG; }
+    hipLaunchKernelGGL((k_pca_small<PCA_ARD>), dim3(1), dim3(256), 0, h->stream, a);
     HIPCHK(hipGetLastError());
     return PYVB_OK;
 }

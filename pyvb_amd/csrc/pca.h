@@ -64,7 +64,14 @@ struct pyvb_pca {
     bool pairs_ready;                    // pca_prepare_pairs() has been called for this handle's device
     int nchunkB; long chunk_rowsB;       // k_pca_pairs' partition of the rows: a workgroup per CU
     pyvb_comm* comm; int rank, world;
+    // Gamma precision parents of the columns of W (pyvb_pca_set_column_precisions, PCA_ARD): [AR_COUNT][q], allocated by the first
+    // call that gives hyperpriors, never on a handle that makes none.  ard_on is what the launchers read; pyvb_pca_set_priors clears it.
+    double* ard; bool ard_on;
 };
+// rows of pyvb_pca::ard, [q] each.  qa_i = a0_i + d / 2 never changes (nodes_todo.py:125-128): lgamma, digamma and ln of the
+// shape parameters are formed on the host, as for Beta.  AR_LN_REF = ln qa - ln qb (pass_down_lndet / d, nodes_todo.py:147);
+// AR_LN_EXACT = psi(qa) - ln qb = E[ln alpha]; both follow qb on the device.
+enum { AR_A0 = 0, AR_B0, AR_QA, AR_QB, AR_LGAMMA_A0, AR_LGAMMA_QA, AR_DIGAMMA_QA, AR_LN_QA, AR_LN_REF, AR_LN_EXACT, AR_COUNT };
 
 int pca_launch_small(pyvb_pca* h, int mode);
 int pca_prepare_pairs();                                    // once per device, before the first k_pca_pairs: its dynamic-LDS limit
@@ -73,5 +80,6 @@ int pca_launch_sweep(pyvb_pca* h, const PcaSweepPlan& p);   // (materialise,) pa
 int pca_materialize_x(pyvb_pca* h, long vlo, long vhi);     // the unstored entries of rows [vlo, vhi) into X
 int pca_launch_reduce(pyvb_pca* h, int what);
 int pca_launch_rowqld(pyvb_pca* h, double* out, int logdet = 0);      // out: device [N]; logdet: ln det qcov instead of q_ln_det
-enum { PCA_W = 0, PCA_PREPZ = 1, PCA_MU = 2, PCA_BETA = 3, PCA_ELBO = 4, PCA_X0 = 5, PCA_APPLY = 6,
-       PCA_RUN_HEAD = 16, PCA_RUN_MID = 17, PCA_RUN_TAIL = 18 };     // runs of steps in one launch (k_pca.hip: pca_launch_small)
+int pca_launch_ard(pyvb_pca* h, bool derive);               // PCA_ARD alone; derive: qb is the caller's, form W_pp and the log terms from it
+enum { PCA_W = 0, PCA_PREPZ = 1, PCA_MU = 2, PCA_BETA = 3, PCA_ELBO = 4, PCA_X0 = 5, PCA_APPLY = 6, PCA_ARD = 7,
+       PCA_RUN_HEAD = 16, PCA_RUN_MID = 17, PCA_RUN_TAIL = 18, PCA_RUN_HEAD_ARD = 19 };     // runs of steps in one launch (k_pca.hip: pca_launch_small)

@@ -53,6 +53,23 @@ class PCABatch(object):
              _f64(pri["Mu_prior_mean"], (d,), "Mu_prior_mean"), _f64(pri["Mu_prior_prec"], (d,), "Mu_prior_prec")]
         C.check(C.lib.pyvb_pca_set_priors(self._h, *[C.dptr(x) for x in a], float(pri["beta_a0"]), float(pri["beta_b0"])))
 
+    def set_column_precisions(self, a0, b0, qb):
+        """Gamma precision parents for the columns of W (automatic relevance determination): column i gets
+        Gamma(d, a0[i], b0[i]) with the initial rate qb[i] in place of its Constant precision; scalars are broadcast to [q].
+        Call after set_priors (which, called again, takes the parents away).  iterate() then updates them in every pass."""
+        a = [np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=np.float64), (self.q,))) for v in (a0, b0, qb)]
+        C.check(C.lib.pyvb_pca_set_column_precisions(self._h, *[C.dptr(x) for x in a]))
+
+    def column_precisions(self):
+        """(qa, qb), [q] each: <alpha_i> = qa[i] / qb[i]."""
+        qa, qb = np.empty(self.q), np.empty(self.q)
+        C.check(C.lib.pyvb_pca_get_column_precisions(self._h, C.dptr(qa), C.dptr(qb)))
+        return qa, qb
+
+    def update_column_precisions(self):
+        """[al.update() for al in alphas], for stage-wise use (the crawl order has it after update_Z)."""
+        C.check(C.lib.pyvb_pca_update_column_precisions(self._h))
+
     def set_data(self, X):
         """X [N, d] with NaN where an entry is missing (Gaussian.observe, gaussian.py:74-100)."""
         C.check(C.lib.pyvb_pca_set_data(self._h, C.dptr(_f64(X, (self.N, self.d), "X"))))
@@ -157,11 +174,14 @@ class PCABatch(object):
     @classmethod
     def from_problem(cls, init, pri, device=0):
         """init: dict with obs [N,d] bool, X [N,d] (data / initial means of the missing entries), W_mean, Z, Z_cov,
-        Mu_mean, beta_b (tests/golden/make_golden.py: pca_problem)."""
+        Mu_mean, beta_b (tests/golden/make_golden.py: pca_problem).  pri["W_alpha"] = (a0, b0, qb), optional: Gamma precision
+        parents for the columns of W (set_column_precisions)."""
         N, d = init["X"].shape
         q = init["Z"].shape[1]
         b = cls(N, d, q, device)
         b.set_priors(pri)
+        if pri.get("W_alpha") is not None:
+            b.set_column_precisions(*pri["W_alpha"])
         b.set_data(np.where(init["obs"], init["X"], np.nan))
         b.set_state(X_missing=init["X"], W_mean=init["W_mean"], Z=init["Z"], Z_cov=init["Z_cov"],
                     Mu_mean=init["Mu_mean"], beta_b=float(init["beta_b"]))
