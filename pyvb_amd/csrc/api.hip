@@ -161,6 +161,7 @@ static int lds_create(pyvb_lds** out, int device, int N, int T, int D, int K, in
     h->status_host.assign(n, 0);
     h->reported.assign(n, 0);
     TRY(dev_alloc(&h->pri_block, g.priors));       // one block, cut below in the order LdsGeometry.priors lists
+    TRY(dev_alloc(&h->w0, L.DP));
     double* p = h->pri_block;
     h->pri.x0_mean = p; p += D; h->pri.x0_prec = p; p += D * D;
     h->pri.A_pm = p; p += D * D; h->pri.A_pp = p; p += D * D;
@@ -310,6 +311,7 @@ int pyvb_lds_set_priors(pyvb_lds* h, const double* x0_mean, const double* x0_pre
     int rc;
     if ((rc = h2d(h, h->pri.x0_mean, x0_mean, D))) return rc;
     if ((rc = h2d(h, h->pri.x0_prec, x0_prec, (size_t)D * D))) return rc;
+    if (!h->big && (rc = launch_w0(h))) return rc;         // (the 128-wide class forms L0 m0 in k_prep_big)
     if ((rc = h2d(h, h->pri.A_pm, A_pm, (size_t)D * D))) return rc;
     if ((rc = h2d(h, h->pri.A_pp, A_pp, (size_t)D * D))) return rc;
     if ((rc = h2d(h, h->pri.C_pm, C_pm, (size_t)K * D))) return rc;

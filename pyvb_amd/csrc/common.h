@@ -48,6 +48,7 @@ struct pyvb_lds {
     int bound;                      // PYVB_BOUND_REFERENCE / PYVB_BOUND_EXACT: which lower bound k_elbo / k_elbo_dense form
     Priors pri;
     double *pri_block;
+    double *w0;                     // [DP] L0 m0 of the prior of X_0 (k_prep.hip: k_w0), as of the last pyvb_lds_set_priors
     ArdBuffers ard[2];              // Gamma parents of the columns of A ([0]) and C ([1]); all null / off unless the caller asked
     // derived
     double *Sigma, *qld_x;          // as of the last X update: [N][3][D][D], [N][3]
@@ -116,6 +117,7 @@ struct pyvb_lds {
 
 // ---- launchers implemented in the kernel translation units ----
 int launch_prep(pyvb_lds* h);
+int launch_w0(pyvb_lds* h);         // L0 m0 from the priors of X_0 on the device: after every change of them
 // A sweep reads X[src] and writes X[1 - src]; read_cache: a backward sweep that starts from the c_t a forward one left in U.
 // keep_x = false: a forward sweep whose states nobody reads (the backward one follows and reads c_t).
 int launch_sweep(pyvb_lds* h, int direction, int src, bool read_cache, bool keep_x);

@@ -16,7 +16,8 @@
 #include "gj.h"
 
 struct PrepArgs {
-    const double *A_mean, *A_var, *C_mean, *C_var, *Q_a, *Q_b, *R_a, *R_b, *x0_mean, *x0_prec;
+    const double *A_mean, *A_var, *C_mean, *C_var, *Q_a, *Q_b, *R_a, *R_b, *x0_prec;
+    const double* w0;                   // [DP] L0 m0, formed when the priors are set (k_w0)
     double *Sigma, *qld, *lnd, *gains, *scratch;     // lnd: ln det Sigma of the three classes beside qld
     // Wishart noise (DENSE): E[Q] [D][D], E[Q] <A> [D][D], E[R] <C> [K][D], tr(S_i E[Q]) [D], tr(S'_i E[R]) [D] per replicate
     const double *Qbar, *QA, *RC, *trA, *trC;
@@ -302,11 +303,7 @@ __global__ void __launch_bounds__(PREP_THREADS) k_prep(PrepArgs a) {
         }
     }
     if (tid < 64) { g[L.oqr + tid] = qbar[tid]; g[L.oqr + 64 + tid] = rbar[tid]; }
-    if (tid < DP) {      // L0 m0: the Constant mean parent of X_0 through its Constant precision
-        double s = 0.0;
-        if (tid < D) for (int j = 0; j < D; ++j) s += a.x0_prec[tid * D + j] * a.x0_mean[j];
-        g[L.ow0 + tid] = s;
-    }
+    if (tid < DP) g[L.ow0 + tid] = a.w0[tid];       // L0 m0 depends on the priors alone: k_w0 below
     // gains of the interior class
 #pragma unroll
     for (int ra = 0; ra < 4; ++ra)
@@ -379,6 +376,25 @@ __global__ void __launch_bounds__(PREP_THREADS) k_prep(PrepArgs a) {
     if (tid == 0) a.warm[n * 2 + 1] = J;
 }
 
+// L0 m0: the Constant mean parent of X_0 through its Constant precision, row tid of it; rows from D on are zero.  One
+// workgroup, once per pyvb_lds_set_priors -- k_prep formed it for every replicate in every iteration, a memory round trip per
+// entry of the row.
+struct W0Args { const double *x0_mean, *x0_prec; double* w0; int D, DP; };
+__global__ void __launch_bounds__(128) k_w0(W0Args a) {
+    const int tid = threadIdx.x, D = a.D;
+    if (tid >= a.DP) return;
+    double s = 0.0;
+    if (tid < D) for (int j = 0; j < D; ++j) s += a.x0_prec[tid * D + j] * a.x0_mean[j];
+    a.w0[tid] = s;
+}
+
+int launch_w0(pyvb_lds* h) {
+    W0Args a; a.x0_mean = h->pri.x0_mean; a.x0_prec = h->pri.x0_prec; a.w0 = h->w0; a.D = h->D; a.DP = h->L.DP;
+    hipLaunchKernelGGL(k_w0, dim3(1), dim3(128), 0, h->stream, a);
+    HIPCHK(hipGetLastError());
+    return PYVB_OK;
+}
+
 template <int DT, int KT>
 static void launch_prep_t(pyvb_lds* h, const PrepArgs& a) {
     if (h->dense) hipLaunchKernelGGL((k_prep<DT, KT, true>), dim3(h->N), dim3(PREP_THREADS), 0, h->stream, a);
@@ -390,7 +406,7 @@ int launch_prep(pyvb_lds* h) {
     PrepArgs a;
     a.A_mean = h->A_mean; a.A_var = h->A_var; a.C_mean = h->C_mean; a.C_var = h->C_var;
     a.Q_a = h->Q_a; a.Q_b = h->Q_b; a.R_a = h->R_a; a.R_b = h->R_b;
-    a.x0_mean = h->pri.x0_mean; a.x0_prec = h->pri.x0_prec;
+    a.x0_prec = h->pri.x0_prec; a.w0 = h->w0;
     a.Sigma = h->Sigma_new; a.qld = h->qld_x_new; a.lnd = h->lnd_x_new; a.gains = h->gains; a.scratch = h->scratch;
     a.warm = h->warm; a.status = h->status; a.active = h->active;
     a.Qbar = h->Qbar; a.QA = h->QA; a.RC = h->RC; a.trA = h->trA; a.trC = h->trC;

@@ -39,46 +39,53 @@ struct SweepArgs {
 // Multiplication.pass_up_m1_m2 / pass_down_Ex, node.py:182-242), lane = row, one wavefront:
 //   t = 0   : v = L0 m0 + <A>^T<Q> mu_1 + <C>^T<R> y_0         mu_0     = Sigma_0 v
 //   t = T-1 : v = <Q><A> mu_{T-2}       + <C>^T<R> y_{T-1}     mu_{T-1} = Sigma_2 v
-// i.e. qmu = qcov (sum of the m2 messages), as the reference has it.  nb(j) is entry j of the one
-// neighbour's mean, vs 64 doubles of LDS.
+// i.e. qmu = qcov (sum of the m2 messages), as the reference has it.
 // With Wishart noise the expected precisions are dense: QA = <Q><A>, RC = <R><C> take the place of the scaled rows
 // (<A>^T<Q> = QA^T, <C>^T<R> = RC^T; the expectations are symmetric).
-template <class NB>
-__device__ __forceinline__ double boundary_update(bool first, const double* g, const Layout& L, const double* Am, const double* Cm,
-                                                  int D, int K, int lane, NB nb, const double* y, double* vs,
-                                                  const double* QA = nullptr, const double* RC = nullptr) {
-    const double* qb = g + L.oqr;
-    const double* rb = qb + 64;
-    double v = 0.0;
-    if (QA) {
-        if (lane < D) {
-            if (first) {
-                v = g[L.ow0 + lane];
-                for (int i = 0; i < D; ++i) v += QA[(size_t)i * D + lane] * nb(i);
-            } else {
-                for (int j = 0; j < D; ++j) v += QA[(size_t)lane * D + j] * nb(j);
-            }
-            for (int k = 0; k < K; ++k) v += RC[(size_t)k * D + lane] * y[k];
-        }
-    } else if (lane < D) {
-        if (first) {
-            v = g[L.ow0 + lane];
-            for (int i = 0; i < D; ++i) v += Am[(size_t)i * D + lane] * (qb[i] * nb(i));
-        } else {
-            double s = 0.0;
-            for (int j = 0; j < D; ++j) s += Am[(size_t)lane * D + j] * nb(j);
-            v = qb[lane] * s;
-        }
-        for (int k = 0; k < K; ++k) v += Cm[(size_t)k * D + lane] * (rb[k] * y[k]);
+//
+// Each of the three products is a chain of multiply-adds over i = 0 .. n-1 in this order, one matrix entry per lane and
+// step.  Fetched one entry per step the chain waits a memory round trip per step (some 190 per node, with every wavefront
+// of the launch doing the same and the matrix pipe idle); so the entries come in blocks of BOUNDARY_BLOCK, all loads of a
+// block issued before the first use, from clamped places and with zero selected outside n (the idiom of the sweep loop):
+// ceil(n / 16) waits per product.
+constexpr int BOUNDARY_BLOCK = 16;      // 32 VGPRs in flight; the kernels stay without scratch (profiles/sweep_boundary_resource_usage.txt)
+
+// v + sum_i M[i * stride + off] * u[i] over i < n <= NP in the order i = 0, 1, ...; u: LDS, zero from n on
+template <int NP>
+__device__ __forceinline__ double boundary_chain(double v, const double* M, size_t stride, size_t off, int n, const double* u) {
+#pragma unroll
+    for (int b = 0; b < NP; b += BOUNDARY_BLOCK) {
+        if (b >= n) break;
+        double m[BOUNDARY_BLOCK];
+#pragma unroll
+        for (int e = 0; e < BOUNDARY_BLOCK; ++e) m[e] = M[(size_t)(b + e < n ? b + e : n - 1) * stride + off];
+#pragma unroll
+        for (int e = 0; e < BOUNDARY_BLOCK; ++e) v += (b + e < n ? m[e] : 0.0) * u[b + e];
     }
-    vs[lane] = v;
+    return v;
+}
+
+// xn: entry `lane` of the one neighbour's mean (lanes from D on: anything); ux, uy, vs: 64 doubles of LDS each, which hand
+// the wave-uniform factors round -- q_i mu_i (or mu_i), r_k y_k (or y_k), then v_j -- each fetched or formed once, by lane i
+template <int DP, int KP>
+__device__ __forceinline__ double boundary_update(bool first, const double* g, const Layout& L, const double* Am, const double* Cm,
+                                                  int D, int K, int lane, double xn, const double* y, double* ux, double* uy, double* vs,
+                                                  const double* QA = nullptr, const double* RC = nullptr) {
+    const bool dense = QA != nullptr;
+    const int lc = lane < D ? lane : D - 1, kc = lane < K ? lane : K - 1;       // lanes past the end redo the last row; their result is dropped
+    const double qb = g[L.oqr + lc], rb = g[L.oqr + 64 + kc], yk = y[kc], w0 = g[L.ow0 + lc];
+    ux[lane] = lane < D ? ((first && !dense) ? qb * xn : xn) : 0.0;
+    uy[lane] = lane < K ? (dense ? yk : rb * yk) : 0.0;
     __syncthreads();
-    const double* S = g + (first ? L.oS0 : L.oS2);
-    double s = 0.0;
-    if (lane < D)
-        for (int j = 0; j < D; ++j) s += S[(size_t)j * L.DP + lane] * vs[j];      // Sigma is symmetric
+    // first: column lc of the matrix (<A>^T<Q> mu), else row lc (<Q><A> mu)
+    double v = boundary_chain<DP>(first ? w0 : 0.0, dense ? QA : Am, first ? D : 1, (size_t)lc * (first ? 1 : D), D, ux);
+    if (!first && !dense) v = qb * v;
+    v = boundary_chain<KP>(v, dense ? RC : Cm, D, lc, K, uy);
+    vs[lane] = lane < D ? v : 0.0;
     __syncthreads();
-    return s;
+    const double s = boundary_chain<DP>(0.0, g + (first ? L.oS0 : L.oS2), L.DP, lc, D, vs);      // Sigma is symmetric
+    __syncthreads();
+    return lane < D ? s : 0.0;
 }
 
 // FULL: D == 16*DT and K == 16*KT (no padded rows/columns, 16-byte aligned rows)
@@ -93,10 +100,10 @@ __device__ __forceinline__ double boundary_update(bool first, const double* g, c
 // SPLIT: several wavefronts per replicate (a.W > 1, few replicates); without it the part offsets fold to constants.
 template <int DT, int KT, bool FULL, int MODE, bool SPLIT>
 __global__ void __launch_bounds__(64) k_sweep(SweepArgs a) {
-    constexpr int DS = 4 * DT, KS = 4 * KT, DP = 16 * DT;
+    constexpr int DS = 4 * DT, KS = 4 * KT, DP = 16 * DT, KP = 16 * KT;
     __shared__ double gl[MODE == 2 ? DP * 17 : DT * KS * 64];     // G as MFMA A operands; MODE 2: the state tile, transposed (below)
     __shared__ double xs[64];               // boundary state exchange
-    __shared__ double vs[64];               // boundary_update scratch
+    __shared__ double vs[64], ux[64], uy[64];       // boundary_update scratch
     const int n = blockIdx.x, w = SPLIT ? blockIdx.y : 0, lane = threadIdx.x, c = lane & 15, q = lane >> 4;
     if (!a.active[n]) return;
     const int T = a.T, D = a.D, K = a.K;
@@ -148,8 +155,8 @@ __global__ void __launch_bounds__(64) k_sweep(SweepArgs a) {
     const double* RCm = a.RC ? a.RC + (size_t)n * K * D : nullptr;
     if (!SPLIT || ow <= J) {
         const double* xo = Xo + (size_t)(t_first + sgn) * DP;
-        const double s = boundary_update(fwd, g, L, Am, Cm, D, K, lane, [&](int j) { return xo[xpos(j)]; },
-                                         Yn + (size_t)t_first * K, vs, QAm, RCm);
+        const double s = boundary_update<DP, KP>(fwd, g, L, Am, Cm, D, K, lane, xo[xpos(lane < D ? lane : D - 1)],
+                                                 Yn + (size_t)t_first * K, ux, uy, vs, QAm, RCm);
         if (w == 0 && lane < DP) Xn[(size_t)t_first * DP + xpos(lane)] = (lane < D) ? s : 0.0;
         xs[lane] = (lane < D) ? s : 0.0;
     }
@@ -387,8 +394,8 @@ __global__ void __launch_bounds__(64) k_sweep(SweepArgs a) {
     // ---- closing boundary node (t = T_n-1 forward, 0 backward): only the new neighbour; done by the
     // wavefront that owns the last interior node
     if (!SPLIT || w == ((Tint > 0) ? (Tint - 1) / Lw : 0)) {
-        const double s = boundary_update(!fwd, g, L, Am, Cm, D, K, lane, [&](int j) { return xs[j]; },
-                                         Yn + (size_t)t_last * K, vs, QAm, RCm);
+        const double s = boundary_update<DP, KP>(!fwd, g, L, Am, Cm, D, K, lane, xs[lane],
+                                                 Yn + (size_t)t_last * K, ux, uy, vs, QAm, RCm);
         if (lane < DP) Xn[(size_t)t_last * DP + xpos(lane)] = (lane < D) ? s : 0.0;
     }
 }
@@ -415,11 +422,12 @@ __global__ void __launch_bounds__(64) k_step(StepArgs a) {
     const int cls = (t == 0) ? 0 : (t == TL - 1 ? 2 : 1);
     const int row = lane % DP;
     if (cls != 1) {
-        __shared__ double vs[64];
+        __shared__ double vs[64], ux[64], uy[64];
         const double* nbr = X + (size_t)(cls == 0 ? 1 : TL - 2) * DP;
-        const double s = boundary_update(cls == 0, g, L, a.A_mean + (size_t)n * D * D, a.C_mean + (size_t)n * K * D, D, K, lane,
-                                         [&](int j) { return nbr[xpos(j)]; }, y, vs,
-                                         a.QA ? a.QA + (size_t)n * D * D : nullptr, a.RC ? a.RC + (size_t)n * K * D : nullptr);
+        // (compiled for the largest tile shape: blocks of rows past D or K are skipped, so every shape runs its own chain)
+        const double s = boundary_update<64, 64>(cls == 0, g, L, a.A_mean + (size_t)n * D * D, a.C_mean + (size_t)n * K * D, D, K, lane,
+                                                 nbr[xpos(lane < D ? lane : D - 1)], y, ux, uy, vs,
+                                                 a.QA ? a.QA + (size_t)n * D * D : nullptr, a.RC ? a.RC + (size_t)n * K * D : nullptr);
         if (lane < DP) X[(size_t)t * DP + xpos(lane)] = (lane < D) ? s : 0.0;
         return;
     }
