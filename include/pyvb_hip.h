@@ -195,6 +195,26 @@ int pyvb_lds_set_column_precisions(pyvb_lds* h, int which, const double* a0, con
 int pyvb_lds_get_column_precisions(pyvb_lds* h, int which, double* qa, double* qb);   /* [N][D] each; NULL = skip */
 int pyvb_lds_update_column_precisions(pyvb_lds* h, int which);     /* [al.update() for al in alphas of that matrix] */
 
+/* Sparse A and C: DiagonalGamma precision parents for the columns of A (which = 0, rows = D) or C (which = 1, rows = K), a
+ * precision of its own for every entry.  Column i becomes Gaussian(rows, pm_i, DiagonalGamma(rows, a0_i, b0_i)) (gaussian.py:55-61;
+ * nodes_todo.py:159-204): the prior precision of the column is diag(qa[i][.] / qb[n][i][.]), qa[i][k] = a0[i][k] + 1/2 is fixed by
+ * the graph, and
+ *   dg_i.update():  qb[n][i][k] = b0[i][k] + 1/2 ((M[k,i] - pm[k,i])^2 + V[i][k])      (known entries: M = value, V = 0).
+ * The lower bound takes sum_k (ln qa - ln qb) (reference mode, quirk Q2) or sum_k (psi(qa) - ln qb) (exact mode) as the column's
+ * ln det, and adds the nodes' own terms to part 2 (A) and part 3 (C).
+ *   a0[D][rows], b0[D][rows]: [column][row] as A_prior_prec is, shared by the replicates like every prior.
+ *   qb[N][D][rows]: initial state.  On a handle with tied models it is taken from each model's first row and copied to its other
+ *   rows, as pyvb_lds_set_column_precisions does.
+ * A matrix's columns have Constant, Gamma or DiagonalGamma parents: the most recent setter for that matrix wins, A and C may have
+ * different kinds, and pyvb_lds_set_priors returns both to Constant parents.  The three iterate entries run forward, backward, A,
+ * C, Q, R, the precision parents of A, then of C, bound.  Switched-off and converged replicates keep their qb.
+ * PYVB_E_UNSUPPORTED: Wishart noise, or max(D, K) > 64.  PYVB_E_ARG: which outside {0, 1}; a non-finite or non-positive a0, b0
+ * or qb (the message names the column and row, for qb the replicate too); get / update for a matrix without DiagonalGamma parents
+ * (and pyvb_lds_get_column_precisions / pyvb_lds_update_column_precisions for a matrix that has them). */
+int pyvb_lds_set_entry_precisions(pyvb_lds* h, int which, const double* a0, const double* b0, const double* qb);
+int pyvb_lds_get_entry_precisions(pyvb_lds* h, int which, double* qa, double* qb);   /* [N][D][rows] each; NULL = skip */
+int pyvb_lds_update_entry_precisions(pyvb_lds* h, int which);      /* [dg.update() for dg in the parents of that matrix] */
+
 /* Explicit posterior state instead of the constructors' random initialisation
  * (gaussian.py:70-72, nodes_todo.py:119,177). */
 int pyvb_lds_set_state(pyvb_lds* h, const double* X, const double* A_mean, const double* A_colvar,

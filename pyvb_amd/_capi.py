@@ -55,6 +55,9 @@ SIGNATURES = {
     "pyvb_lds_set_column_precisions": (ctypes.c_int, [_h, ctypes.c_int, _dp, _dp, _dp]),
     "pyvb_lds_get_column_precisions": (ctypes.c_int, [_h, ctypes.c_int, _dp, _dp]),
     "pyvb_lds_update_column_precisions": (ctypes.c_int, [_h, ctypes.c_int]),
+    "pyvb_lds_set_entry_precisions": (ctypes.c_int, [_h, ctypes.c_int, _dp, _dp, _dp]),
+    "pyvb_lds_get_entry_precisions": (ctypes.c_int, [_h, ctypes.c_int, _dp, _dp]),
+    "pyvb_lds_update_entry_precisions": (ctypes.c_int, [_h, ctypes.c_int]),
     "pyvb_lds_set_state": (ctypes.c_int, [_h] + [_dp] * 7),
     "pyvb_lds_get_state": (ctypes.c_int, [_h] + [_dp] * 9),
     "pyvb_lds_get_posterior_classes": (ctypes.c_int, [_h, _dp, _dp]),

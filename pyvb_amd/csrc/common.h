@@ -26,6 +26,17 @@ struct ArdBuffers {
     double *qb, *ex, *ld_ref, *ld_exact;    // [N][D] each: see ColumnPrior (params.h)
 };
 
+// DiagonalGamma parents of the columns of one matrix (pyvb_lds_set_entry_precisions, k_ard.hip: k_entry): a precision of its own
+// for every entry.  One allocation, made by the first call that gives the matrix such parents, never on a handle that makes none.
+// `on` is what make_args reads; pyvb_lds_set_priors and pyvb_lds_set_column_precisions of that matrix clear it.
+struct EntryBuffers {
+    bool on;
+    double *a0, *b0, *qa;                   // [D][rows] each, shared by the replicates; qa = a0 + 1/2
+    double *lnqa, *psi, *cst;               // [D][rows] each, formed by the setter: ln qa, psi(qa), the part of the node's own term without qb
+    double *qb, *ex;                        // [N][D][rows]: qb and qa / qb
+    double *ld_ref, *ld_exact, *own;        // [N][D]: see ColumnPrior (params.h)
+};
+
 struct EventPair;
 struct KernelTimer {
     double total_ms; int launches;
@@ -50,6 +61,7 @@ struct pyvb_lds {
     double *pri_block;
     double *w0;                     // [DP] L0 m0 of the prior of X_0 (k_prep.hip: k_w0), as of the last pyvb_lds_set_priors
     ArdBuffers ard[2];              // Gamma parents of the columns of A ([0]) and C ([1]); all null / off unless the caller asked
+    EntryBuffers entry[2];          // DiagonalGamma parents of the same; a matrix has at most one kind `on`
     // derived
     double *Sigma, *qld_x;          // as of the last X update: [N][3][D][D], [N][3]
     double *Sigma_new, *qld_x_new;  // written by k_prep for the current parameters
@@ -133,6 +145,8 @@ int launch_cols(pyvb_lds* h, int which, int c0, int c1, int fuse = 0);   // whic
 int launch_resid(pyvb_lds* h, int which);     // 0 = Q, 1 = R
 // k_ard.hip: [al.update() for al in alphas] of A (0), C (1) or both (2); derive: form qa / qb and the log-determinants from qb as given
 int launch_ard(pyvb_lds* h, int which, bool derive);
+// k_ard.hip: [dg.update() for dg in the DiagonalGamma parents] of the columns of A (0), C (1) or both (2); derive as above
+int launch_entry(pyvb_lds* h, int which, bool derive);
 int launch_noise(pyvb_lds* h, int which);
 int launch_elbo(pyvb_lds* h, hipStream_t stream = nullptr);                           // stream: the handle's main one unless given
 int launch_elbo_sum(pyvb_lds* h, double* out = nullptr, hipStream_t stream = nullptr);    // out: h->elbo_sum unless given; [7], out[6] = replicates still running

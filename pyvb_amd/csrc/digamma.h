@@ -11,7 +11,8 @@
 // test_device_special_functions).
 // Poles: a negative integer below -64 gives NaN; 0 and the negative integers down to -64 meet 1 / 0 in the recurrence and give
 // +-inf or NaN, as they always did.  The bounds never pass one.
-__device__ static inline double digamma_pos(double x) {
+// (__host__ too: pyvb_lds_set_entry_precisions forms psi(qa) of the DiagonalGamma parents once, on the host.)
+__host__ __device__ static inline double digamma_pos(double x) {
     if (!(x - x == 0.0) || x < -4.5e15) return x > 0 ? x : __builtin_nan("");      // below -2^52 every double is an integer: a pole
     double r = 0.0;
     if (x < -64.0) {

@@ -189,7 +189,8 @@ __global__ void __launch_bounds__(64 * NW) k_elbo(ParamArgs a) {
                 else r -= 0.5 * missing * LN2PI - 0.5 * lvar - 0.5 * missing;
             }
             // the column's Gamma parent, if it has one (k_ard.hip): its own term, the same in both modes (nodes_todo.py:149-157)
-            if (cp.qb) r += gamma_llb(cp.a0[i], cp.b0[i], cp.qa[i], cp.qb[(size_t)n * D + i]);
+            // DiagonalGamma parents (k_entry): the sum of the rows' own terms as that kernel left it
+            if (cp.qb) r += cp.own ? cp.own[(size_t)n * D + i] : gamma_llb(cp.a0[i], cp.b0[i], cp.qa[i], cp.qb[(size_t)n * D + i]);
             return r;
         };
         la = column(D, a.cpA, a.pri.A_pm, a.A_mean + (size_t)n * D * D, a.A_var + (size_t)n * D * D, a.pri.A_obs,
@@ -261,11 +262,20 @@ ParamArgs make_args(pyvb_lds* h) {
     a.N = h->N; a.T = h->T; a.D = h->D; a.K = h->K; a.noise = h->noise; a.L = h->L; a.c0 = 0; a.c1 = h->D; a.which0 = 0; a.fuse = 0; a.sxx = nullptr; a.W = 1;
     a.active = h->active;
     a.len = h->len; a.Lw = 0; a.first = h->first;
-    // the prior precisions of the columns (params.h: ColumnPrior): Constant parents, or the Gamma parents of pyvb_lds_set_column_precisions
+    // the prior precisions of the columns (params.h: ColumnPrior): Constant parents, the Gamma parents of
+    // pyvb_lds_set_column_precisions or the DiagonalGamma parents of pyvb_lds_set_entry_precisions
     for (int w = 0; w < 2; ++w) {
         ColumnPrior& cp = w == 0 ? a.cpA : a.cpC;
         const ArdBuffers& g = h->ard[w];
-        if (g.on) {
+        const EntryBuffers& e = h->entry[w];
+        const int rows = w == 0 ? h->D : h->K;
+        cp.lnqa = cp.psi = cp.cst = nullptr; cp.own = nullptr;
+        if (e.on) {
+            cp.pp = e.ex; cp.pp_n = h->D * rows; cp.pp_c = rows; cp.pp_r = 1;
+            cp.pld = h->bound == PYVB_BOUND_EXACT ? e.ld_exact : e.ld_ref; cp.pld_n = h->D;
+            cp.a0 = e.a0; cp.b0 = e.b0; cp.qa = e.qa; cp.qb = e.qb; cp.ex = e.ex; cp.ld_ref = e.ld_ref; cp.ld_exact = e.ld_exact;
+            cp.lnqa = e.lnqa; cp.psi = e.psi; cp.cst = e.cst; cp.own = e.own;
+        } else if (g.on) {
             cp.pp = g.ex; cp.pp_n = h->D; cp.pp_c = 1; cp.pp_r = 0;
             cp.pld = h->bound == PYVB_BOUND_EXACT ? g.ld_exact : g.ld_ref; cp.pld_n = h->D;
             cp.a0 = g.a0; cp.b0 = g.b0; cp.qa = g.qa; cp.qb = g.qb; cp.ex = g.ex; cp.ld_ref = g.ld_ref; cp.ld_exact = g.ld_exact;

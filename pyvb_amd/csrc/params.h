@@ -11,13 +11,18 @@
 //   precision of row k of column i in replicate n:  pp[n * pp_n + i * pp_c + k * pp_r]
 //   ln det of column i's prior precision:            pld[n * pld_n + i]
 // Constant parents: strides (0, rows, 1) over Priors::A_pp / C_pp and (0) over A_pld / C_pld.  Gamma parents: (D, 1, 0) over the
-// expectations qa / qb and (D) over the log-determinants of the handle's bound mode.
+// expectations qa / qb and (D) over the log-determinants of the handle's bound mode.  DiagonalGamma parents (one Gamma per entry,
+// k_ard.hip: k_entry): (D rows, rows, 1) over the expectations and (D) over the log-determinants.
 struct ColumnPrior {
     const double* pp; int pp_n, pp_c, pp_r;
     const double* pld; int pld_n;
     // Gamma parents alpha_i ~ Gamma(a0_i, b0_i) of the columns; all null with Constant parents
     const double *a0, *b0, *qa;             // [D]; qa_i = a0_i + rows / 2 is fixed by the graph (nodes_todo.py:125-128)
     double *qb, *ex, *ld_ref, *ld_exact;    // [N][D]: qb, qa / qb, rows (ln qa - ln qb) (quirk Q2), rows (psi(qa) - ln qb)
+    // DiagonalGamma parents: a0, b0, qa are [D][rows] (qa = a0 + 1/2), qb and ex [N][D][rows], ld_ref / ld_exact [N][D] the sums
+    // over the rows of ln qa - ln qb / psi(qa) - ln qb, and the four below are set; all null otherwise
+    const double *lnqa, *psi, *cst;         // [D][rows]: ln qa, psi(qa), the part of gamma_llb(a0, b0, qa, qb) that does not depend on qb
+    double* own;                            // [N][D]: sum over the rows of the nodes' own terms
 };
 
 struct ParamArgs {
@@ -45,7 +50,8 @@ struct ParamArgs {
     const unsigned char* first;     // k_elbo: [N] 1 = first replicate of its model (pyvb_lds_create_tied), or null: every one is
     int Lw;                 // k_moments: interior nodes per part of sxx, cut from the handle's T as k_sweep cuts them
     ColumnPrior cpA, cpC;   // k_cols, k_elbo, k_ard: the prior precisions of the columns of A and C
-    int derive;             // k_ard: 1 = qb is given (pyvb_lds_set_column_precisions): form what follows from it, in every row
+    int derive;             // k_ard, k_entry: 1 = qb is given (pyvb_lds_set_column_precisions, pyvb_lds_set_entry_precisions): form
+                            // what follows from it, in every row
 };
 
 // layout of the per-replicate moment block written by k_moments (all row-major, no padding)

@@ -25,13 +25,14 @@ def _f64(a, shape, name):
 
 _STATE_KEYS = ("X", "A_mean", "A_colvar", "C_mean", "C_colvar", "Q_b", "R_b")
 _ALPHA_KEYS = ("A_alpha_b", "C_alpha_b")        # [1, D] each: qb of the columns' Gamma parents, where a series' state carries them
+_ENTRY_KEYS = ("A_entry_b", "C_entry_b")        # [1, D, rows] each: qb of the columns' DiagonalGamma parents, likewise
 
 
 def pad_series(series):
     """series: list of (Y_n[T_n, K], st0_n), st0_n as synth.initial_state(T_n, D, K, 1) gives it.  Returns (Y[N, T, K],
     st0, lengths) with T = max T_n: the inputs of a handle with chain lengths.  Rows t >= T_n of Y and of st0["X"] are
-    padding (zeros here); no result depends on what they hold.  A_alpha_b / C_alpha_b (set_column_precisions) travel along where
-    the states carry them."""
+    padding (zeros here); no result depends on what they hold.  A_alpha_b / C_alpha_b (set_column_precisions) and A_entry_b /
+    C_entry_b (set_entry_precisions) travel along where the states carry them."""
     N = len(series)
     if N == 0:
         raise ValueError("no series")
@@ -47,7 +48,7 @@ def pad_series(series):
                                  % (n, y.shape, x.shape, lengths[n], K, lengths[n], D))
         Y[n, :lengths[n]], X[n, :lengths[n]] = y, x
     st0 = {"X": X}
-    for k in _STATE_KEYS[1:] + tuple(k for k in _ALPHA_KEYS if k in series[0][1]):
+    for k in _STATE_KEYS[1:] + tuple(k for k in _ALPHA_KEYS + _ENTRY_KEYS if k in series[0][1]):
         st0[k] = np.concatenate([np.asarray(st[k], dtype=np.float64) for _, st in series])       # each [1, ...]
     return Y, st0, lengths
 
@@ -68,6 +69,7 @@ class LDSBatch(object):
         self.N, self.T, self.D, self.K, self.noise, self.device = int(N), int(T), int(D), int(K), noise, int(device)
         self.bound = "reference"
         self._ard = set()               # the matrices ("A", "C") whose columns have Gamma parents (set_column_precisions)
+        self._entry = set()             # those whose columns have DiagonalGamma parents, one precision per entry (set_entry_precisions)
         h = C.ctypes.c_void_p()
         if models is not None:
             ln = None if lengths is None else np.ascontiguousarray(lengths, dtype=np.int32)
@@ -120,12 +122,14 @@ class LDSBatch(object):
         if self.noise == "wishart":     # Wishart(dim, v0, w0): Q_a0 / R_a0 hold v0, Q_b0 / R_b0 the matrices w0
             self._check(C.lib.pyvb_lds_set_priors(self._h, *([C.dptr(a) for a in arrs] + [None] * 4)))
             self._ard.clear()
+            self._entry.clear()
             qw0, rw0 = _f64(pri["Q_b0"], (D, D), "Q_w0"), _f64(pri["R_b0"], (K, K), "R_w0")
             self._check(C.lib.pyvb_lds_set_wishart_priors(self._h, float(pri["Q_a0"]), C.dptr(qw0), float(pri["R_a0"]), C.dptr(rw0)))
             return
         arrs += [bc(pri["Q_a0"], D), bc(pri["Q_b0"], D), bc(pri["R_a0"], K), bc(pri["R_b0"], K)]
         self._check(C.lib.pyvb_lds_set_priors(self._h, *[C.dptr(a) for a in arrs]))
         self._ard.clear()               # the columns have Constant parents again
+        self._entry.clear()
 
     def set_observations(self, Y):
         """Y[N,T,K]; NaN = missing entry (the rows concerned become variational nodes: set_output_state, update_Y).
@@ -202,6 +206,7 @@ class LDSBatch(object):
             a0, b0, qb = bc(a0, (self.D,)), bc(b0, (self.D,)), bc(qb, (self.N, self.D))
             self._check(_capi.lib.pyvb_lds_set_column_precisions(self._h, which, _capi.dptr(a0), _capi.dptr(b0), _capi.dptr(qb)))
             self._ard.add("AC"[which])
+            self._entry.discard("AC"[which])        # one kind of parent per matrix: the most recent setter wins
 
     def column_precisions(self):
         """{"A": (qa[N, D], qb[N, D]), "C": ...} of the matrices that have Gamma parents; E[alpha] = qa / qb."""
@@ -220,6 +225,47 @@ class LDSBatch(object):
                 self.update_column_precisions(w)
             return
         self._check(C.lib.pyvb_lds_update_column_precisions(self._h, {"A": 0, "C": 1}.get(which, which)))
+
+    def _rows(self, nm):
+        return self.D if nm == "A" else self.K
+
+    def set_entry_precisions(self, A=None, C=None):
+        """DiagonalGamma precision parents for the columns of A and / or C, a precision of its own for every entry (sparse
+        transition / loading matrices): each a tuple (a0[D, rows], b0[D, rows], qb[N, D, rows]) in [column][row] order as
+        A_prior_prec is, rows = D for A and K for C -- alpha[i][k] ~ Gamma(a0[i][k], b0[i][k]) is the prior precision of entry
+        (k, i), qb its initial posterior rate.  Scalars are broadcast.  Call after set_priors, which returns the columns to
+        Constant parents; it replaces Gamma parents of the same matrix (set_column_precisions) and is replaced by them.
+        DiagonalGamma / Gamma noise and max(D, K) <= 64 only."""
+        from . import _capi             # (the argument C shadows the module's alias here)
+        for which, t in ((0, A), (1, C)):
+            if t is None:
+                continue
+            a0, b0, qb = t
+            rows = self._rows("AC"[which])
+            bc = lambda v, shape: np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=np.float64), shape))
+            a0, b0, qb = bc(a0, (self.D, rows)), bc(b0, (self.D, rows)), bc(qb, (self.N, self.D, rows))
+            self._check(_capi.lib.pyvb_lds_set_entry_precisions(self._h, which, _capi.dptr(a0), _capi.dptr(b0), _capi.dptr(qb)))
+            self._entry.add("AC"[which])
+            self._ard.discard("AC"[which])
+
+    def entry_precisions(self):
+        """{"A": (qa[N, D, D], qb[N, D, D]), "C": (qa[N, D, K], qb[N, D, K])} of the matrices that have DiagonalGamma parents, in
+        [column][row] order; E[alpha] = qa / qb."""
+        out = {}
+        for nm in sorted(self._entry):
+            qa, qb = np.empty((self.N, self.D, self._rows(nm))), np.empty((self.N, self.D, self._rows(nm)))
+            self._check(C.lib.pyvb_lds_get_entry_precisions(self._h, "AC".index(nm), C.dptr(qa), C.dptr(qb)))
+            out[nm] = (qa, qb)
+        return out
+
+    def update_entry_precisions(self, which=None):
+        """[dg.update() for dg in the DiagonalGamma parents] of the columns of which = "A" (or 0), "C" (or 1); None: of every
+        matrix that has such parents, A first."""
+        if which is None:
+            for w in sorted(self._entry):
+                self.update_entry_precisions(w)
+            return
+        self._check(C.lib.pyvb_lds_update_entry_precisions(self._h, {"A": 0, "C": 1}.get(which, which)))
 
     # -- outputs ----------------------------------------------------------------------------
     def get_state(self, what=("X", "A_mean", "A_colvar", "C_mean", "C_colvar", "Q_a", "Q_b", "R_a", "R_b")):
@@ -320,7 +366,8 @@ class LDSBatch(object):
         return out
 
     def iterate(self, niters=1):
-        """niters x (forward sweep, backward sweep, A, C, Q, R, [the columns' Gamma parents,] lower bound); asynchronous."""
+        """niters x (forward sweep, backward sweep, A, C, Q, R, [the columns' Gamma / DiagonalGamma parents,] lower bound);
+        asynchronous."""
         self._check(C.lib.pyvb_lds_iterate(self._h, int(niters)))
 
     def elbo_history(self, last=4096):
@@ -489,4 +536,8 @@ class LDSBatch(object):
         ard = {w: (pri[w + "_alpha_a0"], pri[w + "_alpha_b0"], st0[w + "_alpha_b"]) for w in ("A", "C") if pri.get(w + "_alpha_a0") is not None}
         if ard:
             b.set_column_precisions(**ard)
+        # DiagonalGamma parents, one precision per entry: A_entry_a0, A_entry_b0 in pri, A_entry_b in st0 (the same for C)
+        ent = {w: (pri[w + "_entry_a0"], pri[w + "_entry_b0"], st0[w + "_entry_b"]) for w in ("A", "C") if pri.get(w + "_entry_a0") is not None}
+        if ent:
+            b.set_entry_precisions(**ent)
         return b
