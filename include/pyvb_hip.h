@@ -395,6 +395,24 @@ int pyvb_pca_set_data(pyvb_pca* h, const double* X);
 int pyvb_pca_set_column_precisions(pyvb_pca* h, const double* a0, const double* b0, const double* qb);  /* [q] each */
 int pyvb_pca_get_column_precisions(pyvb_pca* h, double* qa, double* qb);                               /* [q]; NULL = skip */
 int pyvb_pca_update_column_precisions(pyvb_pca* h);            /* [al.update() for al in alphas] */
+/* Sparse loadings: column i of W gets the precision parent DiagonalGamma(d, a0_i, b0_i), a Gamma per entry, in place of its Constant
+ * one -- Ws = [Gaussian(d, pmu_i, DiagonalGamma(d, a0_i, b0_i)) for i in range(q)], which gaussian.py:55-61 accepts.  Arrays are
+ * [column i][row k], as W_prior_prec.  The column sees pprec = diag(qa_i / qb_i) (gaussian.py:113, nodes_todo.py:192-193),
+ * qa_ik = a0_ik + 1/2 (nodes_todo.py:183-186); dg_i.update() is qb_ik = b0_ik + 1/2 ((<W>[k][i] - pmu[k][i])^2 + var W[k][i])
+ * (nodes_todo.py:187-190); the column's own bound term takes 1/2 sum_k (ln qa_ik - ln qb_ik) -- the reference's
+ * 1/2 ln prod_k (qa_ik / qb_ik) (nodes_todo.py:195-197) as a sum of logarithms, which does not overflow where entries are pruned --
+ * (PYVB_BOUND_EXACT: 1/2 sum_k (psi(qa_ik) - ln qb_ik)), and each parent adds its DiagonalGamma.log_lower_bound
+ * (nodes_todo.py:199-204) to parts[0], the W class.
+ * pyvb_pca_set_entry_precisions: a0, b0 and the initial qb (the reference draws it at random, nodes_todo.py:177), all finite and
+ * positive; call it after pyvb_pca_set_priors, whose W_prior_prec it replaces by qa / qb -- and which, called again, gives the
+ * columns their Constant parents back.  All columns of W have one kind of parent: of this setter and
+ * pyvb_pca_set_column_precisions the most recent call holds, and get / update of the other kind return PYVB_E_ARG.
+ * pyvb_pca_iterate then runs [dg.update() for dg in parents] in every pass, behind the W update (fetch_network has it after the
+ * Z_n; it commutes with them); stage-wise callers use pyvb_pca_update_entry_precisions.
+ * update / get on a handle without these parents, a NULL handle or array, a value that is not finite and positive: PYVB_E_ARG. */
+int pyvb_pca_set_entry_precisions(pyvb_pca* h, const double* a0, const double* b0, const double* qb);  /* [q][d] each */
+int pyvb_pca_get_entry_precisions(pyvb_pca* h, double* qa, double* qb);                                /* [q][d]; NULL = skip */
+int pyvb_pca_update_entry_precisions(pyvb_pca* h);             /* [dg.update() for dg in parents] */
 /* explicit posterior state; X_missing[N][d] supplies the posterior means of the missing entries only */
 int pyvb_pca_set_state(pyvb_pca* h, const double* X_missing, const double* W_mean, const double* Z, const double* Z_cov,
                        const double* Mu_mean, const double* beta_b);

@@ -112,6 +112,9 @@ SIGNATURES = {
     "pyvb_pca_set_column_precisions": (ctypes.c_int, [_h, _dp, _dp, _dp]),
     "pyvb_pca_get_column_precisions": (ctypes.c_int, [_h, _dp, _dp]),
     "pyvb_pca_update_column_precisions": (ctypes.c_int, [_h]),
+    "pyvb_pca_set_entry_precisions": (ctypes.c_int, [_h, _dp, _dp, _dp]),
+    "pyvb_pca_get_entry_precisions": (ctypes.c_int, [_h, _dp, _dp]),
+    "pyvb_pca_update_entry_precisions": (ctypes.c_int, [_h]),
     "pyvb_pca_set_state": (ctypes.c_int, [_h] + [_dp] * 6),
     "pyvb_pca_set_unpinned_rows": (ctypes.c_int, [_h, _dp, _dp]),
     "pyvb_pca_set_initial_variances": (ctypes.c_int, [_h, _dp, _dp]),

@@ -827,18 +827,39 @@ def bind(node):
 # -------------------------------------------------------------------------------------------------
 def describe_pca(start):
     """Recognise  X_n ~ N(W * Z_n + Mu, Beta)  with W = hstack of Gaussian columns, Mu Gaussian, Beta Gamma,
-    Z_n ~ N(0, I); returns the pieces, the priors and the observation mask (no GPU involved)."""
+    Z_n ~ N(0, I); returns the pieces, the priors and the observation mask (no GPU involved).  The columns of W have Constant
+    precision parents, or a Gamma each (Bishop's VB-PCA: pri["W_alpha"]), or a DiagonalGamma each (sparse loadings:
+    pri["W_entry"]); `parents` lists those nodes, column by column."""
     comp = component(start)
     stacks = [n for n in comp if isinstance(n, N.hstack)]
     gammas = [n for n in comp if isinstance(n, (N.Gamma, N.DiagonalGamma, N.Wishart))]
     adds = [n for n in comp if isinstance(n, N.Addition)]
-    if len(stacks) != 1 or len(gammas) != 1 or not isinstance(gammas[0], N.Gamma) or not adds:
-        _fail("expected one hstack matrix, one Gamma precision and Addition nodes (the PCA graph)")
-    W, Beta = stacks[0], gammas[0]
+    # Beta is the precision parent of the X_n, the Gaussians whose mean is an Addition
+    noise = {id(n.precision_parent): n.precision_parent for n in comp if isinstance(n, N.Gaussian) and isinstance(n.mean_parent, N.Addition)}
+    if len(stacks) != 1 or len(noise) != 1 or not isinstance(list(noise.values())[0], N.Gamma) or not adds:
+        _fail("expected one hstack matrix, one Gamma noise precision and Addition nodes (the PCA graph)")
+    W, Beta = stacks[0], list(noise.values())[0]
     Ws = W.parents
     d, q = W.shape
     if d > 256 or q > 32:
         _fail("the fused PCA kernels are built for d <= 256, q <= 32")
+    # the precision parents of the columns: one kind for all of them
+    parents = [getattr(w, "precision_parent", None) for w in Ws]
+    if any(isinstance(p, N.Wishart) for p in parents):
+        _fail("a column of W has a Wishart precision parent")
+    if len(set(type(p) for p in parents)) != 1:
+        _fail("the columns of W have precision parents of mixed kinds")
+    if isinstance(parents[0], (N.Gamma, N.DiagonalGamma)):
+        if len(set(id(p) for p in parents)) != q:
+            _fail("a precision parent is shared by two columns of W")
+        if any(len(p.children) != 1 for p in parents):
+            _fail("a column's precision parent has further children")
+        if any(p.shape[0] != d for p in parents):
+            _fail("a column's precision parent has another dimension than the column")
+    else:
+        parents = []
+    if len(gammas) != 1 + len(parents):
+        _fail("precision nodes besides the noise precision and the columns' parents")
     Mu, Zs, Xs = None, [], []
     # the X_n in construction order = the order in which Beta adopted them as children
     for x in Beta.children:
@@ -876,11 +897,20 @@ def describe_pca(start):
         zc = np.mean([z.__dict__["_h_qcov"] for z in Zs], axis=0)
     pri = {
         "W_prior_mean": np.hstack([w.mean_parent.value for w in Ws]).astype(float),
-        "W_prior_prec": np.stack([_diag_constant(w.precision_parent, "a column's prior precision") for w in Ws]),
+        "W_prior_prec": np.ones((q, d)) if parents else
+                        np.stack([_diag_constant(w.precision_parent, "a column's prior precision") for w in Ws]),
         "Mu_prior_mean": Mu.mean_parent.value.reshape(-1).astype(float),
         "Mu_prior_prec": _diag_constant(Mu.precision_parent, "the offset's prior precision"),
         "beta_a0": float(Beta.a0), "beta_b0": float(Beta.b0),
     }
+    # qb as the nodes hold it (the constructors' draw, an assignment, or what another plan left): a graph that is bound anew
+    # after an assignment keeps the value.  W_prior_prec above is a placeholder the setter overwrites by qa / qb.
+    if parents and isinstance(parents[0], N.Gamma):
+        pri["W_alpha"] = (np.array([float(p.a0) for p in parents]), np.array([float(p.b0) for p in parents]),
+                          np.array([float(np.asarray(p.__dict__["_h_qb"], dtype=float).reshape(-1)[0]) for p in parents]))
+    elif parents:
+        pri["W_entry"] = (np.stack([np.asarray(p.a0s, dtype=float) for p in parents]), np.stack([np.asarray(p.b0s, dtype=float) for p in parents]),
+                          np.stack([np.broadcast_to(np.asarray(p.__dict__["_h_qb"], dtype=float).reshape(-1), (d,)) for p in parents]))
     N_ = len(Xs)
     obs = np.ones((N_, d), dtype=bool)
     X = np.empty((N_, d))
@@ -904,23 +934,28 @@ def describe_pca(start):
             "Z": np.hstack([z.__dict__["_h_qmu"] for z in Zs]).T.copy(), "Z_cov": zc.copy(),
             "Mu_mean": Mu.__dict__["_h_qmu"].reshape(-1).copy(),
             "beta_b": float(np.asarray(Beta.__dict__["_h_qb"], dtype=float).reshape(-1)[0])}
-    return dict(Ws=Ws, W=W, Mu=Mu, Beta=Beta, Zs=Zs, Xs=Xs, init=init, pri=pri)
+    return dict(Ws=Ws, W=W, Mu=Mu, Beta=Beta, Zs=Zs, Xs=Xs, init=init, pri=pri, parents=parents)
 
 
 class PCAPlan(FusedPlan):
-    def __init__(self, Ws, W, Mu, Beta, Zs, Xs, init, pri):
+    def __init__(self, Ws, W, Mu, Beta, Zs, Xs, init, pri, parents=()):
         from .pca import PCABatch
         self.Ws, self.W, self.Mu, self.Beta, self.Zs, self.Xs = Ws, W, Mu, Beta, Zs, Xs
+        # the columns' precision parents, if they are nodes: kind "alpha" (Gamma, a rate per column) or "dg" (DiagonalGamma, a
+        # rate per entry); their qb lives on the handle, qa is fixed by the graph and stays the host attribute
+        self.parents = list(parents)
+        self.pkind = None if not self.parents else ("alpha" if isinstance(self.parents[0], N.Gamma) else "dg")
         self.N, self.d, self.q = len(Xs), W.shape[0], W.shape[1]
         self.obs = init["obs"]
         nmiss = (~self.obs).sum(1)
         self.unpinned = (nmiss > 0) & (nmiss < self.d)       # rows not yet conditioned on their observed entries (first update)
         self.batch = PCABatch.from_problem(init, pri)
-        self.index = {id(n): (kind, i) for kind, row in (("w", Ws), ("z", Zs), ("x", Xs), ("mu", [Mu]), ("beta", [Beta]))
+        self.index = {id(n): (kind, i) for kind, row in (("w", Ws), ("z", Zs), ("x", Xs), ("mu", [Mu]), ("beta", [Beta]),
+                                                         (self.pkind, self.parents))
                       for i, n in enumerate(row)}
         self.cache = None
         self.z_updated = False          # until then Z_n.qcov reads the node's own initial covariance (host)
-        self.n_random_nodes = 2 * self.N + self.q + 2
+        self.n_random_nodes = 2 * self.N + self.q + 2 + len(self.parents)
         FusedPlan.__init__(self, W)
 
     def enqueue(self, node):
@@ -954,12 +989,18 @@ class PCAPlan(FusedPlan):
                 b.update_Mu()
             elif kind == "beta":
                 b.update_Beta()
+            elif kind in ("alpha", "dg"):
+                if (lo, hi) != (0, self.q):     # a single parent: as for a single column
+                    return self._demote(ops[i:])
+                b.update_column_precisions() if kind == "alpha" else b.update_entry_precisions()
             i = j + 1
 
     def _pull(self):
         self.flush()
         if self.cache is None:
             self.cache = self.batch.get_state()
+            if self.pkind:
+                self.cache["W_parent_b"] = (self.batch.column_precisions() if self.pkind == "alpha" else self.batch.entry_precisions())[1]
         return self.cache
 
     def read(self, node, name):
@@ -982,6 +1023,10 @@ class PCAPlan(FusedPlan):
             return node.__dict__.get("_h_" + name)
         if kind == "mu":
             return st["Mu_mean"].reshape(-1, 1).copy() if name == "qmu" else (np.diag(st["Mu_var"]) if name == "qcov" else node.__dict__.get("_h_" + name))
+        if name == "qb" and kind == "alpha":
+            return float(st["W_parent_b"][i])
+        if name == "qb" and kind == "dg":
+            return st["W_parent_b"][i].copy()
         if name == "qb":
             return float(st["beta_b"])
         raise AttributeError(name)
@@ -1014,7 +1059,8 @@ class PCAPlan(FusedPlan):
         for nd in self.Ws + self.Zs + self.Xs + [self.Mu]:
             for name in ("qmu", "qcov"):
                 nd.__dict__["_h_" + name] = self.read(nd, name)
-        self.Beta.__dict__["_h_qb"] = self.read(self.Beta, "qb")
+        for nd in [self.Beta] + self.parents:
+            nd.__dict__["_h_qb"] = self.read(nd, "qb")
         # q_ln_det (gaussian.py:120, quirk Q1): what the updates on this handle left on the device (pyvb_pca_get_qld).  A node
         # that has not been updated on it keeps the value it came with -- the reference sets q_ln_det only in update() too
         qld = self.batch.get_qld()
@@ -1040,7 +1086,7 @@ class PCAPlan(FusedPlan):
 
     def _demote(self, rest):
         """See LDSPlan._demote."""
-        node_of = {self.index[id(n)]: n for n in self.Ws + self.Zs + self.Xs + [self.Mu, self.Beta]}
+        node_of = {self.index[id(n)]: n for n in self.Ws + self.Zs + self.Xs + [self.Mu, self.Beta] + self.parents}
         self._sync_host()
         self._unbind(every=True)
         self.batch.close()

@@ -52,7 +52,7 @@ void pyvb_timing_resolve(pyvb_lds* h) {
 extern "C" {
 
 const char* pyvb_last_error(void) { return g_err; }
-int pyvb_version(void) { return 107; }
+int pyvb_version(void) { return 108; }
 
 int pyvb_device_count(int* count) {
     ARGCHK(count, "count is NULL");

@@ -130,6 +130,7 @@ int pyvb_pca_set_priors(pyvb_pca* h, const double* W_pm, const double* W_pp, con
     HIPCHK(hipMemcpy(h->lnd_W, nanq.data(), nanq.size() * sizeof(double), hipMemcpyHostToDevice));
     HIPCHK(hipStreamSynchronize(h->stream));
     h->ard_on = false;      // the columns of W have Constant parents again: W_pp is the caller's (pyvb_pca_set_column_precisions comes after)
+    h->entry_on = false;    // (and pyvb_pca_set_entry_precisions)
     return PYVB_OK;
 }
 
@@ -165,7 +166,7 @@ int pyvb_pca_set_column_precisions(pyvb_pca* h, const double* a0, const double* 
     int rc;
     if (!h->ard && (rc = h->mem.zeros(&h->ard, AR_COUNT * q))) return rc;
     if ((rc = up(h, h->ard, host.data(), AR_COUNT * q))) return rc;
-    h->ard_on = true;
+    h->ard_on = true; h->entry_on = false;                 // one kind of parent for all columns: the most recent setter's
     // W_pp = qa / qb and the two log terms from qb as given: the first update_W already sees <alpha>
     if ((rc = pca_launch_ard(h, true))) { h->ard_on = false; return rc; }
     HIPCHK(hipStreamSynchronize(h->stream));               // the staging vector is about to go out of scope
@@ -189,6 +190,68 @@ int pyvb_pca_update_column_precisions(pyvb_pca* h) {
     if (rc) return rc;
     ENTER(h);
     return pca_launch_ard(h, false);
+}
+
+// ---- DiagonalGamma parents of the columns of W: a Gamma per entry (sparse loadings; k_pca.hip: PCA_ENTRY) ----
+// As above, nothing PcaState tracks depends on W_pp (pca_plan.h: the statistics, the cached residual and the pending Z update read
+// <W>, var(W), Mu, X and Z), so none of the three entries raises an event and PcaState has no field for the parents.
+static int entry_required(const pyvb_pca* h) {
+    if (!h->entry_on) {
+        pyvb_set_error("the columns of W have no DiagonalGamma precision parents (pyvb_pca_set_entry_precisions)");
+        return PYVB_E_ARG;
+    }
+    return PYVB_OK;
+}
+
+int pyvb_pca_set_entry_precisions(pyvb_pca* h, const double* a0, const double* b0, const double* qb) {
+    ARGCHK(h, "handle is NULL");
+    ARGCHK(a0 && b0 && qb, "a0, b0 and qb are required");
+    const size_t q = (size_t)h->q, d = (size_t)h->d, qd = q * d;
+    for (size_t e = 0; e < qd; ++e) {
+        const int i = (int)(e / d), k = (int)(e % d);
+        if (!(a0[e] > 0.0 && a0[e] - a0[e] == 0.0)) { pyvb_set_error("a0 of entry %d of column %d of W is %g: it must be finite and positive", k, i, a0[e]); return PYVB_E_ARG; }
+        if (!(b0[e] > 0.0 && b0[e] - b0[e] == 0.0)) { pyvb_set_error("b0 of entry %d of column %d of W is %g: it must be finite and positive", k, i, b0[e]); return PYVB_E_ARG; }
+        if (!(qb[e] > 0.0 && qb[e] - qb[e] == 0.0)) { pyvb_set_error("qb of entry %d of column %d of W is %g: it must be finite and positive", k, i, qb[e]); return PYVB_E_ARG; }
+    }
+    std::vector<double> host(EN_COUNT * qd + EN_SCALARS, 0.0);
+    double exact = 0.0;
+    for (size_t e = 0; e < qd; ++e) {
+        const double qa = a0[e] + 0.5;                      // update_a, nodes_todo.py:183-186: one child per entry
+        const double psi = digamma_host(qa);
+        host[EN_A0 * qd + e] = a0[e]; host[EN_B0 * qd + e] = b0[e]; host[EN_QA * qd + e] = qa; host[EN_QB * qd + e] = qb[e];
+        host[EN_CST * qd + e] = (a0[e] - qa) * psi - std::lgamma(a0[e]) + a0[e] * std::log(b0[e]) + std::lgamma(qa) + qa;
+        exact += psi - std::log(qa);
+    }
+    host[EN_COUNT * qd + ES_EXACT] = 0.5 * exact;
+    ENTER(h);
+    int rc;
+    if (!h->entry && (rc = h->mem.zeros(&h->entry, EN_COUNT * qd + EN_SCALARS))) return rc;
+    if ((rc = up(h, h->entry, host.data(), EN_COUNT * qd + EN_SCALARS))) return rc;
+    const bool ard_was = h->ard_on;
+    h->entry_on = true; h->ard_on = false;                 // one kind of parent for all columns: the most recent setter's
+    // W_pp = qa / qb and the sum of the own terms from qb as given: the first update_W already sees the parents
+    if ((rc = pca_launch_entry(h, true))) { h->entry_on = false; h->ard_on = ard_was; return rc; }
+    HIPCHK(hipStreamSynchronize(h->stream));               // the staging vector is about to go out of scope
+    return PYVB_OK;
+}
+
+int pyvb_pca_get_entry_precisions(pyvb_pca* h, double* qa, double* qb) {
+    ARGCHK(h, "handle is NULL");
+    int rc = entry_required(h);
+    if (rc) return rc;
+    ENTER(h);
+    const size_t qd = (size_t)h->q * h->d;
+    if ((rc = down(h, qa, h->entry + EN_QA * qd, qd))) return rc;
+    if ((rc = down(h, qb, h->entry + EN_QB * qd, qd))) return rc;
+    return pyvb_pca_sync(h);
+}
+
+int pyvb_pca_update_entry_precisions(pyvb_pca* h) {
+    ARGCHK(h, "handle is NULL");
+    int rc = entry_required(h);
+    if (rc) return rc;
+    ENTER(h);
+    return pca_launch_entry(h, false);
 }
 
 // rows [N][d] on the host -> padded device rows [N][DP]
@@ -532,7 +595,8 @@ int pyvb_pca_iterate(pyvb_pca* h, int niters) {
             h->st.z_requested();                                        // update_Z, deferred (lin_valid holds after ensure_full)
             // Gamma parents on the columns of W: their update is one more step of the same launch, behind W (it commutes with the Z
             // update, after which the crawl order has it); a handle without them launches what it always launched
-            if ((rc = pca_launch_small(h, h->ard_on ? PCA_RUN_HEAD_ARD : PCA_RUN_HEAD))) { h->st.z_request_failed(); return rc; }
+            // (DiagonalGamma parents on its entries: likewise, PCA_ENTRY in place of PCA_ARD)
+            if ((rc = pca_launch_small(h, h->ard_on ? PCA_RUN_HEAD_ARD : h->entry_on ? PCA_RUN_HEAD_ENTRY : PCA_RUN_HEAD))) { h->st.z_request_failed(); return rc; }
             h->st.linear_step();
             // the X_0 step reads row 0: a no-op after an iteration of this loop (its sweep left vlo == 1), but not after a
             // stage-wise pyvb_pca_update_X(0, N)
@@ -547,6 +611,7 @@ int pyvb_pca_iterate(pyvb_pca* h, int niters) {
         }
         if ((rc = pyvb_pca_update_W(h))) return rc;
         if (h->ard_on && (rc = pca_launch_ard(h, false))) return rc;    // local, not a collective: W is the same on every rank, so alpha is too
+        if (h->entry_on && (rc = pca_launch_entry(h, false))) return rc;  // likewise: qb is the same on every rank
         if ((rc = pyvb_pca_update_Z(h))) return rc;
         const long first = h->row_offset == 0 ? 1 : 0;         // global row 0 lives on the rank with offset 0
         if ((rc = x0_step(h))) return rc;                       // every rank: the exchange is collective

@@ -38,7 +38,9 @@ struct PcaArgs {
     PcaStatsLayout SL;
     // Gamma precision parents of the columns of W (pca.h: AR_*, [AR_COUNT][q]); null on a handle without them
     double* ard;
-    int ard_derive;     // PCA_ARD: qb is the caller's (pyvb_pca_set_column_precisions): form only what follows from it
+    int ard_derive;     // PCA_ARD, PCA_ENTRY: qb is the caller's (pyvb_pca_set_column_precisions, _entry_): form only what follows from it
+    // DiagonalGamma parents, one per entry of W (pca.h: EN_*, [EN_COUNT][q][d] and the ES_* scalars); null on a handle without them
+    double* entry;
 };
 
 __device__ __forceinline__ double wsum(double v) {
@@ -1225,6 +1227,47 @@ __device__ __forceinline__ void pca_small_body(const PcaArgs& a, double* sm, dou
         // what the next w_i.update() and the bound read as the column's prior precision: pprec = (qa_i / qb_i) I (gaussian.py:113)
         if (k < d)
             for (int i = 0; i < q; ++i) a.W_pp[(size_t)i * d + k] = ex[i];
+    } else if constexpr (MODE == PCA_ENTRY) {
+        // [dg.update() for dg in parents]: column i of W has the precision parent DiagonalGamma(d, a0_i, b0_i) (gaussian.py:55-61,
+        // nodes_todo.py:159-204), a Gamma per entry.  Every entry has one child, so qa = a0 + 1/2 is fixed and
+        //   qb[i][k] = b0[i][k] + 1/2 ((<W>[k][i] - pm[k][i])^2 + var(W[k][i])),     W_pp[i][k] = qa[i][k] / qb[i][k]:
+        // what the next w_i.update() and the bound read as the column's diagonal prior precision.  thread = row k; eight columns at
+        // a time, with every load of the eight issued before the first use (indices of entries outside the matrix are clamped to
+        // entry 0, so no load hangs on a branch): the mode is alone on its CU and nothing else hides the trips to L2.
+        // The entry's term of the bound, DiagonalGamma.log_lower_bound (nodes_todo.py:199-204) with all that does not follow qb
+        // folded into EN_CST on the host, is summed per thread over the columns in ascending order, then by bsum: a fixed order,
+        // no atomics.
+        double* en = a.entry;
+        const size_t qd = (size_t)q * d;
+        const int k = tid, derive = a.ard_derive;
+        double own = 0.0;
+        for (int i0 = 0; i0 < q; i0 += 8) {
+            double w[8], pm[8], wv[8], b0[8], qa[8], a0[8], cst[8], qbg[8];
+#pragma unroll
+            for (int ii = 0; ii < 8; ++ii) {
+                const int i = i0 + ii;
+                const bool in = i < q && k < d;
+                const size_t e = in ? (size_t)i * d + k : 0, r = in ? (size_t)k * q + i : 0;
+                b0[ii] = en[EN_B0 * qd + e]; qa[ii] = en[EN_QA * qd + e]; a0[ii] = en[EN_A0 * qd + e]; cst[ii] = en[EN_CST * qd + e];
+                if (derive) { qbg[ii] = en[EN_QB * qd + e]; w[ii] = pm[ii] = wv[ii] = 0.0; }
+                else { qbg[ii] = 0.0; w[ii] = a.W_mean[r]; pm[ii] = a.W_pm[r]; wv[ii] = a.W_var[e]; }
+            }
+#pragma unroll
+            for (int ii = 0; ii < 8; ++ii) {
+                const int i = i0 + ii;
+                if (i < q && k < d) {
+                    const size_t e = (size_t)i * d + k;
+                    const double dw = w[ii] - pm[ii];
+                    const double qb = derive ? qbg[ii] : b0[ii] + 0.5 * (dw * dw + wv[ii]);
+                    const double pp = qa[ii] / qb;
+                    own += cst[ii] - a0[ii] * log(qb) - b0[ii] * pp;
+                    if (!derive) en[EN_QB * qd + e] = qb;
+                    a.W_pp[e] = pp;
+                }
+            }
+        }
+        own = bsum(own, red);
+        if (tid == 0) en[EN_COUNT * qd + ES_OWN] = own;
     } else if constexpr (MODE == PCA_PREPZ) {
         // posterior of the Z_n: precision I + beta <W^T W>, shared by all n; Gz = beta Sigma_z <W>^T
         double* P = sm; double* Sg = sm + 64 * 64;
@@ -1386,6 +1429,14 @@ __device__ __forceinline__ void pca_small_body(const PcaArgs& a, double* sm, dou
             lw += (a0 - 1.0) * Elnx - ar[AR_LGAMMA_A0 * q + tid] + a0 * log(b0) - b0 * ex;
             lw -= (aqa - 1.0) * Elnx - ar[AR_LGAMMA_QA * q + tid] + aqa * log(aqb) - aqb * ex;
         }
+        if (a.entry && tid == 0) {
+            // DiagonalGamma parents: W_pp[i][k] = qa_ik / qb_ik, so the per-entry sum above already holds the reference's
+            // 1/2 ln det = 1/2 sum_k (ln qa_ik - ln qb_ik) of every column, as a sum of logarithms; the exact bound has
+            // psi(qa_ik) in place of ln qa_ik (ES_EXACT).  Then the parents' own terms as PCA_ENTRY left them, with the W class.
+            const double* es = a.entry + (size_t)EN_COUNT * q * d;
+            lw += es[ES_OWN];
+            if (exact) lw += es[ES_EXACT];
+        }
         const double LW = bsum(lw, red);
         double lm = 0.0;
         if (tid < d) {
@@ -1437,6 +1488,7 @@ static PcaArgs pca_args(pyvb_pca* h) {
     a.keep_z0 = 0; a.z_deferred = 0; a.x0_prep = 0;
     a.W_x = h->W_x; a.Mu_x = h->Mu_x; a.vin_lo = a.vin_hi = 0; a.save_wx = 0;
     a.ard = h->ard_on ? h->ard : nullptr; a.ard_derive = 0;
+    a.entry = h->entry_on ? h->entry : nullptr;
     return a;
 }
 
@@ -1454,6 +1506,8 @@ int pca_launch_small(pyvb_pca* h, int mode) {
         // the same with Gamma parents on the columns of W: their update commutes with the Z update (it reads its own column of
         // <W>, var(W) and the prior mean, and feeds the next W update and the bound only) and runs right behind W
         PCA_SMALL(PCA_RUN_HEAD_ARD, PCA_W, PCA_ARD, PCA_PREPZ, PCA_APPLY);
+        // and with DiagonalGamma parents on its entries: the same argument per entry
+        PCA_SMALL(PCA_RUN_HEAD_ENTRY, PCA_W, PCA_ENTRY, PCA_PREPZ, PCA_APPLY);
         PCA_SMALL(PCA_RUN_MID, PCA_X0, PCA_APPLY, PCA_MU);
         PCA_SMALL(PCA_RUN_TAIL, PCA_BETA, PCA_ELBO);
 #undef PCA_SMALL
@@ -1468,6 +1522,15 @@ int pca_launch_ard(pyvb_pca* h, bool derive) {
     PcaArgs a = pca_args(h); a.mode = PCA_ARD; a.ard_derive = derive ? 1 : 0;
     if (!a.ard) { pyvb_set_error("no Gamma parents on the columns of W"); return PYVB_E_ARG; }
     hipLaunchKernelGGL((k_pca_small<PCA_ARD>), dim3(1), dim3(256), 0, h->stream, a);
+    HIPCHK(hipGetLastError());
+    return PYVB_OK;
+}
+
+// [dg.update() for dg in parents] alone; derive: from qb as the caller gave it (pyvb_pca_set_entry_precisions)
+int pca_launch_entry(pyvb_pca* h, bool derive) {
+    PcaArgs a = pca_args(h); a.mode = PCA_ENTRY; a.ard_derive = derive ? 1 : 0;
+    if (!a.entry) { pyvb_set_error("no DiagonalGamma parents on the columns of W"); return PYVB_E_ARG; }
+    hipLaunchKernelGGL((k_pca_small<PCA_ENTRY>), dim3(1), dim3(256), 0, h->stream, a);
     HIPCHK(hipGetLastError());
     return PYVB_OK;
 }

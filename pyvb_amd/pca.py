@@ -70,6 +70,25 @@ class PCABatch(object):
         """[al.update() for al in alphas], for stage-wise use (the crawl order has it after update_Z)."""
         C.check(C.lib.pyvb_pca_update_column_precisions(self._h))
 
+    def set_entry_precisions(self, a0, b0, qb):
+        """DiagonalGamma precision parents for the columns of W (sparse loadings): entry k of column i gets Gamma(a0[i][k], b0[i][k])
+        with the initial rate qb[i][k] in place of its Constant precision; [q, d] each, scalars and [q] columns are broadcast.
+        Call after set_priors (which, called again, takes the parents away); it replaces set_column_precisions and the other way
+        round.  iterate() then updates the parents in every pass."""
+        a = [np.ascontiguousarray(np.broadcast_to(v if v.ndim != 1 else v[:, None], (self.q, self.d)))
+             for v in (np.asarray(x, dtype=np.float64) for x in (a0, b0, qb))]
+        C.check(C.lib.pyvb_pca_set_entry_precisions(self._h, *[C.dptr(x) for x in a]))
+
+    def entry_precisions(self):
+        """(qa, qb), [q, d] each: the prior precision of W[k][i] is qa[i][k] / qb[i][k]."""
+        qa, qb = np.empty((self.q, self.d)), np.empty((self.q, self.d))
+        C.check(C.lib.pyvb_pca_get_entry_precisions(self._h, C.dptr(qa), C.dptr(qb)))
+        return qa, qb
+
+    def update_entry_precisions(self):
+        """[dg.update() for dg in parents], for stage-wise use (the crawl order has it after update_Z)."""
+        C.check(C.lib.pyvb_pca_update_entry_precisions(self._h))
+
     def set_data(self, X):
         """X [N, d] with NaN where an entry is missing (Gaussian.observe, gaussian.py:74-100)."""
         C.check(C.lib.pyvb_pca_set_data(self._h, C.dptr(_f64(X, (self.N, self.d), "X"))))
@@ -175,13 +194,16 @@ class PCABatch(object):
     def from_problem(cls, init, pri, device=0):
         """init: dict with obs [N,d] bool, X [N,d] (data / initial means of the missing entries), W_mean, Z, Z_cov,
         Mu_mean, beta_b (tests/golden/make_golden.py: pca_problem).  pri["W_alpha"] = (a0, b0, qb), optional: Gamma precision
-        parents for the columns of W (set_column_precisions)."""
+        parents for the columns of W (set_column_precisions); pri["W_entry"] = (a0, b0, qb), optional: DiagonalGamma parents,
+        a precision per entry (set_entry_precisions)."""
         N, d = init["X"].shape
         q = init["Z"].shape[1]
         b = cls(N, d, q, device)
         b.set_priors(pri)
         if pri.get("W_alpha") is not None:
             b.set_column_precisions(*pri["W_alpha"])
+        if pri.get("W_entry") is not None:
+            b.set_entry_precisions(*pri["W_entry"])
         b.set_data(np.where(init["obs"], init["X"], np.nan))
         b.set_state(X_missing=init["X"], W_mean=init["W_mean"], Z=init["Z"], Z_cov=init["Z_cov"],
                     Mu_mean=init["Mu_mean"], beta_b=float(init["beta_b"]))
