@@ -66,6 +66,11 @@ enum { PYVB_FORWARD = 0, PYVB_BACKWARD = 1 };
 #define PYVB_BOUND_REFERENCE 0
 #define PYVB_BOUND_EXACT 1
 
+/* the kind of precision parent the columns of a matrix have (pyvb_lds_get_column_parents, pyvb_pca_get_column_parents) */
+#define PYVB_PARENTS_CONSTANT 0
+#define PYVB_PARENTS_GAMMA 1
+#define PYVB_PARENTS_DIAGONAL_GAMMA 2
+
 /* which kernels pyvb_lds_timing_get() reports on */
 enum { PYVB_K_PREP = 0, PYVB_K_SWEEP_FWD = 1, PYVB_K_STATS = 2, PYVB_K_PARAMS = 3, PYVB_K_STEP = 4,
        PYVB_K_SWEEP_BWD = 5, PYVB_K_ELBO = 6, PYVB_K_GY = 7 /* 128-wide class: G y_t ahead of a sweep */, PYVB_K_COUNT = 8 };
@@ -214,6 +219,8 @@ int pyvb_lds_update_column_precisions(pyvb_lds* h, int which);     /* [al.update
 int pyvb_lds_set_entry_precisions(pyvb_lds* h, int which, const double* a0, const double* b0, const double* qb);
 int pyvb_lds_get_entry_precisions(pyvb_lds* h, int which, double* qa, double* qb);   /* [N][D][rows] each; NULL = skip */
 int pyvb_lds_update_entry_precisions(pyvb_lds* h, int which);      /* [dg.update() for dg in the parents of that matrix] */
+/* The kind in force, PYVB_PARENTS_*, of the columns of A (kind[0]) and C (kind[1]).  Needs no device.  PYVB_E_ARG: NULL. */
+int pyvb_lds_get_column_parents(pyvb_lds* h, int kind[2]);
 
 /* Explicit posterior state instead of the constructors' random initialisation
  * (gaussian.py:70-72, nodes_todo.py:119,177). */
@@ -413,6 +420,8 @@ int pyvb_pca_update_column_precisions(pyvb_pca* h);            /* [al.update() f
 int pyvb_pca_set_entry_precisions(pyvb_pca* h, const double* a0, const double* b0, const double* qb);  /* [q][d] each */
 int pyvb_pca_get_entry_precisions(pyvb_pca* h, double* qa, double* qb);                                /* [q][d]; NULL = skip */
 int pyvb_pca_update_entry_precisions(pyvb_pca* h);             /* [dg.update() for dg in parents] */
+/* The kind in force, PYVB_PARENTS_*, of the columns of W.  Needs no device.  PYVB_E_ARG: NULL. */
+int pyvb_pca_get_column_parents(pyvb_pca* h, int* kind);
 /* explicit posterior state; X_missing[N][d] supplies the posterior means of the missing entries only */
 int pyvb_pca_set_state(pyvb_pca* h, const double* X_missing, const double* W_mean, const double* Z, const double* Z_cov,
                        const double* Mu_mean, const double* beta_b);

@@ -17,6 +17,8 @@ NOISE_DIAGONAL_GAMMA, NOISE_GAMMA, NOISE_WISHART = 0, 1, 2
 FORWARD, BACKWARD = 0, 1
 BOUND_REFERENCE, BOUND_EXACT = 0, 1
 BOUND_MODES = {"reference": BOUND_REFERENCE, "exact": BOUND_EXACT}
+PARENTS_CONSTANT, PARENTS_GAMMA, PARENTS_DIAGONAL_GAMMA = 0, 1, 2        # PYVB_PARENTS_*: the kind of a matrix's column parents
+PARENTS = ("constant", "gamma", "diagonal_gamma")
 PCA_SWEEP_STORE, PCA_SWEEP_COLUMNS, PCA_SWEEP_PAIRS = 0, 1, 2
 PCA_SWEEPS = {"store": PCA_SWEEP_STORE, "columns": PCA_SWEEP_COLUMNS, "pairs": PCA_SWEEP_PAIRS}
 FAIL_STATES, FAIL_COLUMNS, FAIL_NOISE = 1, 2, 4      # PYVB_FAIL_*: bits of pyvb_lds_get_status
@@ -58,6 +60,7 @@ SIGNATURES = {
     "pyvb_lds_set_entry_precisions": (ctypes.c_int, [_h, ctypes.c_int, _dp, _dp, _dp]),
     "pyvb_lds_get_entry_precisions": (ctypes.c_int, [_h, ctypes.c_int, _dp, _dp]),
     "pyvb_lds_update_entry_precisions": (ctypes.c_int, [_h, ctypes.c_int]),
+    "pyvb_lds_get_column_parents": (ctypes.c_int, [_h, _ip]),
     "pyvb_lds_set_state": (ctypes.c_int, [_h] + [_dp] * 7),
     "pyvb_lds_get_state": (ctypes.c_int, [_h] + [_dp] * 9),
     "pyvb_lds_get_posterior_classes": (ctypes.c_int, [_h, _dp, _dp]),
@@ -115,6 +118,7 @@ SIGNATURES = {
     "pyvb_pca_set_entry_precisions": (ctypes.c_int, [_h, _dp, _dp, _dp]),
     "pyvb_pca_get_entry_precisions": (ctypes.c_int, [_h, _dp, _dp]),
     "pyvb_pca_update_entry_precisions": (ctypes.c_int, [_h]),
+    "pyvb_pca_get_column_parents": (ctypes.c_int, [_h, _ip]),
     "pyvb_pca_set_state": (ctypes.c_int, [_h] + [_dp] * 6),
     "pyvb_pca_set_unpinned_rows": (ctypes.c_int, [_h, _dp, _dp]),
     "pyvb_pca_set_initial_variances": (ctypes.c_int, [_h, _dp, _dp]),
@@ -183,6 +187,11 @@ def check(rc):
         if rc == E_LINALG:
             raise np.linalg.LinAlgError(msg)
         raise PyvbHipError(rc, msg)
+
+
+def broadcast(v, shape):
+    """v (a scalar or anything numpy broadcasts) as a C-contiguous float64 array of `shape`: what the setters of priors hand to dptr"""
+    return np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=np.float64), shape))
 
 
 def dptr(a):

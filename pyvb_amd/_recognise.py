@@ -938,6 +938,9 @@ def describe_pca(start):
 
 
 class PCAPlan(FusedPlan):
+    PARENT_METHODS = {"alpha": ("update_column_precisions", "column_precisions"),       # pkind -> the batch's update and getter
+                      "dg": ("update_entry_precisions", "entry_precisions")}
+
     def __init__(self, Ws, W, Mu, Beta, Zs, Xs, init, pri, parents=()):
         from .pca import PCABatch
         self.Ws, self.W, self.Mu, self.Beta, self.Zs, self.Xs = Ws, W, Mu, Beta, Zs, Xs
@@ -989,10 +992,10 @@ class PCAPlan(FusedPlan):
                 b.update_Mu()
             elif kind == "beta":
                 b.update_Beta()
-            elif kind in ("alpha", "dg"):
+            elif kind in self.PARENT_METHODS:
                 if (lo, hi) != (0, self.q):     # a single parent: as for a single column
                     return self._demote(ops[i:])
-                b.update_column_precisions() if kind == "alpha" else b.update_entry_precisions()
+                getattr(b, self.PARENT_METHODS[kind][0])()
             i = j + 1
 
     def _pull(self):
@@ -1000,7 +1003,7 @@ class PCAPlan(FusedPlan):
         if self.cache is None:
             self.cache = self.batch.get_state()
             if self.pkind:
-                self.cache["W_parent_b"] = (self.batch.column_precisions() if self.pkind == "alpha" else self.batch.entry_precisions())[1]
+                self.cache["W_parent_b"] = getattr(self.batch, self.PARENT_METHODS[self.pkind][1])()[1]
         return self.cache
 
     def read(self, node, name):

@@ -1,7 +1,6 @@
 // Host side of libpyvb_hip.so: handle lifetime, host<->device copies, the dependency tracking that
 // decides which kernels a node-level call needs, timing, and the RCCL all-reduce of the lower bound.
 #include "common.h"
-#include "digamma.h"
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -52,7 +51,7 @@ void pyvb_timing_resolve(pyvb_lds* h) {
 extern "C" {
 
 const char* pyvb_last_error(void) { return g_err; }
-int pyvb_version(void) { return 108; }
+int pyvb_version(void) { return 109; }
 
 int pyvb_device_count(int* count) {
     ARGCHK(count, "count is NULL");
@@ -348,194 +347,106 @@ int pyvb_lds_set_priors(pyvb_lds* h, const double* x0_mean, const double* x0_pre
         if ((rc = h2d(h, h->R_a, ra.data(), ra.size()))) return rc;
         HIPCHK(hipStreamSynchronize(h->stream));       // qa, ra are about to go out of scope
     }
-    h->ard[0].on = h->ard[1].on = false;       // the columns have Constant parents again (pyvb_lds_set_column_precisions comes after)
-    h->entry[0].on = h->entry[1].on = false;   // (and so does pyvb_lds_set_entry_precisions)
+    h->parents[0].clear(); h->parents[1].clear();      // the columns have Constant parents again (the setters of others come after)
     h->st.parameters_changed();
     return PYVB_OK;
 }
 
-// ---- Gamma parents of the columns of A / C (automatic relevance determination, k_ard.hip) ----
-static int ard_which(const pyvb_lds* h, int which, bool need_on) {
+// ---- The precision parents of the columns of A / C: a Gamma per column (automatic relevance determination, k_ard.hip: k_ard) or a
+// DiagonalGamma per column, a precision of its own for every entry (k_ard.hip: k_entry).  Which kind a matrix has, the checks and
+// the staging are column_parents.h; a setter is gate, check, stage, upload, launch, commit.
+static ParentWords lds_words(int which) { return {which == 0 ? "A" : "C", false}; }
+
+// need: the kind a getter or an update serves; 0: a setter, which any matrix admits
+static int parents_gate(const pyvb_lds* h, int which, int need) {
+    ARGCHK(h, "handle is NULL");
     ARGCHK(which == 0 || which == 1, "which must be 0 (A) or 1 (C)");
-    if (need_on && h->entry[which].on) {
-        pyvb_set_error("the columns of %s have DiagonalGamma precision parents, one per entry: pyvb_lds_get_entry_precisions / pyvb_lds_update_entry_precisions serve them",
-                       which == 0 ? "A" : "C");
-        return PYVB_E_ARG;
-    }
-    if (need_on && !h->ard[which].on) {
-        pyvb_set_error("the columns of %s have Constant precision parents: no hyperpriors were given (pyvb_lds_set_column_precisions)",
-                       which == 0 ? "A" : "C");
-        return PYVB_E_ARG;
-    }
-    return PYVB_OK;
+    return need ? h->parents[which].require(need, lds_words(which)) : PYVB_OK;
 }
 
-int pyvb_lds_set_column_precisions(pyvb_lds* h, int which, const double* a0, const double* b0, const double* qb) {
-    ARGCHK(h, "handle is NULL");
-    int rc = ard_which(h, which, false);
+static int launch_parents(pyvb_lds* h, int kind, int which, bool derive) {
+    return kind == PARENTS_GAMMA ? launch_ard(h, which, derive) : launch_entry(h, which, derive);
+}
+
+// extent of a0 / b0 / a replicate's qb, and the rows per column of those arrays (0: one value per column)
+static size_t parents_per(const pyvb_lds* h, int which, int kind, size_t* rows) {
+    *rows = kind == PARENTS_GAMMA ? 0 : (size_t)(which == 0 ? h->D : h->K);
+    return kind == PARENTS_GAMMA ? (size_t)h->D : (size_t)h->D * *rows;
+}
+
+static int set_parents(pyvb_lds* h, int which, int kind, const double* a0, const double* b0, const double* qb) {
+    int rc = parents_gate(h, which, 0);
     if (rc) return rc;
+    const char* name = kind == PARENTS_GAMMA ? "Gamma" : "DiagonalGamma";
     if (h->dense) {
-        pyvb_set_error("Gamma precision parents of the columns are served with DiagonalGamma and Gamma noise only, not with Wishart noise (k_wishart.hip)");
+        pyvb_set_error("%s precision parents of the columns are served with DiagonalGamma and Gamma noise only, not with Wishart noise (k_wishart.hip)", name);
         return PYVB_E_UNSUPPORTED;
     }
     if (h->big) {
-        pyvb_set_error("Gamma precision parents of the columns are served for max(D, K) <= 64 only, not in the 128-wide class (k_big.hip): D = %d, K = %d", h->D, h->K);
+        pyvb_set_error("%s precision parents of the columns are served for max(D, K) <= 64 only, not in the 128-wide class (k_big.hip): D = %d, K = %d", name, h->D, h->K);
         return PYVB_E_UNSUPPORTED;
     }
     ARGCHK(a0 && b0 && qb, "a0, b0 and qb are required");
-    const size_t N = h->N, D = h->D;
-    const int rows = which == 0 ? h->D : h->K;
-    const char* nm = which == 0 ? "A" : "C";
-    for (size_t i = 0; i < D; ++i) {
-        if (!(a0[i] > 0.0 && a0[i] - a0[i] == 0.0)) { pyvb_set_error("a0 of column %d of %s is %g: it must be finite and positive", (int)i, nm, a0[i]); return PYVB_E_ARG; }
-        if (!(b0[i] > 0.0 && b0[i] - b0[i] == 0.0)) { pyvb_set_error("b0 of column %d of %s is %g: it must be finite and positive", (int)i, nm, b0[i]); return PYVB_E_ARG; }
-    }
-    // Chains that share A, C, Q, R: the row of a model's first replicate is the model's state and goes to all its rows
-    std::vector<double> rowsqb(N * D), qa(D);
-    for (size_t n = 0; n < N; ++n) {
-        const double* src = qb + (size_t)h->rep.first_of((int)n) * D;
-        for (size_t i = 0; i < D; ++i) {
-            if (!(src[i] > 0.0 && src[i] - src[i] == 0.0)) {
-                pyvb_set_error("qb of replicate %d, column %d of %s is %g: it must be finite and positive", h->rep.first_of((int)n), (int)i, nm, src[i]);
-                return PYVB_E_ARG;
-            }
-            rowsqb[n * D + i] = src[i];
-        }
-    }
-    for (size_t i = 0; i < D; ++i) qa[i] = a0[i] + 0.5 * rows;      // update_a, nodes_todo.py:125-128: one child of `rows` entries
+    size_t rows;
+    const size_t N = h->N, per = parents_per(h, which, kind, &rows);
+    const ParentWords w = lds_words(which);
+    std::vector<double> head, rowsqb;
+    if ((rc = check_positive(a0, per, rows, "a0", w)) || (rc = check_positive(b0, per, rows, "b0", w)) ||
+        (rc = broadcast_qb(h->rep, qb, per, rows, w, rowsqb))) return rc;
+    if (kind == PARENTS_GAMMA) stage_gamma(head, a0, b0, per, which == 0 ? h->D : h->K);
+    else stage_diagonal_gamma(head, a0, b0, per);
     ENTER(h);
-    ArdBuffers& g = h->ard[which];
-    if (!g.qb) {
-        double* blk = nullptr;
-        if ((rc = h->mem.zeros(&blk, 3 * D + 4 * N * D))) return rc;
-        g.a0 = blk; g.b0 = blk + D; g.qa = blk + 2 * D;
-        g.ex = blk + 3 * D; g.ld_ref = g.ex + N * D; g.ld_exact = g.ld_ref + N * D; g.qb = g.ld_exact + N * D;
-    }
-    if ((rc = h2d(h, g.a0, a0, D)) || (rc = h2d(h, g.b0, b0, D)) || (rc = h2d(h, g.qa, qa.data(), D)) || (rc = h2d(h, g.qb, rowsqb.data(), N * D))) return rc;
-    g.on = true;
-    h->entry[which].on = false;         // one kind of parent per matrix: the most recent setter wins
-    if ((rc = launch_ard(h, which, true))) return rc;       // qa / qb and the two log-determinants of every row, from qb as given
+    ColumnParents& p = h->parents[which];
+    const LdsParentBlock o = lds_parent_block(kind, N, h->D, per);
+    if (!p.block[kind] && (rc = h->mem.zeros(&p.block[kind], o.total))) return rc;
+    if ((rc = h2d(h, p.block[kind], head.data(), o.head)) || (rc = h2d(h, p.block[kind] + o.qb, rowsqb.data(), N * per))) return rc;
+    p.begin(kind);          // one kind of parent per matrix: the most recent setter's, unless its launch fails
+    // qa / qb and the per-column sums of every row, from qb as given
+    if ((rc = p.commit(launch_parents(h, kind, which, true)))) return rc;
     HIPCHK(hipStreamSynchronize(h->stream));               // the staging vectors are about to go out of scope
     // (nothing on the host depends on the column priors: gains, statistics and residuals read the columns, not their parents)
     return PYVB_OK;
 }
 
-int pyvb_lds_get_column_precisions(pyvb_lds* h, int which, double* qa, double* qb) {
-    ARGCHK(h, "handle is NULL");
-    int rc = ard_which(h, which, true);
+static int get_parents(pyvb_lds* h, int which, int kind, double* qa, double* qb) {
+    int rc = parents_gate(h, which, kind);
     if (rc) return rc;
     ENTER(h);
-    const size_t N = h->N, D = h->D;
-    std::vector<double> a(qa ? D : 0);
-    if (qa && (rc = d2h(h, a.data(), h->ard[which].qa, D))) return rc;
-    if ((rc = d2h(h, qb, h->ard[which].qb, N * D))) return rc;
-    if ((rc = pyvb_lds_sync(h))) return rc;
-    for (size_t n = 0; qa && n < N; ++n) memcpy(qa + n * D, a.data(), D * sizeof(double));
-    return PYVB_OK;
-}
-
-int pyvb_lds_update_column_precisions(pyvb_lds* h, int which) {
-    ARGCHK(h, "handle is NULL");
-    int rc = ard_which(h, which, true);
-    if (rc) return rc;
-    ENTER(h);
-    IDLE(h);
-    return launch_ard(h, which, false);
-}
-
-// ---- DiagonalGamma parents of the columns of A / C: a precision per entry (k_ard.hip: k_entry) ----
-static int entry_which(const pyvb_lds* h, int which, bool need_on) {
-    ARGCHK(which == 0 || which == 1, "which must be 0 (A) or 1 (C)");
-    if (need_on && !h->entry[which].on) {
-        pyvb_set_error("the columns of %s have no DiagonalGamma precision parents: no per-entry hyperpriors were given (pyvb_lds_set_entry_precisions)",
-                       which == 0 ? "A" : "C");
-        return PYVB_E_ARG;
-    }
-    return PYVB_OK;
-}
-
-int pyvb_lds_set_entry_precisions(pyvb_lds* h, int which, const double* a0, const double* b0, const double* qb) {
-    ARGCHK(h, "handle is NULL");
-    int rc = entry_which(h, which, false);
-    if (rc) return rc;
-    if (h->dense) {
-        pyvb_set_error("DiagonalGamma precision parents of the columns are served with DiagonalGamma and Gamma noise only, not with Wishart noise (k_wishart.hip)");
-        return PYVB_E_UNSUPPORTED;
-    }
-    if (h->big) {
-        pyvb_set_error("DiagonalGamma precision parents of the columns are served for max(D, K) <= 64 only, not in the 128-wide class (k_big.hip): D = %d, K = %d", h->D, h->K);
-        return PYVB_E_UNSUPPORTED;
-    }
-    ARGCHK(a0 && b0 && qb, "a0, b0 and qb are required");
-    const size_t N = h->N, D = h->D, rows = which == 0 ? h->D : h->K, per = D * rows;
-    const char* nm = which == 0 ? "A" : "C";
-    for (size_t e = 0; e < per; ++e) {
-        const int i = (int)(e / rows), k = (int)(e % rows);
-        if (!(a0[e] > 0.0 && a0[e] - a0[e] == 0.0)) { pyvb_set_error("a0 of column %d, row %d of %s is %g: it must be finite and positive", i, k, nm, a0[e]); return PYVB_E_ARG; }
-        if (!(b0[e] > 0.0 && b0[e] - b0[e] == 0.0)) { pyvb_set_error("b0 of column %d, row %d of %s is %g: it must be finite and positive", i, k, nm, b0[e]); return PYVB_E_ARG; }
-    }
-    // Chains that share A, C, Q, R: the row of a model's first replicate is the model's state and goes to all its rows
-    std::vector<double> rowsqb(N * per);
-    for (size_t n = 0; n < N; ++n) {
-        const double* src = qb + (size_t)h->rep.first_of((int)n) * per;
-        for (size_t e = 0; e < per; ++e) {
-            if (!(src[e] > 0.0 && src[e] - src[e] == 0.0)) {
-                pyvb_set_error("qb of replicate %d, column %d, row %d of %s is %g: it must be finite and positive", h->rep.first_of((int)n),
-                               (int)(e / rows), (int)(e % rows), nm, src[e]);
-                return PYVB_E_ARG;
-            }
-            rowsqb[n * per + e] = src[e];
-        }
-    }
-    // what depends on a0, b0 and qa alone: qa = a0 + 1/2 (update_a, nodes_todo.py:183-186: one child), ln qa, psi(qa), and the part
-    // of log_lower_bound (:199-204) without qb:  (a0 - qa) psi(qa) - lgamma(a0) + a0 ln b0 + lgamma(qa) + qa;  the kernel adds
-    // - a0 ln qb - b0 qa / qb
-    std::vector<double> host(6 * per);
-    for (size_t e = 0; e < per; ++e) {
-        const double qa = a0[e] + 0.5, ps = digamma_pos(qa);
-        host[e] = a0[e]; host[per + e] = b0[e]; host[2 * per + e] = qa;
-        host[3 * per + e] = log(qa); host[4 * per + e] = ps;
-        host[5 * per + e] = (a0[e] - qa) * ps - lgamma(a0[e]) + a0[e] * log(b0[e]) + lgamma(qa) + qa;
-    }
-    ENTER(h);
-    EntryBuffers& g = h->entry[which];
-    if (!g.qb) {
-        double* blk = nullptr;
-        if ((rc = h->mem.zeros(&blk, 6 * per + 2 * N * per + 3 * N * D))) return rc;
-        g.a0 = blk; g.b0 = blk + per; g.qa = blk + 2 * per; g.lnqa = blk + 3 * per; g.psi = blk + 4 * per; g.cst = blk + 5 * per;
-        g.ex = blk + 6 * per; g.qb = g.ex + N * per;
-        g.ld_ref = g.qb + N * per; g.ld_exact = g.ld_ref + N * D; g.own = g.ld_exact + N * D;
-    }
-    if ((rc = h2d(h, g.a0, host.data(), 6 * per)) || (rc = h2d(h, g.qb, rowsqb.data(), N * per))) return rc;
-    g.on = true;
-    h->ard[which].on = false;           // one kind of parent per matrix: the most recent setter wins
-    if ((rc = launch_entry(h, which, true))) return rc;     // qa / qb and the three per-column sums of every row, from qb as given
-    HIPCHK(hipStreamSynchronize(h->stream));               // the staging vectors are about to go out of scope
-    // (nothing on the host depends on the column priors: gains, statistics and residuals read the columns, not their parents)
-    return PYVB_OK;
-}
-
-int pyvb_lds_get_entry_precisions(pyvb_lds* h, int which, double* qa, double* qb) {
-    ARGCHK(h, "handle is NULL");
-    int rc = entry_which(h, which, true);
-    if (rc) return rc;
-    ENTER(h);
-    const size_t N = h->N, per = (size_t)h->D * (which == 0 ? h->D : h->K);
+    size_t rows;
+    const size_t N = h->N, per = parents_per(h, which, kind, &rows);
+    const double* blk = h->parents[which].current();
     std::vector<double> a(qa ? per : 0);
-    if (qa && (rc = d2h(h, a.data(), h->entry[which].qa, per))) return rc;
-    if ((rc = d2h(h, qb, h->entry[which].qb, N * per))) return rc;
+    if (qa && (rc = d2h(h, a.data(), blk + 2 * per, per))) return rc;
+    if ((rc = d2h(h, qb, blk + lds_parent_block(kind, N, h->D, per).qb, N * per))) return rc;
     if ((rc = pyvb_lds_sync(h))) return rc;
     for (size_t n = 0; qa && n < N; ++n) memcpy(qa + n * per, a.data(), per * sizeof(double));
     return PYVB_OK;
 }
 
-int pyvb_lds_update_entry_precisions(pyvb_lds* h, int which) {
-    ARGCHK(h, "handle is NULL");
-    int rc = entry_which(h, which, true);
+static int update_parents(pyvb_lds* h, int which, int kind) {
+    int rc = parents_gate(h, which, kind);
     if (rc) return rc;
     ENTER(h);
     IDLE(h);
-    return launch_entry(h, which, false);
+    return launch_parents(h, kind, which, false);
+}
+
+int pyvb_lds_set_column_precisions(pyvb_lds* h, int which, const double* a0, const double* b0, const double* qb) {
+    return set_parents(h, which, PARENTS_GAMMA, a0, b0, qb);
+}
+int pyvb_lds_get_column_precisions(pyvb_lds* h, int which, double* qa, double* qb) { return get_parents(h, which, PARENTS_GAMMA, qa, qb); }
+int pyvb_lds_update_column_precisions(pyvb_lds* h, int which) { return update_parents(h, which, PARENTS_GAMMA); }
+int pyvb_lds_set_entry_precisions(pyvb_lds* h, int which, const double* a0, const double* b0, const double* qb) {
+    return set_parents(h, which, PARENTS_DIAGONAL_GAMMA, a0, b0, qb);
+}
+int pyvb_lds_get_entry_precisions(pyvb_lds* h, int which, double* qa, double* qb) { return get_parents(h, which, PARENTS_DIAGONAL_GAMMA, qa, qb); }
+int pyvb_lds_update_entry_precisions(pyvb_lds* h, int which) { return update_parents(h, which, PARENTS_DIAGONAL_GAMMA); }
+
+int pyvb_lds_get_column_parents(pyvb_lds* h, int kind[2]) {
+    ARGCHK(h, "handle is NULL");
+    ARGCHK(kind, "kind is NULL");
+    kind[0] = h->parents[0].kind; kind[1] = h->parents[1].kind;
+    return PYVB_OK;
 }
 
 int pyvb_lds_set_wishart_priors(pyvb_lds* h, double Q_v0, const double* Q_w0, double R_v0, const double* R_w0) {
@@ -1126,11 +1037,11 @@ static int iterate_updates(pyvb_lds* h) {
         h->st.noise_updated(2);
         // [al.update() for al in alphas]: they read their own column and feed the next column update only, so they commute with Q
         // and R.  They sit behind the join_elbo above like k_cols: the bound of the iteration before reads qb and qa / qb.
-        const bool aa = h->ard[0].on, ac = h->ard[1].on;
-        if ((aa || ac) && (rc = launch_ard(h, aa && ac ? 2 : (ac ? 1 : 0), false))) return rc;
-        // [dg.update() for dg in ...]: the DiagonalGamma parents of the matrices that have those instead, in the same place
-        const bool ea = h->entry[0].on, ec = h->entry[1].on;
-        if ((ea || ec) && (rc = launch_entry(h, ea && ec ? 2 : (ec ? 1 : 0), false))) return rc;
+        // Then [dg.update() for dg in ...]: the DiagonalGamma parents of the matrices that have those instead, in the same place.
+        for (int kind = PARENTS_GAMMA; kind <= PARENTS_DIAGONAL_GAMMA; ++kind) {
+            const int which = parents_of_kind(h->parents, kind);     // both matrices of a kind: one launch
+            if (which >= 0 && (rc = launch_parents(h, kind, which, false))) return rc;
+        }
     }
     if (h->bound == PYVB_BOUND_EXACT && (rc = ensure_lnd_x(h))) return rc;       // (only before the first complete sweep)
     return PYVB_OK;

@@ -6,17 +6,6 @@
 
 #define ENTER(h) ENTER_DEVICE(h)
 
-// digamma for x > 0 on the host (recurrence up to 10, then the asymptotic series: the positive branch of digamma.h's digamma_pos,
-// kept apart because this translation unit calls it from host code); reached by the tests through L_Beta of the PCA bound only
-static double digamma_host(double x) {
-    if (!(x > 0.0)) return NAN;
-    double r = 0.0;
-    while (x < 10.0) { r -= 1.0 / x; x += 1.0; }
-    const double f = 1.0 / (x * x);
-    const double ser = f * (1.0 / 12 - f * (1.0 / 120 - f * (1.0 / 252 - f * (1.0 / 240 - f * (1.0 / 132 - f * (691.0 / 32760 - f / 12))))));
-    return r + std::log(x) - 0.5 / x - ser;
-}
-
 extern "C" {
 
 int pyvb_pca_destroy(pyvb_pca* h) {
@@ -121,7 +110,7 @@ int pyvb_pca_set_priors(pyvb_pca* h, const double* W_pm, const double* W_pp, con
     HIPCHK(hipMemcpy(sc, h->scal, sizeof(sc), hipMemcpyDeviceToHost));
     sc[PS_BETA_A0] = beta_a0; sc[PS_BETA_B0] = beta_b0;
     sc[PS_BETA_A] = beta_a0 + 0.5 * (double)h->d * (double)h->N_total;      // Gamma.update_a, nodes_todo.py:125-128
-    sc[PS_LGAMMA_A0] = std::lgamma(beta_a0); sc[PS_LGAMMA_A] = std::lgamma(sc[PS_BETA_A]); sc[PS_DIGAMMA_A] = digamma_host(sc[PS_BETA_A]);
+    sc[PS_LGAMMA_A0] = std::lgamma(beta_a0); sc[PS_LGAMMA_A] = std::lgamma(sc[PS_BETA_A]); sc[PS_DIGAMMA_A] = digamma_pos(sc[PS_BETA_A]);
     sc[PS_QLD_Z] = sc[PS_QLD_X] = sc[PS_QLD_MU] = NAN;
     sc[PS_LND_Z] = sc[PS_LND_MU] = NAN;
     HIPCHK(hipMemcpy(h->scal, sc, sizeof(sc), hipMemcpyHostToDevice));
@@ -129,129 +118,74 @@ int pyvb_pca_set_priors(pyvb_pca* h, const double* W_pm, const double* W_pp, con
     HIPCHK(hipMemcpy(h->qld_W, nanq.data(), nanq.size() * sizeof(double), hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(h->lnd_W, nanq.data(), nanq.size() * sizeof(double), hipMemcpyHostToDevice));
     HIPCHK(hipStreamSynchronize(h->stream));
-    h->ard_on = false;      // the columns of W have Constant parents again: W_pp is the caller's (pyvb_pca_set_column_precisions comes after)
-    h->entry_on = false;    // (and pyvb_pca_set_entry_precisions)
+    h->parents.clear();     // the columns of W have Constant parents again: W_pp is the caller's (the setters of others come after)
     return PYVB_OK;
 }
 
-// ---- Gamma parents of the columns of W (automatic relevance determination; k_pca.hip: PCA_ARD) ----
+// ---- The precision parents of the columns of W: a Gamma per column (automatic relevance determination; k_pca.hip: PCA_ARD) or a
+// DiagonalGamma per column, a Gamma per entry (sparse loadings; PCA_ENTRY).  Which kind the columns have, the checks and the
+// staging are column_parents.h; a setter is check, stage, upload, launch, commit.
 // Nothing PcaState tracks depends on W_pp: the statistics are sums over X and Z, the cached residual reads <W>, var(W), Mu and the
-// statistics, the pending Z update reads <W> and var(W).  The prior precisions are read by the next W update and by the bound only,
-// so none of the three entries below raises an event.
-static int ard_required(const pyvb_pca* h) {
-    if (!h->ard_on) {
-        pyvb_set_error("the columns of W have Constant precision parents: no hyperpriors were given (pyvb_pca_set_column_precisions)");
-        return PYVB_E_ARG;
-    }
-    return PYVB_OK;
+// statistics, the pending Z update reads <W> and var(W) (pca_plan.h).  The prior precisions are read by the next W update and by
+// the bound only, so none of the entries below raises an event and PcaState has no field for the parents.
+static const ParentWords W_WORDS = {"W", true};
+
+static int launch_parents(pyvb_pca* h, int kind, bool derive) {
+    return kind == PARENTS_GAMMA ? pca_launch_ard(h, derive) : pca_launch_entry(h, derive);
 }
 
-int pyvb_pca_set_column_precisions(pyvb_pca* h, const double* a0, const double* b0, const double* qb) {
+static int set_parents(pyvb_pca* h, int kind, const double* a0, const double* b0, const double* qb) {
     ARGCHK(h, "handle is NULL");
     ARGCHK(a0 && b0 && qb, "a0, b0 and qb are required");
-    const size_t q = (size_t)h->q;
-    for (size_t i = 0; i < q; ++i) {
-        if (!(a0[i] > 0.0 && a0[i] - a0[i] == 0.0)) { pyvb_set_error("a0 of column %d of W is %g: it must be finite and positive", (int)i, a0[i]); return PYVB_E_ARG; }
-        if (!(b0[i] > 0.0 && b0[i] - b0[i] == 0.0)) { pyvb_set_error("b0 of column %d of W is %g: it must be finite and positive", (int)i, b0[i]); return PYVB_E_ARG; }
-        if (!(qb[i] > 0.0 && qb[i] - qb[i] == 0.0)) { pyvb_set_error("qb of column %d of W is %g: it must be finite and positive", (int)i, qb[i]); return PYVB_E_ARG; }
-    }
-    std::vector<double> host(AR_COUNT * q, 0.0);
-    for (size_t i = 0; i < q; ++i) {
-        const double qa = a0[i] + 0.5 * (double)h->d;       // update_a, nodes_todo.py:125-128: one child of d entries
-        host[AR_A0 * q + i] = a0[i]; host[AR_B0 * q + i] = b0[i]; host[AR_QA * q + i] = qa; host[AR_QB * q + i] = qb[i];
-        host[AR_LGAMMA_A0 * q + i] = std::lgamma(a0[i]); host[AR_LGAMMA_QA * q + i] = std::lgamma(qa);
-        host[AR_DIGAMMA_QA * q + i] = digamma_host(qa); host[AR_LN_QA * q + i] = std::log(qa);
-    }
-    ENTER(h);
+    const bool dg = kind == PARENTS_DIAGONAL_GAMMA;
+    const size_t rows = dg ? (size_t)h->d : 0, n = dg ? (size_t)h->q * h->d : (size_t)h->q;
     int rc;
-    if (!h->ard && (rc = h->mem.zeros(&h->ard, AR_COUNT * q))) return rc;
-    if ((rc = up(h, h->ard, host.data(), AR_COUNT * q))) return rc;
-    h->ard_on = true; h->entry_on = false;                 // one kind of parent for all columns: the most recent setter's
-    // W_pp = qa / qb and the two log terms from qb as given: the first update_W already sees <alpha>
-    if ((rc = pca_launch_ard(h, true))) { h->ard_on = false; return rc; }
+    if ((rc = check_positive(a0, n, rows, "a0", W_WORDS)) || (rc = check_positive(b0, n, rows, "b0", W_WORDS)) ||
+        (rc = check_positive(qb, n, rows, "qb", W_WORDS))) return rc;
+    std::vector<double> host;
+    if (dg) stage_diagonal_gamma(host, a0, b0, n, qb); else stage_gamma(host, a0, b0, n, h->d, qb);
+    ENTER(h);
+    ColumnParents& p = h->parents;
+    if (!p.block[kind] && (rc = h->mem.zeros(&p.block[kind], host.size()))) return rc;
+    if ((rc = up(h, p.block[kind], host.data(), host.size()))) return rc;
+    p.begin(kind);          // one kind of parent for all columns: the most recent setter's, unless its launch fails
+    // W_pp = qa / qb and what else follows qb, from qb as given: the first update_W already sees the parents
+    if ((rc = p.commit(launch_parents(h, kind, true)))) return rc;
     HIPCHK(hipStreamSynchronize(h->stream));               // the staging vector is about to go out of scope
     return PYVB_OK;
 }
 
-int pyvb_pca_get_column_precisions(pyvb_pca* h, double* qa, double* qb) {
+static int get_parents(pyvb_pca* h, int kind, double* qa, double* qb) {
     ARGCHK(h, "handle is NULL");
-    int rc = ard_required(h);
+    int rc = h->parents.require(kind, W_WORDS);
     if (rc) return rc;
     ENTER(h);
-    const size_t q = (size_t)h->q;
-    if ((rc = down(h, qa, h->ard + AR_QA * q, q))) return rc;
-    if ((rc = down(h, qb, h->ard + AR_QB * q, q))) return rc;
+    const size_t n = kind == PARENTS_GAMMA ? (size_t)h->q : (size_t)h->q * h->d;      // (AR_QA == EN_QA, AR_QB == EN_QB)
+    if ((rc = down(h, qa, h->parents.current() + AR_QA * n, n))) return rc;
+    if ((rc = down(h, qb, h->parents.current() + AR_QB * n, n))) return rc;
     return pyvb_pca_sync(h);
 }
 
-int pyvb_pca_update_column_precisions(pyvb_pca* h) {
+static int update_parents(pyvb_pca* h, int kind) {
     ARGCHK(h, "handle is NULL");
-    int rc = ard_required(h);
+    int rc = h->parents.require(kind, W_WORDS);
     if (rc) return rc;
     ENTER(h);
-    return pca_launch_ard(h, false);
+    return launch_parents(h, kind, false);
 }
 
-// ---- DiagonalGamma parents of the columns of W: a Gamma per entry (sparse loadings; k_pca.hip: PCA_ENTRY) ----
-// As above, nothing PcaState tracks depends on W_pp (pca_plan.h: the statistics, the cached residual and the pending Z update read
-// <W>, var(W), Mu, X and Z), so none of the three entries raises an event and PcaState has no field for the parents.
-static int entry_required(const pyvb_pca* h) {
-    if (!h->entry_on) {
-        pyvb_set_error("the columns of W have no DiagonalGamma precision parents (pyvb_pca_set_entry_precisions)");
-        return PYVB_E_ARG;
-    }
+int pyvb_pca_set_column_precisions(pyvb_pca* h, const double* a0, const double* b0, const double* qb) { return set_parents(h, PARENTS_GAMMA, a0, b0, qb); }
+int pyvb_pca_get_column_precisions(pyvb_pca* h, double* qa, double* qb) { return get_parents(h, PARENTS_GAMMA, qa, qb); }
+int pyvb_pca_update_column_precisions(pyvb_pca* h) { return update_parents(h, PARENTS_GAMMA); }
+int pyvb_pca_set_entry_precisions(pyvb_pca* h, const double* a0, const double* b0, const double* qb) { return set_parents(h, PARENTS_DIAGONAL_GAMMA, a0, b0, qb); }
+int pyvb_pca_get_entry_precisions(pyvb_pca* h, double* qa, double* qb) { return get_parents(h, PARENTS_DIAGONAL_GAMMA, qa, qb); }
+int pyvb_pca_update_entry_precisions(pyvb_pca* h) { return update_parents(h, PARENTS_DIAGONAL_GAMMA); }
+
+int pyvb_pca_get_column_parents(pyvb_pca* h, int* kind) {
+    ARGCHK(h, "handle is NULL");
+    ARGCHK(kind, "kind is NULL");
+    *kind = h->parents.kind;
     return PYVB_OK;
-}
-
-int pyvb_pca_set_entry_precisions(pyvb_pca* h, const double* a0, const double* b0, const double* qb) {
-    ARGCHK(h, "handle is NULL");
-    ARGCHK(a0 && b0 && qb, "a0, b0 and qb are required");
-    const size_t q = (size_t)h->q, d = (size_t)h->d, qd = q * d;
-    for (size_t e = 0; e < qd; ++e) {
-        const int i = (int)(e / d), k = (int)(e % d);
-        if (!(a0[e] > 0.0 && a0[e] - a0[e] == 0.0)) { pyvb_set_error("a0 of entry %d of column %d of W is %g: it must be finite and positive", k, i, a0[e]); return PYVB_E_ARG; }
-        if (!(b0[e] > 0.0 && b0[e] - b0[e] == 0.0)) { pyvb_set_error("b0 of entry %d of column %d of W is %g: it must be finite and positive", k, i, b0[e]); return PYVB_E_ARG; }
-        if (!(qb[e] > 0.0 && qb[e] - qb[e] == 0.0)) { pyvb_set_error("qb of entry %d of column %d of W is %g: it must be finite and positive", k, i, qb[e]); return PYVB_E_ARG; }
-    }
-    std::vector<double> host(EN_COUNT * qd + EN_SCALARS, 0.0);
-    double exact = 0.0;
-    for (size_t e = 0; e < qd; ++e) {
-        const double qa = a0[e] + 0.5;                      // update_a, nodes_todo.py:183-186: one child per entry
-        const double psi = digamma_host(qa);
-        host[EN_A0 * qd + e] = a0[e]; host[EN_B0 * qd + e] = b0[e]; host[EN_QA * qd + e] = qa; host[EN_QB * qd + e] = qb[e];
-        host[EN_CST * qd + e] = (a0[e] - qa) * psi - std::lgamma(a0[e]) + a0[e] * std::log(b0[e]) + std::lgamma(qa) + qa;
-        exact += psi - std::log(qa);
-    }
-    host[EN_COUNT * qd + ES_EXACT] = 0.5 * exact;
-    ENTER(h);
-    int rc;
-    if (!h->entry && (rc = h->mem.zeros(&h->entry, EN_COUNT * qd + EN_SCALARS))) return rc;
-    if ((rc = up(h, h->entry, host.data(), EN_COUNT * qd + EN_SCALARS))) return rc;
-    const bool ard_was = h->ard_on;
-    h->entry_on = true; h->ard_on = false;                 // one kind of parent for all columns: the most recent setter's
-    // W_pp = qa / qb and the sum of the own terms from qb as given: the first update_W already sees the parents
-    if ((rc = pca_launch_entry(h, true))) { h->entry_on = false; h->ard_on = ard_was; return rc; }
-    HIPCHK(hipStreamSynchronize(h->stream));               // the staging vector is about to go out of scope
-    return PYVB_OK;
-}
-
-int pyvb_pca_get_entry_precisions(pyvb_pca* h, double* qa, double* qb) {
-    ARGCHK(h, "handle is NULL");
-    int rc = entry_required(h);
-    if (rc) return rc;
-    ENTER(h);
-    const size_t qd = (size_t)h->q * h->d;
-    if ((rc = down(h, qa, h->entry + EN_QA * qd, qd))) return rc;
-    if ((rc = down(h, qb, h->entry + EN_QB * qd, qd))) return rc;
-    return pyvb_pca_sync(h);
-}
-
-int pyvb_pca_update_entry_precisions(pyvb_pca* h) {
-    ARGCHK(h, "handle is NULL");
-    int rc = entry_required(h);
-    if (rc) return rc;
-    ENTER(h);
-    return pca_launch_entry(h, false);
 }
 
 // rows [N][d] on the host -> padded device rows [N][DP]
@@ -585,6 +519,7 @@ int pyvb_pca_elbo(pyvb_pca* h, double parts[5]) {
 int pyvb_pca_iterate(pyvb_pca* h, int niters) {
     ENTER(h);
     ARGCHK(niters >= 0, "niters must be >= 0");
+    static const int RUN_HEAD[PARENTS_KINDS] = {PCA_RUN_HEAD, PCA_RUN_HEAD_ARD, PCA_RUN_HEAD_ENTRY};      // by the kind of W's parents
     int rc;
     for (int it = 0; it < niters; ++it) {
         if (!h->comm) {
@@ -596,7 +531,7 @@ int pyvb_pca_iterate(pyvb_pca* h, int niters) {
             // Gamma parents on the columns of W: their update is one more step of the same launch, behind W (it commutes with the Z
             // update, after which the crawl order has it); a handle without them launches what it always launched
             // (DiagonalGamma parents on its entries: likewise, PCA_ENTRY in place of PCA_ARD)
-            if ((rc = pca_launch_small(h, h->ard_on ? PCA_RUN_HEAD_ARD : h->entry_on ? PCA_RUN_HEAD_ENTRY : PCA_RUN_HEAD))) { h->st.z_request_failed(); return rc; }
+            if ((rc = pca_launch_small(h, RUN_HEAD[h->parents.kind]))) { h->st.z_request_failed(); return rc; }
             h->st.linear_step();
             // the X_0 step reads row 0: a no-op after an iteration of this loop (its sweep left vlo == 1), but not after a
             // stage-wise pyvb_pca_update_X(0, N)
@@ -610,8 +545,8 @@ int pyvb_pca_iterate(pyvb_pca* h, int niters) {
             continue;
         }
         if ((rc = pyvb_pca_update_W(h))) return rc;
-        if (h->ard_on && (rc = pca_launch_ard(h, false))) return rc;    // local, not a collective: W is the same on every rank, so alpha is too
-        if (h->entry_on && (rc = pca_launch_entry(h, false))) return rc;  // likewise: qb is the same on every rank
+        // the parents: local, not a collective: W is the same on every rank, so qb is too
+        if (h->parents.kind != PARENTS_CONSTANT && (rc = launch_parents(h, h->parents.kind, false))) return rc;
         if ((rc = pyvb_pca_update_Z(h))) return rc;
         const long first = h->row_offset == 0 ? 1 : 0;         // global row 0 lives on the rank with offset 0
         if ((rc = x0_step(h))) return rc;                       // every rank: the exchange is collective

@@ -4,6 +4,7 @@
 #include "host.h"
 #include "geometry.h"
 #include "replicates.h"
+#include "column_parents.h"
 
 struct pyvb_comm;
 typedef double d4 __attribute__((ext_vector_type(4)));
@@ -16,25 +17,6 @@ struct Priors {          // device pointers, shared by all replicates
     double *A_pld, *C_pld;   // [D] ln det of each column's diagonal prior precision
     double x0_lndet;     // ln det of x0_prec (Constant.lndet, node.py:301-302)
     double Q_a0_host, R_a0_host, Q_w0_lndet, R_w0_lndet;    // Wishart: v0 and ln det w0 of the two priors
-};
-
-// Gamma parents of the columns of one matrix (pyvb_lds_set_column_precisions, k_ard.hip): allocated by the first call that gives
-// the matrix hyperpriors, never on a handle that makes none.  `on` is what make_args reads; pyvb_lds_set_priors clears it.
-struct ArdBuffers {
-    bool on;
-    double *a0, *b0, *qa;                   // [D] each, shared by the replicates; qa_i = a0_i + rows / 2
-    double *qb, *ex, *ld_ref, *ld_exact;    // [N][D] each: see ColumnPrior (params.h)
-};
-
-// DiagonalGamma parents of the columns of one matrix (pyvb_lds_set_entry_precisions, k_ard.hip: k_entry): a precision of its own
-// for every entry.  One allocation, made by the first call that gives the matrix such parents, never on a handle that makes none.
-// `on` is what make_args reads; pyvb_lds_set_priors and pyvb_lds_set_column_precisions of that matrix clear it.
-struct EntryBuffers {
-    bool on;
-    double *a0, *b0, *qa;                   // [D][rows] each, shared by the replicates; qa = a0 + 1/2
-    double *lnqa, *psi, *cst;               // [D][rows] each, formed by the setter: ln qa, psi(qa), the part of the node's own term without qb
-    double *qb, *ex;                        // [N][D][rows]: qb and qa / qb
-    double *ld_ref, *ld_exact, *own;        // [N][D]: see ColumnPrior (params.h)
 };
 
 struct EventPair;
@@ -60,8 +42,7 @@ struct pyvb_lds {
     Priors pri;
     double *pri_block;
     double *w0;                     // [DP] L0 m0 of the prior of X_0 (k_prep.hip: k_w0), as of the last pyvb_lds_set_priors
-    ArdBuffers ard[2];              // Gamma parents of the columns of A ([0]) and C ([1]); all null / off unless the caller asked
-    EntryBuffers entry[2];          // DiagonalGamma parents of the same; a matrix has at most one kind `on`
+    ColumnParents parents[2];       // the precision parents of the columns of A ([0]) and C ([1]) (column_parents.h); Constant, no block, unless the caller asked
     // derived
     double *Sigma, *qld_x;          // as of the last X update: [N][3][D][D], [N][3]
     double *Sigma_new, *qld_x_new;  // written by k_prep for the current parameters

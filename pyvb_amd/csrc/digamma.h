@@ -1,7 +1,13 @@
 // The one device digamma: k_elbo (k_params.hip), the Wishart bound's psi_multi (k_wishart.hip) and the tape interpreter's
 // U_DIGAMMA (k_tape.hip) all call this function.
 #pragma once
+#ifdef __HIPCC__
 #include <hip/hip_runtime.h>
+#else       // a host compiler (column_parents.h under tests/c/column_parents_driver.cpp): the same function, host only
+#include <cmath>
+#define __host__
+#define __device__
+#endif
 
 // digamma for positive and for negative non-integer arguments: the recurrence up to x >= 10, then the asymptotic series.
 // The recurrence takes 10 - x steps: bounded here, so that no argument (a degenerate qv, -inf, a NaN from bad state) can keep a
@@ -11,7 +17,8 @@
 // test_device_special_functions).
 // Poles: a negative integer below -64 gives NaN; 0 and the negative integers down to -64 meet 1 / 0 in the recurrence and give
 // +-inf or NaN, as they always did.  The bounds never pass one.
-// (__host__ too: pyvb_lds_set_entry_precisions forms psi(qa) of the DiagonalGamma parents once, on the host.)
+// (__host__ too: column_parents.h forms psi(qa) of the columns' precision parents once, on the host, and pyvb_pca_set_priors that of
+// Beta's shape.)
 __host__ __device__ static inline double digamma_pos(double x) {
     if (!(x - x == 0.0) || x < -4.5e15) return x > 0 ? x : __builtin_nan("");      // below -2^52 every double is an integer: a pole
     double r = 0.0;

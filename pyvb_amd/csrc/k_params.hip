@@ -263,26 +263,29 @@ ParamArgs make_args(pyvb_lds* h) {
     a.active = h->active;
     a.len = h->len; a.Lw = 0; a.first = h->first;
     // the prior precisions of the columns (params.h: ColumnPrior): Constant parents, the Gamma parents of
-    // pyvb_lds_set_column_precisions or the DiagonalGamma parents of pyvb_lds_set_entry_precisions
+    // pyvb_lds_set_column_precisions or the DiagonalGamma parents of pyvb_lds_set_entry_precisions, out of the matrix's record
+    // (column_parents.h, which has the layout of a block)
     for (int w = 0; w < 2; ++w) {
         ColumnPrior& cp = w == 0 ? a.cpA : a.cpC;
-        const ArdBuffers& g = h->ard[w];
-        const EntryBuffers& e = h->entry[w];
+        const ColumnParents& p = h->parents[w];
         const int rows = w == 0 ? h->D : h->K;
-        cp.lnqa = cp.psi = cp.cst = nullptr; cp.own = nullptr;
-        if (e.on) {
-            cp.pp = e.ex; cp.pp_n = h->D * rows; cp.pp_c = rows; cp.pp_r = 1;
-            cp.pld = h->bound == PYVB_BOUND_EXACT ? e.ld_exact : e.ld_ref; cp.pld_n = h->D;
-            cp.a0 = e.a0; cp.b0 = e.b0; cp.qa = e.qa; cp.qb = e.qb; cp.ex = e.ex; cp.ld_ref = e.ld_ref; cp.ld_exact = e.ld_exact;
-            cp.lnqa = e.lnqa; cp.psi = e.psi; cp.cst = e.cst; cp.own = e.own;
-        } else if (g.on) {
-            cp.pp = g.ex; cp.pp_n = h->D; cp.pp_c = 1; cp.pp_r = 0;
-            cp.pld = h->bound == PYVB_BOUND_EXACT ? g.ld_exact : g.ld_ref; cp.pld_n = h->D;
-            cp.a0 = g.a0; cp.b0 = g.b0; cp.qa = g.qa; cp.qb = g.qb; cp.ex = g.ex; cp.ld_ref = g.ld_ref; cp.ld_exact = g.ld_exact;
-        } else {
-            cp.pp = w == 0 ? h->pri.A_pp : h->pri.C_pp; cp.pp_n = 0; cp.pp_c = w == 0 ? h->D : h->K; cp.pp_r = 1;
+        const size_t per = p.kind == PARENTS_DIAGONAL_GAMMA ? (size_t)h->D * rows : (size_t)h->D;
+        const LdsParentBlock o = lds_parent_block(p.kind, h->N, h->D, per);
+        double* b = p.current();
+        cp = ColumnPrior();         // every pointer null
+        switch (p.kind) {
+        case PARENTS_DIAGONAL_GAMMA:        // strides (D rows, rows, 1)
+            cp.lnqa = b + 3 * per; cp.psi = b + 4 * per; cp.cst = b + 5 * per; cp.own = b + o.own;
+            [[fallthrough]];
+        case PARENTS_GAMMA:                 // strides (D, 1, 0)
+            cp.a0 = b; cp.b0 = b + per; cp.qa = b + 2 * per;
+            cp.qb = b + o.qb; cp.ex = b + o.ex; cp.ld_ref = b + o.ld_ref; cp.ld_exact = b + o.ld_exact;
+            cp.pp = cp.ex; cp.pp_n = (int)per; cp.pp_c = (int)per / h->D; cp.pp_r = p.kind == PARENTS_DIAGONAL_GAMMA;
+            cp.pld = h->bound == PYVB_BOUND_EXACT ? cp.ld_exact : cp.ld_ref; cp.pld_n = h->D;
+            break;
+        default:                            // Constant parents: the caller's [D][rows] array, shared by the replicates
+            cp.pp = w == 0 ? h->pri.A_pp : h->pri.C_pp; cp.pp_n = 0; cp.pp_c = rows; cp.pp_r = 1;
             cp.pld = w == 0 ? h->pri.A_pld : h->pri.C_pld; cp.pld_n = 0;
-            cp.a0 = cp.b0 = cp.qa = nullptr; cp.qb = cp.ex = cp.ld_ref = cp.ld_exact = nullptr;
         }
     }
     a.derive = 0;

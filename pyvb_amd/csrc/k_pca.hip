@@ -1487,8 +1487,9 @@ static PcaArgs pca_args(pyvb_pca* h) {
     a.res_cached = h->st.res_valid ? 1 : 0;
     a.keep_z0 = 0; a.z_deferred = 0; a.x0_prep = 0;
     a.W_x = h->W_x; a.Mu_x = h->Mu_x; a.vin_lo = a.vin_hi = 0; a.save_wx = 0;
-    a.ard = h->ard_on ? h->ard : nullptr; a.ard_derive = 0;
-    a.entry = h->entry_on ? h->entry : nullptr;
+    // the parents of the columns of W in force (column_parents.h); both null: Constant
+    a.ard = h->parents.kind == PARENTS_GAMMA ? h->parents.current() : nullptr; a.ard_derive = 0;
+    a.entry = h->parents.kind == PARENTS_DIAGONAL_GAMMA ? h->parents.current() : nullptr;
     return a;
 }
 

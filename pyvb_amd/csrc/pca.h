@@ -64,26 +64,10 @@ struct pyvb_pca {
     bool pairs_ready;                    // pca_prepare_pairs() has been called for this handle's device
     int nchunkB; long chunk_rowsB;       // k_pca_pairs' partition of the rows: a workgroup per CU
     pyvb_comm* comm; int rank, world;
-    // Gamma precision parents of the columns of W (pyvb_pca_set_column_precisions, PCA_ARD): [AR_COUNT][q], allocated by the first
-    // call that gives hyperpriors, never on a handle that makes none.  ard_on is what the launchers read; pyvb_pca_set_priors clears it.
-    double* ard; bool ard_on;
-    // DiagonalGamma precision parents, one per entry of W (pyvb_pca_set_entry_precisions, PCA_ENTRY): EN_COUNT arrays [q][d] and
-    // EN_SCALARS doubles behind them, allocated by the first call that gives them, never on another handle.  The columns of W have
-    // one kind of parent: at most one of ard_on and entry_on holds, the most recent setter's; pyvb_pca_set_priors clears both.
-    double* entry; bool entry_on;
+    // The precision parents of the columns of W (column_parents.h, which has the AR_* rows and EN_* arrays of the two blocks): Gamma
+    // (pyvb_pca_set_column_precisions, PCA_ARD), DiagonalGamma, one per entry (pyvb_pca_set_entry_precisions, PCA_ENTRY), or Constant
+    ColumnParents parents;
 };
-// rows of pyvb_pca::ard, [q] each.  qa_i = a0_i + d / 2 never changes (nodes_todo.py:125-128): lgamma, digamma and ln of the
-// shape parameters are formed on the host, as for Beta.  AR_LN_REF = ln qa - ln qb (pass_down_lndet / d, nodes_todo.py:147);
-// AR_LN_EXACT = psi(qa) - ln qb = E[ln alpha]; both follow qb on the device.
-enum { AR_A0 = 0, AR_B0, AR_QA, AR_QB, AR_LGAMMA_A0, AR_LGAMMA_QA, AR_DIGAMMA_QA, AR_LN_QA, AR_LN_REF, AR_LN_EXACT, AR_COUNT };
-// arrays of pyvb_pca::entry, [q][d] each ([column i][row k], as W_var and W_pp).  qa = a0 + 1/2 never changes (every entry has one
-// child, nodes_todo.py:183-186), so everything of DiagonalGamma.log_lower_bound that does not follow qb is one constant per entry,
-//   EN_CST = (a0 - qa) psi(qa) - lnGamma(a0) + a0 ln b0 + lnGamma(qa) + qa,
-// formed on the host; the entry's own term is then EN_CST - a0 ln qb - b0 qa / qb.  Behind the arrays, at EN_COUNT * q * d:
-//   ES_OWN    the sum of the own terms over all entries, as of the last PCA_ENTRY
-//   ES_EXACT  1/2 sum_ik (psi(qa_ik) - ln qa_ik), what the exact bound has over the per-entry 1/2 ln W_pp (host; never changes)
-enum { EN_A0 = 0, EN_B0, EN_QA, EN_QB, EN_CST, EN_COUNT };
-enum { ES_OWN = 0, ES_EXACT, EN_SCALARS = 8 };
 
 int pca_launch_small(pyvb_pca* h, int mode);
 int pca_prepare_pairs();                                    // once per device, before the first k_pca_pairs: its dynamic-LDS limit

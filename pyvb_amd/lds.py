@@ -14,6 +14,8 @@ from . import _capi as C
 __all__ = ["LDSBatch", "pad_series"]
 
 _NOISE = {"diagonal_gamma": C.NOISE_DIAGONAL_GAMMA, "gamma": C.NOISE_GAMMA, "wishart": C.NOISE_WISHART}
+_WHICH = {"A": 0, "C": 1}
+_PARENT_ENTRIES = {"gamma": "column", "diagonal_gamma": "entry"}       # kind (_capi.PARENTS) -> the word in pyvb_*_{set,get,update}_*_precisions
 
 
 def _f64(a, shape, name):
@@ -68,8 +70,6 @@ class LDSBatch(object):
             raise NotImplementedError("noise precision %r has no HIP path (DiagonalGamma, Gamma and Wishart do)" % (noise,))
         self.N, self.T, self.D, self.K, self.noise, self.device = int(N), int(T), int(D), int(K), noise, int(device)
         self.bound = "reference"
-        self._ard = set()               # the matrices ("A", "C") whose columns have Gamma parents (set_column_precisions)
-        self._entry = set()             # those whose columns have DiagonalGamma parents, one precision per entry (set_entry_precisions)
         h = C.ctypes.c_void_p()
         if models is not None:
             ln = None if lengths is None else np.ascontiguousarray(lengths, dtype=np.int32)
@@ -113,7 +113,6 @@ class LDSBatch(object):
         """pri: dict as pyvb_amd.synth.default_priors (Constant parents of X_0 and of the
         columns, Gamma-family hyper-parameters).  Scalars are broadcast for the Gamma kind."""
         D, K = self.D, self.K
-        bc = lambda v, n: np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=np.float64), (n,)))
         arrs = [
             _f64(pri["x0_mean"], (D,), "x0_mean"), _f64(pri["x0_prec"], (D, D), "x0_prec"),
             _f64(pri["A_prior_mean"], (D, D), "A_prior_mean"), _f64(pri["A_prior_prec"], (D, D), "A_prior_prec"),
@@ -121,15 +120,11 @@ class LDSBatch(object):
         ]
         if self.noise == "wishart":     # Wishart(dim, v0, w0): Q_a0 / R_a0 hold v0, Q_b0 / R_b0 the matrices w0
             self._check(C.lib.pyvb_lds_set_priors(self._h, *([C.dptr(a) for a in arrs] + [None] * 4)))
-            self._ard.clear()
-            self._entry.clear()
             qw0, rw0 = _f64(pri["Q_b0"], (D, D), "Q_w0"), _f64(pri["R_b0"], (K, K), "R_w0")
             self._check(C.lib.pyvb_lds_set_wishart_priors(self._h, float(pri["Q_a0"]), C.dptr(qw0), float(pri["R_a0"]), C.dptr(rw0)))
             return
-        arrs += [bc(pri["Q_a0"], D), bc(pri["Q_b0"], D), bc(pri["R_a0"], K), bc(pri["R_b0"], K)]
-        self._check(C.lib.pyvb_lds_set_priors(self._h, *[C.dptr(a) for a in arrs]))
-        self._ard.clear()               # the columns have Constant parents again
-        self._entry.clear()
+        arrs += [C.broadcast(pri["Q_a0"], (D,)), C.broadcast(pri["Q_b0"], (D,)), C.broadcast(pri["R_a0"], (K,)), C.broadcast(pri["R_b0"], (K,))]
+        self._check(C.lib.pyvb_lds_set_priors(self._h, *[C.dptr(a) for a in arrs]))       # (the columns have Constant parents again)
 
     def set_observations(self, Y):
         """Y[N,T,K]; NaN = missing entry (the rows concerned become variational nodes: set_output_state, update_Y).
@@ -192,42 +187,58 @@ class LDSBatch(object):
         c = None if C_obs is None else _f64(C_obs, (self.K, self.D), "C_obs")
         self._check(C.lib.pyvb_lds_set_column_observations(self._h, C.dptr(a), C.dptr(c)))
 
+    # -- the precision parents of the columns: the handle knows which kind a matrix has (column_parents) ------------
+    def _parent_shape(self, nm, kind):
+        """of a0 and b0, and of one replicate's qb"""
+        return (self.D,) if kind == "gamma" else (self.D, self.D if nm == "A" else self.K)
+
+    def _parents_fn(self, verb, kind):
+        return getattr(C.lib, "pyvb_lds_%s_%s_precisions" % (verb, _PARENT_ENTRIES[kind]))
+
+    def _set_parents(self, kind, given):
+        for nm, t in zip("AC", given):
+            if t is not None:
+                shape = self._parent_shape(nm, kind)
+                arrs = [C.broadcast(v, s) for v, s in zip(t, (shape, shape, (self.N,) + shape))]        # a0, b0, qb
+                self._check(self._parents_fn("set", kind)(self._h, _WHICH[nm], *[C.dptr(a) for a in arrs]))
+
+    def _with_parents(self, kind):
+        return [nm for nm, k in sorted(self.column_parents().items()) if k == kind]       # A first
+
+    def _get_parents(self, kind):
+        out = {}
+        for nm in self._with_parents(kind):
+            qa, qb = (np.empty((self.N,) + self._parent_shape(nm, kind)) for _ in "ab")
+            self._check(self._parents_fn("get", kind)(self._h, _WHICH[nm], C.dptr(qa), C.dptr(qb)))
+            out[nm] = (qa, qb)
+        return out
+
+    def _update_parents(self, kind, which):
+        for w in (self._with_parents(kind) if which is None else [which]):
+            self._check(self._parents_fn("update", kind)(self._h, _WHICH.get(w, w)))
+
+    def column_parents(self):
+        """{"A": kind, "C": kind}, each "constant", "gamma" or "diagonal_gamma": the kind of precision parent the columns of the
+        matrix have (pyvb_lds_get_column_parents) -- the most recent setter's, "constant" after set_priors."""
+        kind = (C.ctypes.c_int * 2)()
+        self._check(C.lib.pyvb_lds_get_column_parents(self._h, kind))
+        return {"A": C.PARENTS[kind[0]], "C": C.PARENTS[kind[1]]}
+
     def set_column_precisions(self, A=None, C=None):
         """Gamma precision parents for the columns of A and / or C (automatic relevance determination): each a tuple
         (a0[D], b0[D], qb[N, D]) -- alpha_i ~ Gamma(a0_i, b0_i) is the prior precision of column i, qb its initial posterior
         rate (the reference draws rand()).  Scalars are broadcast.  Call after set_priors, which returns the columns to
         Constant parents.  DiagonalGamma / Gamma noise and max(D, K) <= 64 only."""
-        from . import _capi             # (the argument C shadows the module's alias here)
-        for which, t in ((0, A), (1, C)):
-            if t is None:
-                continue
-            a0, b0, qb = t
-            bc = lambda v, shape: np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=np.float64), shape))
-            a0, b0, qb = bc(a0, (self.D,)), bc(b0, (self.D,)), bc(qb, (self.N, self.D))
-            self._check(_capi.lib.pyvb_lds_set_column_precisions(self._h, which, _capi.dptr(a0), _capi.dptr(b0), _capi.dptr(qb)))
-            self._ard.add("AC"[which])
-            self._entry.discard("AC"[which])        # one kind of parent per matrix: the most recent setter wins
+        self._set_parents("gamma", (A, C))
 
     def column_precisions(self):
         """{"A": (qa[N, D], qb[N, D]), "C": ...} of the matrices that have Gamma parents; E[alpha] = qa / qb."""
-        out = {}
-        for nm in sorted(self._ard):
-            qa, qb = np.empty((self.N, self.D)), np.empty((self.N, self.D))
-            self._check(C.lib.pyvb_lds_get_column_precisions(self._h, "AC".index(nm), C.dptr(qa), C.dptr(qb)))
-            out[nm] = (qa, qb)
-        return out
+        return self._get_parents("gamma")
 
     def update_column_precisions(self, which=None):
         """[al.update() for al in alphas] of the columns of which = "A" (or 0), "C" (or 1); None: of every matrix that has
         Gamma parents, A first."""
-        if which is None:
-            for w in sorted(self._ard):
-                self.update_column_precisions(w)
-            return
-        self._check(C.lib.pyvb_lds_update_column_precisions(self._h, {"A": 0, "C": 1}.get(which, which)))
-
-    def _rows(self, nm):
-        return self.D if nm == "A" else self.K
+        self._update_parents("gamma", which)
 
     def set_entry_precisions(self, A=None, C=None):
         """DiagonalGamma precision parents for the columns of A and / or C, a precision of its own for every entry (sparse
@@ -236,36 +247,17 @@ class LDSBatch(object):
         (k, i), qb its initial posterior rate.  Scalars are broadcast.  Call after set_priors, which returns the columns to
         Constant parents; it replaces Gamma parents of the same matrix (set_column_precisions) and is replaced by them.
         DiagonalGamma / Gamma noise and max(D, K) <= 64 only."""
-        from . import _capi             # (the argument C shadows the module's alias here)
-        for which, t in ((0, A), (1, C)):
-            if t is None:
-                continue
-            a0, b0, qb = t
-            rows = self._rows("AC"[which])
-            bc = lambda v, shape: np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=np.float64), shape))
-            a0, b0, qb = bc(a0, (self.D, rows)), bc(b0, (self.D, rows)), bc(qb, (self.N, self.D, rows))
-            self._check(_capi.lib.pyvb_lds_set_entry_precisions(self._h, which, _capi.dptr(a0), _capi.dptr(b0), _capi.dptr(qb)))
-            self._entry.add("AC"[which])
-            self._ard.discard("AC"[which])
+        self._set_parents("diagonal_gamma", (A, C))
 
     def entry_precisions(self):
         """{"A": (qa[N, D, D], qb[N, D, D]), "C": (qa[N, D, K], qb[N, D, K])} of the matrices that have DiagonalGamma parents, in
         [column][row] order; E[alpha] = qa / qb."""
-        out = {}
-        for nm in sorted(self._entry):
-            qa, qb = np.empty((self.N, self.D, self._rows(nm))), np.empty((self.N, self.D, self._rows(nm)))
-            self._check(C.lib.pyvb_lds_get_entry_precisions(self._h, "AC".index(nm), C.dptr(qa), C.dptr(qb)))
-            out[nm] = (qa, qb)
-        return out
+        return self._get_parents("diagonal_gamma")
 
     def update_entry_precisions(self, which=None):
         """[dg.update() for dg in the DiagonalGamma parents] of the columns of which = "A" (or 0), "C" (or 1); None: of every
         matrix that has such parents, A first."""
-        if which is None:
-            for w in sorted(self._entry):
-                self.update_entry_precisions(w)
-            return
-        self._check(C.lib.pyvb_lds_update_entry_precisions(self._h, {"A": 0, "C": 1}.get(which, which)))
+        self._update_parents("diagonal_gamma", which)
 
     # -- outputs ----------------------------------------------------------------------------
     def get_state(self, what=("X", "A_mean", "A_colvar", "C_mean", "C_colvar", "Q_a", "Q_b", "R_a", "R_b")):

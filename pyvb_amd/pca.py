@@ -53,41 +53,60 @@ class PCABatch(object):
              _f64(pri["Mu_prior_mean"], (d,), "Mu_prior_mean"), _f64(pri["Mu_prior_prec"], (d,), "Mu_prior_prec")]
         C.check(C.lib.pyvb_pca_set_priors(self._h, *[C.dptr(x) for x in a], float(pri["beta_a0"]), float(pri["beta_b0"])))
 
+    # -- the precision parents of the columns of W: the handle knows which kind they have (column_parents) ---------
+    def _parents(self, verb, kind):
+        """the C entry `verb` for that kind of parent, and the shape of its arrays"""
+        word, shape = {"gamma": ("column", (self.q,)), "diagonal_gamma": ("entry", (self.q, self.d))}[kind]
+        return getattr(C.lib, "pyvb_pca_%s_%s_precisions" % (verb, word)), shape
+
+    def _set_parents(self, kind, a0, b0, qb):
+        fn, shape = self._parents("set", kind)
+        arrs = [np.asarray(v, dtype=np.float64) for v in (a0, b0, qb)]
+        # (a value per column where every entry has its own: the same one down the column)
+        arrs = [C.broadcast(v[:, None] if v.ndim == 1 and len(shape) == 2 else v, shape) for v in arrs]
+        C.check(fn(self._h, *[C.dptr(x) for x in arrs]))
+
+    def _get_parents(self, kind):
+        fn, shape = self._parents("get", kind)
+        qa, qb = np.empty(shape), np.empty(shape)
+        C.check(fn(self._h, C.dptr(qa), C.dptr(qb)))
+        return qa, qb
+
+    def column_parents(self):
+        """"constant", "gamma" or "diagonal_gamma": the kind of precision parent the columns of W have
+        (pyvb_pca_get_column_parents) -- the most recent setter's, "constant" after set_priors."""
+        kind = C.ctypes.c_int()
+        C.check(C.lib.pyvb_pca_get_column_parents(self._h, C.ctypes.byref(kind)))
+        return C.PARENTS[kind.value]
+
     def set_column_precisions(self, a0, b0, qb):
         """Gamma precision parents for the columns of W (automatic relevance determination): column i gets
         Gamma(d, a0[i], b0[i]) with the initial rate qb[i] in place of its Constant precision; scalars are broadcast to [q].
         Call after set_priors (which, called again, takes the parents away).  iterate() then updates them in every pass."""
-        a = [np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=np.float64), (self.q,))) for v in (a0, b0, qb)]
-        C.check(C.lib.pyvb_pca_set_column_precisions(self._h, *[C.dptr(x) for x in a]))
+        self._set_parents("gamma", a0, b0, qb)
 
     def column_precisions(self):
         """(qa, qb), [q] each: <alpha_i> = qa[i] / qb[i]."""
-        qa, qb = np.empty(self.q), np.empty(self.q)
-        C.check(C.lib.pyvb_pca_get_column_precisions(self._h, C.dptr(qa), C.dptr(qb)))
-        return qa, qb
+        return self._get_parents("gamma")
 
     def update_column_precisions(self):
         """[al.update() for al in alphas], for stage-wise use (the crawl order has it after update_Z)."""
-        C.check(C.lib.pyvb_pca_update_column_precisions(self._h))
+        C.check(self._parents("update", "gamma")[0](self._h))
 
     def set_entry_precisions(self, a0, b0, qb):
         """DiagonalGamma precision parents for the columns of W (sparse loadings): entry k of column i gets Gamma(a0[i][k], b0[i][k])
         with the initial rate qb[i][k] in place of its Constant precision; [q, d] each, scalars and [q] columns are broadcast.
         Call after set_priors (which, called again, takes the parents away); it replaces set_column_precisions and the other way
         round.  iterate() then updates the parents in every pass."""
-        a = [np.ascontiguousarray(np.broadcast_to(v if v.ndim != 1 else v[:, None], (self.q, self.d)))
-             for v in (np.asarray(x, dtype=np.float64) for x in (a0, b0, qb))]
-        C.check(C.lib.pyvb_pca_set_entry_precisions(self._h, *[C.dptr(x) for x in a]))
+        self._set_parents("diagonal_gamma", a0, b0, qb)
 
     def entry_precisions(self):
         """(qa, qb), [q, d] each: the prior precision of W[k][i] is qa[i][k] / qb[i][k]."""
-        qa, qb = np.empty((self.q, self.d)), np.empty((self.q, self.d))
-        C.check(C.lib.pyvb_pca_get_entry_precisions(self._h, C.dptr(qa), C.dptr(qb)))
-        return qa, qb
+        return self._get_parents("diagonal_gamma")
 
     def update_entry_precisions(self):
         """[dg.update() for dg in parents], for stage-wise use (the crawl order has it after update_Z)."""
-        C.check(C.lib.pyvb_pca_update_entry_precisions(self._h))
+        C.check(self._parents("update", "diagonal_gamma")[0](self._h))
 
     def set_data(self, X):
         """X [N, d] with NaN where an entry is missing (Gaussian.observe, gaussian.py:74-100)."""
