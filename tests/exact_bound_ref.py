@@ -77,12 +77,14 @@ def _y_entropy_exact(st):
     # a latent row's ln det qcov: of inv <R> once it has been updated (NaN before, as its q_ln_det)
     lq = np.where(np.isnan(st["Yqld"]), np.nan, 0.0)
     if latent.any():
-        # the latent rows carry qcov = inv <R> (Yvar its diagonal under diagonal noise); Wishart: -ln det <R>
         if "Yld" in st:
-            K_ = st["C_mean"].shape[1]
-            lrow = -XL.slogdet(O.noise_expect("wishart", st["R_a"], st["R_b"], K_))[1]
-            lq = lq + lrow[:, None]
+            # Wishart: the row carries qcov = inv <R> of the <R> its own update met, which a later update of R does not change.
+            # The state keeps that as the row's q_ln_det = 1 / ln det <R> (O._chol_qld, quirk Q1): ln det qcov = -1 / q_ln_det.
+            # (Taken of the current <R> this was right only for a bound formed straight after update_Y.)
+            with np.errstate(divide="ignore", invalid="ignore"):
+                lq = lq - 1.0 / st["Yqld"]
         else:
+            # diagonal noise: Yvar is the diagonal of qcov
             with np.errstate(divide="ignore", invalid="ignore"):
                 lq = lq + np.log(st["Yvar"]).sum(axis=2)
     tp = np.where(partial, 0.5 * nm * LN2PI + 0.5 * lv + 0.5 * nm, 0.0)

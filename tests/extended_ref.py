@@ -19,6 +19,10 @@ after each iteration under the key (iteration, "bound", mode).  A part is measur
 s_r = sum_p |part_p| of the extended run (the parity suite's convention for the parts):
     e64 = |p64 - pext| / s_r,   e_gpu = |pgpu - pext| / s_r <= FACTOR max(e64, n 2^-52),   e64 <= CAP
 part by part and replicate by replicate (bound_errors, compare_bound).
+
+Outputs with missing entries are also measured row by row (compare_rows): a row's missing entries in units of the row's largest
+one, e_row <= FACTOR max(e64_row, n 2^-52) with e64_row <= CAP, its known entries bitwise -- on cases whose rows are named
+patterns (_missing_rows), in the envelope's order and in orders of their own (lds_trace_order, rows_reference).
 """
 import functools
 import importlib.util
@@ -181,6 +185,62 @@ def _lengths(lengths, D, K, seed):
     return c
 
 
+ROW_PATTERNS = ("all", "one known, first", "one known, last", "one missing, first", "one missing, last", "a tile", "alternating",
+                "upper half", "observed", "Bernoulli", "all")
+ROW_PATTERNS_BIG = {5: "low half", 6: "high half", 7: "the seam"}      # K > 64: instead of the tile, alternating and upper half
+
+
+def _missing_rows(T, K, rng):
+    """(mask [T, K], true = missing; the name of each row's pattern).  Row t takes pattern t mod 11 of ROW_PATTERNS -- for K > 64
+    the three of ROW_PATTERNS_BIG, which meet the kernels' second entry per lane (lane + 64), in place of indices 5..7 -- and the
+    last row is then "all": rows 0 and T - 1 are unobserved nodes at the ends of the chain.  These are the pivot sets a
+    Bernoulli mask meets only by luck: one known entry in a row, one missing entry in lane 0 or lane K - 1, exactly one
+    8-wide tile, every second entry."""
+    k = np.arange(K)
+    mask, names = np.zeros((T, K), dtype=bool), []
+    for t in range(T):
+        p = 10 if t == T - 1 else t % 11
+        name = ROW_PATTERNS_BIG.get(p, ROW_PATTERNS[p]) if K > 64 else ROW_PATTERNS[p]
+        mask[t] = {"all": lambda: k >= 0, "one known, first": lambda: k != 0, "one known, last": lambda: k != K - 1,
+                   "one missing, first": lambda: k == 0, "one missing, last": lambda: k == K - 1,
+                   "a tile": lambda: k < min(8, K - 1), "alternating": lambda: k % 2 == 0, "upper half": lambda: k >= K // 2,
+                   "observed": lambda: k < 0, "Bernoulli": lambda: rng.random(K) < 0.3,
+                   "low half": lambda: k < 64, "high half": lambda: k >= 64, "the seam": lambda: (k == 63) | (k == 64)}[name]()
+        names.append(name)
+    return mask, names
+
+
+def _rows(c, **kw):
+    """The named row patterns on the outputs of a case: replicate 0 takes _missing_rows; a second replicate has exactly one
+    missing entry (row 2, entry 1), so a replicate with almost nothing to do sits beside a full one.  Yq and Yrowvar as
+    _missing draws them.  c["patterns"][n][t] names the pattern of row t of replicate n."""
+    N, T, K = c["Y"].shape
+    assert N in (1, 2)
+    rng = np.random.default_rng(T + K)
+    mask = np.zeros((N, T, K), dtype=bool)
+    mask[0], names = _missing_rows(T, K, rng)
+    c["patterns"] = [names]
+    if N == 2:
+        mask[1, 2, 1] = True
+        c["patterns"].append(["one missing, alone" if t == 2 else "observed" for t in range(T)])
+    c["Y"] = np.where(mask, np.nan, c["Y"])
+    c["st0"]["Yq"] = rng.standard_normal((N, T, K)); c["st0"]["Yrowvar"] = 1.0 / rng.uniform(0.5, 1.5, size=(N, T))
+    c.update(kw)
+    return c
+
+
+def _default_outputs(c, explicit):
+    """A case of _rows with the initial outputs a handle gives itself when it is told none -- N(0, I) on every row that holds
+    NaN -- either spelled out (explicit) or left out of the state."""
+    if explicit:
+        c["st0"]["Yq"] = np.where(np.isnan(c["Y"]).any(axis=2, keepdims=True), 0.0, np.nan_to_num(c["Y"]))
+        c["st0"]["Yrowvar"] = np.ones(c["Y"].shape[:2])
+    else:
+        del c["st0"]["Yq"], c["st0"]["Yrowvar"]
+    c["iters"] = 1
+    return c
+
+
 # name -> (builder, in the warm-up contract?)
 LDS_CASES = {
     "t19_d6_k4":            (lambda: _plain(19, 6, 4, 2, 101), False),
@@ -202,7 +262,35 @@ LDS_CASES = {
     # length 2 is the shortest chain a handle accepts: no interior class, nint = 0 in the bound (no recurrence matrices either,
     # so the case is not in the warm-up contract)
     "lengths_2_17_33_d16_k16": (lambda: _lengths((2, 17, 33), 16, 16, 117), False),
+    # outputs with missing entries in named row patterns (_missing_rows), two iterations with update_Y in both.  Wishart noise:
+    # k_impute_dense, whose every row exchanges on a pivot set of its own -- two replicates, one of them with a single missing
+    # entry; K = 64, where no lane is idle and a row has 63 pivots (with this seed the float64 oracle stays at 5e-13 row by row
+    # after the second update_Y too; a draw whose cov - gain cov^T cancellation puts the one-known rows over the cap is to be
+    # replaced, tests/test_missing_rows_cpu.py decides); T = 3, where one of the kernel's four wavefronts owns no row; the
+    # shortest chain; known columns of C beside dense <y y^T>.  Then the 128-wide class, whose lanes take entries lane and
+    # lane + 64 (K <= 102: the float64 bound is finite, quirk Q2).  Seven
+    # outputs of 72 states leave the Gamma case's second iteration close to the cap on the reference side (e64 5.6e-12 with
+    # this seed, 2.2e-12 row-wise; of seeds 124, 127..130 the others are at 8e-12..2e-11 and over it row-wise).
+    "t11_d5_k9_wishart_rows":   (lambda: _rows(_wishart(11, 5, 9, 2, 118)), False),
+    "t11_d6_k64_wishart_rows":  (lambda: _rows(_wishart(11, 6, 64, 1, 119)), False),
+    "t3_d17_k33_wishart_rows":  (lambda: _rows(_wishart(3, 17, 33, 1, 120)), False),
+    "t2_d3_k2_wishart_rows":    (lambda: _rows(_wishart(2, 3, 2, 1, 121)), False),
+    "t11_d17_k9_wishart_known_rows": (lambda: _rows(_wishart(11, 17, 9, 1, 122, known=True)), False),
+    "t11_d12_k100_rows_big":    (lambda: _rows(_plain(11, 12, 100, 1, 123)), False),
+    "t7_d72_k70_gamma_rows_big": (lambda: _rows(_gamma(7, 72, 70, 1, 128)), False),
 }
+# Cases of tests/test_missing_rows_gpu.py alone.  K = 128 is compared on the outputs only: with the default prior precision the
+# float64 oracle's bound is inf there (quirk Q2), so the case forms no bound and is not in the envelope.
+ROW_CASES = {
+    "t7_d65_k128_rows_big":     lambda: _rows(_plain(7, 65, 128, 1, 125), outputs_only=True),
+    # (seven rows stop at "low half": the high half and the seam with no lane idle in either half need eleven)
+    "t11_d9_k128_rows_big":     lambda: _rows(_plain(11, 9, 128, 1, 126), outputs_only=True),
+    "t11_d5_k9_wishart_rows_default":   lambda: _default_outputs(lds_case("t11_d5_k9_wishart_rows"), False),
+    "t11_d5_k9_wishart_rows_explicit":  lambda: _default_outputs(lds_case("t11_d5_k9_wishart_rows"), True),
+    "t11_d12_k100_rows_big_default":    lambda: _default_outputs(lds_case("t11_d12_k100_rows_big"), False),
+    "t11_d12_k100_rows_big_explicit":   lambda: _default_outputs(lds_case("t11_d12_k100_rows_big"), True),
+}
+ROWS_ENVELOPE = [k for k in LDS_CASES if "_rows" in k]
 WARMUP_CASES = [k for k, v in LDS_CASES.items() if v[1]]
 # The exact bound needs a handle of its own (the mode is set before the first update); these two reach no
 # other instantiation of the bound than t40_d64_k64 and t12_d72_k66_big do, so their long runs are not repeated.
@@ -210,7 +298,7 @@ EXACT_BOUND_CASES = [k for k in LDS_CASES if k not in ("t2402_d64_k64_w1", "t600
 
 
 def lds_case(name):
-    return LDS_CASES[name][0]()
+    return ROW_CASES[name]() if name in ROW_CASES else LDS_CASES[name][0]()
 
 
 class OracleLDS(object):
@@ -432,6 +520,156 @@ def compare_bound_with_reference(name, handle_trace):
             got = arr if rows is None else arr[rows:rows + 1]       # (a non-finite part gives a NaN ratio, which no bound admits)
             out += [(key, row[0] if rows is None else rows) + row[1:] for row in compare_bound(got, ext, e64, n)]
     return out
+
+
+# ----------------------------------------------------------------------------------------------------------------------------
+# outputs with missing entries, row by row
+# ----------------------------------------------------------------------------------------------------------------------------
+# rel() is max-abs over the whole array: a known entry that is no longer pinned (variance 1e-13 for 0.0) disappears under the
+# variance of a fully missing row, and so does the one missing entry of an otherwise observed row being off by 1e-10 of itself.
+# Here every row is measured in units of its own largest missing entry, and its known entries are held to the observation
+# bitwise (the oracle pins them the same way, O.update_Y: "exact pins").
+def lds_trace_order(m, updates, bounds=()):
+    """lds_trace with update_Y only in the iterations whose entry of `updates` is true (iterate() does not update the outputs,
+    as the reference's example loop does not), and the outputs read in the others too, under the stage "outputs kept".  With
+    every entry true the keys and the calls are those of lds_trace(m, len(updates), True, bounds)."""
+    wishart = m.noise == "wishart"
+    for it, upd in enumerate(updates):
+        m.sweep("forward")
+        yield (it, "forward sweep", "X"), np.array(m.read("X"))
+        m.sweep("backward")
+        yield (it, "backward sweep", "X"), np.array(m.read("X"))
+        yield (it, "backward sweep", "Sigma"), np.array(m.read("Sigma"))
+        if upd:
+            m.update_Y()
+        yield (it, "update_Y" if upd else "outputs kept", "Yq"), np.array(m.read("Yq"))
+        yield (it, "update_Y" if upd else "outputs kept", "Yvar"), np.array(m.read("Yvar"))
+        m.update_A()
+        yield (it, "update_A", "A_mean"), np.array(m.read("A_mean"))
+        m.update_C()
+        yield (it, "update_C", "C_mean"), np.array(m.read("C_mean"))
+        m.update_Q()
+        m.update_R()
+        names = ["A_colvar", "C_colvar"] + (["Q_v", "Q_w", "R_v", "R_w", "A_cov", "C_cov"] if wishart else ["Q_b", "R_b"])
+        for nm in names:
+            yield (it, "update_R", nm), np.array(m.read(nm))
+        for mode in bounds:
+            yield (it, "bound", mode), np.array(m.elbo_parts(mode))
+
+
+def row_errors(got, ext, miss):
+    """[N, T]: per row, max over its missing entries of |got - ext| in units of the row's largest missing-entry magnitude in
+    ext; NaN for a row without missing entries."""
+    got, ext = np.asarray(got, dtype=LD), np.asarray(ext, dtype=LD)
+    out = np.full(miss.shape[:2], np.nan)
+    for n, t in zip(*np.nonzero(miss.any(axis=2))):
+        u = miss[n, t]
+        out[n, t] = float(np.abs(got[n, t, u] - ext[n, t, u]).max() / max(np.abs(ext[n, t, u]).max(), LD(1e-300)))
+    return out
+
+
+def is_rows_key(key):
+    return key[1] == "update_Y" and key[2] in ("Yq", "Yvar")
+
+
+def row_iterations(updates):
+    """the iterations after whose update_Y the rows are compared: all that have one"""
+    return tuple(it for it, upd in enumerate(updates) if upd)
+
+
+def lds_float64_rows(name, make=None, updates=None):
+    """[(key, array)] of a fresh run of the float64 oracle through lds_trace_order, without the bounds.  make(Y, st0, pri): the
+    oracle to drive -- tests/test_missing_rows_cpu.py runs OracleLDS with a defect planted in update_Y."""
+    c = lds_case(name)
+    m = (make or OracleLDS)(c["Y"].copy(), {k: v.copy() for k, v in c["st0"].items()}, c["pri"])
+    return list(lds_trace_order(m, updates or (True,) * c["iters"]))
+
+
+@functools.lru_cache(maxsize=None)
+def rows_reference(name, updates=None):
+    """A case with missing outputs run by both oracles through lds_trace_order: a dict with n = max(D, K, T); updates; miss
+    [N, T, K]; ext {key: long-double array} and e64 {key: the float64 oracle's distance from it} as lds_reference has them; rows
+    {key: [N, T] of row_errors of the float64 oracle} for the outputs after each update_Y; bound {key: (ext [N, 6], e64, own)} as
+    lds_bound_reference (empty for a case compared on its outputs only).  Computed once per process, never modified."""
+    require_extended()
+    c = lds_case(name)
+    updates = tuple(updates or (True,) * c["iters"])
+    Y, T = c["Y"], c["Y"].shape[1]
+    D, K = c["st0"]["A_mean"].shape[1], Y.shape[2]
+    miss = np.isnan(Y)
+    modes = () if c.get("outputs_only") else BOUND_MODES
+    m64 = OracleLDS(Y.copy(), {k: v.copy() for k, v in c["st0"].items()}, c["pri"])
+    mx = OracleLDS(to_long(Y), to_long(c["st0"]), to_long(c["pri"]))
+    ext, e64, rows, bnd = {}, {}, {}, {}
+    with np.errstate(all="ignore"):         # (the bound before the first update_Y is NaN in both oracles)
+        for (k64, a64), (kx, ax) in zip(lds_trace_order(m64, updates, modes), lds_trace_order(mx, updates, modes)):
+            assert k64 == kx and ax.dtype == LD, (k64, kx, ax.dtype)
+            if is_bound(kx):
+                ax.setflags(write=False)
+                bnd[kx] = (ax,) + bound_errors(a64, ax)
+                continue
+            ext[kx] = _cut(kx, ax, None, T)
+            e64[kx] = rel(_cut(k64, a64, None, T), ext[kx])
+            ext[kx].setflags(write=False)
+            if is_rows_key(kx):
+                rows[kx] = row_errors(a64, ax, miss)
+    return dict(n=max(D, K, T), updates=updates, miss=miss, ext=ext, e64=e64, rows=rows, bound=bnd)
+
+
+def compare_rows(name, trace, updates=None, tag=None):
+    """The outputs of a trace (a handle's, or an oracle's) after each update_Y against rows_reference(name, updates), row by row.
+    Returns [(key, replicate, row, pattern, e64_row, e_row, e_row / yardstick(e64_row, n), pinned)]: the distances are
+    row_errors', over the row's missing entries (0 for a row that has none); pinned: the row's known entries -- of an observed
+    row all of them -- are bitwise the observation in Yq, exactly 0.0 in Yvar.  A row is in order when its ratio is at most
+    FACTOR and it is pinned (offending_rows).  Prints every row it measured."""
+    c = lds_case(name)
+    ref = rows_reference(name, None if updates is None else tuple(updates))
+    Y, miss, n = c["Y"], ref["miss"], ref["n"]
+    out = []
+    for key, arr in trace:
+        if not is_rows_key(key) or key[0] not in row_iterations(ref["updates"]):
+            continue
+        e_got = row_errors(arr, ref["ext"][key], miss)
+        for r in range(Y.shape[0]):
+            for t in range(Y.shape[1]):
+                known = ~miss[r, t]
+                if key[2] == "Yq":
+                    pinned = np.array_equal(np.ascontiguousarray(arr[r, t, known], dtype=np.float64).view(np.int64), Y[r, t, known].view(np.int64))
+                else:
+                    pinned = bool(np.all(arr[r, t, known] == 0.0))
+                e64r, e = (0.0, 0.0) if known.all() else (float(ref["rows"][key][r, t]), float(e_got[r, t]))
+                ratio = e / yardstick(e64r, n)
+                out.append((key, r, t, c["patterns"][r][t], e64r, e, ratio, pinned))
+                print("%-32s r%d it%d %-4s row %2d %-19s e64 %.2e  e_row %.2e  e_row/y %6.2f%s%s"
+                      % (tag or name, r, key[0], key[2], t, c["patterns"][r][t], e64r, e, ratio, "" if pinned else "  <-- known entries not pinned",
+                         "" if ratio <= FACTOR else "  <-- over"))
+    if out:
+        print("%-32s SUMMARY rows  max e64 %.2e  max e_row %.2e  max e_row/y %.2f" % (tag or name, max(r[4] for r in out), max(r[5] for r in out), max(r[6] for r in out)))
+    return out
+
+
+def offending_rows(rows):
+    return [r for r in rows if not (r[6] <= FACTOR and r[7])]
+
+
+def compare_with_rows_reference(name, trace, updates=None, skip_bound=()):
+    """compare_with_reference and compare_bound_with_reference against rows_reference(name, updates), for the orders lds_reference
+    does not run: ([(None, key, e64, e_gpu, ratio)], [(key, replicate, part index, e64, e_gpu, ratio, own)]).  skip_bound: the
+    iterations whose bound is not compared."""
+    ref = rows_reference(name, None if updates is None else tuple(updates))
+    T = lds_case(name)["Y"].shape[1]
+    out, bnd = [], []
+    for key, arr in trace:
+        if is_bound(key):
+            if key[0] not in skip_bound:
+                ext, e64, _ = ref["bound"][key]
+                bnd += [(key,) + row for row in compare_bound(arr, ext, e64, ref["n"])]
+            continue
+        got = _cut(key, arr, None, T)
+        assert np.all(np.isfinite(got)), "%s: non-finite values in %r" % (name, key)
+        e_gpu = rel(got, ref["ext"][key])
+        out.append((None, key, ref["e64"][key], e_gpu, e_gpu / yardstick(ref["e64"][key], ref["n"])))
+    return out, bnd
 
 
 # ----------------------------------------------------------------------------------------------------------------------------
