@@ -28,6 +28,7 @@
  *   Q_a,Q_b[N][D]   R_a,R_b[N][K]      (PYVB_NOISE_GAMMA: all entries of a row are equal)
  *   Sigma[N][3][D][D], qld_x[N][3]     posterior covariance / q_ln_det of X_0, X_interior, X_{T-1}
  *   elbo parts [N][6] = L_X, L_Y, L_A, L_C, L_Q, L_R
+ *   handles with P inputs (pyvb_lds_create_inputs): U[N][T][P], B_mean[N][D][P] (row, col), B_colvar[N][P][D] (column i, entry k)
  */
 #ifndef PYVB_HIP_H
 #define PYVB_HIP_H
@@ -73,7 +74,8 @@ enum { PYVB_FORWARD = 0, PYVB_BACKWARD = 1 };
 
 /* which kernels pyvb_lds_timing_get() reports on */
 enum { PYVB_K_PREP = 0, PYVB_K_SWEEP_FWD = 1, PYVB_K_STATS = 2, PYVB_K_PARAMS = 3, PYVB_K_STEP = 4,
-       PYVB_K_SWEEP_BWD = 5, PYVB_K_ELBO = 6, PYVB_K_GY = 7 /* 128-wide class: G y_t ahead of a sweep */, PYVB_K_COUNT = 8 };
+       PYVB_K_SWEEP_BWD = 5, PYVB_K_ELBO = 6, PYVB_K_GY = 7 /* 128-wide class: G y_t ahead of a sweep */,
+       PYVB_K_INPUTS = 8 /* handles with inputs: the kernels of k_inputs.hip */, PYVB_K_COUNT = 9 };
 
 const char* pyvb_last_error(void);
 int pyvb_version(void);
@@ -135,6 +137,43 @@ int pyvb_lds_get_lengths(pyvb_lds* h, int* lengths);
 int pyvb_lds_create_tied(pyvb_lds** out, int device, int N, int T, int D, int K, int noise_kind,
                          const int* lengths, const int* model);
 int pyvb_lds_get_models(pyvb_lds* h, int* model);
+
+/* A known input that drives the states: replicate n is the graph of Linear_Dynamic_System.py:46-66 with
+ *     X_t = Gaussian(q, A * X_{t-1} + B * Constant(u_t), Q),   B = hstack(Bs),   t = 1 .. T_n - 1
+ * -- an Addition of two Multiplications as the mean parent (node.py:52-129, :182-276), u_t a known P-vector (a controlled plant, a
+ * stimulus, a seasonal regressor), B [D x P] with independent Gaussian columns and Constant parents like A's
+ * (hstack.pass_up_m1_m2, nodes_todo.py:43-62).  lengths[N] as pyvb_lds_create_lengths takes it, or NULL: every chain has T nodes.
+ *   pyvb_lds_set_inputs        U[N][T][P]: row t drives x_t.  Row 0 and the rows t >= T_n are never read and may hold anything
+ *                              finite.  Call before the first update; a later call replaces the inputs.
+ *   pyvb_lds_get_inputs        U as given.
+ *   pyvb_lds_set_input_priors  B_prior_mean[D][P] (row, col), B_prior_prec[P][D] (column i, diagonal entry k), positive; shared by
+ *                              the replicates as A's are.
+ *   pyvb_lds_set_input_state   B_mean[N][D][P] (row, col), B_colvar[N][P][D] (column i, entry k); NULL = leave.
+ *   pyvb_lds_get_input_state   the same, and q_ln_det / ln det qcov of the columns, qld_B[N][P], lnd_B[N][P] (NaN before a column's
+ *                              first update); NULL = skip.
+ *   pyvb_lds_update_B          [b.update() for b in Bs]: G = sum_{t>=1} u_t u_t^T, H = sum_{t>=1} mu_t u_t^T - <A> sum_t mu_t u_{t+1}^T,
+ *                              row precisions <Q>.
+ * Everything else serves the handle as it stands, with the input's terms: pyvb_lds_sweep and pyvb_lds_update_x (mean parent
+ * <A> mu_{t-1} + <B> u_t; the message of X_{t+1} is <A>^T <Q> (mu_{t+1} - <B> u_{t+1})), pyvb_lds_update_A / _columns(0, ..)
+ * (H = Sx1x - <B> sum_t u_{t+1} mu_t^T), pyvb_lds_update_Q (the second moment of the mean parent, Addition.pass_down_ExxT
+ * node.py:121-129), pyvb_lds_elbo in both modes (L_X with that moment; the columns of B add to part 2 what the columns of A do, so
+ * parts stay [N][6]), pyvb_lds_iterate, pyvb_lds_iterate_until and pyvb_lds_iterate_until_model (forward, backward, As, Bs, Cs, Q, R,
+ * bound), chain lengths, every time split, the activity mask (a switched-off replicate keeps its B), status, communicators.
+ * The inputs ride through the sweeps as 2 P extra output channels (k_inputs.hip), hence the limit of this route:
+ * max(D, K + 2 P) <= 64.
+ * PYVB_E_UNSUPPORTED before any HIP call / launch, the message naming the cause: Wishart noise; max(D, K + 2 P) > 64; outputs that hold
+ * NaN (pyvb_lds_set_observations); known entries of A / C (pyvb_lds_set_column_observations); Gamma / DiagonalGamma precision parents
+ * (pyvb_lds_set_column_precisions, pyvb_lds_set_entry_precisions); shared models are not offered (pyvb_lds_create_tied takes no
+ * inputs, and pyvb_lds_create_inputs no models).
+ * PYVB_E_ARG: P < 1; NULL or non-finite U (the message names replicate, row and channel); a non-positive B_prior_prec; any of the six
+ * entries on a handle created without inputs; an update before pyvb_lds_set_inputs and pyvb_lds_set_input_priors. */
+int pyvb_lds_create_inputs(pyvb_lds** out, int device, int N, int T, int D, int K, int P, int noise_kind, const int* lengths);
+int pyvb_lds_set_inputs(pyvb_lds* h, const double* U);
+int pyvb_lds_get_inputs(pyvb_lds* h, double* U);
+int pyvb_lds_set_input_priors(pyvb_lds* h, const double* B_prior_mean, const double* B_prior_prec);
+int pyvb_lds_set_input_state(pyvb_lds* h, const double* B_mean, const double* B_colvar);
+int pyvb_lds_get_input_state(pyvb_lds* h, double* B_mean, double* B_colvar, double* qld_B, double* lnd_B);
+int pyvb_lds_update_B(pyvb_lds* h);
 
 /* Constant parents (node.py:279-311), shared by all replicates:
  *   x0_mean[D], x0_prec[D][D]                     Gaussian(q, pmu, pprec) for X_0  (:58)

@@ -22,7 +22,7 @@ PARENTS = ("constant", "gamma", "diagonal_gamma")
 PCA_SWEEP_STORE, PCA_SWEEP_COLUMNS, PCA_SWEEP_PAIRS = 0, 1, 2
 PCA_SWEEPS = {"store": PCA_SWEEP_STORE, "columns": PCA_SWEEP_COLUMNS, "pairs": PCA_SWEEP_PAIRS}
 FAIL_STATES, FAIL_COLUMNS, FAIL_NOISE = 1, 2, 4      # PYVB_FAIL_*: bits of pyvb_lds_get_status
-K_PREP, K_SWEEP_FWD, K_STATS, K_PARAMS, K_STEP, K_SWEEP_BWD, K_ELBO, K_GY = range(8)
+K_PREP, K_SWEEP_FWD, K_STATS, K_PARAMS, K_STEP, K_SWEEP_BWD, K_ELBO, K_GY, K_INPUTS = range(9)
 
 _dp = ctypes.POINTER(ctypes.c_double)
 _ip = ctypes.POINTER(ctypes.c_int)
@@ -42,6 +42,13 @@ SIGNATURES = {
     "pyvb_lds_get_lengths": (ctypes.c_int, [_h, _ip]),
     "pyvb_lds_create_tied": (ctypes.c_int, [ctypes.POINTER(_h)] + [ctypes.c_int] * 6 + [_ip, _ip]),
     "pyvb_lds_get_models": (ctypes.c_int, [_h, _ip]),
+    "pyvb_lds_create_inputs": (ctypes.c_int, [ctypes.POINTER(_h)] + [ctypes.c_int] * 7 + [_ip]),
+    "pyvb_lds_set_inputs": (ctypes.c_int, [_h, _dp]),
+    "pyvb_lds_get_inputs": (ctypes.c_int, [_h, _dp]),
+    "pyvb_lds_set_input_priors": (ctypes.c_int, [_h, _dp, _dp]),
+    "pyvb_lds_set_input_state": (ctypes.c_int, [_h, _dp, _dp]),
+    "pyvb_lds_get_input_state": (ctypes.c_int, [_h, _dp, _dp, _dp, _dp]),
+    "pyvb_lds_update_B": (ctypes.c_int, [_h]),
     "pyvb_lds_destroy": (ctypes.c_int, [_h]),
     "pyvb_lds_set_priors": (ctypes.c_int, [_h] + [_dp] * 10),
     "pyvb_lds_set_wishart_priors": (ctypes.c_int, [_h, ctypes.c_double, _dp, ctypes.c_double, _dp]),

@@ -51,7 +51,7 @@ void pyvb_timing_resolve(pyvb_lds* h) {
 extern "C" {
 
 const char* pyvb_last_error(void) { return g_err; }
-int pyvb_version(void) { return 109; }
+int pyvb_version(void) { return 110; }
 
 int pyvb_device_count(int* count) {
     ARGCHK(count, "count is NULL");
@@ -61,7 +61,8 @@ int pyvb_device_count(int* count) {
 
 // The one creation path; lengths null: every chain has T nodes, model null: every replicate is a model.  Arguments are checked
 // and, where a combination is not served, refused before the first HIP call; *out is written once, when everything exists.
-static int lds_create(pyvb_lds** out, int device, int N, int T, int D, int K, int noise_kind, const int* lengths, const int* model) {
+// P: known inputs that drive the states (pyvb_lds_create_inputs), 0: none.
+static int lds_create(pyvb_lds** out, int device, int N, int T, int D, int K, int noise_kind, const int* lengths, const int* model, int P = 0) {
     ARGCHK(out, "out is NULL");
     ARGCHK(N >= 1, "N must be >= 1");
     bool ragged = false, tied = false;
@@ -79,6 +80,15 @@ static int lds_create(pyvb_lds** out, int device, int N, int T, int D, int K, in
     ARGCHK(D >= 1 && D <= 128, "latent dimension D must be in 1..128");
     ARGCHK(K >= 1 && K <= 128, "observed dimension K must be in 1..128");
     ARGCHK(noise_kind == PYVB_NOISE_DIAGONAL_GAMMA || noise_kind == PYVB_NOISE_GAMMA || noise_kind == PYVB_NOISE_WISHART, "unknown noise kind");
+    if (P && noise_kind == PYVB_NOISE_WISHART) {
+        pyvb_set_error("inputs that drive the states are served with DiagonalGamma and Gamma noise only, not with Wishart noise (k_wishart.hip)");
+        return PYVB_E_UNSUPPORTED;
+    }
+    if (P && (D > 64 || K + 2 * P > 64)) {
+        pyvb_set_error("inputs that drive the states ride as 2 P extra output channels and are served for max(D, K + 2 P) <= 64 only, "
+                       "not in the 128-wide class (k_big.hip): D = %d, K = %d, P = %d", D, K, P);
+        return PYVB_E_UNSUPPORTED;
+    }
     if (lengths && (rc = Replicates::check_lengths(N, T, lengths, &ragged))) return rc;
     if (ragged && noise_kind == PYVB_NOISE_WISHART) {
         pyvb_set_error("chains of unequal length are served with DiagonalGamma and Gamma noise only, not with Wishart noise (k_wishart.hip)");
@@ -93,8 +103,9 @@ static int lds_create(pyvb_lds** out, int device, int N, int T, int D, int K, in
     ARGCHK(device >= 0 && device < ndev, "no such device");
     HIPCHK(hipSetDevice(device));
     pyvb_lds* h = new pyvb_lds();       // value-initialised: every pointer null, every flag false
-    h->device = device; h->N = N; h->T = T; h->D = D; h->K = K; h->noise = noise_kind;
-    const LdsGeometry g = lds_geometry(N, T, D, K, noise_kind);     // geometry.h: the shape class, the chunks, the time split, the extents
+    h->device = device; h->N = N; h->T = T; h->D = D; h->K = K; h->noise = noise_kind; h->P = P;
+    // (with inputs the gains, the statistics and the kernels that form them are those of K + 2 P outputs: k_inputs.hip)
+    const LdsGeometry g = lds_geometry(N, T, D, K + 2 * P, noise_kind);     // geometry.h: the shape class, the chunks, the time split, the extents
     h->L = g.L; h->big = g.big; h->dense = g.dense;
     h->nchunk = g.nchunk; h->chunk_len = g.chunk_len; h->W = g.W;
     // (lengths that all equal T, models of one replicate each: a plain handle, len / mstart / first stay null)
@@ -183,6 +194,13 @@ static int lds_create(pyvb_lds** out, int device, int N, int T, int D, int K, in
         TRY(dev_alloc(&h->ldm, n * 2 * D));
     }
     TRYHIP(hipMemset(h->pri.A_obs, 0xFF, ((size_t)D * D + (size_t)K * D) * sizeof(double)));     // all-ones bytes = NaN = nothing observed
+    if (P) {
+        TRY(dev_alloc(&h->Uin, n * T * P)); TRY(dev_alloc(&h->Yt, n * T * (K + 2 * P))); TRY(dev_alloc(&h->Ct, n * (K + 2 * P) * D));
+        TRY(dev_alloc(&h->B_mean, n * D * P)); TRY(dev_alloc(&h->B_var, n * P * D));
+        TRY(h->mem.alloc((void**)&h->qld_B, n * P * sizeof(double), 0xFF)); TRY(h->mem.alloc((void**)&h->lnd_B, n * P * sizeof(double), 0xFF));   // NaN
+        TRY(dev_alloc(&h->B_pm, (size_t)D * P)); TRY(dev_alloc(&h->B_pp, (size_t)P * D)); TRY(dev_alloc(&h->B_pld, P));
+        TRY(dev_alloc(&h->Suu, n * P * P)); TRY(dev_alloc(&h->imom, n * (2 * (size_t)D * P + (size_t)D * D)));
+    }
     h->st.T = T;
     h->st.fresh = (unsigned char*)calloc(T, 1);
     h->world = 1;
@@ -211,6 +229,11 @@ int pyvb_lds_create_lengths(pyvb_lds** out, int device, int N, int T, int D, int
 }
 int pyvb_lds_create_tied(pyvb_lds** out, int device, int N, int T, int D, int K, int noise_kind, const int* lengths, const int* model) {
     return lds_create(out, device, N, T, D, K, noise_kind, lengths, model);
+}
+
+int pyvb_lds_create_inputs(pyvb_lds** out, int device, int N, int T, int D, int K, int P, int noise_kind, const int* lengths) {
+    ARGCHK(P >= 1, "P must be >= 1 (pyvb_lds_create makes a handle without inputs)");
+    return lds_create(out, device, N, T, D, K, noise_kind, lengths, nullptr, P);
 }
 
 int pyvb_lds_get_models(pyvb_lds* h, int* model) {
@@ -378,6 +401,10 @@ static int set_parents(pyvb_lds* h, int which, int kind, const double* a0, const
     int rc = parents_gate(h, which, 0);
     if (rc) return rc;
     const char* name = kind == PARENTS_GAMMA ? "Gamma" : "DiagonalGamma";
+    if (h->P) {
+        pyvb_set_error("%s precision parents of the columns are not served on a handle with inputs (pyvb_lds_create_inputs, k_inputs.hip)", name);
+        return PYVB_E_UNSUPPORTED;
+    }
     if (h->dense) {
         pyvb_set_error("%s precision parents of the columns are served with DiagonalGamma and Gamma noise only, not with Wishart noise (k_wishart.hip)", name);
         return PYVB_E_UNSUPPORTED;
@@ -549,6 +576,15 @@ int pyvb_lds_get_column_cov(pyvb_lds* h, double* A_cov, double* C_cov) {
 
 int pyvb_lds_set_column_observations(pyvb_lds* h, const double* A_obs, const double* C_obs) {
     ENTER(h);
+    if (h->P) {
+        bool known = false;
+        for (size_t i = 0; A_obs && i < (size_t)h->D * h->D && !known; ++i) known = A_obs[i] == A_obs[i];
+        for (size_t i = 0; C_obs && i < (size_t)h->K * h->D && !known; ++i) known = C_obs[i] == C_obs[i];
+        if (known) {
+            pyvb_set_error("known entries of A / C are not served on a handle with inputs (pyvb_lds_create_inputs, k_inputs.hip)");
+            return PYVB_E_UNSUPPORTED;
+        }
+    }
     if (h->dense && h->big) {
         pyvb_set_error("with Wishart noise, known entries of A / C are served for D, K <= 64 only (k_wishart_big.hip)");
         return PYVB_E_UNSUPPORTED;
@@ -599,6 +635,10 @@ int pyvb_lds_set_observations(pyvb_lds* h, const double* Y) {
     } else
         for (size_t i = 0; i < n && !missing; ++i) missing = Y[i] != Y[i];
     int rc;
+    if (missing && h->P) {
+        pyvb_set_error("outputs that hold NaN are not served on a handle with inputs (pyvb_lds_create_inputs, k_missing.hip)");
+        return PYVB_E_UNSUPPORTED;
+    }
     if (missing && h->dense && h->big) {
         pyvb_set_error("with Wishart noise, outputs that hold NaN are served for D, K <= 64 only (k_wishart_big.hip)");
         return PYVB_E_UNSUPPORTED;
@@ -625,6 +665,7 @@ int pyvb_lds_set_observations(pyvb_lds* h, const double* Y) {
         h->has_missing = false;
         if ((rc = h2d(h, h->Y, Y, n))) return rc;
         if ((rc = syy(h))) return rc;
+        if (h->P && (rc = launch_in_assemble(h))) return rc;       // the rows [y_t ; u_t ; u_{t+1}] the sweeps read
         if (h->dense && (rc = launch_syy_full(h))) return rc;
     }
     HIPCHK(hipStreamSynchronize(h->stream));
@@ -688,6 +729,91 @@ int pyvb_lds_update_Y(pyvb_lds* h) {
         if ((rc = syy_missing(h))) return rc;
     }
     h->st.outputs_changed();
+    return PYVB_OK;
+}
+
+// ---- A known input that drives the states (pyvb_lds_create_inputs; the kernels are k_inputs.hip)
+static int inputs_gate(const pyvb_lds* h) {
+    ARGCHK(h, "handle is NULL");
+    ARGCHK(h->P > 0, "the handle was created without inputs (pyvb_lds_create_inputs makes one with)");
+    return PYVB_OK;
+}
+
+int pyvb_lds_set_inputs(pyvb_lds* h, const double* U) {
+    int rc = inputs_gate(h);
+    if (rc) return rc;
+    ARGCHK(U, "U is NULL");
+    const size_t T = h->T, P = h->P;
+    for (int n = 0; n < h->N; ++n)
+        for (size_t i = 0; i < T * P; ++i)
+            if (!std::isfinite(U[(size_t)n * T * P + i])) {
+                pyvb_set_error("U is not finite: replicate %d, row %d, channel %d", n, (int)(i / P), (int)(i % P));
+                return PYVB_E_ARG;
+            }
+    ENTER(h);
+    if ((rc = h2d(h, h->Uin, U, (size_t)h->N * T * P))) return rc;
+    if ((rc = launch_in_assemble(h)) || (rc = launch_in_suu(h))) return rc;
+    HIPCHK(hipStreamSynchronize(h->stream));
+    h->inputs_set = true;
+    h->st.outputs_changed();        // what the sweeps read as outputs has changed: c_t and every sum over t with it
+    return PYVB_OK;
+}
+
+int pyvb_lds_get_inputs(pyvb_lds* h, double* U) {
+    int rc = inputs_gate(h);
+    if (rc) return rc;
+    ARGCHK(U, "U is NULL");
+    ENTER(h);
+    if ((rc = d2h(h, U, h->Uin, (size_t)h->N * h->T * h->P))) return rc;
+    return pyvb_lds_sync(h);
+}
+
+int pyvb_lds_set_input_priors(pyvb_lds* h, const double* B_pm, const double* B_pp) {
+    int rc = inputs_gate(h);
+    if (rc) return rc;
+    ARGCHK(B_pm && B_pp, "B_prior_mean and B_prior_prec are required");
+    const int D = h->D, P = h->P;
+    for (int i = 0; i < P * D; ++i) ARGCHK(B_pp[i] > 0.0 && std::isfinite(B_pp[i]) && std::isfinite(B_pm[i]), "B_prior_prec must be positive and B_prior_mean finite");
+    std::vector<double> ld((size_t)P, 0.0);     // ln det of the diagonal prior precision of every column (node.py:301-302)
+    for (int i = 0; i < P; ++i)
+        for (int k = 0; k < D; ++k) ld[i] += log(B_pp[(size_t)i * D + k]);
+    ENTER(h);
+    if ((rc = h2d(h, h->B_pm, B_pm, (size_t)D * P)) || (rc = h2d(h, h->B_pp, B_pp, (size_t)P * D)) || (rc = h2d(h, h->B_pld, ld.data(), P))) return rc;
+    HIPCHK(hipStreamSynchronize(h->stream));    // ld is about to go out of scope
+    h->input_priors_set = true;
+    h->st.parameters_changed();
+    return PYVB_OK;
+}
+
+int pyvb_lds_set_input_state(pyvb_lds* h, const double* B_mean, const double* B_colvar) {
+    int rc = inputs_gate(h);
+    if (rc) return rc;
+    ENTER(h);
+    const size_t n = (size_t)h->N * h->D * h->P;
+    if ((rc = h2d(h, h->B_mean, B_mean, n)) || (rc = h2d(h, h->B_var, B_colvar, n))) return rc;
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if (B_mean || B_colvar) h->st.parameters_changed();
+    return PYVB_OK;
+}
+
+int pyvb_lds_get_input_state(pyvb_lds* h, double* B_mean, double* B_colvar, double* qld_B, double* lnd_B) {
+    int rc = inputs_gate(h);
+    if (rc) return rc;
+    ENTER(h);
+    const size_t N = h->N, D = h->D, P = h->P;
+    if ((rc = d2h(h, B_mean, h->B_mean, N * D * P)) || (rc = d2h(h, B_colvar, h->B_var, N * P * D)) ||
+        (rc = d2h(h, qld_B, h->qld_B, N * P)) || (rc = d2h(h, lnd_B, h->lnd_B, N * P))) return rc;
+    return pyvb_lds_sync(h);
+}
+
+static int ensure_stats(pyvb_lds* h);
+int pyvb_lds_update_B(pyvb_lds* h) {
+    int rc = inputs_gate(h);
+    if (rc) return rc;
+    ENTER(h);
+    IDLE(h);
+    if ((rc = ensure_stats(h)) || (rc = launch_in_colsB(h))) return rc;
+    h->st.columns_updated(0, false);        // as a column of A: the gains and the residual of Q depend on it
     return PYVB_OK;
 }
 
@@ -864,6 +990,13 @@ static int ensure_lnd_x(pyvb_lds* h) {
     return PYVB_OK;
 }
 
+// a handle with inputs before it has them: the updates would read zeros for u_t and for the parents of B
+static int inputs_ready(const pyvb_lds* h) {
+    ARGCHK(h->inputs_set, "the handle was created with inputs: call pyvb_lds_set_inputs before the first update");
+    ARGCHK(h->input_priors_set, "the handle was created with inputs: call pyvb_lds_set_input_priors before the first update");
+    return PYVB_OK;
+}
+
 static int ensure_gains(pyvb_lds* h) {
     if (h->st.gains_valid) return PYVB_OK;
     int rc;
@@ -871,7 +1004,9 @@ static int ensure_gains(pyvb_lds* h) {
         if ((rc = ensure_expect(h))) return rc;
         if ((rc = launch_dense_pre(h))) return rc;
     }
+    if (h->P && (rc = inputs_ready(h))) return rc;
     if ((rc = launch_prep(h))) return rc;
+    if (h->P && (rc = launch_in_gains(h))) return rc;      // the gains of the input channels, from Sigma_1 as k_prep has just left it
     h->st.gains_formed();
     return PYVB_OK;
 }
@@ -904,6 +1039,7 @@ static int ensure_stats(pyvb_lds* h) {
     if (rc) return rc;
     if ((rc = launch_moments(h, st.sxx_valid))) return rc;
     if ((rc = launch_tie(h, h->mom, (size_t)3 * h->D * h->D + (size_t)h->K * h->D + h->D))) return rc;        // chains that share A, C, Q, R: the moments of a model
+    if (h->P && ((rc = inputs_ready(h)) || (rc = launch_in_moments(h)))) return rc;       // Sxu, Su1x; Sx1x aside
     st.stats_valid = true;
     return PYVB_OK;
 }
@@ -913,7 +1049,9 @@ static int ensure_resid(pyvb_lds* h, int which) {
     if (valid) return PYVB_OK;
     int rc = ensure_stats(h);
     if (rc) return rc;
-    if ((rc = h->dense ? launch_wresid(h, which, 0, h->st.sg_valid[which]) : launch_resid(h, which))) return rc;
+    if (h->P && which == 0) {       // H_A of the current <B>, the residual as k_cols forms it, the terms of <B> alone
+        if ((rc = launch_in_HA(h)) || (rc = launch_resid(h, 0)) || (rc = launch_in_resQ(h))) return rc;
+    } else if ((rc = h->dense ? launch_wresid(h, which, 0, h->st.sg_valid[which]) : launch_resid(h, which))) return rc;
     valid = true;
     return PYVB_OK;
 }
@@ -958,7 +1096,10 @@ int pyvb_lds_update_columns(pyvb_lds* h, int which, int col_begin, int col_end) 
     if (h->dense) {
         if ((rc = ensure_expect(h))) return rc;
         if ((rc = launch_cols_dense(h, which, col_begin, col_end))) return rc;
-    } else if ((rc = launch_cols(h, which, col_begin, col_end))) return rc;
+    } else {
+        if (h->P && which == 0 && (rc = launch_in_HA(h))) return rc;       // H = Sx1x - <B> Su1x
+        if ((rc = launch_cols(h, which, col_begin, col_end))) return rc;
+    }
     h->st.columns_updated(which, h->dense && col_begin == 0 && col_end == h->D);
     return PYVB_OK;
 }
@@ -982,6 +1123,12 @@ static int update_noise(pyvb_lds* h, int which) {
 int pyvb_lds_update_Q(pyvb_lds* h) { ENTER(h); IDLE(h); return update_noise(h, 0); }
 int pyvb_lds_update_R(pyvb_lds* h) { ENTER(h); IDLE(h); return update_noise(h, 1); }
 
+// k_elbo, and on a handle with inputs the columns of B into part 2 behind it
+static int lds_bound(pyvb_lds* h, hipStream_t stream) {
+    const int rc = launch_elbo(h, stream);
+    return rc || !h->P ? rc : launch_in_elbo(h, stream);
+}
+
 int pyvb_lds_elbo(pyvb_lds* h) {
     ENTER(h);
     IDLE(h);
@@ -993,7 +1140,7 @@ int pyvb_lds_elbo(pyvb_lds* h) {
         if ((rc = ensure_expect(h))) return rc;
         return launch_elbo_dense(h);
     }
-    return launch_elbo(h);
+    return lds_bound(h, h->stream);
 }
 
 int pyvb_lds_get_elbo(pyvb_lds* h, double* parts) {
@@ -1031,6 +1178,15 @@ static int iterate_updates(pyvb_lds* h) {
         if ((rc = launch_wresid(h, 2, 1, true))) return rc;    // both residual matrices and both qw = w0 + residual
         h->st.noise_updated(2);
         if ((rc = ensure_expect(h))) return rc;                // E[Q], E[R] of the new posteriors: the bound and the next k_prep read them
+    } else if (h->P) {
+        // As, Bs, Cs, Q, R: B sees the new A, Q the new A and B; C and R do not depend on them and keep their shared launch
+        if ((rc = launch_in_HA(h)) || (rc = launch_cols(h, 0, 0, h->D))) return rc;
+        if ((rc = launch_in_colsB(h))) return rc;
+        if ((rc = launch_cols(h, 1, 0, h->D, 3))) return rc;
+        h->st.columns_updated(2, false);
+        h->st.noise_updated(1);
+        if ((rc = ensure_resid(h, 0)) || (rc = launch_noise(h, 0))) return rc;
+        h->st.noise_updated(0);
     } else {
         if ((rc = launch_cols(h, 2, 0, h->D, 3))) return rc;       // columns, residuals and noise update in one launch
         h->st.columns_updated(2, false);
@@ -1061,7 +1217,7 @@ int pyvb_lds_iterate(pyvb_lds* h, int niters) {
         // and over the ranks when a communicator is attached) go into a history ring (pyvb_lds_get_elbo_history).
         HIPCHK(hipEventRecord(h->ev_params, h->stream));
         HIPCHK(hipStreamWaitEvent(h->side, h->ev_params, 0));
-        if (!idle && (rc = h->dense ? launch_elbo_dense(h, h->side) : launch_elbo(h, h->side))) return rc;
+        if (!idle && (rc = h->dense ? launch_elbo_dense(h, h->side) : lds_bound(h, h->side))) return rc;
         double* slot = h->elbo_hist + (size_t)(h->hist_count % PYVB_ELBO_HISTORY) * 8;
         if ((rc = launch_elbo_sum(h, slot, h->side))) return rc;
         if (h->comm && (rc = pyvb_allreduce_f64(h->comm, slot, 6, h->side))) return rc;
@@ -1099,7 +1255,7 @@ static int iterate_until(pyvb_lds* h, int max_iters, double tol, int check_every
     while (!done && it < max_iters) {
         if (!idle) {
             if ((rc = iterate_updates(h))) return rc;
-            if ((rc = h->dense ? launch_elbo_dense(h, h->stream) : launch_elbo(h, h->stream))) return rc;
+            if ((rc = h->dense ? launch_elbo_dense(h, h->stream) : lds_bound(h, h->stream))) return rc;
             if ((rc = launch_converge(h, tol, it == 0, h->stream))) return rc;
         }
         double* slot = h->elbo_hist + (size_t)(h->hist_count % PYVB_ELBO_HISTORY) * 8;

@@ -100,6 +100,20 @@ struct pyvb_lds {
     double *Yobs, *Yvar, *Yqld, *Yent;      // [N][T][K] observations (NaN = missing), [N][T][K] variances, [N][T], [N]
     double *Ylnd, *YentX;                   // [N][T] ln det qcov beside Yqld; [N] the exact entropy of those rows (added, not subtracted)
     double *Yld, *YcovS;                    // Wishart noise: [N][T] ln det of each row's covariance of missing entries, [N][K][K] sum_t qcov_t
+    // ---- a known input u_t that drives the states, x_t = A x_{t-1} + B u_t (pyvb_lds_create_inputs, k_inputs.hip).  P = 0 and every
+    // pointer null on a handle without inputs.  The inputs ride through the sweeps and the statistics pass as 2 P extra output
+    // channels: those kernels are handed Yt, K + 2 P and Ct in place of Y, K and C_mean (lds_sweep_* below), and L is the layout
+    // of (D, K + 2 P); everything else keeps reading Y, K and C_mean.
+    int P;
+    double *Uin;                    // [N][T][P] the inputs as the caller gave them; row t drives x_t
+    double *Yt;                     // [N][T][K + 2 P] rows [y_t ; u_t ; u_{t+1}], u_t zero in row 0, u_{t+1} zero in a chain's last row
+    double *Ct;                     // [N][K + 2 P][D] <C>, then the rows through which the boundary nodes add <Q><B> u and -<A>^T<Q><B> u
+    double *B_mean, *B_var;         // [N][D][P] (row, col), [N][P][D] (column i, entry k), as A_mean / A_var
+    double *qld_B, *lnd_B;          // [N][P]
+    double *B_pm, *B_pp, *B_pld;    // the Constant parents of the columns of B: [D][P], [P][D], and ln det of each column's precision [P]
+    double *Suu;                    // [N][P][P] sum_{t=1}^{T_n-1} u_t u_t^T, formed when the inputs are set
+    double *imom;                   // [N][2 D P + D D]: Sxu [D][P], Su1x [P][D], and Sx1x as k_moments left it (k_in_moments)
+    bool inputs_set, input_priors_set;
     // ---- the lower bound does not feed the next iteration: inside pyvb_lds_iterate it runs on a side stream
     hipStream_t side;
     hipEvent_t ev_params, ev_elbo;  // parameters of this iteration complete (main) / lower bound of it read them (side)
@@ -108,7 +122,21 @@ struct pyvb_lds {
 };
 #define PYVB_ELBO_HISTORY 4096
 
+// what the sweeps, the single-node update and the statistics pass are handed as outputs, their number and <C>
+static inline int lds_sweep_K(const pyvb_lds* h) { return h->K + 2 * h->P; }
+static inline const double* lds_sweep_Y(const pyvb_lds* h) { return h->P ? h->Yt : h->Y; }
+static inline const double* lds_sweep_C(const pyvb_lds* h) { return h->P ? h->Ct : h->C_mean; }
+
 // ---- launchers implemented in the kernel translation units ----
+// k_inputs.hip (handles with inputs only)
+int launch_in_assemble(pyvb_lds* h);        // Yt from Y and Uin, every row of every replicate
+int launch_in_suu(pyvb_lds* h);             // Suu from Uin
+int launch_in_gains(pyvb_lds* h);           // behind k_prep: the two extra column groups of G, Ct, the ones behind <R>
+int launch_in_moments(pyvb_lds* h);         // behind k_moments: Sxu, Su1x out of the Syx block, Sx1x aside
+int launch_in_HA(pyvb_lds* h);              // H_A = Sx1x - <B> Su1x into the moment block, for the columns of A and the residual of Q
+int launch_in_colsB(pyvb_lds* h);           // [b.update() for b in Bs]
+int launch_in_resQ(pyvb_lds* h);            // the terms of <B> in the residual of Q
+int launch_in_elbo(pyvb_lds* h, hipStream_t stream);       // the columns of B into part 2, behind k_elbo on the same stream
 int launch_prep(pyvb_lds* h);
 int launch_w0(pyvb_lds* h);         // L0 m0 from the priors of X_0 on the device: after every change of them
 // A sweep reads X[src] and writes X[1 - src]; read_cache: a backward sweep that starts from the c_t a forward one left in U.

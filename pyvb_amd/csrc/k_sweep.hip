@@ -442,7 +442,7 @@ __global__ void __launch_bounds__(64) k_step(StepArgs a) {
 
 template <int DT, int KT>
 static int launch_sweep_t(pyvb_lds* h, const SweepArgs& a, bool read_cache) {
-    const bool full = h->D == 16 * DT && h->K == 16 * KT;
+    const bool full = h->D == 16 * DT && a.K == 16 * KT;
     const int mode = a.dir == PYVB_FORWARD ? 1 : (read_cache ? 2 : 0);      // MODE 2 reads c_t from U and writes the interior Sxx (h->sxx)
 #define PYVB_SWEEP_CASE(F, M) do { if (h->W > 1) hipLaunchKernelGGL((k_sweep<DT, KT, F, M, true>), dim3(h->N, h->W), dim3(64), 0, h->stream, a); \
                                    else hipLaunchKernelGGL((k_sweep<DT, KT, F, M, false>), dim3(h->N), dim3(64), 0, h->stream, a); } while (0)
@@ -457,10 +457,11 @@ int launch_sweep(pyvb_lds* h, int direction, int src, bool read_cache, bool keep
     SweepArgs a;
     a.keep_x = (keep_x || direction != PYVB_FORWARD) ? 1 : 0;
     a.W = h->W;
-    a.Xold = h->X[src]; a.Xnew = h->X[1 - src]; a.Y = h->Y; a.gains = h->gains; a.warm = h->warm;
-    a.trash = h->trash; a.U = h->U; a.Sxx = h->sxx; a.A_mean = h->A_mean; a.C_mean = h->C_mean;
+    // (a handle with inputs: the rows [y_t ; u_t ; u_{t+1}], K + 2 P of them, and <C> with the boundary nodes' rows, k_inputs.hip)
+    a.Xold = h->X[src]; a.Xnew = h->X[1 - src]; a.Y = lds_sweep_Y(h); a.gains = h->gains; a.warm = h->warm;
+    a.trash = h->trash; a.U = h->U; a.Sxx = h->sxx; a.A_mean = h->A_mean; a.C_mean = lds_sweep_C(h);
     a.QA = h->dense ? h->QA : nullptr; a.RC = h->dense ? h->RC : nullptr;
-    a.N = h->N; a.T = h->T; a.D = h->D; a.K = h->K; a.dir = direction; a.L = h->L; a.active = h->active; a.len = h->len;
+    a.N = h->N; a.T = h->T; a.D = h->D; a.K = lds_sweep_K(h); a.dir = direction; a.L = h->L; a.active = h->active; a.len = h->len;
     {
         TimedLaunch tl(h, direction == PYVB_FORWARD ? PYVB_K_SWEEP_FWD : PYVB_K_SWEEP_BWD);
         switch (h->L.DT * 10 + h->L.KT) {
@@ -523,9 +524,9 @@ int launch_carry(pyvb_lds* h, const double* src, double* dst, size_t per) {
 int launch_step(pyvb_lds* h, int t) {
     if (h->big) return launch_step_big(h, t);
     StepArgs a;
-    a.X = h->X[h->st.cur]; a.Y = h->Y; a.gains = h->gains; a.A_mean = h->A_mean; a.C_mean = h->C_mean;
+    a.X = h->X[h->st.cur]; a.Y = lds_sweep_Y(h); a.gains = h->gains; a.A_mean = h->A_mean; a.C_mean = lds_sweep_C(h);
     a.QA = h->dense ? h->QA : nullptr; a.RC = h->dense ? h->RC : nullptr;
-    a.N = h->N; a.T = h->T; a.D = h->D; a.K = h->K; a.t = t; a.L = h->L; a.active = h->active; a.len = h->len;
+    a.N = h->N; a.T = h->T; a.D = h->D; a.K = lds_sweep_K(h); a.t = t; a.L = h->L; a.active = h->active; a.len = h->len;
     TimedLaunch tl(h, PYVB_K_STEP);
     hipLaunchKernelGGL(k_step, dim3(h->N), dim3(64), 0, h->stream, a);
     HIPCHK(hipGetLastError());

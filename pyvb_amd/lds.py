@@ -28,6 +28,7 @@ def _f64(a, shape, name):
 _STATE_KEYS = ("X", "A_mean", "A_colvar", "C_mean", "C_colvar", "Q_b", "R_b")
 _ALPHA_KEYS = ("A_alpha_b", "C_alpha_b")        # [1, D] each: qb of the columns' Gamma parents, where a series' state carries them
 _ENTRY_KEYS = ("A_entry_b", "C_entry_b")        # [1, D, rows] each: qb of the columns' DiagonalGamma parents, likewise
+_INPUT_KEYS = ("B_mean", "B_colvar")            # [1, D, P], [1, P, D]: the input gain of a series with a known input, likewise
 
 
 def pad_series(series):
@@ -50,7 +51,7 @@ def pad_series(series):
                                  % (n, y.shape, x.shape, lengths[n], K, lengths[n], D))
         Y[n, :lengths[n]], X[n, :lengths[n]] = y, x
     st0 = {"X": X}
-    for k in _STATE_KEYS[1:] + tuple(k for k in _ALPHA_KEYS + _ENTRY_KEYS if k in series[0][1]):
+    for k in _STATE_KEYS[1:] + tuple(k for k in _ALPHA_KEYS + _ENTRY_KEYS + _INPUT_KEYS if k in series[0][1]):
         st0[k] = np.concatenate([np.asarray(st[k], dtype=np.float64) for _, st in series])       # each [1, ...]
     return Y, st0, lengths
 
@@ -58,8 +59,11 @@ def pad_series(series):
 class LDSBatch(object):
     ELBO_PARTS = ("X", "Y", "A", "C", "Q", "R")
 
-    def __init__(self, N, T, D, K, noise="diagonal_gamma", device=0, lengths=None, models=None):
-        """lengths: int [N], the chain length T_n of each replicate, 2 <= T_n <= T (pyvb_lds_create_lengths); None: all T.
+    def __init__(self, N, T, D, K, noise="diagonal_gamma", device=0, lengths=None, models=None, inputs=0):
+        """inputs: P >= 1 known inputs that drive the states, x_t = A x_{t-1} + B u_t (pyvb_lds_create_inputs): set_inputs gives
+        U [N, T, P], B [D, P] is a matrix of Gaussian columns like A (set_state / get_state: B_mean, B_colvar; set_priors:
+        B_prior_mean, B_prior_prec; update_B).  DiagonalGamma / Gamma noise and max(D, K + 2 P) <= 64; not with models=.  0: none.
+        lengths: int [N], the chain length T_n of each replicate, 2 <= T_n <= T (pyvb_lds_create_lengths); None: all T.
         Arrays stay [N, T, ...]; rows t >= T_n of replicate n are padding: setters accept anything there, getters return
         0.0 in X and in the outputs.
         models: int [N], the model of each replicate (pyvb_lds_create_tied): consecutive replicates with the same id are the
@@ -69,9 +73,20 @@ class LDSBatch(object):
         if noise not in _NOISE:
             raise NotImplementedError("noise precision %r has no HIP path (DiagonalGamma, Gamma and Wishart do)" % (noise,))
         self.N, self.T, self.D, self.K, self.noise, self.device = int(N), int(T), int(D), int(K), noise, int(device)
+        self.P = int(inputs or 0)
         self.bound = "reference"
         h = C.ctypes.c_void_p()
-        if models is not None:
+        if self.P:
+            if models is not None:
+                raise NotImplementedError("chains that share A, C, Q, R (models=) are not served together with inputs")
+            ln = None if lengths is None else np.ascontiguousarray(lengths, dtype=np.int32)
+            if ln is not None and ln.shape != (self.N,):
+                raise AssertionError("lengths has shape %s, expected (%d,)" % (ln.shape, self.N))
+            C.check(C.lib.pyvb_lds_create_inputs(C.ctypes.byref(h), self.device, self.N, self.T, self.D, self.K, self.P, _NOISE[noise],
+                                                 None if ln is None else ln.ctypes.data_as(C._ip)))
+            self.lengths = np.empty(self.N, dtype=np.int32)
+            C.check(C.lib.pyvb_lds_get_lengths(h, self.lengths.ctypes.data_as(C._ip)))
+        elif models is not None:
             ln = None if lengths is None else np.ascontiguousarray(lengths, dtype=np.int32)
             md = np.ascontiguousarray(models, dtype=np.int32)
             for nm, a in (("lengths", ln), ("models", md)):
@@ -125,6 +140,19 @@ class LDSBatch(object):
             return
         arrs += [C.broadcast(pri["Q_a0"], (D,)), C.broadcast(pri["Q_b0"], (D,)), C.broadcast(pri["R_a0"], (K,)), C.broadcast(pri["R_b0"], (K,))]
         self._check(C.lib.pyvb_lds_set_priors(self._h, *[C.dptr(a) for a in arrs]))       # (the columns have Constant parents again)
+        if self.P:      # the Constant parents of the columns of B: B_prior_mean [D, P] (row, col), B_prior_prec [P, D] (column, entry)
+            bm, bp = _f64(pri["B_prior_mean"], (D, self.P), "B_prior_mean"), _f64(pri["B_prior_prec"], (self.P, D), "B_prior_prec")
+            self._check(C.lib.pyvb_lds_set_input_priors(self._h, C.dptr(bm), C.dptr(bp)))
+
+    def set_inputs(self, U):
+        """U[N,T,P]: row t drives x_t; row 0 and, with chain lengths, the rows t >= T_n are never read."""
+        U = _f64(U, (self.N, self.T, self.P), "U")
+        self._check(C.lib.pyvb_lds_set_inputs(self._h, C.dptr(U)))
+
+    def get_inputs(self):
+        U = np.empty((self.N, self.T, self.P))
+        self._check(C.lib.pyvb_lds_get_inputs(self._h, C.dptr(U)))
+        return U
 
     def set_observations(self, Y):
         """Y[N,T,K]; NaN = missing entry (the rows concerned become variational nodes: set_output_state, update_Y).
@@ -149,9 +177,14 @@ class LDSBatch(object):
         self._check(C.lib.pyvb_lds_get_outputs(self._h, C.dptr(q), C.dptr(v), C.dptr(ld)))
         return (q, v, ld) if with_qld else (q, v)
 
-    def set_state(self, X=None, A_mean=None, A_colvar=None, C_mean=None, C_colvar=None, Q_b=None, R_b=None):
-        """X[N,T,D] and the parameter posteriors; padding rows of X (t >= T_n) may hold anything."""
+    def set_state(self, X=None, A_mean=None, A_colvar=None, C_mean=None, C_colvar=None, Q_b=None, R_b=None, B_mean=None, B_colvar=None):
+        """X[N,T,D] and the parameter posteriors; padding rows of X (t >= T_n) may hold anything.  On a handle with inputs also
+        B_mean [N,D,P] and B_colvar [N,P,D]."""
         N, T, D, K = self.N, self.T, self.D, self.K
+        if B_mean is not None or B_colvar is not None:
+            bm = None if B_mean is None else _f64(B_mean, (N, D, self.P), "B_mean")
+            bv = None if B_colvar is None else _f64(B_colvar, (N, self.P, D), "B_colvar")
+            self._check(C.lib.pyvb_lds_set_input_state(self._h, C.dptr(bm), C.dptr(bv)))
         shapes = [("X", X, (N, T, D)), ("A_mean", A_mean, (N, D, D)), ("A_colvar", A_colvar, (N, D, D)),
                   ("C_mean", C_mean, (N, K, D)), ("C_colvar", C_colvar, (N, D, K)), ("Q_b", Q_b, (N, D)), ("R_b", R_b, (N, K))]
         arrs = [None if a is None else _f64(a, s, nm) for nm, a, s in shapes]
@@ -269,6 +302,15 @@ class LDSBatch(object):
         order = ["X", "A_mean", "A_colvar", "C_mean", "C_colvar", "Q_a", "Q_b", "R_a", "R_b"]
         out = {k: np.empty(shapes[k]) for k in order if k in what}
         self._check(C.lib.pyvb_lds_get_state(self._h, *[C.dptr(out.get(k)) for k in order]))
+        if self.P and ("A_mean" in what or "B_mean" in what):       # a handle with inputs: the third matrix beside the two
+            out.update(self.get_input_state(("B_mean", "B_colvar")))
+        return out
+
+    def get_input_state(self, what=("B_mean", "B_colvar", "qld_B", "lnd_B")):
+        """B_mean [N,D,P], B_colvar [N,P,D], and q_ln_det / ln det qcov of the columns of B [N,P] (NaN before their first update)."""
+        shapes = {"B_mean": (self.N, self.D, self.P), "B_colvar": (self.N, self.P, self.D), "qld_B": (self.N, self.P), "lnd_B": (self.N, self.P)}
+        out = {k: np.empty(shapes[k]) for k in shapes if k in what}
+        self._check(C.lib.pyvb_lds_get_input_state(self._h, *[C.dptr(out.get(k)) for k in shapes]))
         return out
 
     def get_posterior_classes(self):
@@ -334,6 +376,10 @@ class LDSBatch(object):
     def update_C(self):
         self._check(C.lib.pyvb_lds_update_C(self._h))
 
+    def update_B(self):
+        """[b.update() for b in Bs]: the columns of the input gain (handles with inputs)."""
+        self._check(C.lib.pyvb_lds_update_B(self._h))
+
     def update_columns(self, which, col_begin, col_end):
         """As[i].update() (which = "A") or Cs[i].update() ("C") for i in [col_begin, col_end), in order."""
         self._check(C.lib.pyvb_lds_update_columns(self._h, 0 if which == "A" else 1, int(col_begin), int(col_end)))
@@ -358,8 +404,8 @@ class LDSBatch(object):
         return out
 
     def iterate(self, niters=1):
-        """niters x (forward sweep, backward sweep, A, C, Q, R, [the columns' Gamma / DiagonalGamma parents,] lower bound);
-        asynchronous."""
+        """niters x (forward sweep, backward sweep, A, [B on a handle with inputs,] C, Q, R, [the columns' Gamma / DiagonalGamma
+        parents,] lower bound); asynchronous."""
         self._check(C.lib.pyvb_lds_iterate(self._h, int(niters)))
 
     def elbo_history(self, last=4096):
@@ -455,7 +501,7 @@ class LDSBatch(object):
 
     def kernel_times(self):
         names = {"prep": C.K_PREP, "sweep_fwd": C.K_SWEEP_FWD, "sweep_bwd": C.K_SWEEP_BWD, "stats": C.K_STATS,
-                 "params": C.K_PARAMS, "elbo": C.K_ELBO, "step": C.K_STEP, "gy": C.K_GY}
+                 "params": C.K_PARAMS, "elbo": C.K_ELBO, "step": C.K_STEP, "gy": C.K_GY, "inputs": C.K_INPUTS}
         out = {}
         for nm, k in names.items():
             ms, cnt = C.ctypes.c_double(), C.ctypes.c_int()
@@ -490,11 +536,19 @@ class LDSBatch(object):
         return bool(np.isnan(np.asarray(Y))[self.live_rows()].any())
 
     @classmethod
-    def from_series(cls, series, pri, device=0):
+    def from_series(cls, series, pri, device=0, U=None):
         """One handle for time series of different lengths: series is a list of (Y_n[T_n, K], st0_n) with st0_n as
-        synth.initial_state(T_n, D, K, 1) gives it; replicate n is the graph with T_n time steps (pad_series)."""
+        synth.initial_state(T_n, D, K, 1) gives it; replicate n is the graph with T_n time steps (pad_series).
+        U: a list of U_n[T_n, P], the known input of every series (st0_n then carries B_mean, B_colvar), padded as Y is."""
         Y, st0, lengths = pad_series(series)
-        return cls.from_problem(Y, st0, pri, device, lengths=lengths)
+        if U is not None:
+            Up = np.zeros(Y.shape[:2] + (np.shape(U[0])[1],))
+            for n, u in enumerate(U):
+                if np.shape(u) != (lengths[n], Up.shape[2]):
+                    raise AssertionError("series %d: U has shape %s, expected (%d, %d)" % (n, np.shape(u), lengths[n], Up.shape[2]))
+                Up[n, :lengths[n]] = u
+            U = Up
+        return cls.from_problem(Y, st0, pri, device, lengths=lengths, U=U)
 
     @classmethod
     def from_trials(cls, trials, pri, device=0):
@@ -508,12 +562,18 @@ class LDSBatch(object):
         return cls.from_problem(Y, st0, pri, device, lengths=lengths, models=models)
 
     @classmethod
-    def from_problem(cls, Y, st0, pri, device=0, lengths=None, models=None):
+    def from_problem(cls, Y, st0, pri, device=0, lengths=None, models=None, U=None):
+        """U [N, T, P]: a known input that drives the states (synth.make_input_problem); st0 then carries B_mean and B_colvar, pri
+        B_prior_mean and B_prior_prec."""
         N, T, K = Y.shape
         D = st0["A_mean"].shape[1]
-        b = cls(N, T, D, K, pri.get("noise", "diagonal_gamma"), device, lengths=lengths, models=models)
+        b = cls(N, T, D, K, pri.get("noise", "diagonal_gamma"), device, lengths=lengths, models=models,
+                inputs=0 if U is None else np.shape(U)[2])
         b.set_priors(pri)
         b.set_observations(Y)
+        if U is not None:
+            b.set_inputs(U)
+            b.set_state(B_mean=st0["B_mean"], B_colvar=st0["B_colvar"])
         if "Yq" in st0 and b.has_missing_outputs(Y):
             b.set_output_state(st0["Yq"], st0["Yrowvar"])
         if b.noise == "wishart":        # the compact initial state carries the diagonal of qw in Q_b / R_b

@@ -10,7 +10,7 @@ Everything here is host-side numpy; it only produces inputs.
 """
 import numpy as np
 
-__all__ = ["simulate_lds", "initial_state", "default_priors", "make_problem"]
+__all__ = ["simulate_lds", "initial_state", "default_priors", "make_problem", "simulate_driven_lds", "make_input_problem"]
 
 
 def simulate_lds(T, D, K, N=1, seed=20240):
@@ -82,6 +82,47 @@ def make_problem(T, D, K, N=1, seed=20240):
     sim = simulate_lds(T, D, K, N, seed)
     st = initial_state(T, D, K, N, seed + 7919)
     return sim["Y"], st, default_priors(D, K)
+
+
+def simulate_driven_lds(T, D, K, P, N=1, seed=20240):
+    """simulate_lds with a known input: x_t = A x_{t-1} + B u_t + Q^{1/2} eps for t >= 1, B = randn [N, D, P], and u_t a
+    sum of a slow sinusoid per channel and white noise (an actuator log: persistent, but exciting every direction).  Row 0 of
+    U drives nothing (x_0 ~ N(0, I)) and is zero.  Returns dict with Y [N,T,K], U [N,T,P] and the true parameters."""
+    rng = np.random.default_rng(seed)
+    A = rng.standard_normal((N, D, D))
+    rad = np.max(np.abs(np.linalg.eigvals(A)), axis=-1)
+    A *= (0.9 / rad)[:, None, None]
+    B = rng.standard_normal((N, D, P))
+    C = 10.0 * rng.standard_normal((N, K, D))
+    Rd = 0.1 * rng.random((N, K))
+    Qd = 0.1 * rng.random((N, D))
+    sq, sr = np.sqrt(Qd), np.sqrt(Rd)
+    phase, period = rng.random((N, 1, P)), 8.0 + 24.0 * rng.random((N, 1, P))
+    U = np.sin(2.0 * np.pi * (np.arange(T)[None, :, None] / period + phase)) + 0.5 * rng.standard_normal((N, T, P))
+    U[:, 0] = 0.0
+    X = np.empty((N, T, D))
+    Y = np.empty((N, T, K))
+    x = rng.standard_normal((N, D))
+    for t in range(T):
+        if t > 0:
+            x = np.einsum("nij,nj->ni", A, x) + np.einsum("nip,np->ni", B, U[:, t]) + sq * rng.standard_normal((N, D))
+        X[:, t] = x
+        Y[:, t] = np.einsum("nkj,nj->nk", C, x) + sr * rng.standard_normal((N, K))
+    return {"Y": Y, "U": U, "X": X, "A": A, "B": B, "C": C, "Q": Qd, "R": Rd}
+
+
+def make_input_problem(T, D, K, P, N=1, seed=20240):
+    """make_problem for the input-driven graph X_t = Gaussian(q, A X_{t-1} + B u_t, Q): (Y, U, st0, pri), st0 with B_mean [N, D, P]
+    and B_colvar [N, P, D] (column, entry) drawn as the columns of A are, pri with B_prior_mean [D, P] and B_prior_prec [P, D]."""
+    sim = simulate_driven_lds(T, D, K, P, N, seed)
+    st = initial_state(T, D, K, N, seed + 7919)
+    rng = np.random.default_rng(seed + 104729)
+    st["B_mean"] = rng.standard_normal((N, D, P))
+    st["B_colvar"] = np.repeat(1.0 / rng.random((N, P, 1)), D, axis=2)
+    pri = default_priors(D, K)
+    pri["B_prior_mean"] = np.zeros((D, P))
+    pri["B_prior_prec"] = np.full((P, D), 1e-3)
+    return sim["Y"], sim["U"], st, pri
 
 
 def pca_rows(lo, hi, d, q, seed, block=10000):
