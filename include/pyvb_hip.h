@@ -533,7 +533,12 @@ int pyvb_pca_comm_init_host(pyvb_pca* h, pyvb_host_allreduce_fn fn, void* user, 
  * opcodes are documented in pyvb_amd/csrc/k_tape.hip and mirrored by pyvb_amd/generic.py), interpreted by one workgroup
  * per launch.  Tapes are uploaded once and replayed (the graph is static).  pyvb_graph_tape_create checks every extent a
  * record touches against the arena (PYVB_E_ARG names the record); gather / scatter indices are data: the kernel skips one
- * that points outside and the next pyvb_graph_sync / pyvb_graph_read returns PYVB_E_ARG. */
+ * that points outside and the next pyvb_graph_sync / pyvb_graph_read returns PYVB_E_ARG.  It also refuses, as malformed, a
+ * T_COPY2D, T_FILL or T_GEMM record of more than 2^22 elements (m n; the k of a T_GEMM is not limited) and a T_DIAG with
+ * flags 1 or T_CHOLINV record with m m > 2^22: up to there the interpreter's division-free row / column of an element is
+ * proven exact (TAPE_MAX_ELEMS, pyvb_amd/csrc/tape.h).  Records of the other opcodes are limited by the arena alone.  A
+ * T_SCATTER whose index pairs repeat leaves an unspecified one of the colliding values (with T_ACC: an unordered
+ * read-modify-write that may lose terms); give it distinct pairs. */
 typedef struct pyvb_graph pyvb_graph;
 int pyvb_graph_create(pyvb_graph** out, int device, size_t arena_doubles);
 int pyvb_graph_destroy(pyvb_graph* g);

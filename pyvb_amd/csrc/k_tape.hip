@@ -28,6 +28,7 @@ template <> struct TapePtr<true> { typedef lds_double* type; };
 // form the addresses, fetch the operands, store -- so: the record is fetched as two 16-byte words one record ahead, and the
 // row / column of an element comes from a float reciprocal with a fix-up instead of two integer divisions (about 80 instructions).
 typedef int __attribute__((ext_vector_type(4))) tape_i4;
+// exact for idx < TAPE_MAX_ELEMS (the derivation is in tape.h; tape_describe admits no larger record of the opcodes that call it)
 __device__ __forceinline__ void tape_divmod(int idx, int n, float rn, int& i, int& j) {
     i = (int)(((float)idx + 0.5f) * rn);
     j = idx - i * n;

@@ -22,6 +22,27 @@ enum {
 #define T_ACC 0x40000000
 // record layout: o[0] opcode, o[1] dst, o[2] a, o[3] b (or a leading dimension / scalar offset), o[4] m, o[5] n, o[6] p, o[7] flags
 //
+// T_SCATTER with repeated (r_i, c_j) pairs: the elements that share a target are stored by different threads in no defined order.
+// Without T_ACC one of their values is left there, which one is not specified; with T_ACC every one of them is an unordered
+// read-modify-write of the target, so terms may be lost.  Emitters give a scatter distinct pairs (a gather may repeat its indices).
+//
+// The element limit.  The interpreter gives element idx of an m x n record its row and column without an integer division
+// (tape_divmod in k_tape.hip): i = (int)((float(idx) + 0.5) * rn), rn the hardware's float reciprocal of n, then one step of
+// fix-up by j = idx - i n.  That is exact for every idx < TAPE_MAX_ELEMS = 2^22:
+//   * x = float(idx) + 0.5 is exact: 2 idx + 1 < 2^24 is an integer of 24 bits (true up to idx < 2^23); n <= 2^22 is exact too;
+//   * rn = (1 / n)(1 + d1): the reciprocal instruction is good to 1 ulp; allowing the rounded float(1 / n) and either neighbour
+//     of it gives |d1| <= 1.5 ulp <= 1.5 * 2^-23.  The product is rounded once, |d2| <= 2^-24.  So the computed quotient is
+//     q' = q (1 + d), q = (idx + 0.5) / n, |d| <= (1.5 * 2^-23 + 2^-24)(1 + 2^-24) = 2^-22 (1 + 2^-24);
+//   * |q' - q| <= q 2^-22 (1 + 2^-24) <= (2^22 - 0.5) / n * 2^-22 (1 + 2^-24) = (1 - 2^-23)(1 + 2^-24) / n < 1 / n;
+//   * with i = idx div n and j = idx mod n the true q = i + (j + 0.5) / n lies in [i + 0.5 / n, i + 1 - 0.5 / n], hence
+//     q' in (i - 0.5 / n, i + 1 + 0.5 / n), q' >= 0, and (int)q' is i - 1, i or i + 1: what the fix-up covers.
+// Beyond the limit the row can be off by more than one (in a float32 simulation first at idx = 8 388 609 for n = 1 with the
+// reciprocal one ulp high, at 12 582 911 for n = 2), and a strided store then lands
+// outside the record's span.  So a record of an opcode that takes this path -- T_COPY2D, T_FILL, T_GEMM (m n; k is free),
+// T_DIAG with flags 1 and T_CHOLINV (m m) -- with more than TAPE_MAX_ELEMS elements is malformed (tape_describe).  The other
+// opcodes address element idx as it is and are limited by the arena alone.
+#define TAPE_MAX_ELEMS (1 << 22)
+//
 // The LDS-window form: when a tape is uploaded the host cuts every block of records that one workgroup
 // interprets into WINDOWS, the longest runs of consecutive records whose extents, merged into segments, fit the LDS budget.  The
 // workgroup takes them in order: load the segments, run the records out of LDS (their offsets rewritten to window positions and

@@ -23,6 +23,9 @@ inline TapeRecord tape_describe(const int* o) {
     if (m < 0 || n < 0) return d;
     const size_t mn = (size_t)m * n, mm = (size_t)m * m;
     const bool R = false, W = true;
+    // the opcodes whose elements get their row and column from tape_divmod: exact up to TAPE_MAX_ELEMS elements (tape.h)
+    const bool by_mn = op == T_COPY2D || op == T_FILL || op == T_GEMM, by_mm = op == T_CHOLINV || (op == T_DIAG && (flags & 1));
+    if ((by_mn && mn > (size_t)TAPE_MAX_ELEMS) || (by_mm && mm > (size_t)TAPE_MAX_ELEMS)) return d;
     auto at = [&](int field, long off, size_t len, bool write) { if (len) d.ext[d.n++] = TapeExtent{off, len, write, field}; };
     auto add = [&](int field, size_t len, bool write) { at(field, o[field], len, write); };
     switch (op) {

@@ -241,3 +241,24 @@ VALIDATION = [
 # only T_NOP, which touches nothing, is accepted
 VALIDATION += [([op, 0, 0, _M, _M, _M, _M, 0], op == G.T_NOP) for op in range(14)]
 VALIDATION += [([op, _M, _M, _M, _M, _M, _M, _M], op == G.T_NOP) for op in range(14)]
+
+# ---- the element limit of the opcodes that take tape_divmod (TAPE_MAX_ELEMS = 2^22, pyvb_amd/csrc/tape.h), against an arena of
+# 2^24 doubles in which every extent below fits: only the limit decides.  Pairs: the largest record accepted, one row more refused.
+TAPE_MAX_ELEMS = 1 << 22
+VALIDATION_BOUND_ARENA = 1 << 24
+_E, _H = TAPE_MAX_ELEMS, 1 << 23
+VALIDATION_BOUND = [
+    ([G.T_FILL, 0, 0, 4, _E // 4, 4, 0, 1], True), ([G.T_FILL, 0, 0, 4, _E // 4 + 1, 4, 0, 1], False),
+    ([G.T_FILL, 0, 0, 1, _E, 1, 0, 0], True), ([G.T_FILL, 0, 0, 1, _E + 1, 1, 0, 0], False),
+    ([G.T_COPY2D, 0, _H, 3, _E // 3, 3, 3, 0], True), ([G.T_COPY2D, 0, _H, 3, _E // 3 + 1, 3, 3, 0], False),     # 4 194 303, 4 194 306
+    ([G.T_COPY2D, 0, _H, _E, 1, _E, _E, 0], True), ([G.T_COPY2D, 0, _H, _E + 1, 1, _E + 1, _E + 1, 0], False),
+    ([G.T_GEMM, 0, _H, _H + 4096, 2048, 2048, 1, 0], True), ([G.T_GEMM, 0, _H, _H + 4096, 2049, 2048, 1, 0], False),
+    ([G.T_GEMM, 0, 64, _H, 1, 1, _E + 1, 0], True),                 # k is not limited: a and b hold 2^22 + 1 doubles each
+    ([G.T_DIAG, 0, _H, 0, 2048, 0, 0, 1], True), ([G.T_DIAG, 0, _H, 0, 2049, 0, 0, 1], False),
+    ([G.T_DIAG, 0, _H, 0, 2049, 0, 0, 0], True),                    # flags 0 reads a[i m + i]: no division
+    ([G.T_CHOLINV, 0, 0, 4 * _E - 2, 2048, 0, _E, 0], True),        # dst = a 0 .. 2^22, scratch 2^22 .. 3 * 2^22, scalars at the end
+    ([G.T_CHOLINV, 0, 0, 4 * _E - 2, 2049, 0, 2049 * 2049, 0], False),      # scratch ends at 3 * 2049^2 = 12 595 203 < 2^24 - 2
+    # the opcodes that address element idx as it is are limited by the arena alone
+    ([G.T_UNARY, 0, _H, 0, _E + 1, 1, 0, 4], True), ([G.T_MUL, 0, _H, _H, 2049, 2048, 0, 0], True),
+    ([G.T_AXPBY, 0, _H, -1, _E + 1, 1, 4 * _E - 1, 0], True), ([G.T_TRACE, 0, _H, 0, 2049, 0, 0, 0], True),
+]
