@@ -23,6 +23,10 @@ part by part and replicate by replicate (bound_errors, compare_bound).
 Outputs with missing entries are also measured row by row (compare_rows): a row's missing entries in units of the row's largest
 one, e_row <= FACTOR max(e64_row, n 2^-52) with e64_row <= CAP, its known entries bitwise -- on cases whose rows are named
 patterns (_missing_rows), in the envelope's order and in orders of their own (lds_trace_order, rows_reference).
+
+VB-PCA is measured row by row too (compare_pca_rows): X over a row's missing entries, Z over the row, X_rowvar, each in the row's own
+unit and by the same rule, the observed entries of X bitwise the data -- on cases whose rows are named patterns aimed at the mask
+words, tiles, blocks and halves of the sweeps (PCA_ROW_PATTERNS, PCA_ROW_CASES, pca_rows_reference).
 """
 import functools
 import importlib.util
@@ -775,10 +779,17 @@ def pca_handle_parts(b):
     return parts
 
 
-def pca_trace(m, N, iters=2, stage_reads=True, bounds=(), parts=None):
+def _pca_rowvar(g):
+    """[N]: the variance a row's missing entries carry -- a handle's X_rowvar, the largest entry of the row in an oracle's X_var
+    (0 where the row is observed, tests/test_pca_gpu.py: _compare)"""
+    return g["X_rowvar"] if "X_rowvar" in g else g["X_var"].max(1)
+
+
+def pca_trace(m, N, iters=2, stage_reads=True, bounds=(), parts=None, rowvar=False):
     """The stages of tests/test_pca_gpu.py: test_stagewise_vs_oracle on m (OraclePCA or a PCABatch).  stage_reads=False reads
     only at the end of each iteration: a read between update_Z and update_X(1, N) makes a handle carry the Z update out on its
-    own, and the fused sweep over the rows (pyvb_amd/csrc/k_pca.hip: the "columns" / "pairs" kinds of PCABatch.set_sweep) is then never run."""
+    own, and the fused sweep over the rows (pyvb_amd/csrc/k_pca.hip: the "columns" / "pairs" kinds of PCABatch.set_sweep) is then never run.
+    rowvar: X_rowvar [N] is yielded wherever X is, from the same read (the row-wise comparison, compare_pca_rows)."""
     for it in range(iters):
         m.update_W()
         if stage_reads:
@@ -792,11 +803,16 @@ def pca_trace(m, N, iters=2, stage_reads=True, bounds=(), parts=None):
             yield (it, "update_Mu", "Mu_mean"), np.array(m.get_state()["Mu_mean"])
         m.update_X(1, N)
         if stage_reads:
-            yield (it, "update_X", "X"), np.array(m.get_state()["X"])
+            g = m.get_state()
+            yield (it, "update_X", "X"), np.array(g["X"])
+            if rowvar:
+                yield (it, "update_X", "X_rowvar"), np.array(_pca_rowvar(g))
         m.update_Beta()
         g = m.get_state()
         for nm in PCA_NAMES:
             yield (it, "update_Beta", nm), np.array(g[nm])
+        if rowvar:
+            yield (it, "update_Beta", "X_rowvar"), np.array(_pca_rowvar(g))
         for mode in bounds:     # the parts [5] of the bound after the iteration (parts: pca_handle_parts(m) for a handle)
             yield (it, "bound", mode), np.array((parts or m.elbo_parts)(mode))
 
@@ -829,3 +845,299 @@ def _pca_reference(N, d, q):
         e64[kx] = rel(a64, ax)
         ax.setflags(write=False)
     return max(d, q, N), ext, e64, mx.st, bnd
+
+
+# ----------------------------------------------------------------------------------------------------------------------------
+# VB-PCA, row by row
+# ----------------------------------------------------------------------------------------------------------------------------
+# rel() over the whole [N, d] array loses an observed entry overwritten by its prediction (which differs from the data by the
+# noise) and the one missing entry of an otherwise observed row being off by 1e-10 of itself.  Here every row is a named
+# pattern, its missing entries are measured in units of the row's largest one, its z in units of the row's largest latent, its
+# variance relative to itself, and its observed entries are held bitwise to the data (P.update_X pins them the same way).
+#
+# What the patterns are aimed at (pyvb_amd/csrc/k_pca.hip): the mask is read one 32-bit word per lane, four entries at a
+# time; a wavefront owns 32-column blocks of two 16-column tiles; a pair of k_pca_pairs splits the row at column 128.
+# Row n takes pattern n mod 16; index 0 is a partly observed one because row 0 is the row the crawl order updates alone,
+# before Mu (its other variants are an argument of pca_rows_problem).
+PCA_ROW_PATTERNS = ("Bernoulli", "all", "one known, first", "one known, last", "one missing, first", "one missing, last",
+                    "a byte of a word", "a word", "a tile", "a block", "alternating", "upper half", "low half", "the seam",
+                    "the last tile", "observed")
+
+
+def pca_pattern_mask(name, d, rng=None):
+    """[d] bool, true = missing, of a named pattern at width d; None where the pattern is empty or degenerate there: nothing
+    missing (but for "observed"), everything missing (but for "all"), or a seam without both its columns.  A pattern that
+    reaches beyond d is cut off at d.  rng: for "Bernoulli" (0.3, redrawn in one entry so that the row is partly observed)."""
+    k = np.arange(d)
+    if name == "Bernoulli":
+        if d < 2:
+            return None
+        m = (rng if rng is not None else np.random.default_rng(d)).random(d) < 0.3
+        if not m.any():
+            m[d // 2] = True
+        if m.all():
+            m[d // 2] = False
+        return m
+    m = {"all": lambda: k >= 0, "one known, first": lambda: k != 0, "one known, last": lambda: k != d - 1,
+         "one missing, first": lambda: k == 0, "one missing, last": lambda: k == d - 1,
+         "a byte of a word": lambda: k == 5, "a word": lambda: (k >= 4) & (k < 8), "a tile": lambda: (k >= 16) & (k < 32),
+         "a block": lambda: (k >= 32) & (k < 64), "alternating": lambda: k % 2 == 0, "upper half": lambda: k >= d // 2,
+         "low half": lambda: k < 128, "the seam": lambda: (k == 127) | (k == 128),
+         "the last tile": lambda: k >= 16 * ((d - 1) // 16), "observed": lambda: k < 0}[name]()
+    if (name != "all" and m.all()) or (name != "observed" and not m.any()) or (name == "the seam" and m.sum() != 2):
+        return None
+    return m
+
+
+def _pca_row_patterns(N, d, rng):
+    """(miss [N, d], the label of every row).  A pattern that is degenerate at d is replaced by the nearest one in
+    PCA_ROW_PATTERNS that is not (the lower index first), and the label says so: "all (for a block)"."""
+    L = len(PCA_ROW_PATTERNS)
+    miss, names = np.zeros((N, d), dtype=bool), []
+    for n in range(N):
+        p = n % L
+        for off in range(L):
+            m, name = None, None
+            for cand in (p - off, p + off):
+                if 0 <= cand < L and m is None:
+                    name = PCA_ROW_PATTERNS[cand]
+                    m = pca_pattern_mask(name, d, rng)
+            if m is not None:
+                break
+        miss[n] = m
+        names.append(name if off == 0 else "%s (for %s)" % (name, PCA_ROW_PATTERNS[p]))
+    return miss, names
+
+
+def pca_has_column_patterns(N, d):
+    """where N and d allow, two column patterns lie over the rows: column d // 3 is missing in every row, and column 2 is
+    observed by row 8 only"""
+    return N > 8 and d >= 3 and d // 3 != 2
+
+
+def pca_rows_problem(N, d, q, row0="partial", unpinned=False):
+    """(init, pri, labels): pca_problem(N, d, q) -- its data, its initial W, Z, Z_cov, Mu, beta_b, its priors -- with the mask
+    replaced by the named row patterns and the two column patterns (pca_has_column_patterns).  The data are the complete
+    matrix pca_problem draws before it hides entries; the initial means of the missing entries are standard normal, as there.
+    row0: "partial" (its pattern, the default), "missing" or "observed" -- the X_0 step with something, everything or nothing
+    to impute; an observed row 0 is exempt from the column patterns (it then is the one row that observes column d // 3).
+    unpinned: init["X_full"] [N, d] standard normal and init["X_var0"] [N] positive -- rows that are not fully observed carry
+    that mean at ALL entries until their first update (P.make_state, PCABatch.from_problem read both)."""
+    assert row0 in ("partial", "missing", "observed")
+    init, pri = pca_problem(N, d, q)
+    # the complete data: the first draws of make_golden.pca_problem, replayed (held to its observed entries below)
+    g = np.random.default_rng(1000 + N + d)
+    W = g.standard_normal((d, q)); Z = g.standard_normal((N, q)); mean = g.standard_normal(d)
+    X = Z @ W.T + mean + g.standard_normal((N, d)) * np.sqrt(1.0 / 20.0)
+    assert np.array_equal(X[init["obs"]], init["X"][init["obs"]])
+    rng = np.random.default_rng(7000 + 3 * N + d)
+    miss, names = _pca_row_patterns(N, d, rng)
+    if row0 == "missing":
+        miss[0], names[0] = True, "all (row 0)"
+    elif row0 == "observed":
+        miss[0], names[0] = False, "observed (row 0)"
+    if pca_has_column_patterns(N, d):
+        keep = miss[0].copy()
+        miss[:, d // 3] = True
+        miss[:, 2] = True
+        miss[8, 2] = False
+        if row0 == "observed":
+            miss[0] = keep
+    init["obs"] = ~miss
+    init["X"] = np.where(miss, rng.standard_normal((N, d)), X)
+    if unpinned:
+        init["X_full"] = rng.standard_normal((N, d))
+        init["X_var0"] = 1.0 / rng.uniform(0.2, 1.0, N)
+    return init, pri, names
+
+
+def _rows_case(N, d, q, sweeps, **kw):
+    c = dict(N=N, d=d, q=q, sweeps=tuple(sweeps), row0="partial", unpinned=False, iters=2, schedules=(True, False), bounds=True)
+    c.update(kw)
+    return c
+
+
+_LONG = dict(iters=1, schedules=(False,))       # one iteration, read at its end only
+# name -> the case; N of the long ones is a function of the device's CU count (256 on MI355X, and in the CPU tests).
+# sweeps: the kinds of PCABatch.set_sweep the case runs under; schedules: stage_reads of pca_trace (True: a read after every
+# stage, so pass 1 and pass 2 run apart; False: a read at the end of the iteration, which lets the fused sweeps run lazily and
+# makes the read go through k_pca_materialize).  What each reaches in k_pca.hip:
+PCA_ROW_CASES = {
+    # pairs<true> without padding; the seam with both halves full; a ragged last tile (6 rows) in a chunk of its own
+    "n70_d256_q16":     _rows_case(70, 256, 16, ("store", "columns", "pairs")),
+    # pairs<true> with 15 padded columns in tile 15; 5 rows in the last tile
+    "n37_d241_q16":     _rows_case(37, 241, 16, ("columns", "pairs")),
+    # pairs<false>, DT = 15: the j < DT test inside half 1's last block; padded latent indices
+    "n70_d240_q7":      _rows_case(70, 240, 7, ("columns", "pairs")),
+    # DT = 9: half 1 owns one real column; pass12 with five wavefronts, the last with one tile
+    "n40_d129_q16":     _rows_case(40, 129, 16, ("store", "columns", "pairs")),
+    # DT = 8: half 1 owns nothing and still exchanges its partial
+    "n33_d128_q5":      _rows_case(33, 128, 5, ("columns", "pairs")),
+    "n20_d17_q1":       _rows_case(20, 17, 1, ("store", "columns", "pairs")),       # DT = 2, q = 1
+    "n16_d64_q16":      _rows_case(16, 64, 16, ("store", "columns")),               # exactly one full tile
+    "n15_d1_q1":        _rows_case(15, 1, 1, ("store", "columns")),                 # d = 1: the patterns degenerate to all / observed
+    # QT = 2 (no lazy sweep): the two sides of the DT >= 13 chunk rule; pass1<2>, pass2<2, false>, pass12<2, false>
+    "n35_d208_q17":     _rows_case(35, 208, 17, ("store",)),
+    "n37_d209_q32":     _rows_case(37, 209, 32, ("store",)),
+    # (d = 208 and 209 are DT = 13 and 14, both on the upper side of the rule; DT = 12 is d = 192.  At these N the tile count
+    # caps the chunks on either side, so the rule shows in the partition only; tests/test_pca_rows_cpu.py holds that)
+    "n35_d192_q17":     _rows_case(35, 192, 17, ("store",)),
+    # rows that wait for their first update: pass2<1, true>, pass12<1, true>, pass2<2, true>, pass12<2, true>
+    "n40_d129_q16_unpinned": _rows_case(40, 129, 16, ("store",), unpinned=True),
+    "n35_d208_q17_unpinned": _rows_case(35, 208, 17, ("store",), unpinned=True),
+    # the X_0 step and keep_z0 with nothing, or everything, to impute
+    "n70_d256_q16_row0_missing":  _rows_case(70, 256, 16, ("columns", "pairs"), row0="missing"),
+    "n70_d256_q16_row0_observed": _rows_case(70, 256, 16, ("columns", "pairs"), row0="observed"),
+    # several tiles a chunk: a pair of k_pca_pairs goes on to a second tile (the ring of register sets and the flag counters
+    # across tiles), k_pca_pass12 takes three steps of two tiles; a ragged last chunk
+    "long_d256_q16":    _rows_case(lambda ncu: 80 * ncu + 24, 256, 16, ("columns", "pairs"), **_LONG),
+    # pairs<false>: pair 0 does three tiles, so the three-ahead ring wraps entirely inside it
+    "long_d32_q16":     _rows_case(lambda ncu: 144 * ncu + 8, 32, 16, ("pairs",), **_LONG),
+    # (81 and 145 rows a CU round up to six and ten tiles a chunk.)  24 rows below 80 a CU it is FIVE: k_pca_pass12 ends on a step
+    # with one tile of its two, pair 0 of k_pca_pairs has a second tile and its three neighbours have none.  Rows and quantities
+    # only: the bound of this size is the case above's, and half the time of a long reference goes into its four evaluations.
+    "long_d256_q16_five_tiles": _rows_case(lambda ncu: 80 * ncu - 24, 256, 16, ("columns", "pairs"), bounds=False, **_LONG),
+}
+PCA_ROW_QUANTITIES = ("X", "Z", "X_rowvar")
+
+
+@functools.lru_cache(maxsize=None)
+def pca_rows_case(name, ncu=256):
+    """The case with its problem: N resolved, init, pri, patterns (the label of every row), miss [N, d], has (rows with a
+    missing entry).  Computed once per process; the arrays are read-only."""
+    c = dict(PCA_ROW_CASES[name])
+    c["name"] = name
+    if callable(c["N"]):
+        c["N"] = int(c["N"](ncu))
+    c["init"], c["pri"], c["patterns"] = pca_rows_problem(c["N"], c["d"], c["q"], row0=c["row0"], unpinned=c["unpinned"])
+    c["miss"] = ~c["init"]["obs"]
+    c["has"] = c["miss"].any(axis=1)
+    c["n"] = max(c["d"], c["q"], c["N"])
+    for v in list(c["init"].values()) + list(c["pri"].values()) + [c["miss"], c["has"]]:
+        if isinstance(v, np.ndarray):
+            v.setflags(write=False)
+    return c
+
+
+def is_pca_rows_key(key):
+    return key[2] in PCA_ROW_QUANTITIES
+
+
+def pca_row_errors(name, got, ext, miss):
+    """[N] of a row quantity against the extended run's, each row in its own unit.  X: max over the row's missing entries of
+    |got - ext| over the largest missing-entry magnitude of ext (row_errors, for all rows at once); NaN for a row without
+    missing entries.  Z: max |z - z_ext| over max |z_ext| of the row.  X_rowvar: |v - v_ext| / |v_ext|, NaN for a row without
+    missing entries."""
+    got, ext = np.asarray(got, dtype=LD), np.asarray(ext, dtype=LD)
+    tiny = LD(1e-300)
+    if name == "X":
+        e = np.where(miss, np.abs(got - ext), LD(0)).max(axis=1) / np.maximum(np.where(miss, np.abs(ext), LD(0)).max(axis=1), tiny)
+        return np.where(miss.any(axis=1), e, np.nan).astype(float)
+    if name == "Z":
+        return (np.abs(got - ext).max(axis=1) / np.maximum(np.abs(ext).max(axis=1), tiny)).astype(float)
+    assert name == "X_rowvar"
+    return np.where(miss.any(axis=1), np.abs(got - ext) / np.maximum(np.abs(ext), tiny), np.nan).astype(float)
+
+
+def _pca_oracle(c, long, make=None):
+    init = {k: (v.copy() if isinstance(v, np.ndarray) else v) for k, v in c["init"].items()}
+    pri = dict(c["pri"])
+    return (make or OraclePCA)(to_long(init) if long else init, to_long(pri) if long else pri, c["N"], c["d"], c["q"])
+
+
+def pca_float64_rows(name, make=None, ncu=256):
+    """[(key, array)] of a fresh run of the float64 oracle through the case's trace, read after every stage where the case has
+    that schedule, without the bounds.  make(init, pri, N, d, q): the oracle to drive -- tests/test_pca_rows_cpu.py runs OraclePCA
+    with a defect planted in update_X."""
+    c = pca_rows_case(name, ncu)
+    return list(pca_trace(_pca_oracle(c, False, make), c["N"], iters=c["iters"], stage_reads=True in c["schedules"], rowvar=True))
+
+
+@functools.lru_cache(maxsize=None)
+def pca_rows_reference(name, ncu=256):
+    """A case of PCA_ROW_CASES run by both oracles: a dict with n = max(d, q, N); ext {key: long-double array} and e64 {key: the
+    float64 oracle's distance from it} as pca_reference has them (X_rowvar among the quantities); rows {key: [N] of pca_row_errors
+    of the float64 oracle} for X, Z and X_rowvar wherever the trace reads them; bound {key: (ext [1, 5], e64, own)} as
+    pca_bound_reference, both modes (empty for a case without bounds).  The oracles are read after every stage where the case has that schedule: a read changes
+    nothing in an oracle, so the keys of the end-of-iteration schedule are among these with the same values.  Computed once
+    per process, never modified."""
+    require_extended()
+    c = pca_rows_case(name, ncu)
+    kw = dict(iters=c["iters"], stage_reads=True in c["schedules"], bounds=BOUND_MODES if c["bounds"] else (), rowvar=True)
+    m64, mx = _pca_oracle(c, False), _pca_oracle(c, True)
+    ext, e64, rows, bnd = {}, {}, {}, {}
+    for (k64, a64), (kx, ax) in zip(pca_trace(m64, c["N"], **kw), pca_trace(mx, c["N"], **kw)):
+        assert k64 == kx and ax.dtype == LD, (k64, kx, ax.dtype)
+        if is_bound(kx):
+            ax = ax[None]
+            ax.setflags(write=False)
+            bnd[kx] = (ax,) + bound_errors(a64, ax)
+            continue
+        ext[kx] = ax
+        if kx[2] == "X_rowvar":         # (zero on the observed rows: measured where a row has a missing entry)
+            e64[kx] = rel(a64[c["has"]], ax[c["has"]]) if c["has"].any() else 0.0
+        else:
+            e64[kx] = rel(a64, ax)
+        ax.setflags(write=False)
+        if is_pca_rows_key(kx):
+            rows[kx] = pca_row_errors(kx[2], a64, ax, c["miss"])
+    return dict(n=c["n"], ext=ext, e64=e64, rows=rows, bound=bnd)
+
+
+def compare_pca_rows(name, trace, tag=None, ncu=256):
+    """X, Z and X_rowvar of a trace (a handle's, or an oracle's; pca_trace with rowvar=True) against pca_rows_reference(name), row
+    by row wherever the trace reads them.  Returns [(key, 0, row, pattern, e64_row, e_row, e_row / yardstick(e64_row, n), pinned)],
+    the layout of compare_rows, so that offending_rows() picks the rows that are out of order: the distances are
+    pca_row_errors' (0 for X and X_rowvar of a row without missing entries); pinned: the observed entries of the row of X -- all
+    of a fully observed row -- are bitwise the data (true for Z and X_rowvar, which have no pin).  Every X the trace reads
+    comes after an update of all rows, so rows that start unpinned have been conditioned by then.
+    Prints every row that is out of order and one line that names the worst row: every row of every read would be some
+    600 000 lines for the whole of tests/test_pca_rows_gpu.py."""
+    c = pca_rows_case(name, ncu)
+    ref = pca_rows_reference(name, ncu)
+    tag = tag or name
+    miss, n, pats, data = c["miss"], c["n"], c["patterns"], c["init"]["X"]
+    out = []
+    for key, arr in trace:
+        if is_bound(key) or not is_pca_rows_key(key):
+            continue
+        assert np.all(np.isfinite(arr)), "%s: non-finite values in %r" % (tag, key)
+        e64r = np.nan_to_num(ref["rows"][key], nan=0.0)
+        e = np.where(np.isnan(ref["rows"][key]), 0.0, pca_row_errors(key[2], arr, ref["ext"][key], miss))
+        ratio = e / np.maximum(e64r, n * U64)
+        if key[2] == "X":
+            same = np.ascontiguousarray(arr, dtype=np.float64).view(np.int64) == np.ascontiguousarray(data).view(np.int64)
+            pinned = (same | miss).all(axis=1)
+        else:
+            pinned = np.ones(c["N"], dtype=bool)
+        out += [(key, 0, r, pats[r], float(e64r[r]), float(e[r]), float(ratio[r]), bool(pinned[r])) for r in range(c["N"])]
+    bad = offending_rows(out)
+    for r in bad:
+        print("%-44s it%d %-11s %-8s row %5d %-30s e64 %.2e  e_row %.2e  e_row/y %6.2f%s%s"
+              % (tag, r[0][0], r[0][1], r[0][2], r[2], r[3], r[4], r[5], r[6], "" if r[7] else "  <-- observed entries not pinned", "" if r[6] <= FACTOR else "  <-- over"))
+    if out:
+        w = max(out, key=lambda r: r[6] if r[6] == r[6] else np.inf)
+        print("%-44s ROWS N %d, %d reads  max e64 %.2e  max e_row %.2e  max e_row/y %.2f (it%d %s %s row %d, %s)  pins lost %d"
+              % (tag, c["N"], len(out) // c["N"], max(r[4] for r in out), max(r[5] for r in out), w[6], w[0][0], w[0][1], w[0][2], w[2], w[3], sum(not r[7] for r in out)))
+    return out
+
+
+def compare_pca_with_rows_reference(name, trace, ncu=256):
+    """The whole-array quantities and the parts of the bound of a trace against pca_rows_reference(name):
+    ([(None, key, e64, e_gpu, ratio)], [(key, 0, part index, e64, e_gpu, ratio, own)]) as compare_with_rows_reference."""
+    c = pca_rows_case(name, ncu)
+    ref = pca_rows_reference(name, ncu)
+    out, bnd = [], []
+    for key, arr in trace:
+        if is_bound(key):
+            ext, e64, _ = ref["bound"][key]
+            bnd += [(key,) + row for row in compare_bound(arr, ext, e64, ref["n"])]
+            continue
+        assert np.all(np.isfinite(arr)), "%s: non-finite values in %r" % (name, key)
+        if key[2] == "X_rowvar":
+            arr, ext = arr[c["has"]], ref["ext"][key][c["has"]]
+            e_gpu = rel(arr, ext) if arr.size else 0.0
+        else:
+            e_gpu = rel(arr, ref["ext"][key])
+        out.append((None, key, ref["e64"][key], e_gpu, e_gpu / yardstick(ref["e64"][key], ref["n"])))
+    return out, bnd
