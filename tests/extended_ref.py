@@ -27,6 +27,11 @@ patterns (_missing_rows), in the envelope's order and in orders of their own (ld
 VB-PCA is measured row by row too (compare_pca_rows): X over a row's missing entries, Z over the row, X_rowvar, each in the row's own
 unit and by the same rule, the observed entries of X bitwise the data -- on cases whose rows are named patterns aimed at the mask
 words, tiles, blocks and halves of the sweeps (PCA_ROW_PATTERNS, PCA_ROW_CASES, pca_rows_reference).
+
+The 128-wide LDS class is measured tile by tile (BIG_CASES, tile_errors, compare_tiles): the last two axes of every matrix
+quantity cut into 16 x 16 tiles, the states into the 16-entry tile of each node, each tile in units of its own largest entry
+of the extended run, e_tile <= FACTOR max(e64_tile, n 2^-52) with e64_tile <= CAP; a tile that is exactly zero in the extended
+run is exactly zero on the handle, and the known entries of A and C are held bitwise (known_offenders).
 """
 import functools
 import importlib.util
@@ -301,7 +306,74 @@ WARMUP_CASES = [k for k, v in LDS_CASES.items() if v[1]]
 EXACT_BOUND_CASES = [k for k in LDS_CASES if k not in ("t2402_d64_k64_w1", "t600_d72_k66_big_w3")]
 
 
+# ----------------------------------------------------------------------------------------------------------------------------
+# the 128-wide class, 64 < max(D, K) <= 128, at every tile count (tests/test_big_envelope_cpu.py, tests/test_big_envelope_gpu.py)
+# ----------------------------------------------------------------------------------------------------------------------------
+def _q2(c):
+    """Where max(D, K) > 102 the column prior precisions are 1e-2: det(1e-3 I) underflows from 103 dimensions on and the float64
+    oracle's bound is -inf (quirk Q2; tests/test_gpu_parity.py: test_stagewise_vs_oracle_beyond_64 does the same)."""
+    D, K = c["st0"]["A_mean"].shape[1], c["Y"].shape[2]
+    if max(D, K) > 102:
+        c["pri"]["A_prior_prec"] = np.full_like(c["pri"]["A_prior_prec"], 1e-2)
+        c["pri"]["C_prior_prec"] = np.full_like(c["pri"]["C_prior_prec"], 1e-2)
+    return c
+
+
+def _known_at_block_edges(T, D, K, seed):
+    """_known (entries (0, 0), (1, 0), (3, 2) and the whole column 4 of A; entry (2, 1) and the whole column 3 of C; column 0 of C
+    free) with known entries of both matrices on either side of the edges of k_cols_big's 16-column blocks: columns 15, 16, 17
+    and 95, and column 96, the one column of the last block at D = 97; the last row of A and of C among them."""
+    c = _known(T, D, K, 1, seed)
+    assert D == 97
+    A_obs, C_obs = c["pri"]["A_obs"], c["pri"]["C_obs"]
+    for j, col in enumerate((15, 16, 17, 95, 96)):
+        A_obs[[7 * j + 3, 16 * j + 15, 16 * j + 16], col] = (0.05 * (j + 1), -0.1, 0.02 * (j - 2))
+        C_obs[[11 * j + 1, 16 * j + 31, 16 * j + 32], col] = (0.5 - 0.25 * j, 1.5, -0.75)
+    # the last row of each.  Entry (last row, 96) stays free: it is a tile of its own, and a tile of known entries alone has no unit
+    # -- the oracle conditions on them by formula and leaves a rounding residue where the handle has 0.0 (known_offenders holds that)
+    A_obs[D - 1, 95] = 0.125; A_obs[D - 1, 16] = -0.0625
+    C_obs[K - 1, 16] = 2.0; C_obs[K - 1, 95] = -1.0
+    assert np.isnan(C_obs[:, 0]).all() and not np.isnan(A_obs[:, 4]).any() and np.isnan(A_obs[D - 1, 96]) and np.isnan(C_obs[K - 1, 96])
+    return c
+
+
+# name -> (builder, in the warm-up contract?).  Two iterations and N = 1 unless the name or the builder says otherwise.  What
+# each is there for (pyvb_amd/csrc/k_big.hip, k_wishart_big.hip; tests/test_big_envelope_cpu.py holds the counts):
+BIG_CASES = {
+    # full width, nothing padded: eight real tiles in every kernel, every tile pair of k_stats_big; 33 interior nodes: Lseg = 3,
+    # eleven live segment columns and five idle; statistics chunks of 12, 12 and 11 rows
+    "t35_d128_k128":        (lambda: _q2(_plain(35, 128, 128, 1, 201)), True),
+    # D & 3 != 0: the scalar stores of Sigma in k_prep_big; K odd: k_gy_big<false> and its clamped loads; one padded row in state
+    # tile 7, one real row in output tile 7; chunks of 16 and 11 rows
+    "t27_d127_k113":        (lambda: _q2(_plain(27, 127, 113, 1, 202)), True),
+    # the smallest shape of the class, one real row in tile 4; two replicates: the strides of the gains block, scratch, trash
+    "t27_d65_k65_n2":       (lambda: _q2(_plain(27, 65, 65, 2, 203)), True),
+    # isotropic noise on the two-wavefront k_noise<2> / k_elbo<2>; one real row in state tile 7
+    "t27_d113_k81_gamma":   (lambda: _q2(_gamma(27, 113, 81, 1, 204)), False),
+    # k_cols_big for C with wavefronts 1..3 owning no row; K odd and below one tile pair
+    "t27_d128_k17":         (lambda: _q2(_plain(27, 128, 17, 1, 205)), True),
+    # D <= 64 < K: two column blocks against 128 rows, Syx row tiles up to 7 against state tiles 0 and 1
+    "t27_d17_k128":         (lambda: _q2(_plain(27, 17, 128, 1, 206)), True),
+    # known entries of A and C at the block edges of k_cols_big.  The seed: the reference's bound takes ln(det) of a partly known
+    # column's covariance over its free entries (gaussian.py:150; 93 to 112 of them here), which float64 represents only between
+    # 1e-308 and 1e308 -- the same hazard as quirk Q2.  With this draw the determinants are within 1e-225 .. 1e218 after both
+    # iterations; with seeds 207, 209, 214, 215, 219 one underflows after the first and the float64 oracle's L_C is -inf.
+    "t27_d97_k113_known":   (lambda: _q2(_known_at_block_edges(27, 97, 113, 218)), False),
+    # gj_wg128 with 128 real pivots in k_wexpect_big and k_cols_wishart_big, covb_pos with RT = 16 -- on the Q side, then on the R side
+    "t20_d128_k81_wishart": (lambda: _q2(_wishart(20, 128, 81, 1, 301, iters=1)), False),
+    "t20_d97_k128_wishart": (lambda: _q2(_wishart(20, 97, 128, 1, 302, iters=1)), False),
+    # columns that warm up from zero at full width; run at W = 1 and at W = 2 (parts of 304 and 294 nodes, Lseg = 19: the warm-up
+    # crosses a part border, with the forward sweep's own c_t buffer) against this one reference
+    "t600_d128_k128_warm":  (lambda: dict(_q2(_plain(600, 128, 128, 1, 208)), iters=1, splits=(1, 2)), True),
+}
+BIG_WARMUP_CASES = [k for k, v in BIG_CASES.items() if v[1]]
+BIG_SPLITS = {"t600_d128_k128_warm": (1, 2)}        # the forced time splits a case is run at (its "splits")
+BIG_EXACT_BOUND_CASES = ["t35_d128_k128", "t27_d127_k113"]      # the others reach no further instantiation of k_elbo<2>
+
+
 def lds_case(name):
+    if name in BIG_CASES:
+        return BIG_CASES[name][0]()
     return ROW_CASES[name]() if name in ROW_CASES else LDS_CASES[name][0]()
 
 
@@ -468,9 +540,15 @@ def lds_bound_reference(name):
     return _lds_reference(name)[1]
 
 
+def lds_tile_reference(name):
+    """[{key: e64 by tile (tile_errors of the float64 oracle)}], one dict per entry of lds_reference(name), from the same two
+    runs; for the cases of BIG_CASES."""
+    return _lds_reference(name)[2]
+
+
 @functools.lru_cache(maxsize=None)
 def _lds_reference(name):
-    """([(rows, T, n, ext, e64, recurrences, run)], [bound records]) for a case: one entry for the whole batch, or one per replicate when the
+    """([(rows, T, n, ext, e64, recurrences, run)], [bound records], [tile records]) for a case: one entry for the whole batch, or one per replicate when the
     replicates have lengths of their own.  ext: {key: long-double array}; e64: {key: distance of the float64 oracle from it};
     recurrences: per iteration (F, B) [N, D, D] of the extended run; run: the extended OracleLDS as the last stage left it.
     Computed once per process, never modified."""
@@ -478,11 +556,11 @@ def _lds_reference(name):
     c = lds_case(name)
     D, K = c["st0"]["A_mean"].shape[1], c["Y"].shape[2]
     missing = bool(np.isnan(c["Y"]).any())
-    runs, bounds = [], []
+    runs, bounds, tiles = [], [], []
     for rows, T, Y, st0 in _problems(c):
         m64 = OracleLDS(Y.copy(), {k: v.copy() for k, v in st0.items()}, c["pri"])
         mx = OracleLDS(to_long(Y), to_long(st0), to_long(c["pri"]))
-        ext, e64, bnd = {}, {}, {}
+        ext, e64, bnd, til = {}, {}, {}, {}
         for (k64, a64), (kx, ax) in zip(lds_trace(m64, c["iters"], missing, BOUND_MODES), lds_trace(mx, c["iters"], missing, BOUND_MODES)):
             assert k64 == kx and ax.dtype == LD, (k64, kx, ax.dtype)
             if is_bound(kx):
@@ -492,9 +570,13 @@ def _lds_reference(name):
             ext[kx] = _cut(kx, ax, None, T)
             e64[kx] = rel(_cut(k64, a64, None, T), ext[kx])
             ext[kx].setflags(write=False)
+            if name in BIG_CASES and kx[2] in TILE_QUANTITIES:
+                til[kx] = tile_errors(_cut(k64, a64, None, T), ext[kx], kx[2])
+                til[kx].setflags(write=False)
         runs.append((rows, T, max(D, K, T), ext, e64, mx.recurrences, mx))
         bounds.append(bnd)
-    return runs, bounds
+        tiles.append(til)
+    return runs, bounds, tiles
 
 
 def compare_with_reference(name, handle_trace):
@@ -674,6 +756,113 @@ def compare_with_rows_reference(name, trace, updates=None, skip_bound=()):
         e_gpu = rel(got, ref["ext"][key])
         out.append((None, key, ref["e64"][key], e_gpu, e_gpu / yardstick(ref["e64"][key], ref["n"])))
     return out, bnd
+
+
+# ----------------------------------------------------------------------------------------------------------------------------
+# the 128-wide class, tile by tile
+# ----------------------------------------------------------------------------------------------------------------------------
+# rel() is a maximum over a whole array.  An off-diagonal 16 x 16 tile of Sigma, or of a column-variance block, is small beside
+# the diagonal, and the kernels of the 128-wide class deal their work out by such tiles: four wavefronts own two row tiles each of
+# the recurrence matrices, k_stats_big forms every pair of the eight state tiles once and stores its mirror, the column pass runs
+# over blocks of 16 columns.  One tile wrong by 1e-10 of itself does not move the max-norm.  Here every tile is measured in units
+# of its own largest entry of the extended run.
+TILE = 16
+TILE_MATRICES = ("Sigma", "A_mean", "C_mean", "A_colvar", "C_colvar", "Q_w", "R_w", "A_cov", "C_cov")
+TILE_QUANTITIES = TILE_MATRICES + ("X",)
+
+
+def _tile_max(a, axes):
+    """max |a| over 16-wide tiles of each of `axes` (the last one or two), a ragged last tile where the extent is no multiple of
+    16: the padding is zero, which changes no maximum of absolute values"""
+    a = np.abs(a)
+    pad = [(0, 0)] * a.ndim
+    for ax in axes:
+        pad[ax] = (0, -a.shape[ax] % TILE)
+    a = np.pad(a, pad)
+    for ax in sorted((ax % a.ndim for ax in axes), reverse=True):      # from the last axis: the earlier positions stay
+        a = a.reshape(a.shape[:ax] + (a.shape[ax] // TILE, TILE) + a.shape[ax + 1:]).max(axis=ax + 1)
+    return a
+
+
+def tile_errors(got, ext, name="matrix"):
+    """float64 [..., ceil(R / 16), ceil(C / 16)] for a matrix quantity [..., R, C] ([..., T, ceil(D / 16)] for name "X" [..., T, D]):
+    per tile max |got - ext| / max |ext|, both over the tile.  A tile that is exactly zero in the extended run measures 0.0 if it
+    is exactly zero in `got` too and inf if it is not."""
+    got, ext = np.asarray(got, dtype=LD), np.asarray(ext, dtype=LD)
+    assert got.shape == ext.shape, (name, got.shape, ext.shape)
+    axes = (-1,) if name == "X" else (-2, -1)
+    d, u = _tile_max(got - ext, axes), _tile_max(ext, axes)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        e = np.where(u == 0, np.where(d == 0, LD(0), LD(np.inf)), d / u)
+    return e.astype(float)
+
+
+def compare_tiles(name, trace, tag=None):
+    """The tiles of a trace (a handle's, or an oracle's) against lds_reference(name) / lds_tile_reference(name), for every quantity
+    of TILE_QUANTITIES after every stage that yields it.  Returns [(run, key, e64 by tile, e by tile, e / yardstick(e64, n) by
+    tile)], the three arrays shaped as tile_errors gives them; a tile is in order when its ratio is at most FACTOR
+    (offending_tiles) -- a tile that is zero in the extended run and not in the trace has ratio inf.  Prints one line per key."""
+    out = []
+    for key, arr in trace:
+        if is_bound(key) or key[2] not in TILE_QUANTITIES:
+            continue
+        for (rows, T, n, ext, _, _, _), til in zip(lds_reference(name), lds_tile_reference(name)):
+            got = _cut(key, arr, rows, T)
+            assert np.all(np.isfinite(got)), "%s: non-finite values in %r" % (name, key)
+            e = tile_errors(got, ext[key], key[2])
+            with np.errstate(invalid="ignore"):
+                ratio = np.where(e == 0, 0.0, e / np.maximum(til[key], n * U64))
+            out.append((rows, key, til[key], e, ratio))
+            w = np.unravel_index(int(np.argmax(np.where(np.isnan(ratio), np.inf, ratio))), ratio.shape)
+            print("%-28s %-4s it%d %-15s %-9s TILES %6d  max e64 %.2e  max e_tile %.2e  max e_tile/y %6.2f at %r%s"
+                  % (tag or name, "" if rows is None else "r%d" % rows, key[0], key[1], key[2], e.size, til[key].max(), e.max(), ratio[w],
+                     tuple(int(i) for i in w), "" if ratio[w] <= FACTOR else "  <-- %d over" % int((~(ratio <= FACTOR)).sum())))
+    return out
+
+
+def offending_tiles(rows):
+    """[(run, key, tile index, e64, e, ratio)] of the tiles of compare_tiles' result that are beyond FACTOR x yardstick"""
+    return [(r, key, tuple(int(i) for i in idx), float(e64[idx]), float(e[idx]), float(ratio[idx]))
+            for r, key, e64, e, ratio in rows for idx in zip(*np.nonzero(~(ratio <= FACTOR)))]
+
+
+def known_offenders(which, mean, colvar, obs):
+    """[(which, replicate, row, column, what)] of the known entries of A or C (obs [rows, D], NaN = not known) that are not held:
+    the mean [N, rows, D] bitwise the given value, the variance (colvar [N, D, rows], column first) exactly 0.0."""
+    known = ~np.isnan(obs)
+    mean, colvar = np.ascontiguousarray(mean, dtype=np.float64), np.asarray(colvar, dtype=np.float64)
+    bad = []
+    for n in range(mean.shape[0]):
+        same = mean[n].view(np.int64) == np.ascontiguousarray(obs, dtype=np.float64).view(np.int64)
+        bad += [(which, n, int(i), int(j), "mean") for i, j in zip(*np.nonzero(known & ~same))]
+        bad += [(which, n, int(i), int(j), "variance") for i, j in zip(*np.nonzero(known & ~(colvar[n].T == 0.0)))]
+    return bad
+
+
+class PinnedHandleLDS(HandleLDS):
+    """HandleLDS that checks the known entries of A and C after every update_A / update_C: self.pins collects known_offenders'
+    findings, self.pin_checks counts the entries looked at."""
+
+    def __init__(self, b, pri):
+        HandleLDS.__init__(self, b)
+        self.obs = {w: pri.get(w + "_obs") for w in ("A", "C")}
+        self.pins, self.pin_checks = [], 0
+
+    def _check(self, w):
+        """(a partly known column is conditioned at its own update, not before: each matrix is looked at after its own)"""
+        obs = self.obs[w]
+        if obs is not None:
+            g = self.b.get_state((w + "_mean", w + "_colvar"))
+            self.pins += known_offenders(w, g[w + "_mean"], g[w + "_colvar"], obs)
+            self.pin_checks += int((~np.isnan(obs)).sum()) * self.b.N
+
+    def update_A(self):
+        self.b.update_A()
+        self._check("A")
+
+    def update_C(self):
+        self.b.update_C()
+        self._check("C")
 
 
 # ----------------------------------------------------------------------------------------------------------------------------
