@@ -1,6 +1,8 @@
-// Host side of libpyvb_hip.so: handle lifetime, host<->device copies, the dependency tracking that
-// decides which kernels a node-level call needs, timing, and the RCCL all-reduce of the lower bound.
+// Host side of libpyvb_hip.so: handle lifetime, argument checks, host<->device copies, the streams of pyvb_lds_iterate, timing,
+// and the RCCL all-reduce of the lower bound.  The dependency tracking that decides which kernels a node-level call needs is
+// lds_flow.h (over LdsState of lds_state.h), instantiated here over the launchers.
 #include "common.h"
+#include "lds_flow.h"
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -270,25 +272,62 @@ static int join_elbo(pyvb_lds* h);
 // pyvb_lds_iterate may have left in flight on the side stream (it reads states and parameters).
 #define ENTER(h) do { ENTER_DEVICE(h); if ((h)->elbo_in_flight) { int _rc = join_elbo(h); if (_rc) return _rc; } } while (0)
 
-// every replicate switched off: the update entries are successful no-ops without a launch
-#define IDLE(h) do { if ((h)->rep.n_active() == 0) return PYVB_OK; } while (0)
-
-// Rows of switched-off replicates sit out the two ping-pongs of the handle: the X buffers (a sweep reads one and writes the
-// other) and the covariance classes (k_prep writes Sigma_new, adopt_classes swaps).  They stay where they were when the row
-// was switched off, and are copied across here, before a getter reads every row, before a setter or a staging copy uses the
-// other X buffer, and before the mask changes -- never on the update path.
-static int settle_parked(pyvb_lds* h) {
-    if (h->rep.n_active() == h->N) return PYVB_OK;
-    int rc;
-    if (h->st.x_park != h->st.cur && (rc = launch_carry(h, h->X[h->st.x_park], h->X[h->st.cur], (size_t)h->T * h->L.DP))) return rc;
-    if (h->st.cls_parked_other) {
+// ---- Which kernels a call launches, and the events it raises, is LdsFlow of lds_flow.h: one copy, compiled here over the
+// launchers and in tests/c/lds_flow_driver.cpp over a recorder.  LdsDevice is what it drives here: every method is one launcher.
+static int launch_parents(pyvb_lds* h, int kind, int which, bool derive);
+static int form_lnd_x(pyvb_lds* h);
+struct LdsDevice {
+    typedef hipStream_t stream_t;
+    pyvb_lds* h;
+    hipStream_t main_stream() const { return h->stream; }
+    int prep() { return launch_prep(h); }
+    int in_gains() { return launch_in_gains(h); }
+    int wexpect() { return launch_wexpect(h); }
+    int dense_pre() { return launch_dense_pre(h); }
+    int sweep(int direction, int src, bool read_cache, bool keep_x) { return launch_sweep(h, direction, src, read_cache, keep_x); }
+    int step(int t) { return launch_step(h, t); }
+    int stats(bool with_sxx) { return launch_stats(h, with_sxx); }
+    int moments(bool sxx_from_sweep) { return launch_moments(h, sxx_from_sweep); }
+    int tie_moments() { return launch_tie(h, h->mom, (size_t)3 * h->D * h->D + (size_t)h->K * h->D + h->D); }
+    int tie_syy() { return launch_tie(h, h->Syy, h->K); }
+    int in_moments() { return launch_in_moments(h); }
+    int in_HA() { return launch_in_HA(h); }
+    int in_colsB() { return launch_in_colsB(h); }
+    int in_resQ() { return launch_in_resQ(h); }
+    int resid(int which) { return launch_resid(h, which); }
+    int wresid(int which, int update, bool use_sg) { return launch_wresid(h, which, update, use_sg); }
+    int cols(int which, int c0, int c1, int fuse = 0) { return launch_cols(h, which, c0, c1, fuse); }
+    int cols_dense(int which, int c0, int c1) { return launch_cols_dense(h, which, c0, c1); }
+    int noise(int which) { return launch_noise(h, which); }
+    int parents(int kind, int which, bool derive) { return launch_parents(h, kind, which, derive); }
+    int syy() { return launch_syy(h); }
+    int syy_missing() { return launch_syy_missing(h); }
+    int syy_full() { return launch_syy_full(h); }
+    int missing_ent_dense(int diag_cov) { return launch_missing_ent_dense(h, diag_cov); }
+    int impute() { return launch_impute(h); }
+    int impute_dense() { return launch_impute_dense(h); }
+    int elbo(hipStream_t stream) { return launch_elbo(h, stream); }
+    int in_elbo(hipStream_t stream) { return launch_in_elbo(h, stream); }
+    int elbo_dense() { return launch_elbo_dense(h); }
+    int carry_x(int src) { return launch_carry(h, h->X[src], h->X[1 - src], (size_t)h->T * h->L.DP); }
+    int carry_classes() {
+        int rc;
         if ((rc = launch_carry(h, h->Sigma_new, h->Sigma, (size_t)3 * h->D * h->D))) return rc;
         if ((rc = launch_carry(h, h->qld_x_new, h->qld_x, 3))) return rc;
-        if ((rc = launch_carry(h, h->lnd_x_new, h->lnd_x, 3))) return rc;
+        return launch_carry(h, h->lnd_x_new, h->lnd_x, 3);
     }
-    h->st.parked_here();
-    return PYVB_OK;
+    void swap_classes() {
+        double* t = h->Sigma; h->Sigma = h->Sigma_new; h->Sigma_new = t;
+        t = h->qld_x; h->qld_x = h->qld_x_new; h->qld_x_new = t;
+        t = h->lnd_x; h->lnd_x = h->lnd_x_new; h->lnd_x_new = t;
+    }
+    int join_elbo() { return ::join_elbo(h); }
+    int form_lnd_x() { return ::form_lnd_x(h); }
+};
+static LdsFlow<LdsDevice> flow(pyvb_lds* h) {
+    return {h->st, {h->T, h->N, h->D, h->P, h->dense, h->big, h->has_missing, h->bound, h->inputs_set, h->input_priors_set, &h->rep, h->parents}, {h}};
 }
+static int settle_parked(pyvb_lds* h) { return flow(h).settle_parked(); }
 
 static int h2d(pyvb_lds* h, double* dst, const double* src, size_t n) { return to_device(h->stream, dst, src, n); }
 static int d2h(pyvb_lds* h, double* dst, const double* src, size_t n) { return to_host(h->stream, dst, src, n); }
@@ -454,8 +493,7 @@ static int update_parents(pyvb_lds* h, int which, int kind) {
     int rc = parents_gate(h, which, kind);
     if (rc) return rc;
     ENTER(h);
-    IDLE(h);
-    return launch_parents(h, kind, which, false);
+    return flow(h).update_parents(which, kind);
 }
 
 int pyvb_lds_set_column_precisions(pyvb_lds* h, int which, const double* a0, const double* b0, const double* qb) {
@@ -599,24 +637,6 @@ int pyvb_lds_set_column_observations(pyvb_lds* h, const double* A_obs, const dou
     return PYVB_OK;
 }
 
-static int ensure_expect(pyvb_lds* h);
-// sum_t <y^2> per chain, then summed over the chains of every model (k_tie.hip: once per production, it is in place)
-static int syy(pyvb_lds* h) {
-    const int rc = launch_syy(h);
-    return rc ? rc : launch_tie(h, h->Syy, h->K);
-}
-static int syy_missing(pyvb_lds* h) {
-    const int rc = launch_syy_missing(h);
-    return rc ? rc : launch_tie(h, h->Syy, h->K);
-}
-// Wishart noise, after the means of the outputs changed: sum_t qmu qmu^T, and the entropy terms of the rows that are not
-// fully observed (diag_cov: they still carry their diagonal initial covariances, whose sum is formed here too)
-static int outputs_changed_dense(pyvb_lds* h, int diag_cov) {
-    int rc;
-    if ((rc = launch_syy_full(h))) return rc;
-    return launch_missing_ent_dense(h, diag_cov);
-}
-
 int pyvb_lds_set_observations(pyvb_lds* h, const double* Y) {
     ENTER(h);
     ARGCHK(Y, "Y is NULL");
@@ -660,11 +680,11 @@ int pyvb_lds_set_observations(pyvb_lds* h, const double* Y) {
         h->has_missing = true;
         // rows with NaN start as N(0, I) until pyvb_lds_set_output_state says otherwise
         if ((rc = launch_missing_init(h, nullptr, nullptr))) return rc;
-        if ((rc = h->dense ? outputs_changed_dense(h, 1) : syy_missing(h))) return rc;
+        if ((rc = h->dense ? flow(h).outputs_changed_dense(1) : flow(h).syy_missing())) return rc;
     } else {
         h->has_missing = false;
         if ((rc = h2d(h, h->Y, Y, n))) return rc;
-        if ((rc = syy(h))) return rc;
+        if ((rc = flow(h).syy())) return rc;
         if (h->P && (rc = launch_in_assemble(h))) return rc;       // the rows [y_t ; u_t ; u_{t+1}] the sweeps read
         if (h->dense && (rc = launch_syy_full(h))) return rc;
     }
@@ -686,7 +706,7 @@ int pyvb_lds_set_output_state(pyvb_lds* h, const double* Yq, const double* Yrowv
     double* dv = h->X[1 - h->st.cur];      // [N][T][DP] >= [N][T]
     int rc;
     if ((rc = h2d(h, dq, Yq, n)) || (rc = h2d(h, dv, Yrowvar, (size_t)h->N * h->T)) ||
-        (rc = launch_missing_init(h, dq, dv)) || (rc = h->dense ? outputs_changed_dense(h, 1) : syy_missing(h))) {
+        (rc = launch_missing_init(h, dq, dv)) || (rc = h->dense ? flow(h).outputs_changed_dense(1) : flow(h).syy_missing())) {
         if (tmp) { (void)hipStreamSynchronize(h->stream); (void)hipFree(tmp); }
         return rc;
     }
@@ -717,19 +737,7 @@ int pyvb_lds_get_outputs(pyvb_lds* h, double* Yq, double* Yvar, double* Yqld) {
 
 int pyvb_lds_update_Y(pyvb_lds* h) {
     ENTER(h);
-    if (!h->has_missing) return PYVB_OK;            // observed nodes never update (gaussian.py:109-110)
-    IDLE(h);
-    int rc;
-    if (h->dense) {
-        if ((rc = ensure_expect(h))) return rc;     // E[R] and its log-determinant
-        if ((rc = launch_impute_dense(h))) return rc;
-        if ((rc = outputs_changed_dense(h, 0))) return rc;
-    } else {
-        if ((rc = launch_impute(h))) return rc;
-        if ((rc = syy_missing(h))) return rc;
-    }
-    h->st.outputs_changed();
-    return PYVB_OK;
+    return flow(h).update_Y();
 }
 
 // ---- A known input that drives the states (pyvb_lds_create_inputs; the kernels are k_inputs.hip)
@@ -806,15 +814,11 @@ int pyvb_lds_get_input_state(pyvb_lds* h, double* B_mean, double* B_colvar, doub
     return pyvb_lds_sync(h);
 }
 
-static int ensure_stats(pyvb_lds* h);
 int pyvb_lds_update_B(pyvb_lds* h) {
     int rc = inputs_gate(h);
     if (rc) return rc;
     ENTER(h);
-    IDLE(h);
-    if ((rc = ensure_stats(h)) || (rc = launch_in_colsB(h))) return rc;
-    h->st.columns_updated(0, false);        // as a column of A: the gains and the residual of Q depend on it
-    return PYVB_OK;
+    return flow(h).update_B();
 }
 
 int pyvb_lds_set_state(pyvb_lds* h, const double* X, const double* A_mean, const double* A_colvar,
@@ -845,9 +849,7 @@ int pyvb_lds_set_state(pyvb_lds* h, const double* X, const double* A_mean, const
     const bool covs = h->dense && (A_colvar || C_colvar);       // diagonal initial covariances
     if (covs && (rc = launch_colvar_to_cov(h))) return rc;
     HIPCHK(hipStreamSynchronize(h->stream));
-    if (X) h->st.x_changed();
-    if (covs) h->st.columns_changed();
-    else if (A_mean || A_colvar || C_mean || C_colvar || Q_b || R_b) h->st.parameters_changed();
+    flow(h).state_given(X, covs, A_mean || A_colvar || C_mean || C_colvar || Q_b || R_b);
     return PYVB_OK;
 }
 
@@ -950,21 +952,10 @@ int pyvb_lds_get_warmup(pyvb_lds* h, int* warm) {
     return pyvb_lds_sync(h);
 }
 
-// ---- recomputing what an event dropped (LdsState, host.h; the table is in DESIGN.md) ---------
-static int ensure_expect(pyvb_lds* h) {        // E[Q], E[R] of the current Wishart posteriors
-    if (h->st.expect_valid) return PYVB_OK;
-    int rc = launch_wexpect(h);
-    if (rc) return rc;
-    h->st.expect_valid = true;
-    return PYVB_OK;
-}
-
-// Covariances of the X_t given by pyvb_lds_set_posterior_classes: ln det of each (Cholesky on the host, NaN where one is not
-// positive definite), formed once, when the exact bound or pyvb_lds_get_logdets first needs it -- not on the default path.
-static int ensure_lnd_x(pyvb_lds* h) {
-    if (!h->st.lnd_x_pending) return PYVB_OK;
+// ln det of every class of Sigma (Cholesky on the host, NaN where one is not positive definite) into lnd_x: what
+// LdsFlow::ensure_lnd_x has carried out when Sigma came from the caller
+static int form_lnd_x(pyvb_lds* h) {
     const size_t N = h->N, D = h->D;
-    { int rc0 = settle_parked(h); if (rc0) return rc0; }       // every row of Sigma is read, every row of lnd_x written
     std::vector<double> S(N * 3 * D * D), lnd(N * 3), L(D * D);
     HIPCHK(hipMemcpyAsync(S.data(), h->Sigma, S.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
@@ -986,161 +977,37 @@ static int ensure_lnd_x(pyvb_lds* h) {
     }
     HIPCHK(hipMemcpyAsync(h->lnd_x, lnd.data(), lnd.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
-    h->st.lnd_x_pending = false;
-    return PYVB_OK;
-}
-
-// a handle with inputs before it has them: the updates would read zeros for u_t and for the parents of B
-static int inputs_ready(const pyvb_lds* h) {
-    ARGCHK(h->inputs_set, "the handle was created with inputs: call pyvb_lds_set_inputs before the first update");
-    ARGCHK(h->input_priors_set, "the handle was created with inputs: call pyvb_lds_set_input_priors before the first update");
-    return PYVB_OK;
-}
-
-static int ensure_gains(pyvb_lds* h) {
-    if (h->st.gains_valid) return PYVB_OK;
-    int rc;
-    if (h->dense) {
-        if ((rc = ensure_expect(h))) return rc;
-        if ((rc = launch_dense_pre(h))) return rc;
-    }
-    if (h->P && (rc = inputs_ready(h))) return rc;
-    if ((rc = launch_prep(h))) return rc;
-    if (h->P && (rc = launch_in_gains(h))) return rc;      // the gains of the input channels, from Sigma_1 as k_prep has just left it
-    h->st.gains_formed();
-    return PYVB_OK;
-}
-
-// The posterior covariance classes that the statistics use are those of the X_t's LAST update; they switch to the freshly
-// prepared ones once every X_t has been updated under the current parameters (LdsState::node_fresh / all_fresh say when).
-static void adopt_classes(pyvb_lds* h) {
-    double* t = h->Sigma; h->Sigma = h->Sigma_new; h->Sigma_new = t;
-    t = h->qld_x; h->qld_x = h->qld_x_new; h->qld_x_new = t;
-    t = h->lnd_x; h->lnd_x = h->lnd_x_new; h->lnd_x_new = t;
-    h->st.classes_adopted(h->rep.n_active() < h->N);
-}
-
-static int ensure_stats(pyvb_lds* h) {
-    LdsState& st = h->st;
-    if (st.stats_valid) return PYVB_OK;
-    if (!st.classes_valid) {
-        // the reference's X_t start with individual random covariances (gaussian.py:70-72); the three-class form the
-        // statistics use exists once every X_t has been updated, or once the caller has supplied the classes
-        pyvb_set_error("the posterior covariances of the X_t are undefined before the first complete sweep "
-                       "(run pyvb_lds_sweep, or give them with pyvb_lds_set_posterior_classes)");
-        return PYVB_E_STALE;
-    }
-    if (st.mixed_cov || (st.gains_valid && st.fresh_count != 0 && st.fresh_count != h->T)) {
-        pyvb_set_error("%d of %d X_t were updated since the parameters changed: their covariances differ; sweep all states first",
-                       st.fresh_count, h->T);
-        return PYVB_E_STALE;
-    }
-    int rc = launch_stats(h, !st.sxx_valid);
-    if (rc) return rc;
-    if ((rc = launch_moments(h, st.sxx_valid))) return rc;
-    if ((rc = launch_tie(h, h->mom, (size_t)3 * h->D * h->D + (size_t)h->K * h->D + h->D))) return rc;        // chains that share A, C, Q, R: the moments of a model
-    if (h->P && ((rc = inputs_ready(h)) || (rc = launch_in_moments(h)))) return rc;       // Sxu, Su1x; Sx1x aside
-    st.stats_valid = true;
-    return PYVB_OK;
-}
-
-static int ensure_resid(pyvb_lds* h, int which) {
-    bool& valid = which == 0 ? h->st.resQ_valid : h->st.resR_valid;
-    if (valid) return PYVB_OK;
-    int rc = ensure_stats(h);
-    if (rc) return rc;
-    if (h->P && which == 0) {       // H_A of the current <B>, the residual as k_cols forms it, the terms of <B> alone
-        if ((rc = launch_in_HA(h)) || (rc = launch_resid(h, 0)) || (rc = launch_in_resQ(h))) return rc;
-    } else if ((rc = h->dense ? launch_wresid(h, which, 0, h->st.sg_valid[which]) : launch_resid(h, which))) return rc;
-    valid = true;
-    return PYVB_OK;
-}
-
-static int sweep(pyvb_lds* h, int direction, bool keep_x) {
-    int rc = ensure_gains(h);
-    if (rc) return rc;
-    // a backward sweep right behind a forward one reads the c_t that one left in U; the 128-wide class fuses no Sxx
-    const bool read_cache = direction == PYVB_BACKWARD && h->st.u_valid;
-    if ((rc = launch_sweep(h, direction, h->st.cur, read_cache, keep_x))) return rc;
-    h->st.sweep_ran(direction, read_cache, !h->big);
-    if (h->st.all_fresh()) adopt_classes(h);
     return PYVB_OK;
 }
 
 int pyvb_lds_sweep(pyvb_lds* h, int direction) {
     ENTER(h);
     ARGCHK(direction == PYVB_FORWARD || direction == PYVB_BACKWARD, "direction must be PYVB_FORWARD or PYVB_BACKWARD");
-    IDLE(h);
-    return sweep(h, direction, true);
+    return flow(h).update_sweep(direction);
 }
 
 int pyvb_lds_update_x(pyvb_lds* h, int t) {
     ENTER(h);
     ARGCHK(t >= 0 && t < h->T, "t out of range");
-    IDLE(h);
-    int rc = ensure_gains(h);
-    if (rc) return rc;
-    if ((rc = launch_step(h, t))) return rc;
-    h->st.x_changed();
-    if (h->st.node_fresh(t)) adopt_classes(h);
-    return PYVB_OK;
+    return flow(h).update_x(t);
 }
 
 int pyvb_lds_update_columns(pyvb_lds* h, int which, int col_begin, int col_end) {
     ENTER(h);
     ARGCHK(which == 0 || which == 1, "which must be 0 (A) or 1 (C)");
     ARGCHK(col_begin >= 0 && col_begin < col_end && col_end <= h->D, "bad column range");
-    IDLE(h);
-    int rc = ensure_stats(h);
-    if (rc) return rc;
-    if (h->dense) {
-        if ((rc = ensure_expect(h))) return rc;
-        if ((rc = launch_cols_dense(h, which, col_begin, col_end))) return rc;
-    } else {
-        if (h->P && which == 0 && (rc = launch_in_HA(h))) return rc;       // H = Sx1x - <B> Su1x
-        if ((rc = launch_cols(h, which, col_begin, col_end))) return rc;
-    }
-    h->st.columns_updated(which, h->dense && col_begin == 0 && col_end == h->D);
-    return PYVB_OK;
+    return flow(h).update_columns(which, col_begin, col_end);
 }
 
 int pyvb_lds_update_A(pyvb_lds* h) { ARGCHK(h, "handle is NULL"); return pyvb_lds_update_columns(h, 0, 0, h->D); }
 int pyvb_lds_update_C(pyvb_lds* h) { ARGCHK(h, "handle is NULL"); return pyvb_lds_update_columns(h, 1, 0, h->D); }
 
-static int update_noise(pyvb_lds* h, int which) {
-    int rc;
-    if (h->dense) {     // Wishart.update: the residual matrix and qw = w0 + it in one launch
-        if ((rc = ensure_stats(h))) return rc;
-        if ((rc = launch_wresid(h, which, 1, h->st.sg_valid[which]))) return rc;
-    } else {
-        if ((rc = ensure_resid(h, which))) return rc;
-        if ((rc = launch_noise(h, which))) return rc;
-    }
-    h->st.noise_updated(which);
-    return PYVB_OK;
-}
-
-int pyvb_lds_update_Q(pyvb_lds* h) { ENTER(h); IDLE(h); return update_noise(h, 0); }
-int pyvb_lds_update_R(pyvb_lds* h) { ENTER(h); IDLE(h); return update_noise(h, 1); }
-
-// k_elbo, and on a handle with inputs the columns of B into part 2 behind it
-static int lds_bound(pyvb_lds* h, hipStream_t stream) {
-    const int rc = launch_elbo(h, stream);
-    return rc || !h->P ? rc : launch_in_elbo(h, stream);
-}
+int pyvb_lds_update_Q(pyvb_lds* h) { ENTER(h); return flow(h).update_noise(0); }
+int pyvb_lds_update_R(pyvb_lds* h) { ENTER(h); return flow(h).update_noise(1); }
 
 int pyvb_lds_elbo(pyvb_lds* h) {
     ENTER(h);
-    IDLE(h);
-    int rc;
-    if ((rc = ensure_resid(h, 0))) return rc;
-    if ((rc = ensure_resid(h, 1))) return rc;
-    if (h->bound == PYVB_BOUND_EXACT && (rc = ensure_lnd_x(h))) return rc;
-    if (h->dense) {
-        if ((rc = ensure_expect(h))) return rc;
-        return launch_elbo_dense(h);
-    }
-    return lds_bound(h, h->stream);
+    return flow(h).elbo();
 }
 
 int pyvb_lds_get_elbo(pyvb_lds* h, double* parts) {
@@ -1161,63 +1028,22 @@ static int join_elbo(pyvb_lds* h) {
     return PYVB_OK;
 }
 
-// The updates of one iteration: forward sweep, backward sweep, A, C, Q, R (the example's loop body, Linear_Dynamic_System.py:70-79)
-static int iterate_updates(pyvb_lds* h) {
-    int rc;
-    // the backward sweep follows at once and reads c_t, not the forward states: those are not written out
-    if ((rc = sweep(h, PYVB_FORWARD, false))) return rc;
-    if ((rc = join_elbo(h))) return rc;
-    if ((rc = sweep(h, PYVB_BACKWARD, true))) return rc;
-    // A and C are independent given the statistics, and so are Q and R given A and C: the pairs
-    // share launches here (same arithmetic as update_A, update_C, update_Q, update_R in turn)
-    if ((rc = ensure_stats(h))) return rc;
-    if (h->dense) {
-        if ((rc = ensure_expect(h))) return rc;
-        if ((rc = launch_cols_dense(h, 2, 0, h->D))) return rc;
-        h->st.columns_updated(2, true);
-        if ((rc = launch_wresid(h, 2, 1, true))) return rc;    // both residual matrices and both qw = w0 + residual
-        h->st.noise_updated(2);
-        if ((rc = ensure_expect(h))) return rc;                // E[Q], E[R] of the new posteriors: the bound and the next k_prep read them
-    } else if (h->P) {
-        // As, Bs, Cs, Q, R: B sees the new A, Q the new A and B; C and R do not depend on them and keep their shared launch
-        if ((rc = launch_in_HA(h)) || (rc = launch_cols(h, 0, 0, h->D))) return rc;
-        if ((rc = launch_in_colsB(h))) return rc;
-        if ((rc = launch_cols(h, 1, 0, h->D, 3))) return rc;
-        h->st.columns_updated(2, false);
-        h->st.noise_updated(1);
-        if ((rc = ensure_resid(h, 0)) || (rc = launch_noise(h, 0))) return rc;
-        h->st.noise_updated(0);
-    } else {
-        if ((rc = launch_cols(h, 2, 0, h->D, 3))) return rc;       // columns, residuals and noise update in one launch
-        h->st.columns_updated(2, false);
-        h->st.noise_updated(2);
-        // [al.update() for al in alphas]: they read their own column and feed the next column update only, so they commute with Q
-        // and R.  They sit behind the join_elbo above like k_cols: the bound of the iteration before reads qb and qa / qb.
-        // Then [dg.update() for dg in ...]: the DiagonalGamma parents of the matrices that have those instead, in the same place.
-        for (int kind = PARENTS_GAMMA; kind <= PARENTS_DIAGONAL_GAMMA; ++kind) {
-            const int which = parents_of_kind(h->parents, kind);     // both matrices of a kind: one launch
-            if (which >= 0 && (rc = launch_parents(h, kind, which, false))) return rc;
-        }
-    }
-    if (h->bound == PYVB_BOUND_EXACT && (rc = ensure_lnd_x(h))) return rc;       // (only before the first complete sweep)
-    return PYVB_OK;
-}
-
 int pyvb_lds_iterate(pyvb_lds* h, int niters) {
     ENTER_DEVICE(h);
     ARGCHK(niters >= 0, "niters must be >= 0");
     int rc;
     // Every replicate switched off: no update is launched, but the (empty) sums still go into the history and through the
     // all-reduce, which the other ranks are waiting in.
-    const bool idle = h->rep.n_active() == 0;
+    LdsFlow<LdsDevice> f = flow(h);
+    const bool idle = f.idle();
     for (int it = 0; it < niters; ++it) {
-        if ((rc = idle ? join_elbo(h) : iterate_updates(h))) return rc;
+        if ((rc = idle ? join_elbo(h) : f.iterate_updates())) return rc;
         // The lower bound (network.py:49) feeds nothing in the next iteration: it is evaluated on the side stream while
         // the main one goes on with k_prep and the forward sweep.  Its per-iteration totals (summed over the replicates,
         // and over the ranks when a communicator is attached) go into a history ring (pyvb_lds_get_elbo_history).
         HIPCHK(hipEventRecord(h->ev_params, h->stream));
         HIPCHK(hipStreamWaitEvent(h->side, h->ev_params, 0));
-        if (!idle && (rc = h->dense ? launch_elbo_dense(h, h->side) : lds_bound(h, h->side))) return rc;
+        if (!idle && (rc = h->dense ? launch_elbo_dense(h, h->side) : f.lds_bound(h->side))) return rc;
         double* slot = h->elbo_hist + (size_t)(h->hist_count % PYVB_ELBO_HISTORY) * 8;
         if ((rc = launch_elbo_sum(h, slot, h->side))) return rc;
         if (h->comm && (rc = pyvb_allreduce_f64(h->comm, slot, 6, h->side))) return rc;
@@ -1250,12 +1076,13 @@ static int iterate_until(pyvb_lds* h, int max_iters, double tol, int check_every
     int rc, it = 0;
     // Nothing to run on this rank: no update is launched, but with a communicator the totals and the running count (0 here)
     // still go through the all-reduce the other ranks are waiting in, until every rank has stopped.
-    const bool idle = h->rep.n_active() == 0;
+    LdsFlow<LdsDevice> f = flow(h);
+    const bool idle = f.idle();
     bool done = idle && !h->comm;
     while (!done && it < max_iters) {
         if (!idle) {
-            if ((rc = iterate_updates(h))) return rc;
-            if ((rc = h->dense ? launch_elbo_dense(h, h->stream) : lds_bound(h, h->stream))) return rc;
+            if ((rc = f.iterate_updates())) return rc;
+            if ((rc = h->dense ? launch_elbo_dense(h, h->stream) : f.lds_bound(h->stream))) return rc;
             if ((rc = launch_converge(h, tol, it == 0, h->stream))) return rc;
         }
         double* slot = h->elbo_hist + (size_t)(h->hist_count % PYVB_ELBO_HISTORY) * 8;
@@ -1274,7 +1101,7 @@ static int iterate_until(pyvb_lds* h, int max_iters, double tol, int check_every
     *iters_run = it;
     HIPCHK(hipStreamSynchronize(h->stream));
     HIPCHK(hipStreamSynchronize(h->side));
-    // the host record: which replicates the test has frozen, and with that how many are left for IDLE, settle_parked and
+    // the host record: which replicates the test has frozen, and with that how many are left for idle(), settle_parked and
     // adopt_classes.  The rows frozen in this call are identical in both X buffers and both class sets, so x_park /
     // cls_parked_other are right for them whatever they say.
     std::vector<unsigned char> conv((size_t)h->N);
@@ -1353,7 +1180,7 @@ int pyvb_lds_get_logdets(pyvb_lds* h, double* lnd_x, double* lnd_A, double* lnd_
     ENTER(h);
     int rc;
     if ((rc = settle_parked(h))) return rc;
-    if (lnd_x && (rc = ensure_lnd_x(h))) return rc;
+    if (lnd_x && (rc = flow(h).ensure_lnd_x())) return rc;
     if ((rc = d2h(h, lnd_x, h->lnd_x, (size_t)h->N * 3))) return rc;
     if ((rc = d2h(h, lnd_A, h->lnd_A, (size_t)h->N * h->D))) return rc;
     if ((rc = d2h(h, lnd_C, h->lnd_C, (size_t)h->N * h->D))) return rc;
