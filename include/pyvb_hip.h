@@ -29,6 +29,7 @@
  *   Sigma[N][3][D][D], qld_x[N][3]     posterior covariance / q_ln_det of X_0, X_interior, X_{T-1}
  *   elbo parts [N][6] = L_X, L_Y, L_A, L_C, L_Q, L_R
  *   handles with P inputs (pyvb_lds_create_inputs): U[N][T][P], B_mean[N][D][P] (row, col), B_colvar[N][P][D] (column i, entry k)
+ *   handles with Pv regressors (pyvb_lds_create_regressors): V[N][T][Pv], E_mean[N][K][Pv] (row, col), E_colvar[N][Pv][K] (column i, entry k)
  */
 #ifndef PYVB_HIP_H
 #define PYVB_HIP_H
@@ -75,7 +76,8 @@ enum { PYVB_FORWARD = 0, PYVB_BACKWARD = 1 };
 /* which kernels pyvb_lds_timing_get() reports on */
 enum { PYVB_K_PREP = 0, PYVB_K_SWEEP_FWD = 1, PYVB_K_STATS = 2, PYVB_K_PARAMS = 3, PYVB_K_STEP = 4,
        PYVB_K_SWEEP_BWD = 5, PYVB_K_ELBO = 6, PYVB_K_GY = 7 /* 128-wide class: G y_t ahead of a sweep */,
-       PYVB_K_INPUTS = 8 /* handles with inputs: the kernels of k_inputs.hip */, PYVB_K_COUNT = 9 };
+       PYVB_K_INPUTS = 8 /* handles with inputs: the kernels of k_inputs.hip */,
+       PYVB_K_REGRESSORS = 9 /* handles with regressors: the kernels of k_regressors.hip */, PYVB_K_COUNT = 10 };
 
 const char* pyvb_last_error(void);
 int pyvb_version(void);
@@ -174,6 +176,46 @@ int pyvb_lds_set_input_priors(pyvb_lds* h, const double* B_prior_mean, const dou
 int pyvb_lds_set_input_state(pyvb_lds* h, const double* B_mean, const double* B_colvar);
 int pyvb_lds_get_input_state(pyvb_lds* h, double* B_mean, double* B_colvar, double* qld_B, double* lnd_B);
 int pyvb_lds_update_B(pyvb_lds* h);
+
+/* Known regressors in the output equation: replicate n is the graph of Linear_Dynamic_System.py:46-66 with
+ *     Y_t = Gaussian(K, C * X_t + E * Constant(v_t), R),   E = hstack(Es),   t = 0 .. T_n - 1
+ * -- an Addition of two Multiplications as the mean parent of the observed Y_t (node.py:52-129, :182-276), v_t a known Pv-vector
+ * (v_t = 1: an output offset; v_t = u_t: direct feedthrough of an input; a seasonal or covariate regressor), E [K x Pv] with
+ * independent Gaussian columns and Constant parents like C's (hstack.pass_up_m1_m2, nodes_todo.py:43-62).  P >= 0 are the inputs
+ * that drive the states, as pyvb_lds_create_inputs takes them (0: none; the six input entries then refuse the handle); Pv >= 1.
+ * lengths[N] as pyvb_lds_create_lengths takes it, or NULL: every chain has T nodes.
+ *   pyvb_lds_set_regressors        V[N][T][Pv]: row t enters y_t, row 0 included.  The rows t >= T_n are never read and may hold
+ *                                  anything finite.  Call before the first update; a later call replaces the regressors.
+ *   pyvb_lds_get_regressors        V as given.
+ *   pyvb_lds_set_regressor_priors  E_prior_mean[K][Pv] (row, col), E_prior_prec[Pv][K] (column i, diagonal entry k), positive;
+ *                                  shared by the replicates as C's are.
+ *   pyvb_lds_set_regressor_state   E_mean[N][K][Pv] (row, col), E_colvar[N][Pv][K] (column i, entry k); NULL = leave.
+ *   pyvb_lds_get_regressor_state   the same, and q_ln_det / ln det qcov of the columns, qld_E[N][Pv], lnd_E[N][Pv] (NaN before a
+ *                                  column's first update); NULL = skip.
+ *   pyvb_lds_update_E              [e.update() for e in Es]: G = sum_t v_t v_t^T, H = sum_t y_t v_t^T - <C> sum_t mu_t v_t^T,
+ *                                  row precisions <R>.
+ * Everything else serves the handle as it stands, with the regressors' terms: pyvb_lds_sweep and pyvb_lds_update_x (the message of
+ * Y_t is <C>^T <R> (y_t - <E> v_t)), pyvb_lds_update_C / _columns(1, ..) (H = Syx - <E> sum_t v_t mu_t^T), pyvb_lds_update_R (the
+ * second moment of the mean parent, Addition.pass_down_ExxT node.py:121-129), pyvb_lds_elbo in both modes (L_Y with that residual;
+ * the columns of E add to part 3 what the columns of C do, so parts stay [N][6]), pyvb_lds_iterate, pyvb_lds_iterate_until and
+ * pyvb_lds_iterate_until_model (forward, backward, As, [Bs], Cs, Es, Q, R, bound), chain lengths, every time split, the activity
+ * mask (a switched-off replicate keeps its E), status, communicators.
+ * The regressors ride through the sweeps as Pv extra output channels behind the 2 P of the inputs (k_regressors.hip), hence the
+ * limit of this route, the only cap on Pv: max(D, K + 2 P + Pv) <= 64.
+ * PYVB_E_UNSUPPORTED before any HIP call / launch, the message naming the regressors and the cause: Wishart noise;
+ * max(D, K + 2 P + Pv) > 64; outputs that hold NaN (pyvb_lds_set_observations); known entries of A / C
+ * (pyvb_lds_set_column_observations); Gamma / DiagonalGamma precision parents (pyvb_lds_set_column_precisions,
+ * pyvb_lds_set_entry_precisions); shared models are not offered (pyvb_lds_create_tied takes no regressors).
+ * PYVB_E_ARG: Pv < 1; P < 0; NULL or non-finite V (the message names replicate, row and channel); a non-positive E_prior_prec; any
+ * of the six entries on a handle created without regressors; an update before pyvb_lds_set_regressors and
+ * pyvb_lds_set_regressor_priors. */
+int pyvb_lds_create_regressors(pyvb_lds** out, int device, int N, int T, int D, int K, int P, int Pv, int noise_kind, const int* lengths);
+int pyvb_lds_set_regressors(pyvb_lds* h, const double* V);
+int pyvb_lds_get_regressors(pyvb_lds* h, double* V);
+int pyvb_lds_set_regressor_priors(pyvb_lds* h, const double* E_prior_mean, const double* E_prior_prec);
+int pyvb_lds_set_regressor_state(pyvb_lds* h, const double* E_mean, const double* E_colvar);
+int pyvb_lds_get_regressor_state(pyvb_lds* h, double* E_mean, double* E_colvar, double* qld_E, double* lnd_E);
+int pyvb_lds_update_E(pyvb_lds* h);
 
 /* Constant parents (node.py:279-311), shared by all replicates:
  *   x0_mean[D], x0_prec[D][D]                     Gaussian(q, pmu, pprec) for X_0  (:58)

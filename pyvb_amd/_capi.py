@@ -22,7 +22,7 @@ PARENTS = ("constant", "gamma", "diagonal_gamma")
 PCA_SWEEP_STORE, PCA_SWEEP_COLUMNS, PCA_SWEEP_PAIRS = 0, 1, 2
 PCA_SWEEPS = {"store": PCA_SWEEP_STORE, "columns": PCA_SWEEP_COLUMNS, "pairs": PCA_SWEEP_PAIRS}
 FAIL_STATES, FAIL_COLUMNS, FAIL_NOISE = 1, 2, 4      # PYVB_FAIL_*: bits of pyvb_lds_get_status
-K_PREP, K_SWEEP_FWD, K_STATS, K_PARAMS, K_STEP, K_SWEEP_BWD, K_ELBO, K_GY, K_INPUTS = range(9)
+K_PREP, K_SWEEP_FWD, K_STATS, K_PARAMS, K_STEP, K_SWEEP_BWD, K_ELBO, K_GY, K_INPUTS, K_REGRESSORS = range(10)
 
 _dp = ctypes.POINTER(ctypes.c_double)
 _ip = ctypes.POINTER(ctypes.c_int)
@@ -49,6 +49,13 @@ SIGNATURES = {
     "pyvb_lds_set_input_state": (ctypes.c_int, [_h, _dp, _dp]),
     "pyvb_lds_get_input_state": (ctypes.c_int, [_h, _dp, _dp, _dp, _dp]),
     "pyvb_lds_update_B": (ctypes.c_int, [_h]),
+    "pyvb_lds_create_regressors": (ctypes.c_int, [ctypes.POINTER(_h)] + [ctypes.c_int] * 8 + [_ip]),
+    "pyvb_lds_set_regressors": (ctypes.c_int, [_h, _dp]),
+    "pyvb_lds_get_regressors": (ctypes.c_int, [_h, _dp]),
+    "pyvb_lds_set_regressor_priors": (ctypes.c_int, [_h, _dp, _dp]),
+    "pyvb_lds_set_regressor_state": (ctypes.c_int, [_h, _dp, _dp]),
+    "pyvb_lds_get_regressor_state": (ctypes.c_int, [_h, _dp, _dp, _dp, _dp]),
+    "pyvb_lds_update_E": (ctypes.c_int, [_h]),
     "pyvb_lds_destroy": (ctypes.c_int, [_h]),
     "pyvb_lds_set_priors": (ctypes.c_int, [_h] + [_dp] * 10),
     "pyvb_lds_set_wishart_priors": (ctypes.c_int, [_h, ctypes.c_double, _dp, ctypes.c_double, _dp]),

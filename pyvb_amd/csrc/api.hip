@@ -53,7 +53,7 @@ void pyvb_timing_resolve(pyvb_lds* h) {
 extern "C" {
 
 const char* pyvb_last_error(void) { return g_err; }
-int pyvb_version(void) { return 110; }
+int pyvb_version(void) { return 111; }
 
 int pyvb_device_count(int* count) {
     ARGCHK(count, "count is NULL");
@@ -63,8 +63,9 @@ int pyvb_device_count(int* count) {
 
 // The one creation path; lengths null: every chain has T nodes, model null: every replicate is a model.  Arguments are checked
 // and, where a combination is not served, refused before the first HIP call; *out is written once, when everything exists.
-// P: known inputs that drive the states (pyvb_lds_create_inputs), 0: none.
-static int lds_create(pyvb_lds** out, int device, int N, int T, int D, int K, int noise_kind, const int* lengths, const int* model, int P = 0) {
+// P: known inputs that drive the states (pyvb_lds_create_inputs), 0: none.  Pv: known regressors in the output equation
+// (pyvb_lds_create_regressors), 0: none.
+static int lds_create(pyvb_lds** out, int device, int N, int T, int D, int K, int noise_kind, const int* lengths, const int* model, int P = 0, int Pv = 0) {
     ARGCHK(out, "out is NULL");
     ARGCHK(N >= 1, "N must be >= 1");
     bool ragged = false, tied = false;
@@ -82,11 +83,20 @@ static int lds_create(pyvb_lds** out, int device, int N, int T, int D, int K, in
     ARGCHK(D >= 1 && D <= 128, "latent dimension D must be in 1..128");
     ARGCHK(K >= 1 && K <= 128, "observed dimension K must be in 1..128");
     ARGCHK(noise_kind == PYVB_NOISE_DIAGONAL_GAMMA || noise_kind == PYVB_NOISE_GAMMA || noise_kind == PYVB_NOISE_WISHART, "unknown noise kind");
-    if (P && noise_kind == PYVB_NOISE_WISHART) {
+    if (Pv && noise_kind == PYVB_NOISE_WISHART) {
+        pyvb_set_error("regressors in the output equation are served with DiagonalGamma and Gamma noise only, not with Wishart noise (k_wishart.hip)");
+        return PYVB_E_UNSUPPORTED;
+    }
+    if (Pv && (D > 64 || K + 2 * P + Pv > 64)) {
+        pyvb_set_error("regressors in the output equation ride as Pv extra output channels and are served for max(D, K + 2 P + Pv) <= 64 only, "
+                       "not in the 128-wide class (k_big.hip): D = %d, K = %d, P = %d, Pv = %d", D, K, P, Pv);
+        return PYVB_E_UNSUPPORTED;
+    }
+    if (!Pv && P && noise_kind == PYVB_NOISE_WISHART) {
         pyvb_set_error("inputs that drive the states are served with DiagonalGamma and Gamma noise only, not with Wishart noise (k_wishart.hip)");
         return PYVB_E_UNSUPPORTED;
     }
-    if (P && (D > 64 || K + 2 * P > 64)) {
+    if (!Pv && P && (D > 64 || K + 2 * P > 64)) {
         pyvb_set_error("inputs that drive the states ride as 2 P extra output channels and are served for max(D, K + 2 P) <= 64 only, "
                        "not in the 128-wide class (k_big.hip): D = %d, K = %d, P = %d", D, K, P);
         return PYVB_E_UNSUPPORTED;
@@ -105,9 +115,10 @@ static int lds_create(pyvb_lds** out, int device, int N, int T, int D, int K, in
     ARGCHK(device >= 0 && device < ndev, "no such device");
     HIPCHK(hipSetDevice(device));
     pyvb_lds* h = new pyvb_lds();       // value-initialised: every pointer null, every flag false
-    h->device = device; h->N = N; h->T = T; h->D = D; h->K = K; h->noise = noise_kind; h->P = P;
-    // (with inputs the gains, the statistics and the kernels that form them are those of K + 2 P outputs: k_inputs.hip)
-    const LdsGeometry g = lds_geometry(N, T, D, K + 2 * P, noise_kind);     // geometry.h: the shape class, the chunks, the time split, the extents
+    h->device = device; h->N = N; h->T = T; h->D = D; h->K = K; h->noise = noise_kind; h->P = P; h->Pv = Pv;
+    // (with inputs and regressors the gains, the statistics and the kernels that form them are those of K + 2 P + Pv outputs:
+    // k_inputs.hip, k_regressors.hip)
+    const LdsGeometry g = lds_geometry(N, T, D, K + 2 * P + Pv, noise_kind);     // geometry.h: the shape class, the chunks, the time split, the extents
     h->L = g.L; h->big = g.big; h->dense = g.dense;
     h->nchunk = g.nchunk; h->chunk_len = g.chunk_len; h->W = g.W;
     // (lengths that all equal T, models of one replicate each: a plain handle, len / mstart / first stay null)
@@ -196,8 +207,16 @@ static int lds_create(pyvb_lds** out, int device, int N, int T, int D, int K, in
         TRY(dev_alloc(&h->ldm, n * 2 * D));
     }
     TRYHIP(hipMemset(h->pri.A_obs, 0xFF, ((size_t)D * D + (size_t)K * D) * sizeof(double)));     // all-ones bytes = NaN = nothing observed
+    if (P || Pv) { TRY(dev_alloc(&h->Yt, n * T * (K + 2 * P + Pv))); TRY(dev_alloc(&h->Ct, n * (K + 2 * P + Pv) * D)); }
+    if (Pv) {
+        TRY(dev_alloc(&h->Vin, n * T * Pv));
+        TRY(dev_alloc(&h->E_mean, n * K * Pv)); TRY(dev_alloc(&h->E_var, n * Pv * K));
+        TRY(h->mem.alloc((void**)&h->qld_E, n * Pv * sizeof(double), 0xFF)); TRY(h->mem.alloc((void**)&h->lnd_E, n * Pv * sizeof(double), 0xFF));   // NaN
+        TRY(dev_alloc(&h->E_pm, (size_t)K * Pv)); TRY(dev_alloc(&h->E_pp, (size_t)Pv * K)); TRY(dev_alloc(&h->E_pld, Pv));
+        TRY(dev_alloc(&h->Svv, n * Pv * Pv)); TRY(dev_alloc(&h->Syv, n * K * Pv)); TRY(dev_alloc(&h->rmom, n * ((size_t)Pv * D + (size_t)K * D)));
+    }
     if (P) {
-        TRY(dev_alloc(&h->Uin, n * T * P)); TRY(dev_alloc(&h->Yt, n * T * (K + 2 * P))); TRY(dev_alloc(&h->Ct, n * (K + 2 * P) * D));
+        TRY(dev_alloc(&h->Uin, n * T * P));
         TRY(dev_alloc(&h->B_mean, n * D * P)); TRY(dev_alloc(&h->B_var, n * P * D));
         TRY(h->mem.alloc((void**)&h->qld_B, n * P * sizeof(double), 0xFF)); TRY(h->mem.alloc((void**)&h->lnd_B, n * P * sizeof(double), 0xFF));   // NaN
         TRY(dev_alloc(&h->B_pm, (size_t)D * P)); TRY(dev_alloc(&h->B_pp, (size_t)P * D)); TRY(dev_alloc(&h->B_pld, P));
@@ -236,6 +255,12 @@ int pyvb_lds_create_tied(pyvb_lds** out, int device, int N, int T, int D, int K,
 int pyvb_lds_create_inputs(pyvb_lds** out, int device, int N, int T, int D, int K, int P, int noise_kind, const int* lengths) {
     ARGCHK(P >= 1, "P must be >= 1 (pyvb_lds_create makes a handle without inputs)");
     return lds_create(out, device, N, T, D, K, noise_kind, lengths, nullptr, P);
+}
+
+int pyvb_lds_create_regressors(pyvb_lds** out, int device, int N, int T, int D, int K, int P, int Pv, int noise_kind, const int* lengths) {
+    ARGCHK(Pv >= 1, "Pv must be >= 1 (pyvb_lds_create and pyvb_lds_create_inputs make handles without regressors)");
+    ARGCHK(P >= 0, "P must be >= 0");
+    return lds_create(out, device, N, T, D, K, noise_kind, lengths, nullptr, P, Pv);
 }
 
 int pyvb_lds_get_models(pyvb_lds* h, int* model) {
@@ -308,6 +333,12 @@ struct LdsDevice {
     int impute_dense() { return launch_impute_dense(h); }
     int elbo(hipStream_t stream) { return launch_elbo(h, stream); }
     int in_elbo(hipStream_t stream) { return launch_in_elbo(h, stream); }
+    int rg_gains() { return launch_rg_gains(h); }
+    int rg_moments() { return launch_rg_moments(h); }
+    int rg_HC() { return launch_rg_HC(h); }
+    int rg_colsE() { return launch_rg_colsE(h); }
+    int rg_resR() { return launch_rg_resR(h); }
+    int rg_elbo(hipStream_t stream) { return launch_rg_elbo(h, stream); }
     int elbo_dense() { return launch_elbo_dense(h); }
     int carry_x(int src) { return launch_carry(h, h->X[src], h->X[1 - src], (size_t)h->T * h->L.DP); }
     int carry_classes() {
@@ -325,7 +356,8 @@ struct LdsDevice {
     int form_lnd_x() { return ::form_lnd_x(h); }
 };
 static LdsFlow<LdsDevice> flow(pyvb_lds* h) {
-    return {h->st, {h->T, h->N, h->D, h->P, h->dense, h->big, h->has_missing, h->bound, h->inputs_set, h->input_priors_set, &h->rep, h->parents}, {h}};
+    return {h->st, {h->T, h->N, h->D, h->P, h->dense, h->big, h->has_missing, h->bound, h->inputs_set, h->input_priors_set, &h->rep, h->parents,
+                        h->Pv, h->regressors_set, h->regressor_priors_set}, {h}};
 }
 static int settle_parked(pyvb_lds* h) { return flow(h).settle_parked(); }
 
@@ -440,6 +472,10 @@ static int set_parents(pyvb_lds* h, int which, int kind, const double* a0, const
     int rc = parents_gate(h, which, 0);
     if (rc) return rc;
     const char* name = kind == PARENTS_GAMMA ? "Gamma" : "DiagonalGamma";
+    if (h->Pv) {
+        pyvb_set_error("%s precision parents of the columns are not served on a handle with regressors (pyvb_lds_create_regressors, k_regressors.hip)", name);
+        return PYVB_E_UNSUPPORTED;
+    }
     if (h->P) {
         pyvb_set_error("%s precision parents of the columns are not served on a handle with inputs (pyvb_lds_create_inputs, k_inputs.hip)", name);
         return PYVB_E_UNSUPPORTED;
@@ -614,10 +650,14 @@ int pyvb_lds_get_column_cov(pyvb_lds* h, double* A_cov, double* C_cov) {
 
 int pyvb_lds_set_column_observations(pyvb_lds* h, const double* A_obs, const double* C_obs) {
     ENTER(h);
-    if (h->P) {
+    if (h->P || h->Pv) {
         bool known = false;
         for (size_t i = 0; A_obs && i < (size_t)h->D * h->D && !known; ++i) known = A_obs[i] == A_obs[i];
         for (size_t i = 0; C_obs && i < (size_t)h->K * h->D && !known; ++i) known = C_obs[i] == C_obs[i];
+        if (known && h->Pv) {
+            pyvb_set_error("known entries of A / C are not served on a handle with regressors (pyvb_lds_create_regressors, k_regressors.hip)");
+            return PYVB_E_UNSUPPORTED;
+        }
         if (known) {
             pyvb_set_error("known entries of A / C are not served on a handle with inputs (pyvb_lds_create_inputs, k_inputs.hip)");
             return PYVB_E_UNSUPPORTED;
@@ -647,6 +687,7 @@ int pyvb_lds_set_observations(pyvb_lds* h, const double* Y) {
             const double* Yr = Y + (size_t)r * h->T * h->K;
             for (size_t i = 0; i < (size_t)h->rep.length(r) * h->K; ++i)
                 if (Yr[i] != Yr[i]) {
+                    if (h->Pv) { missing = true; break; }       // (refused below, naming the regressors)
                     pyvb_set_error("outputs that hold NaN are not served together with chains of unequal length (k_missing.hip): "
                                    "replicate %d, t = %d of its %d nodes", r, (int)(i / h->K), h->rep.length(r));
                     return PYVB_E_UNSUPPORTED;
@@ -655,6 +696,11 @@ int pyvb_lds_set_observations(pyvb_lds* h, const double* Y) {
     } else
         for (size_t i = 0; i < n && !missing; ++i) missing = Y[i] != Y[i];
     int rc;
+    if (missing && h->Pv) {
+        pyvb_set_error("outputs that hold NaN are not served on a handle with regressors (pyvb_lds_create_regressors, k_missing.hip): "
+                       "sum_t y_t v_t^T and the imputation would both change");
+        return PYVB_E_UNSUPPORTED;
+    }
     if (missing && h->P) {
         pyvb_set_error("outputs that hold NaN are not served on a handle with inputs (pyvb_lds_create_inputs, k_missing.hip)");
         return PYVB_E_UNSUPPORTED;
@@ -685,7 +731,8 @@ int pyvb_lds_set_observations(pyvb_lds* h, const double* Y) {
         h->has_missing = false;
         if ((rc = h2d(h, h->Y, Y, n))) return rc;
         if ((rc = flow(h).syy())) return rc;
-        if (h->P && (rc = launch_in_assemble(h))) return rc;       // the rows [y_t ; u_t ; u_{t+1}] the sweeps read
+        if (h->P && !h->Pv && (rc = launch_in_assemble(h))) return rc;       // the rows [y_t ; u_t ; u_{t+1}] the sweeps read
+        if (h->Pv && ((rc = launch_rg_assemble(h)) || (rc = launch_rg_sums(h)))) return rc;      // [y_t ; u_t ; u_{t+1} ; v_t], and Syv
         if (h->dense && (rc = launch_syy_full(h))) return rc;
     }
     HIPCHK(hipStreamSynchronize(h->stream));
@@ -760,7 +807,7 @@ int pyvb_lds_set_inputs(pyvb_lds* h, const double* U) {
             }
     ENTER(h);
     if ((rc = h2d(h, h->Uin, U, (size_t)h->N * T * P))) return rc;
-    if ((rc = launch_in_assemble(h)) || (rc = launch_in_suu(h))) return rc;
+    if ((rc = h->Pv ? launch_rg_assemble(h) : launch_in_assemble(h)) || (rc = launch_in_suu(h))) return rc;
     HIPCHK(hipStreamSynchronize(h->stream));
     h->inputs_set = true;
     h->st.outputs_changed();        // what the sweeps read as outputs has changed: c_t and every sum over t with it
@@ -819,6 +866,87 @@ int pyvb_lds_update_B(pyvb_lds* h) {
     if (rc) return rc;
     ENTER(h);
     return flow(h).update_B();
+}
+
+// ---- Known regressors in the output equation (pyvb_lds_create_regressors; the kernels are k_regressors.hip)
+static int regressors_gate(const pyvb_lds* h) {
+    ARGCHK(h, "handle is NULL");
+    ARGCHK(h->Pv > 0, "the handle was created without regressors (pyvb_lds_create_regressors makes one with)");
+    return PYVB_OK;
+}
+
+int pyvb_lds_set_regressors(pyvb_lds* h, const double* V) {
+    int rc = regressors_gate(h);
+    if (rc) return rc;
+    ARGCHK(V, "V is NULL");
+    const size_t T = h->T, Pv = h->Pv;
+    for (int n = 0; n < h->N; ++n)
+        for (size_t i = 0; i < T * Pv; ++i)
+            if (!std::isfinite(V[(size_t)n * T * Pv + i])) {
+                pyvb_set_error("V is not finite: replicate %d, row %d, channel %d", n, (int)(i / Pv), (int)(i % Pv));
+                return PYVB_E_ARG;
+            }
+    ENTER(h);
+    if ((rc = h2d(h, h->Vin, V, (size_t)h->N * T * Pv))) return rc;
+    if ((rc = launch_rg_assemble(h)) || (rc = launch_rg_sums(h))) return rc;
+    HIPCHK(hipStreamSynchronize(h->stream));
+    h->regressors_set = true;
+    h->st.outputs_changed();        // what the sweeps read as outputs has changed: c_t and every sum over t with it
+    return PYVB_OK;
+}
+
+int pyvb_lds_get_regressors(pyvb_lds* h, double* V) {
+    int rc = regressors_gate(h);
+    if (rc) return rc;
+    ARGCHK(V, "V is NULL");
+    ENTER(h);
+    if ((rc = d2h(h, V, h->Vin, (size_t)h->N * h->T * h->Pv))) return rc;
+    return pyvb_lds_sync(h);
+}
+
+int pyvb_lds_set_regressor_priors(pyvb_lds* h, const double* E_pm, const double* E_pp) {
+    int rc = regressors_gate(h);
+    if (rc) return rc;
+    ARGCHK(E_pm && E_pp, "E_prior_mean and E_prior_prec are required");
+    const int K = h->K, Pv = h->Pv;
+    for (int i = 0; i < Pv * K; ++i) ARGCHK(E_pp[i] > 0.0 && std::isfinite(E_pp[i]) && std::isfinite(E_pm[i]), "E_prior_prec must be positive and E_prior_mean finite");
+    std::vector<double> ld((size_t)Pv, 0.0);    // ln det of the diagonal prior precision of every column (node.py:301-302)
+    for (int i = 0; i < Pv; ++i)
+        for (int k = 0; k < K; ++k) ld[i] += log(E_pp[(size_t)i * K + k]);
+    ENTER(h);
+    if ((rc = h2d(h, h->E_pm, E_pm, (size_t)K * Pv)) || (rc = h2d(h, h->E_pp, E_pp, (size_t)Pv * K)) || (rc = h2d(h, h->E_pld, ld.data(), Pv))) return rc;
+    HIPCHK(hipStreamSynchronize(h->stream));    // ld is about to go out of scope
+    h->regressor_priors_set = true;
+    h->st.parameters_changed();
+    return PYVB_OK;
+}
+
+int pyvb_lds_set_regressor_state(pyvb_lds* h, const double* E_mean, const double* E_colvar) {
+    int rc = regressors_gate(h);
+    if (rc) return rc;
+    ENTER(h);
+    const size_t n = (size_t)h->N * h->K * h->Pv;
+    if ((rc = h2d(h, h->E_mean, E_mean, n)) || (rc = h2d(h, h->E_var, E_colvar, n))) return rc;
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if (E_mean || E_colvar) h->st.parameters_changed();
+    return PYVB_OK;
+}
+
+int pyvb_lds_get_regressor_state(pyvb_lds* h, double* E_mean, double* E_colvar, double* qld_E, double* lnd_E) {
+    int rc = regressors_gate(h);
+    if (rc) return rc;
+    ENTER(h);
+    const size_t N = h->N, K = h->K, Pv = h->Pv;
+    if ((rc = d2h(h, E_mean, h->E_mean, N * K * Pv)) || (rc = d2h(h, E_colvar, h->E_var, N * Pv * K)) ||
+        (rc = d2h(h, qld_E, h->qld_E, N * Pv)) || (rc = d2h(h, lnd_E, h->lnd_E, N * Pv))) return rc;
+    return pyvb_lds_sync(h);
+}
+
+int pyvb_lds_update_E(pyvb_lds* h) {
+    int rc = regressors_gate(h);
+    if (rc) return rc;
+    ENTER(h);
+    return flow(h).update_E();
 }
 
 int pyvb_lds_set_state(pyvb_lds* h, const double* X, const double* A_mean, const double* A_colvar,
@@ -927,7 +1055,7 @@ int pyvb_lds_set_time_split(pyvb_lds* h, int W) {
     if (rc) return rc;
     HIPCHK(hipStreamSynchronize(h->stream));
     if (W != h->W) {
-        const LdsGeometry g = lds_geometry(h->N, h->T, h->D, h->K, h->noise).with_time_split(W);
+        const LdsGeometry g = lds_geometry(h->N, h->T, h->D, lds_sweep_K(h), h->noise).with_time_split(W);
         double* p = nullptr;
         rc = h->mem.zeros(&p, g.sxx);
         if (rc) { h->mem.release(p); return rc; }

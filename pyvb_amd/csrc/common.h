@@ -106,14 +106,25 @@ struct pyvb_lds {
     // of (D, K + 2 P); everything else keeps reading Y, K and C_mean.
     int P;
     double *Uin;                    // [N][T][P] the inputs as the caller gave them; row t drives x_t
-    double *Yt;                     // [N][T][K + 2 P] rows [y_t ; u_t ; u_{t+1}], u_t zero in row 0, u_{t+1} zero in a chain's last row
-    double *Ct;                     // [N][K + 2 P][D] <C>, then the rows through which the boundary nodes add <Q><B> u and -<A>^T<Q><B> u
+    double *Yt;                     // [N][T][K + 2 P + Pv] rows [y_t ; u_t ; u_{t+1} ; v_t], u_t zero in row 0, u_{t+1} zero in a chain's last row
+    double *Ct;                     // [N][K + 2 P + Pv][D] <C>, then the rows through which the boundary nodes add <Q><B> u and -<A>^T<Q><B> u
     double *B_mean, *B_var;         // [N][D][P] (row, col), [N][P][D] (column i, entry k), as A_mean / A_var
     double *qld_B, *lnd_B;          // [N][P]
     double *B_pm, *B_pp, *B_pld;    // the Constant parents of the columns of B: [D][P], [P][D], and ln det of each column's precision [P]
     double *Suu;                    // [N][P][P] sum_{t=1}^{T_n-1} u_t u_t^T, formed when the inputs are set
     double *imom;                   // [N][2 D P + D D]: Sxu [D][P], Su1x [P][D], and Sx1x as k_moments left it (k_in_moments)
     bool inputs_set, input_priors_set;
+    // ---- known regressors in the output equation, y_t = C x_t + E v_t (pyvb_lds_create_regressors, k_regressors.hip).  Pv = 0 and
+    // every pointer null on a handle without.  The regressors are Pv more output channels behind the 2 P of the inputs: Yt, Ct and
+    // L are those of K + 2 P + Pv outputs, and Yt / Ct exist when P or Pv is set.
+    int Pv;
+    double *Vin;                    // [N][T][Pv] the regressors as the caller gave them; row t enters y_t
+    double *E_mean, *E_var;         // [N][K][Pv] (row, col), [N][Pv][K] (column i, entry k), as C_mean / C_var
+    double *qld_E, *lnd_E;          // [N][Pv]
+    double *E_pm, *E_pp, *E_pld;    // the Constant parents of the columns of E: [K][Pv], [Pv][K], ln det of each column's precision [Pv]
+    double *Svv, *Syv;              // [N][Pv][Pv] sum_{t<T_n} v_t v_t^T, [N][K][Pv] sum_{t<T_n} y_t v_t^T: formed when V or Y is set
+    double *rmom;                   // [N][Pv D + K D]: Svx [Pv][D], and Syx as k_moments left it (k_rg_moments)
+    bool regressors_set, regressor_priors_set;
     // ---- the lower bound does not feed the next iteration: inside pyvb_lds_iterate it runs on a side stream
     hipStream_t side;
     hipEvent_t ev_params, ev_elbo;  // parameters of this iteration complete (main) / lower bound of it read them (side)
@@ -123,9 +134,9 @@ struct pyvb_lds {
 #define PYVB_ELBO_HISTORY 4096
 
 // what the sweeps, the single-node update and the statistics pass are handed as outputs, their number and <C>
-static inline int lds_sweep_K(const pyvb_lds* h) { return h->K + 2 * h->P; }
-static inline const double* lds_sweep_Y(const pyvb_lds* h) { return h->P ? h->Yt : h->Y; }
-static inline const double* lds_sweep_C(const pyvb_lds* h) { return h->P ? h->Ct : h->C_mean; }
+static inline int lds_sweep_K(const pyvb_lds* h) { return h->K + 2 * h->P + h->Pv; }
+static inline const double* lds_sweep_Y(const pyvb_lds* h) { return h->P || h->Pv ? h->Yt : h->Y; }
+static inline const double* lds_sweep_C(const pyvb_lds* h) { return h->P || h->Pv ? h->Ct : h->C_mean; }
 
 // ---- launchers implemented in the kernel translation units ----
 // k_inputs.hip (handles with inputs only)
@@ -137,6 +148,15 @@ int launch_in_HA(pyvb_lds* h);              // H_A = Sx1x - <B> Su1x into the mo
 int launch_in_colsB(pyvb_lds* h);           // [b.update() for b in Bs]
 int launch_in_resQ(pyvb_lds* h);            // the terms of <B> in the residual of Q
 int launch_in_elbo(pyvb_lds* h, hipStream_t stream);       // the columns of B into part 2, behind k_elbo on the same stream
+// k_regressors.hip (handles with regressors only)
+int launch_rg_assemble(pyvb_lds* h);        // Yt from Y, Uin and Vin, every row of every replicate
+int launch_rg_sums(pyvb_lds* h);            // Svv, Syv from Vin and Y
+int launch_rg_gains(pyvb_lds* h);           // behind k_prep and k_in_gains: the column group of the v_t channels, their rows of Ct, the ones behind <R>
+int launch_rg_moments(pyvb_lds* h);         // behind k_moments: Svx out of the Syx block, Syx aside
+int launch_rg_HC(pyvb_lds* h);              // H_C = Syx - <E> Svx into the moment block, for the columns of C and the residual of R
+int launch_rg_colsE(pyvb_lds* h);           // [e.update() for e in Es]
+int launch_rg_resR(pyvb_lds* h);            // the terms of <E> in the residual of R
+int launch_rg_elbo(pyvb_lds* h, hipStream_t stream);       // the columns of E into part 3, behind k_elbo on the same stream
 int launch_prep(pyvb_lds* h);
 int launch_w0(pyvb_lds* h);         // L0 m0 from the priors of X_0 on the device: after every change of them
 // A sweep reads X[src] and writes X[1 - src]; read_cache: a backward sweep that starts from the c_t a forward one left in U.

@@ -37,6 +37,7 @@ struct InArgs {
     const unsigned char* active;
     const int* len;
     int N, T, D, K, P, bound;
+    int Pv;     // the regressors' channels behind the 2 P of the inputs (k_regressors.hip): the rows of Ct they add
     Layout L;
 };
 
@@ -92,7 +93,7 @@ __global__ void __launch_bounds__(64) k_in_gains(InArgs a) {
     const double* Am = a.A_mean + (size_t)n * D * D;
     const double* Bm = a.B_mean + (size_t)n * D * P;
     const double* S1 = a.Sigma1 + ((size_t)n * 3 + 1) * D * D;
-    double* Ct = a.Ct + (size_t)n * (K + 2 * P) * D;
+    double* Ct = a.Ct + (size_t)n * (K + 2 * P + a.Pv) * D;
     const int lc = lane < D ? lane : D - 1;
     const double qbar = lane < D ? a.Q_a[(size_t)n * D + lc] / a.Q_b[(size_t)n * D + lc] : 0.0;
     for (int c = 0; c < 64; ++c) WV[lane * 65 + c] = (lane < D && c < P) ? qbar * Bm[(size_t)lc * P + c] : 0.0;
@@ -257,7 +258,7 @@ static InArgs in_args(pyvb_lds* h) {
     a.B_pm = h->B_pm; a.B_pp = h->B_pp; a.B_pld = h->B_pld;
     a.part = h->stats; a.nchunk = h->nchunk; a.mom = h->mom; a.imom = h->imom; a.resQ = h->resQ; a.elbo = h->elbo;
     a.active = h->active; a.len = h->len;
-    a.N = h->N; a.T = h->T; a.D = h->D; a.K = h->K; a.P = h->P; a.bound = h->bound; a.L = h->L;
+    a.N = h->N; a.T = h->T; a.D = h->D; a.K = h->K; a.P = h->P; a.Pv = h->Pv; a.bound = h->bound; a.L = h->L;
     return a;
 }
 

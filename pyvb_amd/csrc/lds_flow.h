@@ -16,8 +16,13 @@
 //   join_elbo()        the main stream waits for a lower bound in flight on the side stream
 //   form_lnd_x()       ln det of every class of Sigma on the host, and its two copies
 // with main_stream() and a type stream_t for the two calls that take a stream.
+// A Dev that serves handles with regressors (LdsFacts::Pv > 0, k_regressors.hip) has also
+//   rg_gains, rg_moments, rg_HC, rg_colsE, rg_resR, rg_elbo(stream)
+// They are called through a compile-time detection, so a Dev without them (only ever run with Pv = 0) still compiles.
 #pragma once
 #include <cstddef>
+#include <type_traits>
+#include <utility>
 #include "../../include/pyvb_hip.h"
 #include "lds_state.h"
 #include "replicates.h"
@@ -34,13 +39,24 @@ struct LdsFacts {
     bool inputs_set, input_priors_set;
     const Replicates* rep;          // host-only records of the handle, read through
     const ColumnParents* parents;   // [2]
+    int Pv;                         // regressors in the output equation, fixed at creation (0: none)
+    bool regressors_set, regressor_priors_set;
 };
+
+template <class Dev, class = void> struct dev_has_regressors : std::false_type {};
+template <class Dev> struct dev_has_regressors<Dev, std::void_t<decltype(std::declval<Dev&>().rg_gains())>> : std::true_type {};
 
 template <class Dev>
 struct LdsFlow {
     LdsState& st;
     LdsFacts in;
     Dev dev;
+
+    // the steps of k_regressors.hip, where Dev has them
+#define PYVB_RG_STEP(name) int name() { if constexpr (dev_has_regressors<Dev>::value) return dev.name(); else return PYVB_OK; }
+    PYVB_RG_STEP(rg_gains) PYVB_RG_STEP(rg_moments) PYVB_RG_STEP(rg_HC) PYVB_RG_STEP(rg_colsE) PYVB_RG_STEP(rg_resR)
+#undef PYVB_RG_STEP
+    int rg_elbo(typename Dev::stream_t stream) { if constexpr (dev_has_regressors<Dev>::value) return dev.rg_elbo(stream); else return PYVB_OK; }
 
     // every replicate switched off: the update entries are successful no-ops without a launch
     bool idle() const { return in.rep->n_active() == 0; }
@@ -102,6 +118,13 @@ struct LdsFlow {
         return PYVB_OK;
     }
 
+    // a handle with regressors before it has them: the updates would read zeros for v_t and for the parents of E
+    int regressors_ready() const {
+        if (!in.regressors_set) { pyvb_set_error("%s", "the handle was created with regressors: call pyvb_lds_set_regressors before the first update"); return PYVB_E_ARG; }
+        if (!in.regressor_priors_set) { pyvb_set_error("%s", "the handle was created with regressors: call pyvb_lds_set_regressor_priors before the first update"); return PYVB_E_ARG; }
+        return PYVB_OK;
+    }
+
     int ensure_gains() {
         if (st.gains_valid) return PYVB_OK;
         int rc;
@@ -110,8 +133,10 @@ struct LdsFlow {
             if ((rc = dev.dense_pre())) return rc;
         }
         if (in.P && (rc = inputs_ready())) return rc;
+        if (in.Pv && (rc = regressors_ready())) return rc;
         if ((rc = dev.prep())) return rc;
         if (in.P && (rc = dev.in_gains())) return rc;      // the gains of the input channels, from Sigma_1 as k_prep has just left it
+        if (in.Pv && (rc = rg_gains())) return rc;         // those of the regressors' channels, behind them
         st.gains_formed();
         return PYVB_OK;
     }
@@ -137,11 +162,13 @@ struct LdsFlow {
                            st.fresh_count, in.T);
             return PYVB_E_STALE;
         }
-        int rc = dev.stats(!st.sxx_valid);
-        if (rc) return rc;
+        int rc;
+        if (in.Pv && (rc = regressors_ready())) return rc;      // before any launch
+        if ((rc = dev.stats(!st.sxx_valid))) return rc;
         if ((rc = dev.moments(st.sxx_valid))) return rc;
         if ((rc = dev.tie_moments())) return rc;        // chains that share A, C, Q, R: the moments of a model
         if (in.P && ((rc = inputs_ready()) || (rc = dev.in_moments()))) return rc;       // Sxu, Su1x; Sx1x aside
+        if (in.Pv && (rc = rg_moments())) return rc;        // Svx; Syx aside
         st.stats_valid = true;
         return PYVB_OK;
     }
@@ -153,6 +180,8 @@ struct LdsFlow {
         if (rc) return rc;
         if (in.P && which == 0) {       // H_A of the current <B>, the residual as k_cols forms it, the terms of <B> alone
             if ((rc = dev.in_HA()) || (rc = dev.resid(0)) || (rc = dev.in_resQ())) return rc;
+        } else if (in.Pv && which == 1) {   // H_C of the current <E>, the residual as k_cols forms it, the terms of <E> alone
+            if ((rc = rg_HC()) || (rc = dev.resid(1)) || (rc = rg_resR())) return rc;
         } else if ((rc = in.dense ? dev.wresid(which, 0, st.sg_valid[which]) : dev.resid(which))) return rc;
         valid = true;
         return PYVB_OK;
@@ -191,6 +220,7 @@ struct LdsFlow {
             if ((rc = dev.cols_dense(which, col_begin, col_end))) return rc;
         } else {
             if (in.P && which == 0 && (rc = dev.in_HA())) return rc;       // H = Sx1x - <B> Su1x
+            if (in.Pv && which == 1 && (rc = rg_HC())) return rc;          // H = Syx - <E> Svx
             if ((rc = dev.cols(which, col_begin, col_end))) return rc;
         }
         st.columns_updated(which, in.dense && col_begin == 0 && col_end == in.D);
@@ -202,6 +232,14 @@ struct LdsFlow {
         int rc;
         if ((rc = ensure_stats()) || (rc = dev.in_colsB())) return rc;
         st.columns_updated(0, false);        // as a column of A: the gains and the residual of Q depend on it
+        return PYVB_OK;
+    }
+
+    int update_E() {
+        if (idle()) return PYVB_OK;
+        int rc;
+        if ((rc = ensure_stats()) || (rc = rg_colsE())) return rc;
+        st.columns_updated(1, false);        // as a column of C: the gains and the residual of R depend on it
         return PYVB_OK;
     }
 
@@ -237,10 +275,12 @@ struct LdsFlow {
         return PYVB_OK;
     }
 
-    // k_elbo, and on a handle with inputs the columns of B into part 2 behind it
+    // k_elbo, and on a handle with inputs the columns of B into part 2 behind it, with regressors those of E into part 3
     int lds_bound(typename Dev::stream_t stream) {
-        const int rc = dev.elbo(stream);
-        return rc || !in.P ? rc : dev.in_elbo(stream);
+        int rc = dev.elbo(stream);
+        if (!rc && in.P) rc = dev.in_elbo(stream);
+        if (!rc && in.Pv) rc = rg_elbo(stream);
+        return rc;
     }
 
     int elbo() {
@@ -273,6 +313,23 @@ struct LdsFlow {
             if ((rc = dev.wresid(2, 1, true))) return rc;    // both residual matrices and both qw = w0 + residual
             st.noise_updated(2);
             if ((rc = ensure_expect())) return rc;                // E[Q], E[R] of the new posteriors: the bound and the next k_prep read them
+        } else if (in.Pv) {
+            // As, [Bs], Cs, Es, Q, R: E sees the new C and sits between C and R, which therefore share no launch; without inputs
+            // A and Q keep theirs
+            if (in.P) {
+                if ((rc = dev.in_HA()) || (rc = dev.cols(0, 0, in.D))) return rc;
+                if ((rc = dev.in_colsB())) return rc;
+            } else if ((rc = dev.cols(0, 0, in.D, 3))) return rc;
+            if ((rc = rg_HC()) || (rc = dev.cols(1, 0, in.D))) return rc;
+            if ((rc = rg_colsE())) return rc;
+            st.columns_updated(2, false);
+            if (!in.P) st.noise_updated(0);
+            else {
+                if ((rc = ensure_resid(0)) || (rc = dev.noise(0))) return rc;
+                st.noise_updated(0);
+            }
+            if ((rc = ensure_resid(1)) || (rc = dev.noise(1))) return rc;
+            st.noise_updated(1);
         } else if (in.P) {
             // As, Bs, Cs, Q, R: B sees the new A, Q the new A and B; C and R do not depend on them and keep their shared launch
             if ((rc = dev.in_HA()) || (rc = dev.cols(0, 0, in.D))) return rc;

@@ -29,6 +29,7 @@ _STATE_KEYS = ("X", "A_mean", "A_colvar", "C_mean", "C_colvar", "Q_b", "R_b")
 _ALPHA_KEYS = ("A_alpha_b", "C_alpha_b")        # [1, D] each: qb of the columns' Gamma parents, where a series' state carries them
 _ENTRY_KEYS = ("A_entry_b", "C_entry_b")        # [1, D, rows] each: qb of the columns' DiagonalGamma parents, likewise
 _INPUT_KEYS = ("B_mean", "B_colvar")            # [1, D, P], [1, P, D]: the input gain of a series with a known input, likewise
+_REGRESSOR_KEYS = ("E_mean", "E_colvar")        # [1, K, Pv], [1, Pv, K]: the regressors' gain of a series with known regressors, likewise
 
 
 def pad_series(series):
@@ -51,7 +52,7 @@ def pad_series(series):
                                  % (n, y.shape, x.shape, lengths[n], K, lengths[n], D))
         Y[n, :lengths[n]], X[n, :lengths[n]] = y, x
     st0 = {"X": X}
-    for k in _STATE_KEYS[1:] + tuple(k for k in _ALPHA_KEYS + _ENTRY_KEYS + _INPUT_KEYS if k in series[0][1]):
+    for k in _STATE_KEYS[1:] + tuple(k for k in _ALPHA_KEYS + _ENTRY_KEYS + _INPUT_KEYS + _REGRESSOR_KEYS if k in series[0][1]):
         st0[k] = np.concatenate([np.asarray(st[k], dtype=np.float64) for _, st in series])       # each [1, ...]
     return Y, st0, lengths
 
@@ -59,8 +60,12 @@ def pad_series(series):
 class LDSBatch(object):
     ELBO_PARTS = ("X", "Y", "A", "C", "Q", "R")
 
-    def __init__(self, N, T, D, K, noise="diagonal_gamma", device=0, lengths=None, models=None, inputs=0):
-        """inputs: P >= 1 known inputs that drive the states, x_t = A x_{t-1} + B u_t (pyvb_lds_create_inputs): set_inputs gives
+    def __init__(self, N, T, D, K, noise="diagonal_gamma", device=0, lengths=None, models=None, inputs=0, regressors=0):
+        """regressors: Pv >= 1 known regressors in the output equation, y_t = C x_t + E v_t (pyvb_lds_create_regressors):
+        set_regressors gives V [N, T, Pv] (V = 1: an output offset), E [K, Pv] is a matrix of Gaussian columns like C (set_state /
+        get_state: E_mean, E_colvar; set_priors: E_prior_mean, E_prior_prec; update_E).  Composes with inputs=; DiagonalGamma /
+        Gamma noise and max(D, K + 2 P + Pv) <= 64; not with models=.  0: none.
+        inputs: P >= 1 known inputs that drive the states, x_t = A x_{t-1} + B u_t (pyvb_lds_create_inputs): set_inputs gives
         U [N, T, P], B [D, P] is a matrix of Gaussian columns like A (set_state / get_state: B_mean, B_colvar; set_priors:
         B_prior_mean, B_prior_prec; update_B).  DiagonalGamma / Gamma noise and max(D, K + 2 P) <= 64; not with models=.  0: none.
         lengths: int [N], the chain length T_n of each replicate, 2 <= T_n <= T (pyvb_lds_create_lengths); None: all T.
@@ -74,11 +79,21 @@ class LDSBatch(object):
             raise NotImplementedError("noise precision %r has no HIP path (DiagonalGamma, Gamma and Wishart do)" % (noise,))
         self.N, self.T, self.D, self.K, self.noise, self.device = int(N), int(T), int(D), int(K), noise, int(device)
         self.P = int(inputs or 0)
+        self.Pv = int(regressors or 0)
         self.bound = "reference"
         h = C.ctypes.c_void_p()
-        if self.P:
+        if self.Pv and models is None:
+            ln = None if lengths is None else np.ascontiguousarray(lengths, dtype=np.int32)
+            if ln is not None and ln.shape != (self.N,):
+                raise AssertionError("lengths has shape %s, expected (%d,)" % (ln.shape, self.N))
+            C.check(C.lib.pyvb_lds_create_regressors(C.ctypes.byref(h), self.device, self.N, self.T, self.D, self.K, self.P, self.Pv,
+                                                     _NOISE[noise], None if ln is None else ln.ctypes.data_as(C._ip)))
+            self.lengths = np.empty(self.N, dtype=np.int32)
+            C.check(C.lib.pyvb_lds_get_lengths(h, self.lengths.ctypes.data_as(C._ip)))
+        elif self.P or self.Pv:
             if models is not None:
-                raise NotImplementedError("chains that share A, C, Q, R (models=) are not served together with inputs")
+                raise NotImplementedError("chains that share A, C, Q, R (models=) are not served together with %s"
+                                          % ("inputs" if self.P else "regressors"))
             ln = None if lengths is None else np.ascontiguousarray(lengths, dtype=np.int32)
             if ln is not None and ln.shape != (self.N,):
                 raise AssertionError("lengths has shape %s, expected (%d,)" % (ln.shape, self.N))
@@ -143,6 +158,9 @@ class LDSBatch(object):
         if self.P:      # the Constant parents of the columns of B: B_prior_mean [D, P] (row, col), B_prior_prec [P, D] (column, entry)
             bm, bp = _f64(pri["B_prior_mean"], (D, self.P), "B_prior_mean"), _f64(pri["B_prior_prec"], (self.P, D), "B_prior_prec")
             self._check(C.lib.pyvb_lds_set_input_priors(self._h, C.dptr(bm), C.dptr(bp)))
+        if self.Pv:     # those of the columns of E: E_prior_mean [K, Pv] (row, col), E_prior_prec [Pv, K] (column, entry)
+            em, ep = _f64(pri["E_prior_mean"], (K, self.Pv), "E_prior_mean"), _f64(pri["E_prior_prec"], (self.Pv, K), "E_prior_prec")
+            self._check(C.lib.pyvb_lds_set_regressor_priors(self._h, C.dptr(em), C.dptr(ep)))
 
     def set_inputs(self, U):
         """U[N,T,P]: row t drives x_t; row 0 and, with chain lengths, the rows t >= T_n are never read."""
@@ -153,6 +171,16 @@ class LDSBatch(object):
         U = np.empty((self.N, self.T, self.P))
         self._check(C.lib.pyvb_lds_get_inputs(self._h, C.dptr(U)))
         return U
+
+    def set_regressors(self, V):
+        """V[N,T,Pv]: row t enters y_t, row 0 included; with chain lengths, the rows t >= T_n are never read."""
+        V = _f64(V, (self.N, self.T, self.Pv), "V")
+        self._check(C.lib.pyvb_lds_set_regressors(self._h, C.dptr(V)))
+
+    def get_regressors(self):
+        V = np.empty((self.N, self.T, self.Pv))
+        self._check(C.lib.pyvb_lds_get_regressors(self._h, C.dptr(V)))
+        return V
 
     def set_observations(self, Y):
         """Y[N,T,K]; NaN = missing entry (the rows concerned become variational nodes: set_output_state, update_Y).
@@ -177,10 +205,15 @@ class LDSBatch(object):
         self._check(C.lib.pyvb_lds_get_outputs(self._h, C.dptr(q), C.dptr(v), C.dptr(ld)))
         return (q, v, ld) if with_qld else (q, v)
 
-    def set_state(self, X=None, A_mean=None, A_colvar=None, C_mean=None, C_colvar=None, Q_b=None, R_b=None, B_mean=None, B_colvar=None):
+    def set_state(self, X=None, A_mean=None, A_colvar=None, C_mean=None, C_colvar=None, Q_b=None, R_b=None, B_mean=None, B_colvar=None,
+                  E_mean=None, E_colvar=None):
         """X[N,T,D] and the parameter posteriors; padding rows of X (t >= T_n) may hold anything.  On a handle with inputs also
-        B_mean [N,D,P] and B_colvar [N,P,D]."""
+        B_mean [N,D,P] and B_colvar [N,P,D], on one with regressors E_mean [N,K,Pv] and E_colvar [N,Pv,K]."""
         N, T, D, K = self.N, self.T, self.D, self.K
+        if E_mean is not None or E_colvar is not None:
+            em = None if E_mean is None else _f64(E_mean, (N, K, self.Pv), "E_mean")
+            ev = None if E_colvar is None else _f64(E_colvar, (N, self.Pv, K), "E_colvar")
+            self._check(C.lib.pyvb_lds_set_regressor_state(self._h, C.dptr(em), C.dptr(ev)))
         if B_mean is not None or B_colvar is not None:
             bm = None if B_mean is None else _f64(B_mean, (N, D, self.P), "B_mean")
             bv = None if B_colvar is None else _f64(B_colvar, (N, self.P, D), "B_colvar")
@@ -304,6 +337,15 @@ class LDSBatch(object):
         self._check(C.lib.pyvb_lds_get_state(self._h, *[C.dptr(out.get(k)) for k in order]))
         if self.P and ("A_mean" in what or "B_mean" in what):       # a handle with inputs: the third matrix beside the two
             out.update(self.get_input_state(("B_mean", "B_colvar")))
+        if self.Pv and ("C_mean" in what or "E_mean" in what):      # a handle with regressors: their gain beside C
+            out.update(self.get_regressor_state(("E_mean", "E_colvar")))
+        return out
+
+    def get_regressor_state(self, what=("E_mean", "E_colvar", "qld_E", "lnd_E")):
+        """E_mean [N,K,Pv], E_colvar [N,Pv,K], and q_ln_det / ln det qcov of the columns of E [N,Pv] (NaN before their first update)."""
+        shapes = {"E_mean": (self.N, self.K, self.Pv), "E_colvar": (self.N, self.Pv, self.K), "qld_E": (self.N, self.Pv), "lnd_E": (self.N, self.Pv)}
+        out = {k: np.empty(shapes[k]) for k in shapes if k in what}
+        self._check(C.lib.pyvb_lds_get_regressor_state(self._h, *[C.dptr(out.get(k)) for k in shapes]))
         return out
 
     def get_input_state(self, what=("B_mean", "B_colvar", "qld_B", "lnd_B")):
@@ -380,6 +422,10 @@ class LDSBatch(object):
         """[b.update() for b in Bs]: the columns of the input gain (handles with inputs)."""
         self._check(C.lib.pyvb_lds_update_B(self._h))
 
+    def update_E(self):
+        """[e.update() for e in Es]: the columns of the regressors' gain (handles with regressors)."""
+        self._check(C.lib.pyvb_lds_update_E(self._h))
+
     def update_columns(self, which, col_begin, col_end):
         """As[i].update() (which = "A") or Cs[i].update() ("C") for i in [col_begin, col_end), in order."""
         self._check(C.lib.pyvb_lds_update_columns(self._h, 0 if which == "A" else 1, int(col_begin), int(col_end)))
@@ -404,8 +450,8 @@ class LDSBatch(object):
         return out
 
     def iterate(self, niters=1):
-        """niters x (forward sweep, backward sweep, A, [B on a handle with inputs,] C, Q, R, [the columns' Gamma / DiagonalGamma
-        parents,] lower bound); asynchronous."""
+        """niters x (forward sweep, backward sweep, A, [B on a handle with inputs,] C, [E on a handle with regressors,] Q, R, [the
+        columns' Gamma / DiagonalGamma parents,] lower bound); asynchronous."""
         self._check(C.lib.pyvb_lds_iterate(self._h, int(niters)))
 
     def elbo_history(self, last=4096):
@@ -502,6 +548,8 @@ class LDSBatch(object):
     def kernel_times(self):
         names = {"prep": C.K_PREP, "sweep_fwd": C.K_SWEEP_FWD, "sweep_bwd": C.K_SWEEP_BWD, "stats": C.K_STATS,
                  "params": C.K_PARAMS, "elbo": C.K_ELBO, "step": C.K_STEP, "gy": C.K_GY, "inputs": C.K_INPUTS}
+        if self.Pv:     # the kernels of k_regressors.hip, on the handles that launch them
+            names["regressors"] = C.K_REGRESSORS
         out = {}
         for nm, k in names.items():
             ms, cnt = C.ctypes.c_double(), C.ctypes.c_int()
@@ -536,19 +584,23 @@ class LDSBatch(object):
         return bool(np.isnan(np.asarray(Y))[self.live_rows()].any())
 
     @classmethod
-    def from_series(cls, series, pri, device=0, U=None):
+    def from_series(cls, series, pri, device=0, U=None, V=None):
         """One handle for time series of different lengths: series is a list of (Y_n[T_n, K], st0_n) with st0_n as
         synth.initial_state(T_n, D, K, 1) gives it; replicate n is the graph with T_n time steps (pad_series).
-        U: a list of U_n[T_n, P], the known input of every series (st0_n then carries B_mean, B_colvar), padded as Y is."""
+        U: a list of U_n[T_n, P], the known input of every series (st0_n then carries B_mean, B_colvar), padded as Y is.
+        V: a list of V_n[T_n, Pv], the known regressors of every series' outputs (st0_n then carries E_mean, E_colvar), likewise."""
         Y, st0, lengths = pad_series(series)
-        if U is not None:
-            Up = np.zeros(Y.shape[:2] + (np.shape(U[0])[1],))
-            for n, u in enumerate(U):
-                if np.shape(u) != (lengths[n], Up.shape[2]):
-                    raise AssertionError("series %d: U has shape %s, expected (%d, %d)" % (n, np.shape(u), lengths[n], Up.shape[2]))
-                Up[n, :lengths[n]] = u
-            U = Up
-        return cls.from_problem(Y, st0, pri, device, lengths=lengths, U=U)
+
+        def padded(L, nm):
+            if L is None:
+                return None
+            Lp = np.zeros(Y.shape[:2] + (np.shape(L[0])[1],))
+            for n, u in enumerate(L):
+                if np.shape(u) != (lengths[n], Lp.shape[2]):
+                    raise AssertionError("series %d: %s has shape %s, expected (%d, %d)" % (n, nm, np.shape(u), lengths[n], Lp.shape[2]))
+                Lp[n, :lengths[n]] = u
+            return Lp
+        return cls.from_problem(Y, st0, pri, device, lengths=lengths, U=padded(U, "U"), V=padded(V, "V"))
 
     @classmethod
     def from_trials(cls, trials, pri, device=0):
@@ -562,15 +614,19 @@ class LDSBatch(object):
         return cls.from_problem(Y, st0, pri, device, lengths=lengths, models=models)
 
     @classmethod
-    def from_problem(cls, Y, st0, pri, device=0, lengths=None, models=None, U=None):
+    def from_problem(cls, Y, st0, pri, device=0, lengths=None, models=None, U=None, V=None):
         """U [N, T, P]: a known input that drives the states (synth.make_input_problem); st0 then carries B_mean and B_colvar, pri
-        B_prior_mean and B_prior_prec."""
+        B_prior_mean and B_prior_prec.  V [N, T, Pv]: known regressors in the output equation (synth.make_regression_problem); st0
+        then carries E_mean and E_colvar, pri E_prior_mean and E_prior_prec."""
         N, T, K = Y.shape
         D = st0["A_mean"].shape[1]
         b = cls(N, T, D, K, pri.get("noise", "diagonal_gamma"), device, lengths=lengths, models=models,
-                inputs=0 if U is None else np.shape(U)[2])
+                inputs=0 if U is None else np.shape(U)[2], regressors=0 if V is None else np.shape(V)[2])
         b.set_priors(pri)
         b.set_observations(Y)
+        if V is not None:
+            b.set_regressors(V)
+            b.set_state(E_mean=st0["E_mean"], E_colvar=st0["E_colvar"])
         if U is not None:
             b.set_inputs(U)
             b.set_state(B_mean=st0["B_mean"], B_colvar=st0["B_colvar"])

@@ -10,7 +10,8 @@ Everything here is host-side numpy; it only produces inputs.
 """
 import numpy as np
 
-__all__ = ["simulate_lds", "initial_state", "default_priors", "make_problem", "simulate_driven_lds", "make_input_problem"]
+__all__ = ["simulate_lds", "initial_state", "default_priors", "make_problem", "simulate_driven_lds", "make_input_problem",
+           "make_regression_problem"]
 
 
 def simulate_lds(T, D, K, N=1, seed=20240):
@@ -123,6 +124,29 @@ def make_input_problem(T, D, K, P, N=1, seed=20240):
     pri["B_prior_mean"] = np.zeros((D, P))
     pri["B_prior_prec"] = np.full((P, D), 1e-3)
     return sim["Y"], sim["U"], st, pri
+
+
+def make_regression_problem(T, D, K, P, Pv, N=1, seed=20240):
+    """make_problem for the graph with known regressors in the output equation, Y_t = Gaussian(K, C X_t + E v_t, R), and P >= 0
+    inputs that drive the states: (Y, U, V, st0, pri), U None for P = 0.  V [N, T, Pv]: channel 0 is the constant 1 (an output
+    offset), the others a slow sinusoid plus white noise; the simulated outputs carry E v_t with a true E = 3 randn [N, K, Pv].
+    st0 has E_mean [N, K, Pv] and E_colvar [N, Pv, K] (column, entry) drawn as those of B are, pri E_prior_mean [K, Pv] and
+    E_prior_prec [Pv, K]."""
+    if P:
+        Y, U, st, pri = make_input_problem(T, D, K, P, N, seed)
+    else:
+        (Y, st, pri), U = make_problem(T, D, K, N, seed), None
+    rng = np.random.default_rng(seed + 1299709)
+    E = 3.0 * rng.standard_normal((N, K, Pv))
+    phase, period = rng.random((N, 1, Pv)), 8.0 + 24.0 * rng.random((N, 1, Pv))
+    V = np.sin(2.0 * np.pi * (np.arange(T)[None, :, None] / period + phase)) + 0.5 * rng.standard_normal((N, T, Pv))
+    V[:, :, 0] = 1.0
+    Y = Y + np.einsum("nkp,ntp->ntk", E, V)
+    st["E_mean"] = rng.standard_normal((N, K, Pv))
+    st["E_colvar"] = np.repeat(1.0 / rng.random((N, Pv, 1)), K, axis=2)
+    pri["E_prior_mean"] = np.zeros((K, Pv))
+    pri["E_prior_prec"] = np.full((Pv, K), 1e-3)
+    return Y, U, V, st, pri
 
 
 def pca_rows(lo, hi, d, q, seed, block=10000):
