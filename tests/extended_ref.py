@@ -32,6 +32,12 @@ The 128-wide LDS class is measured tile by tile (BIG_CASES, tile_errors, compare
 quantity cut into 16 x 16 tiles, the states into the 16-entry tile of each node, each tile in units of its own largest entry
 of the extended run, e_tile <= FACTOR max(e64_tile, n 2^-52) with e64_tile <= CAP; a tile that is exactly zero in the extended
 run is exactly zero on the handle, and the known entries of A and C are held bitwise (known_offenders).
+
+Known inputs and regressors are measured chain by chain, channel by channel and end node by end node (channel_errors,
+compare_channels; the cases are inputs_ref.CHANNEL_CASES and regressors_ref.CHANNEL_CASES): every quantity and every part of both
+bounds of each replicate on its own, column p of B_mean / E_mean and row p of B_colvar / E_colvar, X at nodes 0, 1, T_n - 2 and
+T_n - 1, each in units of its own largest entry of the extended run, e_unit <= FACTOR max(e64_unit, n 2^-52) with n = max(T_n, D, K)
+of the chain's own length and e64_unit <= CAP; a unit that is exactly zero in the extended run is exactly zero on the handle.
 """
 import functools
 import importlib.util
@@ -1330,3 +1336,149 @@ def compare_pca_with_rows_reference(name, trace, ncu=256):
             e_gpu = rel(arr, ref["ext"][key])
         out.append((None, key, ref["e64"][key], e_gpu, e_gpu / yardstick(ref["e64"][key], ref["n"])))
     return out, bnd
+
+
+# ----------------------------------------------------------------------------------------------------------------------------
+# known inputs and regressors, channel by channel
+# ----------------------------------------------------------------------------------------------------------------------------
+# rel() is a maximum over [N, ...] with the replicates stacked.  A chain of 2 nodes beside one of 77, the column of B under an
+# input a thousand times its neighbour's (the column is a thousandth of the neighbour's), the two nodes of X that the boundary
+# terms -<A>^T<Q> e_1 and <Q> e_{T-1} are added to: each is a small part of such an array, and off by 1e-10 of itself it does not
+# move the max-norm.  Here the units are
+#   chain     every quantity of a trace and every part of both bounds, replicate by replicate (a part in units of its replicate's
+#             s_r, as bound_errors has it);
+#   channel   column p of B_mean / E_mean and row p of B_colvar / E_colvar of each replicate;
+#   node      X at nodes 0, 1, T_n - 2 and T_n - 1 of each replicate, each on its own, the rest of the chain together, and the
+#             padding rows t >= T_n, which are zero in the reference
+# each in units of its own largest entry of the extended run, e_unit <= FACTOR max(e64_unit, n 2^-52) with n = max(T_n, D, K) of
+# the chain's own length and e64_unit <= CAP (on the cases of regressors_ref.KAPPA_CASES the yardstick also admits one rounding of
+# the cancelling sum behind R_b, measured on the reference side and capped at CAP: the kappa-clause of DESIGN.md section 17); a unit that is exactly zero in the extended run (the mean column of a dead channel
+# with prior mean 0) is exactly zero or it is out of order.  inputs_ref.CHANNEL_CASES and regressors_ref.CHANNEL_CASES are the
+# cases; R below is either module.
+CHANNEL_QUANTITIES = ("B_mean", "B_colvar", "E_mean", "E_colvar")
+CHANNEL_KINDS = ("chain", "channel", "node")
+
+
+def _unit_error(got, ext):
+    d, u = np.abs(got - ext).max(), np.abs(ext).max()
+    if u == 0:
+        return 0.0 if d == 0 else np.inf
+    return float(d / u)
+
+
+def end_nodes(Tn):
+    """the nodes of a chain of Tn that are units of their own: 0, 1, T_n - 2, T_n - 1"""
+    return sorted({0, 1, Tn - 2, Tn - 1})
+
+
+def channel_errors(got, ext, key, lengths):
+    """{(kind, replicate, index): max |got - ext| / max |ext| over the unit} for the array of a trace key against the extended
+    run's, both in the handle's layout [N, ...].  index: "" for a chain unit (a part's name for a bound key), the channel for a
+    channel unit, the node, "rest" or "padding" for a node unit.  A unit that is exactly zero in ext measures 0.0 if it is exactly
+    zero in got too and inf if it is not."""
+    got, ext = np.asarray(got, dtype=LD), np.asarray(ext, dtype=LD)
+    assert got.shape == ext.shape, (key, got.shape, ext.shape)
+    out = {}
+    if is_bound(key):
+        e = bound_errors(got, ext)[0]
+        return {("chain", r, LDS_PARTS[p]): float(e[r, p]) for r in range(e.shape[0]) for p in range(e.shape[1])}
+    q = key[2]
+    for r, Tn in enumerate(int(t) for t in lengths):
+        g, x = got[r], ext[r]
+        if q == "X":
+            T = x.shape[0]
+            for t in end_nodes(Tn):
+                out["node", r, t] = _unit_error(g[t], x[t])
+            if Tn > 4:
+                out["node", r, "rest"] = _unit_error(g[2:Tn - 2], x[2:Tn - 2])
+            if Tn < T:
+                out["node", r, "padding"] = _unit_error(g[Tn:], x[Tn:])
+            g, x = g[:Tn], x[:Tn]
+        elif q == "Sigma" and Tn <= 2:
+            g, x = g[[0, 2]], x[[0, 2]]
+        elif q in CHANNEL_QUANTITIES:
+            for p in range(x.shape[1] if q.endswith("_mean") else x.shape[0]):
+                out["channel", r, p] = _unit_error(g[:, p], x[:, p]) if q.endswith("_mean") else _unit_error(g[p], x[p])
+        out["chain", r, ""] = _unit_error(g, x)
+    return out
+
+
+def _channel_record(R, prob, f64, ext):
+    """prob: (Y, U, st0, pri, lengths, ...) of inputs_ref or (Y, U, V, st0, pri, lengths, ...) of regressors_ref"""
+    Y = prob[0]
+    i = [isinstance(v, dict) for v in prob].index(True)
+    st0, ln = prob[i], prob[i + 2]
+    lengths = np.full(Y.shape[0], Y.shape[1], dtype=np.int32) if ln is None else np.asarray(ln, dtype=np.int32)
+    assert [k for k, _ in ext] == [k for k, _ in f64][:len(ext)] and all(a.dtype == LD for _, a in ext)
+    for _, a in f64 + ext:
+        a.setflags(write=False)
+    return dict(lengths=lengths, D=st0["A_mean"].shape[1], K=Y.shape[2], keys=[k for k, _ in f64], f64=[a for _, a in f64],
+                ext=[a for _, a in ext], e64=[channel_errors(a, x, k, lengths) for (k, a), (_, x) in zip(f64, ext)])
+
+
+def channel_reference_of(R, prob, iters, ext_iters=None):
+    """The two runs of R.channel_run (R: inputs_ref or regressors_ref) on a problem as R.channel_problem gives it: a dict with
+    lengths [N], D, K, keys, ext [the extended run's arrays, in the order of keys], e64 [channel_errors of the float64 comparator],
+    f64 [its arrays; iters iterations, the extended run ext_iters of them]."""
+    require_extended()
+    return _channel_record(R, prob, R.channel_run(prob, False, iters), R.channel_run(prob, True, iters if ext_iters is None else ext_iters))
+
+
+@functools.lru_cache(maxsize=None)
+def channel_reference(R, name):
+    """channel_reference_of for a case of R.CHANNEL_CASES, from R.channel_trace's cached runs.  Computed once per process, never
+    modified."""
+    require_extended()
+    ref = _channel_record(R, R.channel_problem(name), R.channel_trace(name), R.channel_trace(name, extended=True))
+    if name in getattr(R, "KAPPA_CASES", ()):       # the kappa-clause: what one rounding of a cancelling sum does to every unit
+        runs = R.kappa_allowance(name)
+        assert all([k for k, _ in run] == ref["keys"][:len(ref["ext"])] for run in runs)
+        cond = []
+        for i, (key, x) in enumerate(zip(ref["keys"], ref["ext"])):
+            es = [channel_errors(run[i][1], x, key, ref["lengths"]) for run in runs]
+            cond.append({u: min(max(e[u] for e in es), CAP) for u in es[0]})
+        ref["cond"] = cond
+    return ref
+
+
+def compare_channels(ref, trace, tag):
+    """The units of a trace (a handle's, or a comparator's: [(key, array)] as run_stages gives it) against a reference of
+    channel_reference / channel_reference_of, for every key of the trace that the extended run has.  Returns [(key, kind, replicate, index,
+    e64_unit, e_unit, e_unit / yardstick(e64_unit, n))], n = max(T_n, D, K) of the replicate's own chain; a unit is in order when
+    its ratio is at most FACTOR (offending_units) -- a unit that is zero in the extended run and not in the trace has ratio inf.
+    Prints every unit that is out of order and the worst unit of each quantity and kind."""
+    out = []
+    index = {k: i for i, k in enumerate(ref["keys"])}
+    assert trace and all(k in index for k, _ in trace), "the trace's keys are not the reference's"
+    for key, arr in trace:
+        if index[key] >= len(ref["ext"]):
+            continue
+        ext, e64 = ref["ext"][index[key]], ref["e64"][index[key]]
+        cond = ref["cond"][index[key]] if "cond" in ref else {}
+        assert np.all(np.isfinite(arr)), "%s: non-finite values in %r" % (tag, key)
+        for (kind, r, idx), e in channel_errors(arr, ext, key, ref["lengths"]).items():
+            n = max(int(ref["lengths"][r]), ref["D"], ref["K"])
+            y = max(yardstick(e64[kind, r, idx], n), cond.get((kind, r, idx), 0.0))
+            out.append((key, kind, r, idx, e64[kind, r, idx], e, 0.0 if e == 0 else e / y))
+    line = "%-34s it%d %-8s %-9s %-7s r%d %-9s e64 %.2e  e_unit %.2e  e_unit/y %6.2f%s"
+    for row in offending_units(out):
+        print(line % ((tag, row[0][0]) + row[0][1:] + row[1:] + ("  <-- over",)))
+    worst = {}
+    for row in out:
+        k = (row[0][2] if not is_bound(row[0]) else "bound " + row[0][2], row[1])
+        if k not in worst or not row[6] <= worst[k][6]:
+            worst[k] = row
+    for k in sorted(worst):
+        row = worst[k]
+        print(line % ((tag + " WORST", row[0][0]) + row[0][1:] + row[1:] + ("",)))
+    for kind in CHANNEL_KINDS:
+        for what, sel in (("", lambda row: not is_bound(row[0])), (" of the bound", lambda row: is_bound(row[0]))):
+            rows = [row for row in out if row[1] == kind and sel(row)]
+            if rows:
+                print("%-34s SUMMARY by %-7s%-13s units %5d  max e64 %.2e  max e_unit %.2e  max e_unit/y %.2f"
+                      % (tag, kind, what, len(rows), max(r[4] for r in rows), max(r[5] for r in rows), max(r[6] for r in rows)))
+    return out
+
+
+def offending_units(rows):
+    return [row for row in rows if not row[6] <= FACTOR]

@@ -167,13 +167,13 @@ class Model(object):
         return self.elbo_parts(bound)
 
 
-def models(Y, U, st0, pri, lengths=None):
+def models(Y, U, st0, pri, lengths=None, cls=Model):
     """What LDSBatch.from_problem(Y, st0, pri, U=U, lengths=) was given, as a list of (rows, Model): one model of all N replicates
     where the chains have one length, one per replicate otherwise (rows past a chain's end are cut off)."""
     N, T = Y.shape[:2]
     if lengths is None or all(int(t) == T for t in lengths):
-        return [(list(range(N)), Model(Y, U, st0, pri))]
-    return [([n], Model(Y[n:n + 1, :Tn], U[n:n + 1, :Tn], {k: (v[n:n + 1, :Tn] if k == "X" else v[n:n + 1]) for k, v in st0.items()}, pri))
+        return [(list(range(N)), cls(Y, U, st0, pri))]
+    return [([n], cls(Y[n:n + 1, :Tn], U[n:n + 1, :Tn], {k: (v[n:n + 1, :Tn] if k == "X" else v[n:n + 1]) for k, v in st0.items()}, pri))
             for n, Tn in enumerate(int(t) for t in lengths)]
 
 
@@ -274,6 +274,104 @@ def trace(name, extended=False):
         ms = models(Y, U, st0, pri, ln)
         _cache[key] = run_stages(lambda stage: [do_stage(m, stage) for _, m in ms], lambda: snapshot(ms, CASES[name][0]),
                                  lambda mode: np.concatenate([m.elbo_parts(mode) for _, m in ms]), CASES[name][6] if extended else ITERS)
+    return _cache[key]
+
+
+# ----------------------------------------------------------------------------------------------------------------------------
+# Channel by channel (tests/test_input_channels_cpu.py, tests/test_input_channels_gpu.py; extended_ref.compare_channels).  The
+# problems are synth.make_input_problem's with the channels of U replaced by named patterns -- channel p takes pattern p mod 8 --
+# and with finite random values, not zeros, in row 0 of U (u_0 is never used) and in the padding rows t >= T_n of U and Y.
+# X's padding stays zero.  T, D, K, P, chain lengths or None, time split or None, iterations of the extended run, big (small = 1 / big).
+# ----------------------------------------------------------------------------------------------------------------------------
+U_PATTERNS = ("as drawn", "x big", "x small", "impulse at t = 1", "impulse at t = T_n - 1", "dead: nonzero at t = 0 only", "constant 1",
+              "as drawn")
+CHANNEL_CASES = {
+    "t48_d5k2p31": (48, 5, 2, 31, None, None, 2, 1e3),          # P = IN_PMAX, Kt = 64 at one state tile; two W tiles, CT = 4
+    "t27_d17k3p17": (27, 17, 3, 17, None, None, 2, 1e3),        # one real column in W's second tile, read after V's first tile was
+                                                                # stored over its padding; DT = 2 with one real row
+    "t27_d33k32p16": (27, 33, 32, 16, None, None, 2, 1e3),      # P a full tile, Kt = 64, the gain columns start on an operand-tile edge
+    "t48_d64k2p31": (48, 64, 2, 31, None, None, 1, 1e3),        # the cap at full state width (one long-double iteration)
+    "t700_d8k8p5_w4": (700, 8, 8, 5, None, 4, 2, 1e3),          # the impulses at t = 1 and T - 1 in the first and last wavefront's part
+    "lengths_d16k10p9": (77, 16, 10, 9, (2, 3, 19, 60, 77), None, 2, 30.0),    # every pattern in every chain, live padding in U and Y
+}
+# (chosen so that the float64 comparator is within extended_ref.CAP unit by unit, tests/test_input_channels_cpu.py; a draw over
+# it is replaced, never tolerated)
+CHANNEL_SEEDS = {"t48_d5k2p31": 33400, "t27_d17k3p17": 33410, "t27_d33k32p16": 33420, "t48_d64k2p31": 33430, "t700_d8k8p5_w4": 33440,
+                 "lengths_d16k10p9": 33450}
+
+
+def channel_lengths(name):
+    """int [N]: the chain length of every replicate of a case of CHANNEL_CASES"""
+    T, ln = CHANNEL_CASES[name][0], CHANNEL_CASES[name][4]
+    return np.full(2, T, dtype=np.int32) if ln is None else np.asarray(ln, dtype=np.int32)
+
+
+def pattern_inputs(U, lengths, big, rng):
+    """(U with channel p of every replicate replaced by pattern p mod 8 of U_PATTERNS on the rows 1 .. T_n - 1 that are used, the
+    label of every [replicate][channel]).  Row 0, which no chain uses, and the padding rows t >= T_n are drawn anew: finite, not zero
+    (row 0 is the only nonzero row of a dead channel).  Where two patterns coincide (T_n = 2: t = 1 is T_n - 1) the label says so."""
+    U = U.copy()
+    N, T, P = U.shape
+    labels = []
+    for n, Tn in enumerate(int(t) for t in lengths):
+        labels.append([])
+        U[n, 0] = rng.standard_normal(P)
+        for p in range(P):
+            k, name = p % 8, U_PATTERNS[p % 8]
+            u = U[n, 1:Tn, p]
+            if k == 1:
+                u *= big
+            elif k == 2:
+                u /= big
+            elif k in (3, 4):
+                u[:] = 0.0
+                u[0 if k == 3 else Tn - 2] = 1.0
+                if Tn == 2:
+                    name = "impulse at t = 1 = T_n - 1"
+            elif k == 5:
+                u[:] = 0.0
+                assert U[n, 0, p] != 0.0
+            elif k == 6:
+                u[:] = 1.0
+            labels[-1].append(name)
+        U[n, Tn:] = rng.standard_normal((T - Tn, P))
+    return U, labels
+
+
+def channel_problem(name):
+    """(Y, U, st0, pri, lengths or None, the labels [replicate][channel] of U) of a case of CHANNEL_CASES; shared: do not write."""
+    if ("channel problem", name) not in _cache:
+        from pyvb_amd import synth
+        T, D, K, P, ln, _, _, big = CHANNEL_CASES[name]
+        lengths = channel_lengths(name)
+        Y, U, st0, pri = synth.make_input_problem(T, D, K, P, len(lengths), seed=CHANNEL_SEEDS[name])
+        rng = np.random.default_rng(CHANNEL_SEEDS[name] + 1)
+        U, labels = pattern_inputs(U, lengths, big, rng)
+        live = (np.arange(T)[None, :] < lengths[:, None])[:, :, None]
+        Y = np.where(live, Y, rng.standard_normal(Y.shape))
+        st0["X"] = np.where(live, st0["X"], 0.0)
+        for a in [Y, U] + list(st0.values()):
+            a.setflags(write=False)
+        _cache["channel problem", name] = (Y, U, st0, pri, None if ln is None else lengths, labels)
+    return _cache["channel problem", name]
+
+
+def channel_run(prob, extended=False, iters=ITERS, cls=Model):
+    """run_stages of the comparator on a problem (Y, U, st0, pri, lengths, ...), in float64 or cast up to long double"""
+    Y, U, st0, pri, ln = prob[:5]
+    if extended:
+        import extended_ref as ER
+        Y, U, st0, pri = ER.to_long(Y), ER.to_long(U), ER.to_long(st0), ER.to_long(pri)
+    ms = models(Y, U, st0, pri, ln, cls)
+    return run_stages(lambda stage: [do_stage(m, stage) for _, m in ms], lambda: snapshot(ms, Y.shape[1]),
+                      lambda mode: np.concatenate([m.elbo_parts(mode) for _, m in ms]), iters)
+
+
+def channel_trace(name, extended=False):
+    """trace() for a case of CHANNEL_CASES.  Cached; shared between the tests."""
+    key = ("channel trace", name, extended)
+    if key not in _cache:
+        _cache[key] = channel_run(channel_problem(name), extended, CHANNEL_CASES[name][6] if extended else ITERS)
     return _cache[key]
 
 

