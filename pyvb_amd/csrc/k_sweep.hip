@@ -15,7 +15,9 @@
 // recurrence is a contraction (spectral radius <= 1/2) they warm up from zero J steps early, with
 // J from k_prep such that ||R^J|| <= 1e-18, or from t = first if that is nearer -- in which case
 // the segment reproduces the sequential chain exactly.
+#include <type_traits>
 #include "common.h"
+#include "sweep_plan.h"
 
 struct SweepArgs {
     const double* Xold; double* Xnew; const double* Y; const double* gains; const int* warm;
@@ -98,7 +100,9 @@ __device__ __forceinline__ double boundary_update(bool first, const double* g, c
 // c rows are stored in accumulator order, [tile m][lane group q][register r], so a lane moves 32
 // contiguous bytes per tile.
 // SPLIT: several wavefronts per replicate (a.W > 1, few replicates); without it the part offsets fold to constants.
-template <int DT, int KT, bool FULL, int MODE, bool SPLIT>
+// KEEPX (MODE 1): the interior rows of Xnew are wanted (SweepArgs.keep_x).  Without it the loop stores no state at all -- not
+// even into the trash row -- and the one row the backward sweep reads, next to the far boundary, is stored behind the loop.
+template <int DT, int KT, bool FULL, int MODE, bool SPLIT, bool KEEPX = true>
 __global__ void __launch_bounds__(64) k_sweep(SweepArgs a) {
     constexpr int DS = 4 * DT, KS = 4 * KT, DP = 16 * DT, KP = 16 * KT;
     __shared__ double gl[MODE == 2 ? DP * 17 : DT * KS * 64];     // G as MFMA A operands; MODE 2: the state tile, transposed (below)
@@ -140,11 +144,13 @@ __global__ void __launch_bounds__(64) k_sweep(SweepArgs a) {
     // segments but those that reach the chain's first node within J steps warm up from zero.
     // Lw is cut from the handle's T for every replicate (k_moments counts a replicate's parts the same way):
     // a shorter chain fills the first parts and leaves the others without nodes (Tw <= 0).
-    const int Tint = TL - 2;
-    const int Lw = SPLIT ? split_part_len(T, a.W) : Tint;
-    const int ow = SPLIT ? w * Lw : 0;                       // interior nodes before this part
-    const int Tw = (Tint - ow < Lw) ? Tint - ow : Lw;        // interior nodes of this part (<= 0: none)
+    // (sweep_plan.h holds the cut, the columns' first steps and how each column starts: one definition for kernel and tests)
     const int J = a.warm[n * 2 + a.dir];
+    const SweepPart part = sweep_part(TL, T, SPLIT ? a.W : 1, w, J, MODE == 1 && fwd);       // (every forward sweep is MODE 1)
+    const int Tint = part.Tint;
+    const int Lw = SPLIT ? split_part_len(T, a.W) : Tint;
+    const int ow = part.ow;                                  // interior nodes before this part
+    const int Tw = part.Tw;                                  // interior nodes of this part (<= 0: none)
 
     // ---- first boundary node (t = 0 forward, T-1 backward): only the old neighbour.  Every wavefront
     // whose warm-up can reach it computes it; the first one stores it.
@@ -166,22 +172,22 @@ __global__ void __launch_bounds__(64) k_sweep(SweepArgs a) {
 
     // ---- interior: this part's nodes in 16 segments
     if (Tw > 0) {
-        const int Lseg = (Tw + 15) >> 4;
-        const int cL = c * Lseg;
-        const int before = ow + cL;                              // interior nodes between the chain's start and this column
-        const int jc = -(J < before ? J : before);               // first loop index of this column
-        const int jstart = -((J < ow + 15 * Lseg) ? J : ow + 15 * Lseg);   // of the wave (its last column starts earliest)
-        // starting state: the true boundary value when the warm-up reaches it, else zero
+        const int Lseg = part.Lseg;
+        const SweepColumn col = sweep_column(part, c);
+        const int before = col.before;                           // interior nodes between the chain's start and this column
+        const int jstart = sweep_first_step(part);               // of the wave (the earliest of its columns)
+        // starting state: the true boundary value when the warm-up reaches it, else zero (a warm-up from zero J steps early,
+        // or, forward and unsplit, a start at the column's own first node that the correction loop below makes good)
         d4 x[DT];
 #pragma unroll
         for (int m = 0; m < DT; ++m)
 #pragma unroll
-            for (int r = 0; r < 4; ++r) x[m][r] = (jc == -before) ? xs[16 * m + 4 * r + q] : 0.0;
+            for (int r = 0; r < 4; ++r) x[m][r] = (col.kind == SWEEP_START_BOUNDARY) ? xs[16 * m + 4 * r + q] : 0.0;
 
         // time index of this column at loop index j:  t = tbase + sgn * j
         const int tbase = fwd ? (1 + before) : (TL - 2 - before);
         const int tsafe = fwd ? 1 : TL - 2;      // an interior row that always exists: what inactive columns read
-        auto active = [&](int j) { int tt = cL + j; return j >= jc && j < Lseg && tt < Tw; };
+        auto active = [&](int j) { return sweep_active(part, col, j); };
         // input registers: y_t and the old neighbour mean, as B operands in permuted k order.
         // Loads are unconditional and unmasked: an inactive column reads a valid row and computes
         // a value that the select after the step discards (MFMA columns do not mix), and padded
@@ -229,7 +235,7 @@ __global__ void __launch_bounds__(64) k_sweep(SweepArgs a) {
             for (int r = 0; r < 4; ++r) x[m][r] = act ? acc[m][r] : x[m][r];
         };
         auto pending_row = [&](int j, bool act) {
-            return (act && j >= 0 && (a.keep_x || before + j == Tint - 1)) ? Xn + (size_t)(tbase + sgn * j) * DP : trash;
+            return (act && j >= 0 && (KEEPX || before + j == Tint - 1)) ? Xn + (size_t)(tbase + sgn * j) * DP : trash;
         };
         auto finish_step = [&](int j, const d4* acc) {
             const bool act = active(j);
@@ -287,26 +293,38 @@ __global__ void __launch_bounds__(64) k_sweep(SweepArgs a) {
             };
 #pragma unroll
             for (int p = 0; p < PF; ++p) { load_u(jstart + p, ub[p]); store_x(trash + 64 * p); }
-            for (int j = jstart; j < Lseg; j += PF) {
+            // counted: may a state of this step or of the one before enter Sxx?  Not while the whole wavefront warms up
+            // (j + p < 0 in every column): the tile in LDS is zero and stays zero, so those steps neither read nor stage nor
+            // multiply it.
+            auto step = [&](int j, int p, d4* ubp, auto counted) {
+                constexpr bool COUNTED = decltype(counted)::value;
+                d4 acc[DT];
+                double xt[DT][4];
+                if constexpr (COUNTED) tile_read(xt);       // the previous step's states
 #pragma unroll
-                for (int p = 0; p < PF; ++p) {
-                    d4 acc[DT];
-                    double xt[DT][4];
-                    tile_read(xt);                      // the previous step's states
-#pragma unroll
-                    for (int m = 0; m < DT; ++m) acc[m] = ub[p][m];
-                    __builtin_amdgcn_sched_barrier(0);
-                    load_u(j + p + PF, ub[p]);
-                    store_x(out_pending);
-                    __builtin_amdgcn_sched_barrier(0);
-                    mul_resident(acc, rn, x);
-                    const bool act = active(j + p);
-                    const bool keep = act && j + p >= 0;      // warm-up steps and idle columns do not count
-                    tile_accumulate(xt);
-                    finish_step(j + p, acc);
+                for (int m = 0; m < DT; ++m) acc[m] = ubp[m];
+                __builtin_amdgcn_sched_barrier(0);
+                load_u(j + p + PF, ubp);
+                store_x(out_pending);
+                __builtin_amdgcn_sched_barrier(0);
+                mul_resident(acc, rn, x);
+                const bool act = active(j + p);
+                [[maybe_unused]] const bool keep = act && j + p >= 0;      // warm-up steps and idle columns do not count
+                if constexpr (COUNTED) tile_accumulate(xt);
+                finish_step(j + p, acc);
+                if constexpr (COUNTED) {
 #pragma unroll
                     for (int m = 0; m < DT; ++m) tile_stage(m, keep);
                 }
+            };
+            int j = jstart;
+            for (; j + PF <= 0; j += PF) {
+#pragma unroll
+                for (int p = 0; p < PF; ++p) step(j, p, ub[p], std::false_type{});
+            }
+            for (; j < Lseg; j += PF) {
+#pragma unroll
+                for (int p = 0; p < PF; ++p) step(j, p, ub[p], std::true_type{});
             }
             {
                 double xt[DT][4];
@@ -331,7 +349,7 @@ __global__ void __launch_bounds__(64) k_sweep(SweepArgs a) {
         // loop head sees the same number of younger operations on both incoming edges and the wait
         // for the first loads does not also cover the stores behind them.
         load_y(jstart, yv);
-        store_x(trash);
+        if constexpr (KEEPX) store_x(trash);
         if constexpr (MODE == 1) store_x(trash + 64);  // stands for the c_t store
         load_o(jstart, mo);
         for (int j = jstart; j < Lseg; ++j) {
@@ -354,7 +372,7 @@ __global__ void __launch_bounds__(64) k_sweep(SweepArgs a) {
                 // the next loads queue up behind them.
                 __builtin_amdgcn_sched_barrier(0);
                 load_y(j + 1, yv);
-                store_x(out_pending);
+                if constexpr (KEEPX) store_x(out_pending);
                 __builtin_amdgcn_sched_barrier(0);
             }
             // R mu_{t-dir} (new): the previous accumulators are the B operands
@@ -375,7 +393,8 @@ __global__ void __launch_bounds__(64) k_sweep(SweepArgs a) {
             }
             finish_step(j, acc);
         }
-        store_x(out_pending);
+        if constexpr (KEEPX) store_x(out_pending);
+        else store_x((col.count > 0 && before + col.count == Tint) ? Xn + (size_t)(tbase + sgn * (col.count - 1)) * DP : trash);    // the last interior node
         }
         // the column that holds the last interior node hands its state to the closing boundary step
         const int clast = (Tw - 1) / Lseg;
@@ -389,6 +408,67 @@ __global__ void __launch_bounds__(64) k_sweep(SweepArgs a) {
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
         __builtin_amdgcn_s_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+        if constexpr (MODE == 1 && !SPLIT) {
+            // ---- seam correction (sweep_plan.h).  A column that started from zero at its own first node has computed
+            // mu_t - F^(k+1) e and c_t - F^(k+1) e at its (k+1)-th node, e the final state of the column to its left, which
+            // is exact by now.  e comes one lane along within the row of 16; then J steps of delta <- F delta, one product
+            // each, added to the stored c row of that node (and to the X row when the rows are kept).  Beyond J steps delta
+            // is below the bound that sizes the warm-up.  Other columns carry delta = 0 and aim at the trash row.
+            // Memory operations as in the main loop: a step's loads are issued ahead of the stores of the step before, and
+            // the prologue issues the same sequence.
+            const int ncorr = sweep_correction_steps(part);     // wave-uniform
+            if (ncorr > 0) {
+                const bool seam = col.kind == SWEEP_START_SEAM;
+                d4 dl[DT];
+#pragma unroll
+                for (int m = 0; m < DT; ++m)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const double e = __shfl_up(x[m][r], 1, 16);
+                        dl[m][r] = seam ? e : 0.0;
+                    }
+                auto correct = [&](auto keep) {
+                    constexpr bool KEEP = decltype(keep)::value;
+                    auto c_row = [&](int k) { return seam ? Un + (size_t)(tbase + k) * DP : trash; };
+                    // (the row next to the far boundary stays as the main loop stored it, as it does when the rows are not
+                    // kept: it can only be a column's J-th node, where delta is below the bound)
+                    auto x_row = [&](int k) { return (seam && before + k != Tint - 1) ? Xn + (size_t)(tbase + k) * DP : trash + 64; };
+                    auto load_row = [&](const double* p, d4* dst) {
+#pragma unroll
+                        for (int m = 0; m < DT; ++m) dst[m] = *reinterpret_cast<const d4*>(p + (m * 4 + q) * 4);
+                    };
+                    auto store_row = [&](double* p, const d4* src) {
+#pragma unroll
+                        for (int m = 0; m < DT; ++m) *reinterpret_cast<d4*>(p + (m * 4 + q) * 4) = src[m];
+                    };
+                    d4 cb[DT], xb[DT];
+                    load_row(c_row(0), cb);
+                    if constexpr (KEEP) load_row(x_row(0), xb);
+                    store_row(trash + 128, dl);
+                    if constexpr (KEEP) store_row(trash + 192, dl);
+                    for (int k = 0; k < ncorr; ++k) {
+                        d4 acc[DT], cs[DT], xc[DT];
+#pragma unroll
+                        for (int m = 0; m < DT; ++m) acc[m] = d4{0.0, 0.0, 0.0, 0.0};
+                        mul_resident(acc, rn, dl);
+#pragma unroll
+                        for (int m = 0; m < DT; ++m) {
+                            dl[m] = acc[m];
+                            cs[m] = cb[m] + acc[m];
+                            if constexpr (KEEP) xc[m] = xb[m] + acc[m];
+                        }
+                        const int kn = k + 1 < ncorr ? k + 1 : k;       // the last step fetches its own row again: not used
+                        __builtin_amdgcn_sched_barrier(0);
+                        load_row(c_row(kn), cb);
+                        if constexpr (KEEP) load_row(x_row(kn), xb);
+                        store_row(c_row(k), cs);
+                        if constexpr (KEEP) store_row(x_row(k), xc);
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
+                };
+                correct(std::integral_constant<bool, KEEPX>{});
+            }
+        }
     }
 
     // ---- closing boundary node (t = T_n-1 forward, 0 backward): only the new neighbour; done by the
@@ -444,10 +524,12 @@ template <int DT, int KT>
 static int launch_sweep_t(pyvb_lds* h, const SweepArgs& a, bool read_cache) {
     const bool full = h->D == 16 * DT && a.K == 16 * KT;
     const int mode = a.dir == PYVB_FORWARD ? 1 : (read_cache ? 2 : 0);      // MODE 2 reads c_t from U and writes the interior Sxx (h->sxx)
-#define PYVB_SWEEP_CASE(F, M) do { if (h->W > 1) hipLaunchKernelGGL((k_sweep<DT, KT, F, M, true>), dim3(h->N, h->W), dim3(64), 0, h->stream, a); \
-                                   else hipLaunchKernelGGL((k_sweep<DT, KT, F, M, false>), dim3(h->N), dim3(64), 0, h->stream, a); } while (0)
-    if (full) { if (mode == 1) PYVB_SWEEP_CASE(true, 1); else if (mode == 2) PYVB_SWEEP_CASE(true, 2); else PYVB_SWEEP_CASE(true, 0); }
-    else { if (mode == 1) PYVB_SWEEP_CASE(false, 1); else if (mode == 2) PYVB_SWEEP_CASE(false, 2); else PYVB_SWEEP_CASE(false, 0); }
+#define PYVB_SWEEP_CASE(F, M, X) do { if (h->W > 1) hipLaunchKernelGGL((k_sweep<DT, KT, F, M, true, X>), dim3(h->N, h->W), dim3(64), 0, h->stream, a); \
+                                      else hipLaunchKernelGGL((k_sweep<DT, KT, F, M, false, X>), dim3(h->N), dim3(64), 0, h->stream, a); } while (0)
+#define PYVB_SWEEP_FORWARD(F) do { if (a.keep_x) PYVB_SWEEP_CASE(F, 1, true); else PYVB_SWEEP_CASE(F, 1, false); } while (0)
+    if (full) { if (mode == 1) PYVB_SWEEP_FORWARD(true); else if (mode == 2) PYVB_SWEEP_CASE(true, 2, true); else PYVB_SWEEP_CASE(true, 0, true); }
+    else { if (mode == 1) PYVB_SWEEP_FORWARD(false); else if (mode == 2) PYVB_SWEEP_CASE(false, 2, true); else PYVB_SWEEP_CASE(false, 0, true); }
+#undef PYVB_SWEEP_FORWARD
 #undef PYVB_SWEEP_CASE
     return PYVB_OK;
 }
