@@ -76,8 +76,8 @@ enum { PYVB_FORWARD = 0, PYVB_BACKWARD = 1 };
 /* which kernels pyvb_lds_timing_get() reports on */
 enum { PYVB_K_PREP = 0, PYVB_K_SWEEP_FWD = 1, PYVB_K_STATS = 2, PYVB_K_PARAMS = 3, PYVB_K_STEP = 4,
        PYVB_K_SWEEP_BWD = 5, PYVB_K_ELBO = 6, PYVB_K_GY = 7 /* 128-wide class: G y_t ahead of a sweep */,
-       PYVB_K_INPUTS = 8 /* handles with inputs: the kernels of k_inputs.hip */,
-       PYVB_K_REGRESSORS = 9 /* handles with regressors: the kernels of k_regressors.hip */, PYVB_K_COUNT = 10 };
+       PYVB_K_INPUTS = 8 /* handles with inputs: the kernels of k_known.hip */,
+       PYVB_K_REGRESSORS = 9 /* handles with regressors: the kernels of k_known.hip */, PYVB_K_COUNT = 10 };
 
 const char* pyvb_last_error(void);
 int pyvb_version(void);
@@ -161,7 +161,7 @@ int pyvb_lds_get_models(pyvb_lds* h, int* model);
  * node.py:121-129), pyvb_lds_elbo in both modes (L_X with that moment; the columns of B add to part 2 what the columns of A do, so
  * parts stay [N][6]), pyvb_lds_iterate, pyvb_lds_iterate_until and pyvb_lds_iterate_until_model (forward, backward, As, Bs, Cs, Q, R,
  * bound), chain lengths, every time split, the activity mask (a switched-off replicate keeps its B), status, communicators.
- * The inputs ride through the sweeps as 2 P extra output channels (k_inputs.hip), hence the limit of this route:
+ * The inputs ride through the sweeps as 2 P extra output channels (k_known.hip), hence the limit of this route:
  * max(D, K + 2 P) <= 64.
  * PYVB_E_UNSUPPORTED before any HIP call / launch, the message naming the cause: Wishart noise; max(D, K + 2 P) > 64; outputs that hold
  * NaN (pyvb_lds_set_observations); known entries of A / C (pyvb_lds_set_column_observations); Gamma / DiagonalGamma precision parents
@@ -200,7 +200,7 @@ int pyvb_lds_update_B(pyvb_lds* h);
  * the columns of E add to part 3 what the columns of C do, so parts stay [N][6]), pyvb_lds_iterate, pyvb_lds_iterate_until and
  * pyvb_lds_iterate_until_model (forward, backward, As, [Bs], Cs, Es, Q, R, bound), chain lengths, every time split, the activity
  * mask (a switched-off replicate keeps its E), status, communicators.
- * The regressors ride through the sweeps as Pv extra output channels behind the 2 P of the inputs (k_regressors.hip), hence the
+ * The regressors ride through the sweeps as Pv extra output channels behind the 2 P of the inputs (k_known.hip), hence the
  * limit of this route, the only cap on Pv: max(D, K + 2 P + Pv) <= 64.
  * PYVB_E_UNSUPPORTED before any HIP call / launch, the message naming the regressors and the cause: Wishart noise;
  * max(D, K + 2 P + Pv) > 64; outputs that hold NaN (pyvb_lds_set_observations); known entries of A / C

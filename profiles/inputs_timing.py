@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""What a known input costs on the fused LDS path (pyvb_lds_create_inputs, k_inputs.hip): time per iteration at N = 1024 replicates of
+"""What a known input costs on the fused LDS path (pyvb_lds_create_inputs, k_known.hip): time per iteration at N = 1024 replicates of
 T = 10^4 steps for
     inputs   D = 32, K = 32, P = 8     the rows [y_t ; u_t ; u_{t+1}] are 48 wide
     plain32  D = 32, K = 32            the same model without the input
@@ -7,7 +7,7 @@ T = 10^4 steps for
 so plain48 -> inputs is what the new small kernels and the separate launches of A, B, C, Q, R add.  The three handles are timed in
 turn, three rounds each (alternating, so that a drift of the machine shows as spread, not as a difference), a host clock around
 `steps` iterations that end in a synchronise, after a warm-up; then one more window per handle with the event timers on, for the
-time and the launches per kernel (kernel_times; "inputs" is every kernel of k_inputs.hip together).
+time and the launches per kernel (kernel_times; "inputs" is every kernel of k_known.hip together).
 
     python profiles/inputs_timing.py [N] [T] [steps] > profiles/inputs_timing.txt
 """

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""What known regressors in the output equation cost on the fused LDS path (pyvb_lds_create_regressors, k_regressors.hip): time per
+"""What known regressors in the output equation cost on the fused LDS path (pyvb_lds_create_regressors, k_known.hip): time per
 iteration at N = 1024 replicates of T = 10^4 steps for
     regressors  D = 32, K = 32, Pv = 8    the rows [y_t ; v_t] are 40 wide
     plain32     D = 32, K = 32            the same model without the regressors
@@ -7,7 +7,7 @@ iteration at N = 1024 replicates of T = 10^4 steps for
 so plain40 -> regressors is what the new small kernels and the separate launches of C, E, R add.  The three handles are timed in turn,
 three rounds each (alternating, so that a drift of the machine shows as spread, not as a difference), a host clock around `steps`
 iterations that end in a synchronise, after a warm-up; then one more window per handle with the event timers on, for the time and the
-launches per kernel (kernel_times; "regressors" is every kernel of k_regressors.hip together) and their share of the iteration.
+launches per kernel (kernel_times; "regressors" is every kernel of k_known.hip together) and their share of the iteration.
 
     python profiles/regressors_timing.py [N] [T] [steps] > profiles/regressors_timing.txt
 """
@@ -79,7 +79,7 @@ def main():
         print("%-10s per iteration, ms (launches): %s" % (k, "  ".join("%s %.4f (%g)" % (nm, v[0] / STEPS, v[1] / STEPS) for nm, v in sorted(kt.items()) if v[1])))
         if "regressors" in kt:
             total = sum(v[0] for v in kt.values())
-            print("%-10s the kernels of k_regressors.hip: %.4f ms of the %.4f ms the kernels of an iteration take, %.2f %%" %
+            print("%-10s the kernels of k_known.hip: %.4f ms of the %.4f ms the kernels of an iteration take, %.2f %%" %
                   (k, kt["regressors"][0] / STEPS, total / STEPS, 100.0 * kt["regressors"][0] / total))
         assert np.all(np.isfinite(b.elbo_history(1)))
         b.close()

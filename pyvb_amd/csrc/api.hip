@@ -61,6 +61,20 @@ int pyvb_device_count(int* count) {
     return PYVB_OK;
 }
 
+// the buffers of one side's known channels (KnownChannels, common.h); nothing on a handle without them
+static int known_alloc(pyvb_lds* h, int side) {
+    KnownChannels& k = h->known[side];
+    if (!k.width) return PYVB_OK;
+    const size_t n = h->N, D = h->D, rows = lds_known_rows(h, side), W = k.width;
+    int rc;
+    if ((rc = h->mem.zeros(&k.in, n * h->T * W)) || (rc = h->mem.zeros(&k.mean, n * rows * W)) || (rc = h->mem.zeros(&k.var, n * W * rows)) ||
+        (rc = h->mem.alloc((void**)&k.qld, n * W * sizeof(double), 0xFF)) || (rc = h->mem.alloc((void**)&k.lnd, n * W * sizeof(double), 0xFF)) ||    // NaN
+        (rc = h->mem.zeros(&k.pm, rows * W)) || (rc = h->mem.zeros(&k.pp, W * rows)) || (rc = h->mem.zeros(&k.pld, W)) ||
+        (rc = h->mem.zeros(&k.gram, n * W * W)) || (rc = h->mem.zeros(&k.cross_lhs, n * rows * W)) || (rc = h->mem.zeros(&k.cross_x, n * W * D)) ||
+        (rc = h->mem.zeros(&k.saved, n * rows * D))) return rc;
+    return PYVB_OK;
+}
+
 // The one creation path; lengths null: every chain has T nodes, model null: every replicate is a model.  Arguments are checked
 // and, where a combination is not served, refused before the first HIP call; *out is written once, when everything exists.
 // P: known inputs that drive the states (pyvb_lds_create_inputs), 0: none.  Pv: known regressors in the output equation
@@ -115,9 +129,9 @@ static int lds_create(pyvb_lds** out, int device, int N, int T, int D, int K, in
     ARGCHK(device >= 0 && device < ndev, "no such device");
     HIPCHK(hipSetDevice(device));
     pyvb_lds* h = new pyvb_lds();       // value-initialised: every pointer null, every flag false
-    h->device = device; h->N = N; h->T = T; h->D = D; h->K = K; h->noise = noise_kind; h->P = P; h->Pv = Pv;
+    h->device = device; h->N = N; h->T = T; h->D = D; h->K = K; h->noise = noise_kind; h->known[0].width = P; h->known[1].width = Pv;
     // (with inputs and regressors the gains, the statistics and the kernels that form them are those of K + 2 P + Pv outputs:
-    // k_inputs.hip, k_regressors.hip)
+    // k_known.hip)
     const LdsGeometry g = lds_geometry(N, T, D, K + 2 * P + Pv, noise_kind);     // geometry.h: the shape class, the chunks, the time split, the extents
     h->L = g.L; h->big = g.big; h->dense = g.dense;
     h->nchunk = g.nchunk; h->chunk_len = g.chunk_len; h->W = g.W;
@@ -208,20 +222,7 @@ static int lds_create(pyvb_lds** out, int device, int N, int T, int D, int K, in
     }
     TRYHIP(hipMemset(h->pri.A_obs, 0xFF, ((size_t)D * D + (size_t)K * D) * sizeof(double)));     // all-ones bytes = NaN = nothing observed
     if (P || Pv) { TRY(dev_alloc(&h->Yt, n * T * (K + 2 * P + Pv))); TRY(dev_alloc(&h->Ct, n * (K + 2 * P + Pv) * D)); }
-    if (Pv) {
-        TRY(dev_alloc(&h->Vin, n * T * Pv));
-        TRY(dev_alloc(&h->E_mean, n * K * Pv)); TRY(dev_alloc(&h->E_var, n * Pv * K));
-        TRY(h->mem.alloc((void**)&h->qld_E, n * Pv * sizeof(double), 0xFF)); TRY(h->mem.alloc((void**)&h->lnd_E, n * Pv * sizeof(double), 0xFF));   // NaN
-        TRY(dev_alloc(&h->E_pm, (size_t)K * Pv)); TRY(dev_alloc(&h->E_pp, (size_t)Pv * K)); TRY(dev_alloc(&h->E_pld, Pv));
-        TRY(dev_alloc(&h->Svv, n * Pv * Pv)); TRY(dev_alloc(&h->Syv, n * K * Pv)); TRY(dev_alloc(&h->rmom, n * ((size_t)Pv * D + (size_t)K * D)));
-    }
-    if (P) {
-        TRY(dev_alloc(&h->Uin, n * T * P));
-        TRY(dev_alloc(&h->B_mean, n * D * P)); TRY(dev_alloc(&h->B_var, n * P * D));
-        TRY(h->mem.alloc((void**)&h->qld_B, n * P * sizeof(double), 0xFF)); TRY(h->mem.alloc((void**)&h->lnd_B, n * P * sizeof(double), 0xFF));   // NaN
-        TRY(dev_alloc(&h->B_pm, (size_t)D * P)); TRY(dev_alloc(&h->B_pp, (size_t)P * D)); TRY(dev_alloc(&h->B_pld, P));
-        TRY(dev_alloc(&h->Suu, n * P * P)); TRY(dev_alloc(&h->imom, n * (2 * (size_t)D * P + (size_t)D * D)));
-    }
+    for (int side = 0; side < 2; ++side) TRY(known_alloc(h, side));
     h->st.T = T;
     h->st.fresh = (unsigned char*)calloc(T, 1);
     h->world = 1;
@@ -306,7 +307,7 @@ struct LdsDevice {
     pyvb_lds* h;
     hipStream_t main_stream() const { return h->stream; }
     int prep() { return launch_prep(h); }
-    int in_gains() { return launch_in_gains(h); }
+    int known_gains(int side) { return launch_known_gains(h, side); }
     int wexpect() { return launch_wexpect(h); }
     int dense_pre() { return launch_dense_pre(h); }
     int sweep(int direction, int src, bool read_cache, bool keep_x) { return launch_sweep(h, direction, src, read_cache, keep_x); }
@@ -315,10 +316,10 @@ struct LdsDevice {
     int moments(bool sxx_from_sweep) { return launch_moments(h, sxx_from_sweep); }
     int tie_moments() { return launch_tie(h, h->mom, (size_t)3 * h->D * h->D + (size_t)h->K * h->D + h->D); }
     int tie_syy() { return launch_tie(h, h->Syy, h->K); }
-    int in_moments() { return launch_in_moments(h); }
-    int in_HA() { return launch_in_HA(h); }
-    int in_colsB() { return launch_in_colsB(h); }
-    int in_resQ() { return launch_in_resQ(h); }
+    int known_moments(int side) { return launch_known_moments(h, side); }
+    int known_H(int side) { return launch_known_H(h, side); }
+    int known_cols(int side) { return launch_known_cols(h, side); }
+    int known_resid(int side) { return launch_known_resid(h, side); }
     int resid(int which) { return launch_resid(h, which); }
     int wresid(int which, int update, bool use_sg) { return launch_wresid(h, which, update, use_sg); }
     int cols(int which, int c0, int c1, int fuse = 0) { return launch_cols(h, which, c0, c1, fuse); }
@@ -332,13 +333,7 @@ struct LdsDevice {
     int impute() { return launch_impute(h); }
     int impute_dense() { return launch_impute_dense(h); }
     int elbo(hipStream_t stream) { return launch_elbo(h, stream); }
-    int in_elbo(hipStream_t stream) { return launch_in_elbo(h, stream); }
-    int rg_gains() { return launch_rg_gains(h); }
-    int rg_moments() { return launch_rg_moments(h); }
-    int rg_HC() { return launch_rg_HC(h); }
-    int rg_colsE() { return launch_rg_colsE(h); }
-    int rg_resR() { return launch_rg_resR(h); }
-    int rg_elbo(hipStream_t stream) { return launch_rg_elbo(h, stream); }
+    int known_elbo(int side, hipStream_t stream) { return launch_known_elbo(h, side, stream); }
     int elbo_dense() { return launch_elbo_dense(h); }
     int carry_x(int src) { return launch_carry(h, h->X[src], h->X[1 - src], (size_t)h->T * h->L.DP); }
     int carry_classes() {
@@ -356,8 +351,9 @@ struct LdsDevice {
     int form_lnd_x() { return ::form_lnd_x(h); }
 };
 static LdsFlow<LdsDevice> flow(pyvb_lds* h) {
-    return {h->st, {h->T, h->N, h->D, h->P, h->dense, h->big, h->has_missing, h->bound, h->inputs_set, h->input_priors_set, &h->rep, h->parents,
-                        h->Pv, h->regressors_set, h->regressor_priors_set}, {h}};
+    const KnownChannels* k = h->known;
+    return {h->st, {h->T, h->N, h->D, h->dense, h->big, h->has_missing, h->bound, &h->rep, h->parents,
+                    {k[0].width, k[1].width}, {k[0].set, k[1].set}, {k[0].priors_set, k[1].priors_set}}, {h}};
 }
 static int settle_parked(pyvb_lds* h) { return flow(h).settle_parked(); }
 
@@ -472,12 +468,12 @@ static int set_parents(pyvb_lds* h, int which, int kind, const double* a0, const
     int rc = parents_gate(h, which, 0);
     if (rc) return rc;
     const char* name = kind == PARENTS_GAMMA ? "Gamma" : "DiagonalGamma";
-    if (h->Pv) {
-        pyvb_set_error("%s precision parents of the columns are not served on a handle with regressors (pyvb_lds_create_regressors, k_regressors.hip)", name);
+    if (h->known[1].width) {
+        pyvb_set_error("%s precision parents of the columns are not served on a handle with regressors (pyvb_lds_create_regressors, k_known.hip)", name);
         return PYVB_E_UNSUPPORTED;
     }
-    if (h->P) {
-        pyvb_set_error("%s precision parents of the columns are not served on a handle with inputs (pyvb_lds_create_inputs, k_inputs.hip)", name);
+    if (h->known[0].width) {
+        pyvb_set_error("%s precision parents of the columns are not served on a handle with inputs (pyvb_lds_create_inputs, k_known.hip)", name);
         return PYVB_E_UNSUPPORTED;
     }
     if (h->dense) {
@@ -650,16 +646,16 @@ int pyvb_lds_get_column_cov(pyvb_lds* h, double* A_cov, double* C_cov) {
 
 int pyvb_lds_set_column_observations(pyvb_lds* h, const double* A_obs, const double* C_obs) {
     ENTER(h);
-    if (h->P || h->Pv) {
+    if (h->known[0].width || h->known[1].width) {
         bool known = false;
         for (size_t i = 0; A_obs && i < (size_t)h->D * h->D && !known; ++i) known = A_obs[i] == A_obs[i];
         for (size_t i = 0; C_obs && i < (size_t)h->K * h->D && !known; ++i) known = C_obs[i] == C_obs[i];
-        if (known && h->Pv) {
-            pyvb_set_error("known entries of A / C are not served on a handle with regressors (pyvb_lds_create_regressors, k_regressors.hip)");
+        if (known && h->known[1].width) {
+            pyvb_set_error("known entries of A / C are not served on a handle with regressors (pyvb_lds_create_regressors, k_known.hip)");
             return PYVB_E_UNSUPPORTED;
         }
         if (known) {
-            pyvb_set_error("known entries of A / C are not served on a handle with inputs (pyvb_lds_create_inputs, k_inputs.hip)");
+            pyvb_set_error("known entries of A / C are not served on a handle with inputs (pyvb_lds_create_inputs, k_known.hip)");
             return PYVB_E_UNSUPPORTED;
         }
     }
@@ -687,7 +683,7 @@ int pyvb_lds_set_observations(pyvb_lds* h, const double* Y) {
             const double* Yr = Y + (size_t)r * h->T * h->K;
             for (size_t i = 0; i < (size_t)h->rep.length(r) * h->K; ++i)
                 if (Yr[i] != Yr[i]) {
-                    if (h->Pv) { missing = true; break; }       // (refused below, naming the regressors)
+                    if (h->known[1].width) { missing = true; break; }       // (refused below, naming the regressors)
                     pyvb_set_error("outputs that hold NaN are not served together with chains of unequal length (k_missing.hip): "
                                    "replicate %d, t = %d of its %d nodes", r, (int)(i / h->K), h->rep.length(r));
                     return PYVB_E_UNSUPPORTED;
@@ -696,12 +692,12 @@ int pyvb_lds_set_observations(pyvb_lds* h, const double* Y) {
     } else
         for (size_t i = 0; i < n && !missing; ++i) missing = Y[i] != Y[i];
     int rc;
-    if (missing && h->Pv) {
+    if (missing && h->known[1].width) {
         pyvb_set_error("outputs that hold NaN are not served on a handle with regressors (pyvb_lds_create_regressors, k_missing.hip): "
                        "sum_t y_t v_t^T and the imputation would both change");
         return PYVB_E_UNSUPPORTED;
     }
-    if (missing && h->P) {
+    if (missing && h->known[0].width) {
         pyvb_set_error("outputs that hold NaN are not served on a handle with inputs (pyvb_lds_create_inputs, k_missing.hip)");
         return PYVB_E_UNSUPPORTED;
     }
@@ -731,8 +727,8 @@ int pyvb_lds_set_observations(pyvb_lds* h, const double* Y) {
         h->has_missing = false;
         if ((rc = h2d(h, h->Y, Y, n))) return rc;
         if ((rc = flow(h).syy())) return rc;
-        if (h->P && !h->Pv && (rc = launch_in_assemble(h))) return rc;       // the rows [y_t ; u_t ; u_{t+1}] the sweeps read
-        if (h->Pv && ((rc = launch_rg_assemble(h)) || (rc = launch_rg_sums(h)))) return rc;      // [y_t ; u_t ; u_{t+1} ; v_t], and Syv
+        if ((h->known[0].width || h->known[1].width) && (rc = launch_known_assemble(h))) return rc;      // the rows [y_t ; u_t ; u_{t+1} ; v_t] the sweeps read
+        if (h->known[1].width && (rc = launch_known_gram(h, 1))) return rc;      // Syv
         if (h->dense && (rc = launch_syy_full(h))) return rc;
     }
     HIPCHK(hipStreamSynchronize(h->stream));
@@ -787,167 +783,115 @@ int pyvb_lds_update_Y(pyvb_lds* h) {
     return flow(h).update_Y();
 }
 
-// ---- A known input that drives the states (pyvb_lds_create_inputs; the kernels are k_inputs.hip)
-static int inputs_gate(const pyvb_lds* h) {
+// ---- Known channels: an input that drives the states (side 0, pyvb_lds_create_inputs) and regressors in the output equation
+// (side 1, pyvb_lds_create_regressors); KnownChannels of common.h, the kernels are k_known.hip.  One copy of every entry, with
+// the side's words in the messages.
+static const struct { const char *what, *chan, *gain; } known_words[2] = {{"inputs", "U", "B"}, {"regressors", "V", "E"}};
+
+static int known_gate(const pyvb_lds* h, int side) {
     ARGCHK(h, "handle is NULL");
-    ARGCHK(h->P > 0, "the handle was created without inputs (pyvb_lds_create_inputs makes one with)");
+    if (h->known[side].width <= 0) {
+        pyvb_set_error("the handle was created without %s (pyvb_lds_create_%s makes one with)", known_words[side].what, known_words[side].what);
+        return PYVB_E_ARG;
+    }
     return PYVB_OK;
 }
 
-int pyvb_lds_set_inputs(pyvb_lds* h, const double* U) {
-    int rc = inputs_gate(h);
+static int known_set_channels(pyvb_lds* h, int side, const double* U) {
+    int rc = known_gate(h, side);
     if (rc) return rc;
-    ARGCHK(U, "U is NULL");
-    const size_t T = h->T, P = h->P;
+    const char* name = known_words[side].chan;
+    if (!U) { pyvb_set_error("%s is NULL", name); return PYVB_E_ARG; }
+    KnownChannels& k = h->known[side];
+    const size_t T = h->T, P = k.width;
     for (int n = 0; n < h->N; ++n)
         for (size_t i = 0; i < T * P; ++i)
             if (!std::isfinite(U[(size_t)n * T * P + i])) {
-                pyvb_set_error("U is not finite: replicate %d, row %d, channel %d", n, (int)(i / P), (int)(i % P));
+                pyvb_set_error("%s is not finite: replicate %d, row %d, channel %d", name, n, (int)(i / P), (int)(i % P));
                 return PYVB_E_ARG;
             }
     ENTER(h);
-    if ((rc = h2d(h, h->Uin, U, (size_t)h->N * T * P))) return rc;
-    if ((rc = h->Pv ? launch_rg_assemble(h) : launch_in_assemble(h)) || (rc = launch_in_suu(h))) return rc;
+    if ((rc = h2d(h, k.in, U, (size_t)h->N * T * P))) return rc;
+    if ((rc = launch_known_assemble(h)) || (rc = launch_known_gram(h, side))) return rc;
     HIPCHK(hipStreamSynchronize(h->stream));
-    h->inputs_set = true;
+    k.set = true;
     h->st.outputs_changed();        // what the sweeps read as outputs has changed: c_t and every sum over t with it
     return PYVB_OK;
 }
 
-int pyvb_lds_get_inputs(pyvb_lds* h, double* U) {
-    int rc = inputs_gate(h);
+static int known_get_channels(pyvb_lds* h, int side, double* U) {
+    int rc = known_gate(h, side);
     if (rc) return rc;
-    ARGCHK(U, "U is NULL");
+    if (!U) { pyvb_set_error("%s is NULL", known_words[side].chan); return PYVB_E_ARG; }
     ENTER(h);
-    if ((rc = d2h(h, U, h->Uin, (size_t)h->N * h->T * h->P))) return rc;
+    if ((rc = d2h(h, U, h->known[side].in, (size_t)h->N * h->T * h->known[side].width))) return rc;
     return pyvb_lds_sync(h);
 }
 
-int pyvb_lds_set_input_priors(pyvb_lds* h, const double* B_pm, const double* B_pp) {
-    int rc = inputs_gate(h);
+static int known_set_priors(pyvb_lds* h, int side, const double* pm, const double* pp) {
+    int rc = known_gate(h, side);
     if (rc) return rc;
-    ARGCHK(B_pm && B_pp, "B_prior_mean and B_prior_prec are required");
-    const int D = h->D, P = h->P;
-    for (int i = 0; i < P * D; ++i) ARGCHK(B_pp[i] > 0.0 && std::isfinite(B_pp[i]) && std::isfinite(B_pm[i]), "B_prior_prec must be positive and B_prior_mean finite");
+    const char* g = known_words[side].gain;
+    if (!(pm && pp)) { pyvb_set_error("%s_prior_mean and %s_prior_prec are required", g, g); return PYVB_E_ARG; }
+    KnownChannels& k = h->known[side];
+    const int D = lds_known_rows(h, side), P = k.width;
+    for (int i = 0; i < P * D; ++i)
+        if (!(pp[i] > 0.0 && std::isfinite(pp[i]) && std::isfinite(pm[i]))) {
+            pyvb_set_error("%s_prior_prec must be positive and %s_prior_mean finite", g, g);
+            return PYVB_E_ARG;
+        }
     std::vector<double> ld((size_t)P, 0.0);     // ln det of the diagonal prior precision of every column (node.py:301-302)
     for (int i = 0; i < P; ++i)
-        for (int k = 0; k < D; ++k) ld[i] += log(B_pp[(size_t)i * D + k]);
+        for (int r = 0; r < D; ++r) ld[i] += log(pp[(size_t)i * D + r]);
     ENTER(h);
-    if ((rc = h2d(h, h->B_pm, B_pm, (size_t)D * P)) || (rc = h2d(h, h->B_pp, B_pp, (size_t)P * D)) || (rc = h2d(h, h->B_pld, ld.data(), P))) return rc;
+    if ((rc = h2d(h, k.pm, pm, (size_t)D * P)) || (rc = h2d(h, k.pp, pp, (size_t)P * D)) || (rc = h2d(h, k.pld, ld.data(), P))) return rc;
     HIPCHK(hipStreamSynchronize(h->stream));    // ld is about to go out of scope
-    h->input_priors_set = true;
+    k.priors_set = true;
     h->st.parameters_changed();
     return PYVB_OK;
 }
 
-int pyvb_lds_set_input_state(pyvb_lds* h, const double* B_mean, const double* B_colvar) {
-    int rc = inputs_gate(h);
+static int known_set_state(pyvb_lds* h, int side, const double* mean, const double* colvar) {
+    int rc = known_gate(h, side);
     if (rc) return rc;
     ENTER(h);
-    const size_t n = (size_t)h->N * h->D * h->P;
-    if ((rc = h2d(h, h->B_mean, B_mean, n)) || (rc = h2d(h, h->B_var, B_colvar, n))) return rc;
+    const size_t n = (size_t)h->N * lds_known_rows(h, side) * h->known[side].width;
+    if ((rc = h2d(h, h->known[side].mean, mean, n)) || (rc = h2d(h, h->known[side].var, colvar, n))) return rc;
     HIPCHK(hipStreamSynchronize(h->stream));
-    if (B_mean || B_colvar) h->st.parameters_changed();
+    if (mean || colvar) h->st.parameters_changed();
     return PYVB_OK;
 }
 
-int pyvb_lds_get_input_state(pyvb_lds* h, double* B_mean, double* B_colvar, double* qld_B, double* lnd_B) {
-    int rc = inputs_gate(h);
+static int known_get_state(pyvb_lds* h, int side, double* mean, double* colvar, double* qld, double* lnd) {
+    int rc = known_gate(h, side);
     if (rc) return rc;
     ENTER(h);
-    const size_t N = h->N, D = h->D, P = h->P;
-    if ((rc = d2h(h, B_mean, h->B_mean, N * D * P)) || (rc = d2h(h, B_colvar, h->B_var, N * P * D)) ||
-        (rc = d2h(h, qld_B, h->qld_B, N * P)) || (rc = d2h(h, lnd_B, h->lnd_B, N * P))) return rc;
+    const KnownChannels& k = h->known[side];
+    const size_t N = h->N, D = lds_known_rows(h, side), P = k.width;
+    if ((rc = d2h(h, mean, k.mean, N * D * P)) || (rc = d2h(h, colvar, k.var, N * P * D)) ||
+        (rc = d2h(h, qld, k.qld, N * P)) || (rc = d2h(h, lnd, k.lnd, N * P))) return rc;
     return pyvb_lds_sync(h);
 }
 
-int pyvb_lds_update_B(pyvb_lds* h) {
-    int rc = inputs_gate(h);
+static int known_update_gain(pyvb_lds* h, int side) {
+    int rc = known_gate(h, side);
     if (rc) return rc;
     ENTER(h);
-    return flow(h).update_B();
+    return flow(h).update_gain(side);
 }
 
-// ---- Known regressors in the output equation (pyvb_lds_create_regressors; the kernels are k_regressors.hip)
-static int regressors_gate(const pyvb_lds* h) {
-    ARGCHK(h, "handle is NULL");
-    ARGCHK(h->Pv > 0, "the handle was created without regressors (pyvb_lds_create_regressors makes one with)");
-    return PYVB_OK;
-}
-
-int pyvb_lds_set_regressors(pyvb_lds* h, const double* V) {
-    int rc = regressors_gate(h);
-    if (rc) return rc;
-    ARGCHK(V, "V is NULL");
-    const size_t T = h->T, Pv = h->Pv;
-    for (int n = 0; n < h->N; ++n)
-        for (size_t i = 0; i < T * Pv; ++i)
-            if (!std::isfinite(V[(size_t)n * T * Pv + i])) {
-                pyvb_set_error("V is not finite: replicate %d, row %d, channel %d", n, (int)(i / Pv), (int)(i % Pv));
-                return PYVB_E_ARG;
-            }
-    ENTER(h);
-    if ((rc = h2d(h, h->Vin, V, (size_t)h->N * T * Pv))) return rc;
-    if ((rc = launch_rg_assemble(h)) || (rc = launch_rg_sums(h))) return rc;
-    HIPCHK(hipStreamSynchronize(h->stream));
-    h->regressors_set = true;
-    h->st.outputs_changed();        // what the sweeps read as outputs has changed: c_t and every sum over t with it
-    return PYVB_OK;
-}
-
-int pyvb_lds_get_regressors(pyvb_lds* h, double* V) {
-    int rc = regressors_gate(h);
-    if (rc) return rc;
-    ARGCHK(V, "V is NULL");
-    ENTER(h);
-    if ((rc = d2h(h, V, h->Vin, (size_t)h->N * h->T * h->Pv))) return rc;
-    return pyvb_lds_sync(h);
-}
-
-int pyvb_lds_set_regressor_priors(pyvb_lds* h, const double* E_pm, const double* E_pp) {
-    int rc = regressors_gate(h);
-    if (rc) return rc;
-    ARGCHK(E_pm && E_pp, "E_prior_mean and E_prior_prec are required");
-    const int K = h->K, Pv = h->Pv;
-    for (int i = 0; i < Pv * K; ++i) ARGCHK(E_pp[i] > 0.0 && std::isfinite(E_pp[i]) && std::isfinite(E_pm[i]), "E_prior_prec must be positive and E_prior_mean finite");
-    std::vector<double> ld((size_t)Pv, 0.0);    // ln det of the diagonal prior precision of every column (node.py:301-302)
-    for (int i = 0; i < Pv; ++i)
-        for (int k = 0; k < K; ++k) ld[i] += log(E_pp[(size_t)i * K + k]);
-    ENTER(h);
-    if ((rc = h2d(h, h->E_pm, E_pm, (size_t)K * Pv)) || (rc = h2d(h, h->E_pp, E_pp, (size_t)Pv * K)) || (rc = h2d(h, h->E_pld, ld.data(), Pv))) return rc;
-    HIPCHK(hipStreamSynchronize(h->stream));    // ld is about to go out of scope
-    h->regressor_priors_set = true;
-    h->st.parameters_changed();
-    return PYVB_OK;
-}
-
-int pyvb_lds_set_regressor_state(pyvb_lds* h, const double* E_mean, const double* E_colvar) {
-    int rc = regressors_gate(h);
-    if (rc) return rc;
-    ENTER(h);
-    const size_t n = (size_t)h->N * h->K * h->Pv;
-    if ((rc = h2d(h, h->E_mean, E_mean, n)) || (rc = h2d(h, h->E_var, E_colvar, n))) return rc;
-    HIPCHK(hipStreamSynchronize(h->stream));
-    if (E_mean || E_colvar) h->st.parameters_changed();
-    return PYVB_OK;
-}
-
-int pyvb_lds_get_regressor_state(pyvb_lds* h, double* E_mean, double* E_colvar, double* qld_E, double* lnd_E) {
-    int rc = regressors_gate(h);
-    if (rc) return rc;
-    ENTER(h);
-    const size_t N = h->N, K = h->K, Pv = h->Pv;
-    if ((rc = d2h(h, E_mean, h->E_mean, N * K * Pv)) || (rc = d2h(h, E_colvar, h->E_var, N * Pv * K)) ||
-        (rc = d2h(h, qld_E, h->qld_E, N * Pv)) || (rc = d2h(h, lnd_E, h->lnd_E, N * Pv))) return rc;
-    return pyvb_lds_sync(h);
-}
-
-int pyvb_lds_update_E(pyvb_lds* h) {
-    int rc = regressors_gate(h);
-    if (rc) return rc;
-    ENTER(h);
-    return flow(h).update_E();
-}
+int pyvb_lds_set_inputs(pyvb_lds* h, const double* U) { return known_set_channels(h, 0, U); }
+int pyvb_lds_get_inputs(pyvb_lds* h, double* U) { return known_get_channels(h, 0, U); }
+int pyvb_lds_set_input_priors(pyvb_lds* h, const double* B_pm, const double* B_pp) { return known_set_priors(h, 0, B_pm, B_pp); }
+int pyvb_lds_set_input_state(pyvb_lds* h, const double* B_mean, const double* B_colvar) { return known_set_state(h, 0, B_mean, B_colvar); }
+int pyvb_lds_get_input_state(pyvb_lds* h, double* B_mean, double* B_colvar, double* qld_B, double* lnd_B) { return known_get_state(h, 0, B_mean, B_colvar, qld_B, lnd_B); }
+int pyvb_lds_update_B(pyvb_lds* h) { return known_update_gain(h, 0); }
+int pyvb_lds_set_regressors(pyvb_lds* h, const double* V) { return known_set_channels(h, 1, V); }
+int pyvb_lds_get_regressors(pyvb_lds* h, double* V) { return known_get_channels(h, 1, V); }
+int pyvb_lds_set_regressor_priors(pyvb_lds* h, const double* E_pm, const double* E_pp) { return known_set_priors(h, 1, E_pm, E_pp); }
+int pyvb_lds_set_regressor_state(pyvb_lds* h, const double* E_mean, const double* E_colvar) { return known_set_state(h, 1, E_mean, E_colvar); }
+int pyvb_lds_get_regressor_state(pyvb_lds* h, double* E_mean, double* E_colvar, double* qld_E, double* lnd_E) { return known_get_state(h, 1, E_mean, E_colvar, qld_E, lnd_E); }
+int pyvb_lds_update_E(pyvb_lds* h) { return known_update_gain(h, 1); }
 
 int pyvb_lds_set_state(pyvb_lds* h, const double* X, const double* A_mean, const double* A_colvar,
                        const double* C_mean, const double* C_colvar, const double* Q_b, const double* R_b) {

@@ -19,6 +19,30 @@ struct Priors {          // device pointers, shared by all replicates
     double Q_a0_host, R_a0_host, Q_w0_lndet, R_w0_lndet;    // Wishart: v0 and ln det w0 of the two priors
 };
 
+// The known channels of one equation of the model with their gain: the inputs u_t and B of the state equation, or the regressors
+// v_t and E of the output equation.  `rows` below is the equation's own dimension, D or K.  Which of <A> / <C>, Q / R, resQ / resR,
+// H_A / H_C and part 2 / 3 of the bound a record is attached to follows from its index on the handle (k_known.hip: known_args).
+//                                   state equation (side 0)        output equation (side 1)
+//   width                           P                              Pv
+//   channels, gain                  u_t, B                         v_t, E
+//   matrix beside the gain, noise   A, Q                           C, R
+//   gram                            Suu = sum_{t>=1} u_t u_t^T     Svv = sum_t v_t v_t^T
+//   cross_lhs                       Sxu = sum_{t>=1} mu_t u_t^T    Syv = sum_t y_t v_t^T
+//   cross_x                         Su1x = sum u_{t+1} mu_t^T      Svx = sum_t v_t mu_t^T
+//   saved                           Sx1x                           Syx
+struct KnownChannels {
+    int width;                      // 0: the handle has no such channels
+    double *in;                     // [N][T][width] the channels as the caller gave them; row t drives x_t / enters y_t
+    double *mean, *var;             // [N][rows][width] (row, col), [N][width][rows] (column i, entry k), as A_mean / A_var
+    double *qld, *lnd;              // [N][width]
+    double *pm, *pp, *pld;          // the Constant parents of the gain's columns: [rows][width], [width][rows], ln det of each column's precision [width]
+    double *gram;                   // [N][width][width], formed when the channels are set
+    double *cross_lhs;              // [N][rows][width]: side 0 out of the statistics pass (k_known_moments), side 1 when V or Y is set
+    double *cross_x;                // [N][width][D] out of the statistics pass
+    double *saved;                  // [N][rows][D] the moment block's Sx1x / Syx as k_moments left it: the block's copy becomes H_A / H_C
+    bool set, priors_set;           // the channels / the parents of the gain have been given
+};
+
 struct EventPair;
 struct KernelTimer {
     double total_ms; int launches;
@@ -100,31 +124,15 @@ struct pyvb_lds {
     double *Yobs, *Yvar, *Yqld, *Yent;      // [N][T][K] observations (NaN = missing), [N][T][K] variances, [N][T], [N]
     double *Ylnd, *YentX;                   // [N][T] ln det qcov beside Yqld; [N] the exact entropy of those rows (added, not subtracted)
     double *Yld, *YcovS;                    // Wishart noise: [N][T] ln det of each row's covariance of missing entries, [N][K][K] sum_t qcov_t
-    // ---- a known input u_t that drives the states, x_t = A x_{t-1} + B u_t (pyvb_lds_create_inputs, k_inputs.hip).  P = 0 and every
-    // pointer null on a handle without inputs.  The inputs ride through the sweeps and the statistics pass as 2 P extra output
-    // channels: those kernels are handed Yt, K + 2 P and Ct in place of Y, K and C_mean (lds_sweep_* below), and L is the layout
-    // of (D, K + 2 P); everything else keeps reading Y, K and C_mean.
-    int P;
-    double *Uin;                    // [N][T][P] the inputs as the caller gave them; row t drives x_t
+    // ---- known channels: an input u_t that drives the states, x_t = A x_{t-1} + B u_t (pyvb_lds_create_inputs), and regressors in
+    // the output equation, y_t = C x_t + E v_t (pyvb_lds_create_regressors); the kernels are k_known.hip.  known[0] is the state
+    // equation (B, u; width P), known[1] the output equation (E, v; width Pv): width 0 and every pointer null on a handle without.
+    // The channels ride through the sweeps and the statistics pass as 2 P + Pv extra output channels: those kernels are handed Yt,
+    // K + 2 P + Pv and Ct in place of Y, K and C_mean (lds_sweep_* below), and L is the layout of (D, K + 2 P + Pv); everything else
+    // keeps reading Y, K and C_mean.  Yt and Ct exist when P or Pv is set.
+    KnownChannels known[2];
     double *Yt;                     // [N][T][K + 2 P + Pv] rows [y_t ; u_t ; u_{t+1} ; v_t], u_t zero in row 0, u_{t+1} zero in a chain's last row
-    double *Ct;                     // [N][K + 2 P + Pv][D] <C>, then the rows through which the boundary nodes add <Q><B> u and -<A>^T<Q><B> u
-    double *B_mean, *B_var;         // [N][D][P] (row, col), [N][P][D] (column i, entry k), as A_mean / A_var
-    double *qld_B, *lnd_B;          // [N][P]
-    double *B_pm, *B_pp, *B_pld;    // the Constant parents of the columns of B: [D][P], [P][D], and ln det of each column's precision [P]
-    double *Suu;                    // [N][P][P] sum_{t=1}^{T_n-1} u_t u_t^T, formed when the inputs are set
-    double *imom;                   // [N][2 D P + D D]: Sxu [D][P], Su1x [P][D], and Sx1x as k_moments left it (k_in_moments)
-    bool inputs_set, input_priors_set;
-    // ---- known regressors in the output equation, y_t = C x_t + E v_t (pyvb_lds_create_regressors, k_regressors.hip).  Pv = 0 and
-    // every pointer null on a handle without.  The regressors are Pv more output channels behind the 2 P of the inputs: Yt, Ct and
-    // L are those of K + 2 P + Pv outputs, and Yt / Ct exist when P or Pv is set.
-    int Pv;
-    double *Vin;                    // [N][T][Pv] the regressors as the caller gave them; row t enters y_t
-    double *E_mean, *E_var;         // [N][K][Pv] (row, col), [N][Pv][K] (column i, entry k), as C_mean / C_var
-    double *qld_E, *lnd_E;          // [N][Pv]
-    double *E_pm, *E_pp, *E_pld;    // the Constant parents of the columns of E: [K][Pv], [Pv][K], ln det of each column's precision [Pv]
-    double *Svv, *Syv;              // [N][Pv][Pv] sum_{t<T_n} v_t v_t^T, [N][K][Pv] sum_{t<T_n} y_t v_t^T: formed when V or Y is set
-    double *rmom;                   // [N][Pv D + K D]: Svx [Pv][D], and Syx as k_moments left it (k_rg_moments)
-    bool regressors_set, regressor_priors_set;
+    double *Ct;                     // [N][K + 2 P + Pv][D] <C>, then the rows through which the boundary nodes add <Q><B> u, -<A>^T<Q><B> u and -<C>^T<R><E> v
     // ---- the lower bound does not feed the next iteration: inside pyvb_lds_iterate it runs on a side stream
     hipStream_t side;
     hipEvent_t ev_params, ev_elbo;  // parameters of this iteration complete (main) / lower bound of it read them (side)
@@ -134,29 +142,23 @@ struct pyvb_lds {
 #define PYVB_ELBO_HISTORY 4096
 
 // what the sweeps, the single-node update and the statistics pass are handed as outputs, their number and <C>
-static inline int lds_sweep_K(const pyvb_lds* h) { return h->K + 2 * h->P + h->Pv; }
-static inline const double* lds_sweep_Y(const pyvb_lds* h) { return h->P || h->Pv ? h->Yt : h->Y; }
-static inline const double* lds_sweep_C(const pyvb_lds* h) { return h->P || h->Pv ? h->Ct : h->C_mean; }
+static inline int lds_sweep_K(const pyvb_lds* h) { return h->K + 2 * h->known[0].width + h->known[1].width; }
+static inline const double* lds_sweep_Y(const pyvb_lds* h) { return h->known[0].width || h->known[1].width ? h->Yt : h->Y; }
+static inline const double* lds_sweep_C(const pyvb_lds* h) { return h->known[0].width || h->known[1].width ? h->Ct : h->C_mean; }
+
+// the rows of the gain of known[side]: the dimension of the equation it stands in
+static inline int lds_known_rows(const pyvb_lds* h, int side) { return side ? h->K : h->D; }
 
 // ---- launchers implemented in the kernel translation units ----
-// k_inputs.hip (handles with inputs only)
-int launch_in_assemble(pyvb_lds* h);        // Yt from Y and Uin, every row of every replicate
-int launch_in_suu(pyvb_lds* h);             // Suu from Uin
-int launch_in_gains(pyvb_lds* h);           // behind k_prep: the two extra column groups of G, Ct, the ones behind <R>
-int launch_in_moments(pyvb_lds* h);         // behind k_moments: Sxu, Su1x out of the Syx block, Sx1x aside
-int launch_in_HA(pyvb_lds* h);              // H_A = Sx1x - <B> Su1x into the moment block, for the columns of A and the residual of Q
-int launch_in_colsB(pyvb_lds* h);           // [b.update() for b in Bs]
-int launch_in_resQ(pyvb_lds* h);            // the terms of <B> in the residual of Q
-int launch_in_elbo(pyvb_lds* h, hipStream_t stream);       // the columns of B into part 2, behind k_elbo on the same stream
-// k_regressors.hip (handles with regressors only)
-int launch_rg_assemble(pyvb_lds* h);        // Yt from Y, Uin and Vin, every row of every replicate
-int launch_rg_sums(pyvb_lds* h);            // Svv, Syv from Vin and Y
-int launch_rg_gains(pyvb_lds* h);           // behind k_prep and k_in_gains: the column group of the v_t channels, their rows of Ct, the ones behind <R>
-int launch_rg_moments(pyvb_lds* h);         // behind k_moments: Svx out of the Syx block, Syx aside
-int launch_rg_HC(pyvb_lds* h);              // H_C = Syx - <E> Svx into the moment block, for the columns of C and the residual of R
-int launch_rg_colsE(pyvb_lds* h);           // [e.update() for e in Es]
-int launch_rg_resR(pyvb_lds* h);            // the terms of <E> in the residual of R
-int launch_rg_elbo(pyvb_lds* h, hipStream_t stream);       // the columns of E into part 3, behind k_elbo on the same stream
+// k_known.hip (handles with known channels only); side: 0 = the inputs of the state equation, 1 = the regressors of the output equation
+int launch_known_assemble(pyvb_lds* h);             // Yt from Y, the inputs and the regressors, every row of every replicate
+int launch_known_gram(pyvb_lds* h, int side);       // Suu from the inputs / Svv and Syv from the regressors and Y
+int launch_known_gains(pyvb_lds* h, int side);      // behind k_prep: the side's column groups of G, its rows of Ct, the ones behind <R>
+int launch_known_moments(pyvb_lds* h, int side);    // behind k_moments: the cross sums out of the Syx block, Sx1x / Syx aside
+int launch_known_H(pyvb_lds* h, int side);          // H_A = Sx1x - <B> Su1x / H_C = Syx - <E> Svx into the moment block, for the columns of A / C and the residual of Q / R
+int launch_known_cols(pyvb_lds* h, int side);       // [b.update() for b in Bs] / [e.update() for e in Es]
+int launch_known_resid(pyvb_lds* h, int side);      // the terms of <B> / <E> in the residual of Q / R
+int launch_known_elbo(pyvb_lds* h, int side, hipStream_t stream);   // the columns of B / E into part 2 / 3, behind k_elbo on the same stream
 int launch_prep(pyvb_lds* h);
 int launch_w0(pyvb_lds* h);         // L0 m0 from the priors of X_0 on the device: after every change of them
 // A sweep reads X[src] and writes X[1 - src]; read_cache: a backward sweep that starts from the c_t a forward one left in U.

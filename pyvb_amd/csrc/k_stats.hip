@@ -256,7 +256,7 @@ static void launch_stats_t(pyvb_lds* h, const StatsArgs& a, bool with_sxx) {
 int launch_stats(pyvb_lds* h, bool with_sxx) {
     if (h->big) return launch_stats_big(h);
     StatsArgs a;
-    // (a handle with inputs: on the rows [y_t ; u_t ; u_{t+1}] the Syx block comes out as [Syx ; Sxu^T ; Su1x], k_inputs.hip)
+    // (a handle with inputs: on the rows [y_t ; u_t ; u_{t+1}] the Syx block comes out as [Syx ; Sxu^T ; Su1x], k_known.hip)
     a.X = h->X[h->st.cur]; a.Y = lds_sweep_Y(h); a.part = h->stats; a.zeros = h->zeros; a.active = h->active; a.len = h->len;
     a.N = h->N; a.T = h->T; a.D = h->D; a.K = lds_sweep_K(h); a.nchunk = h->nchunk; a.chunk_len = h->chunk_len; a.L = h->L;
     {

@@ -539,7 +539,7 @@ int launch_sweep(pyvb_lds* h, int direction, int src, bool read_cache, bool keep
     SweepArgs a;
     a.keep_x = (keep_x || direction != PYVB_FORWARD) ? 1 : 0;
     a.W = h->W;
-    // (a handle with inputs: the rows [y_t ; u_t ; u_{t+1}], K + 2 P of them, and <C> with the boundary nodes' rows, k_inputs.hip)
+    // (a handle with inputs: the rows [y_t ; u_t ; u_{t+1}], K + 2 P of them, and <C> with the boundary nodes' rows, k_known.hip)
     a.Xold = h->X[src]; a.Xnew = h->X[1 - src]; a.Y = lds_sweep_Y(h); a.gains = h->gains; a.warm = h->warm;
     a.trash = h->trash; a.U = h->U; a.Sxx = h->sxx; a.A_mean = h->A_mean; a.C_mean = lds_sweep_C(h);
     a.QA = h->dense ? h->QA : nullptr; a.RC = h->dense ? h->RC : nullptr;

@@ -7,22 +7,20 @@
 // handle", has the dependency table and the step list of an iteration per class of handle.
 //
 // Dev has, each returning the status of the launcher it stands for (common.h):
-//   prep, in_gains, wexpect, dense_pre, sweep(direction, src, read_cache, keep_x), step(t), stats(with_sxx), moments(sxx_from_sweep),
-//   tie_moments, tie_syy, in_moments, in_HA, in_colsB, in_resQ, resid(which), wresid(which, update, use_sg), cols(which, c0, c1, fuse),
+//   prep, wexpect, dense_pre, sweep(direction, src, read_cache, keep_x), step(t), stats(with_sxx), moments(sxx_from_sweep),
+//   tie_moments, tie_syy, resid(which), wresid(which, update, use_sg), cols(which, c0, c1, fuse),
 //   cols_dense(which, c0, c1), noise(which), parents(kind, which, derive), syy, syy_missing, syy_full, missing_ent_dense(diag_cov),
-//   impute, impute_dense, elbo(stream), in_elbo(stream), elbo_dense(), carry_x(src), carry_classes
+//   impute, impute_dense, elbo(stream), elbo_dense(), carry_x(src), carry_classes,
+// for the known channels of the state equation (side 0: inputs, B) and of the output equation (side 1: regressors, E), k_known.hip:
+//   known_gains(side), known_moments(side), known_H(side), known_cols(side), known_resid(side), known_elbo(side, stream)
 // and three operations that are not launches:
 //   swap_classes()     the pointers Sigma / qld_x / lnd_x change places with their *_new
 //   join_elbo()        the main stream waits for a lower bound in flight on the side stream
 //   form_lnd_x()       ln det of every class of Sigma on the host, and its two copies
 // with main_stream() and a type stream_t for the two calls that take a stream.
-// A Dev that serves handles with regressors (LdsFacts::Pv > 0, k_regressors.hip) has also
-//   rg_gains, rg_moments, rg_HC, rg_colsE, rg_resR, rg_elbo(stream)
-// They are called through a compile-time detection, so a Dev without them (only ever run with Pv = 0) still compiles.
+// `which` and `side` count alike: 0 is the state equation (A, B, Q), 1 the output equation (C, E, R).
 #pragma once
 #include <cstddef>
-#include <type_traits>
-#include <utility>
 #include "../../include/pyvb_hip.h"
 #include "lds_state.h"
 #include "replicates.h"
@@ -32,19 +30,16 @@ void pyvb_set_error(const char* fmt, ...);
 
 // What the flow reads of a handle beside its state, filled from the handle at the call
 struct LdsFacts {
-    int T, N, D, P;                 // fixed at creation
+    int T, N, D;                    // fixed at creation
     bool dense, big;
     bool has_missing;               // as of this call
     int bound;
-    bool inputs_set, input_priors_set;
     const Replicates* rep;          // host-only records of the handle, read through
     const ColumnParents* parents;   // [2]
-    int Pv;                         // regressors in the output equation, fixed at creation (0: none)
-    bool regressors_set, regressor_priors_set;
+    // the known channels of the state equation ([0]) and of the output equation ([1]) (KnownChannels, common.h)
+    int width[2];                   // P, Pv: fixed at creation (0: none)
+    bool known_set[2], known_priors_set[2];     // as of this call
 };
-
-template <class Dev, class = void> struct dev_has_regressors : std::false_type {};
-template <class Dev> struct dev_has_regressors<Dev, std::void_t<decltype(std::declval<Dev&>().rg_gains())>> : std::true_type {};
 
 template <class Dev>
 struct LdsFlow {
@@ -52,11 +47,7 @@ struct LdsFlow {
     LdsFacts in;
     Dev dev;
 
-    // the steps of k_regressors.hip, where Dev has them
-#define PYVB_RG_STEP(name) int name() { if constexpr (dev_has_regressors<Dev>::value) return dev.name(); else return PYVB_OK; }
-    PYVB_RG_STEP(rg_gains) PYVB_RG_STEP(rg_moments) PYVB_RG_STEP(rg_HC) PYVB_RG_STEP(rg_colsE) PYVB_RG_STEP(rg_resR)
-#undef PYVB_RG_STEP
-    int rg_elbo(typename Dev::stream_t stream) { if constexpr (dev_has_regressors<Dev>::value) return dev.rg_elbo(stream); else return PYVB_OK; }
+    bool known(int side) const { return in.width[side] > 0; }
 
     // every replicate switched off: the update entries are successful no-ops without a launch
     bool idle() const { return in.rep->n_active() == 0; }
@@ -111,17 +102,18 @@ struct LdsFlow {
         return PYVB_OK;
     }
 
-    // a handle with inputs before it has them: the updates would read zeros for u_t and for the parents of B
-    int inputs_ready() const {
-        if (!in.inputs_set) { pyvb_set_error("%s", "the handle was created with inputs: call pyvb_lds_set_inputs before the first update"); return PYVB_E_ARG; }
-        if (!in.input_priors_set) { pyvb_set_error("%s", "the handle was created with inputs: call pyvb_lds_set_input_priors before the first update"); return PYVB_E_ARG; }
-        return PYVB_OK;
-    }
-
-    // a handle with regressors before it has them: the updates would read zeros for v_t and for the parents of E
-    int regressors_ready() const {
-        if (!in.regressors_set) { pyvb_set_error("%s", "the handle was created with regressors: call pyvb_lds_set_regressors before the first update"); return PYVB_E_ARG; }
-        if (!in.regressor_priors_set) { pyvb_set_error("%s", "the handle was created with regressors: call pyvb_lds_set_regressor_priors before the first update"); return PYVB_E_ARG; }
+    // a handle with known channels before it has them: the updates would read zeros for u_t / v_t and for the parents of B / E
+    int known_ready(int side) const {
+        static const char* const what[2] = {"inputs", "regressors"};
+        static const char* const one[2] = {"input", "regressor"};
+        if (!in.known_set[side]) {
+            pyvb_set_error("the handle was created with %s: call pyvb_lds_set_%s before the first update", what[side], what[side]);
+            return PYVB_E_ARG;
+        }
+        if (!in.known_priors_set[side]) {
+            pyvb_set_error("the handle was created with %s: call pyvb_lds_set_%s_priors before the first update", what[side], one[side]);
+            return PYVB_E_ARG;
+        }
         return PYVB_OK;
     }
 
@@ -132,11 +124,11 @@ struct LdsFlow {
             if ((rc = ensure_expect())) return rc;
             if ((rc = dev.dense_pre())) return rc;
         }
-        if (in.P && (rc = inputs_ready())) return rc;
-        if (in.Pv && (rc = regressors_ready())) return rc;
+        for (int side = 0; side < 2; ++side)
+            if (known(side) && (rc = known_ready(side))) return rc;
         if ((rc = dev.prep())) return rc;
-        if (in.P && (rc = dev.in_gains())) return rc;      // the gains of the input channels, from Sigma_1 as k_prep has just left it
-        if (in.Pv && (rc = rg_gains())) return rc;         // those of the regressors' channels, behind them
+        for (int side = 0; side < 2; ++side)        // the gains of the known channels, from Sigma_1 as k_prep has just left it
+            if (known(side) && (rc = dev.known_gains(side))) return rc;
         st.gains_formed();
         return PYVB_OK;
     }
@@ -163,12 +155,13 @@ struct LdsFlow {
             return PYVB_E_STALE;
         }
         int rc;
-        if (in.Pv && (rc = regressors_ready())) return rc;      // before any launch
+        if (known(1) && (rc = known_ready(1))) return rc;       // before any launch
         if ((rc = dev.stats(!st.sxx_valid))) return rc;
         if ((rc = dev.moments(st.sxx_valid))) return rc;
         if ((rc = dev.tie_moments())) return rc;        // chains that share A, C, Q, R: the moments of a model
-        if (in.P && ((rc = inputs_ready()) || (rc = dev.in_moments()))) return rc;       // Sxu, Su1x; Sx1x aside
-        if (in.Pv && (rc = rg_moments())) return rc;        // Svx; Syx aside
+        if (known(0) && (rc = known_ready(0))) return rc;       // (the inputs have always been asked for here, behind the launches)
+        for (int side = 0; side < 2; ++side)            // Sxu, Su1x / Svx; Sx1x / Syx aside
+            if (known(side) && (rc = dev.known_moments(side))) return rc;
         st.stats_valid = true;
         return PYVB_OK;
     }
@@ -178,10 +171,8 @@ struct LdsFlow {
         if (valid) return PYVB_OK;
         int rc = ensure_stats();
         if (rc) return rc;
-        if (in.P && which == 0) {       // H_A of the current <B>, the residual as k_cols forms it, the terms of <B> alone
-            if ((rc = dev.in_HA()) || (rc = dev.resid(0)) || (rc = dev.in_resQ())) return rc;
-        } else if (in.Pv && which == 1) {   // H_C of the current <E>, the residual as k_cols forms it, the terms of <E> alone
-            if ((rc = rg_HC()) || (rc = dev.resid(1)) || (rc = rg_resR())) return rc;
+        if (known(which)) {     // H_A / H_C of the current gain, the residual as k_cols forms it, the terms of the gain alone
+            if ((rc = dev.known_H(which)) || (rc = dev.resid(which)) || (rc = dev.known_resid(which))) return rc;
         } else if ((rc = in.dense ? dev.wresid(which, 0, st.sg_valid[which]) : dev.resid(which))) return rc;
         valid = true;
         return PYVB_OK;
@@ -219,27 +210,19 @@ struct LdsFlow {
             if ((rc = ensure_expect())) return rc;
             if ((rc = dev.cols_dense(which, col_begin, col_end))) return rc;
         } else {
-            if (in.P && which == 0 && (rc = dev.in_HA())) return rc;       // H = Sx1x - <B> Su1x
-            if (in.Pv && which == 1 && (rc = rg_HC())) return rc;          // H = Syx - <E> Svx
+            if (known(which) && (rc = dev.known_H(which))) return rc;       // H = Sx1x - <B> Su1x / Syx - <E> Svx
             if ((rc = dev.cols(which, col_begin, col_end))) return rc;
         }
         st.columns_updated(which, in.dense && col_begin == 0 && col_end == in.D);
         return PYVB_OK;
     }
 
-    int update_B() {
+    // the columns of B (side 0) / E (side 1)
+    int update_gain(int side) {
         if (idle()) return PYVB_OK;
         int rc;
-        if ((rc = ensure_stats()) || (rc = dev.in_colsB())) return rc;
-        st.columns_updated(0, false);        // as a column of A: the gains and the residual of Q depend on it
-        return PYVB_OK;
-    }
-
-    int update_E() {
-        if (idle()) return PYVB_OK;
-        int rc;
-        if ((rc = ensure_stats()) || (rc = rg_colsE())) return rc;
-        st.columns_updated(1, false);        // as a column of C: the gains and the residual of R depend on it
+        if ((rc = ensure_stats()) || (rc = dev.known_cols(side))) return rc;
+        st.columns_updated(side, false);        // as a column of A / C: the gains and the residual of Q / R depend on it
         return PYVB_OK;
     }
 
@@ -275,11 +258,11 @@ struct LdsFlow {
         return PYVB_OK;
     }
 
-    // k_elbo, and on a handle with inputs the columns of B into part 2 behind it, with regressors those of E into part 3
+    // k_elbo, and behind it the columns of B into part 2 on a handle with inputs, those of E into part 3 with regressors
     int lds_bound(typename Dev::stream_t stream) {
         int rc = dev.elbo(stream);
-        if (!rc && in.P) rc = dev.in_elbo(stream);
-        if (!rc && in.Pv) rc = rg_elbo(stream);
+        for (int side = 0; side < 2; ++side)
+            if (!rc && known(side)) rc = dev.known_elbo(side, stream);
         return rc;
     }
 
@@ -313,33 +296,7 @@ struct LdsFlow {
             if ((rc = dev.wresid(2, 1, true))) return rc;    // both residual matrices and both qw = w0 + residual
             st.noise_updated(2);
             if ((rc = ensure_expect())) return rc;                // E[Q], E[R] of the new posteriors: the bound and the next k_prep read them
-        } else if (in.Pv) {
-            // As, [Bs], Cs, Es, Q, R: E sees the new C and sits between C and R, which therefore share no launch; without inputs
-            // A and Q keep theirs
-            if (in.P) {
-                if ((rc = dev.in_HA()) || (rc = dev.cols(0, 0, in.D))) return rc;
-                if ((rc = dev.in_colsB())) return rc;
-            } else if ((rc = dev.cols(0, 0, in.D, 3))) return rc;
-            if ((rc = rg_HC()) || (rc = dev.cols(1, 0, in.D))) return rc;
-            if ((rc = rg_colsE())) return rc;
-            st.columns_updated(2, false);
-            if (!in.P) st.noise_updated(0);
-            else {
-                if ((rc = ensure_resid(0)) || (rc = dev.noise(0))) return rc;
-                st.noise_updated(0);
-            }
-            if ((rc = ensure_resid(1)) || (rc = dev.noise(1))) return rc;
-            st.noise_updated(1);
-        } else if (in.P) {
-            // As, Bs, Cs, Q, R: B sees the new A, Q the new A and B; C and R do not depend on them and keep their shared launch
-            if ((rc = dev.in_HA()) || (rc = dev.cols(0, 0, in.D))) return rc;
-            if ((rc = dev.in_colsB())) return rc;
-            if ((rc = dev.cols(1, 0, in.D, 3))) return rc;
-            st.columns_updated(2, false);
-            st.noise_updated(1);
-            if ((rc = ensure_resid(0)) || (rc = dev.noise(0))) return rc;
-            st.noise_updated(0);
-        } else {
+        } else if (!known(0) && !known(1)) {
             if ((rc = dev.cols(2, 0, in.D, 3))) return rc;       // columns, residuals and noise update in one launch
             st.columns_updated(2, false);
             st.noise_updated(2);
@@ -350,6 +307,21 @@ struct LdsFlow {
                 const int which = parents_of_kind(in.parents, kind);     // both matrices of a kind: one launch
                 if (which >= 0 && (rc = dev.parents(kind, which, false))) return rc;
             }
+        } else {
+            // As, [Bs], Cs, [Es], Q, R.  The gain of an equation sees the new matrix beside it and the noise sees both, so an equation
+            // with known channels takes its steps one by one; one without keeps its columns, residual and noise in one launch.
+            for (int which = 0; which < 2; ++which) {
+                if (!known(which)) { if ((rc = dev.cols(which, 0, in.D, 3))) return rc; }
+                else if ((rc = dev.known_H(which)) || (rc = dev.cols(which, 0, in.D)) || (rc = dev.known_cols(which))) return rc;
+            }
+            st.columns_updated(2, false);
+            for (int which = 0; which < 2; ++which)
+                if (!known(which)) st.noise_updated(which);
+            for (int which = 0; which < 2; ++which)
+                if (known(which)) {
+                    if ((rc = ensure_resid(which)) || (rc = dev.noise(which))) return rc;
+                    st.noise_updated(which);
+                }
         }
         if (in.bound == PYVB_BOUND_EXACT && (rc = ensure_lnd_x())) return rc;       // (only before the first complete sweep)
         return PYVB_OK;

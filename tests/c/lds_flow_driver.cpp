@@ -1,14 +1,14 @@
 // Runs the update flow of a pyvb_lds handle (pyvb_amd/csrc/lds_flow.h over LdsState of lds_state.h) on a file of call sequences, for
-// tests/test_lds_flow_cpu.py, which builds it with the address and undefined-behaviour sanitizers.  LdsFlow is instantiated here
+// tests/test_lds_flow_cpu.py and tests/test_lds_flow_regressors_cpu.py, which build it with the address and undefined-behaviour sanitizers.  LdsFlow is instantiated here
 // itself, the header that ships, over a device that writes one line per step in place of a launch.  What api.hip keeps -- the
 // copies and the staging of getters and setters, the loops of pyvb_lds_iterate / iterate_until, the change of mask -- is a line of
 // output each ("copy", "stage", "mask", "bound", "converge"), behind the settle_parked or the event api.hip has there.  No checks
 // of its own: the test reads the output.
-//   init T N D P dense big              a new handle, as pyvb_lds_create leaves it
-//   sweep dir | x t | cols which c0 c1 | B | parents which kind | Q | R | Y | elbo       the update entries
+//   init T N D P dense big [Pv]         a new handle, as pyvb_lds_create leaves it (Pv: 0 unless given)
+//   sweep dir | x t | cols which c0 c1 | B | E | parents which kind | Q | R | Y | elbo       the update entries
 //   iterate n | until n conv...         pyvb_lds_iterate(n); pyvb_lds_iterate_until that ran n iterations and left the N conv bytes
 //   priors | wishart_priors | wishart_state | column_cov | column_obs | observations missing | output_state | inputs |
-//   input_priors | input_state | state x covs parameters | classes | time_split | set_parents which kind       the setters' events
+//   input_priors | input_state | regressors | regressor_priors | regressor_state | state x covs parameters | classes | time_split | set_parents which kind       the setters' events
 //   get_state | get_classes | get_logdets | active m...  | bound mode
 // Output: "> command", the steps of the call -- the names of LdsDevice in api.hip with their arguments, streams as 0 (main) and
 // 1 (side) --, "! status message" where the call failed, and the state after it:
@@ -41,7 +41,6 @@ struct Recorder {
     }
     int main_stream() const { return 0; }
     int prep() { return say("prep"); }
-    int in_gains() { return say("in_gains"); }
     int wexpect() { return say("wexpect"); }
     int dense_pre() { return say("dense_pre"); }
     int sweep(int direction, int src, bool read_cache, bool keep_x) { return say("sweep %d %d %d %d", direction, src, (int)read_cache, (int)keep_x); }
@@ -50,10 +49,13 @@ struct Recorder {
     int moments(bool sxx_from_sweep) { return say("moments %d", (int)sxx_from_sweep); }
     int tie_moments() { return say("tie moments"); }
     int tie_syy() { return say("tie syy"); }
-    int in_moments() { return say("in_moments"); }
-    int in_HA() { return say("in_HA"); }
-    int in_colsB() { return say("in_colsB"); }
-    int in_resQ() { return say("in_resQ"); }
+    // the steps of the known channels under the names they have per side: in_* for the inputs (0), rg_* for the regressors (1)
+    int known_gains(int side) { return say(side ? "rg_gains" : "in_gains"); }
+    int known_moments(int side) { return say(side ? "rg_moments" : "in_moments"); }
+    int known_H(int side) { return say(side ? "rg_HC" : "in_HA"); }
+    int known_cols(int side) { return say(side ? "rg_colsE" : "in_colsB"); }
+    int known_resid(int side) { return say(side ? "rg_resR" : "in_resQ"); }
+    int known_elbo(int side, int stream) { return say("%s_elbo %d", side ? "rg" : "in", stream); }
     int resid(int which) { return say("resid %d", which); }
     int wresid(int which, int update, bool use_sg) { return say("wresid %d %d %d", which, update, (int)use_sg); }
     int cols(int which, int c0, int c1, int fuse = 0) { return say("cols %d %d %d %d", which, c0, c1, fuse); }
@@ -67,7 +69,6 @@ struct Recorder {
     int impute() { return say("impute"); }
     int impute_dense() { return say("impute_dense"); }
     int elbo(int stream) { return say("elbo %d", stream); }
-    int in_elbo(int stream) { return say("in_elbo %d", stream); }
     int elbo_dense() { return say("elbo_dense 0"); }
     int carry_x(int src) { return say("carry x %d", src); }
     int carry_classes() { return say("carry classes"); }
@@ -88,12 +89,12 @@ struct Handle {
         facts.rep = &rep; facts.parents = parents;
         return {st, facts, {out}};
     }
-    void init(int T, int N, int D, int P, bool dense, bool big) {
+    void init(int T, int N, int D, int P, bool dense, bool big, int Pv) {
         st = LdsState();            // as in a value-initialised handle
         fresh.assign((size_t)T, 0);
         st.T = T; st.fresh = fresh.data();
         facts = LdsFacts();
-        facts.T = T; facts.N = N; facts.D = D; facts.P = P; facts.dense = dense; facts.big = big;
+        facts.T = T; facts.N = N; facts.D = D; facts.width[0] = P; facts.width[1] = Pv; facts.dense = dense; facts.big = big;
         facts.bound = PYVB_BOUND_REFERENCE;
         rep.init(N, T, nullptr, nullptr);
         parents[0] = parents[1] = ColumnParents();
@@ -149,7 +150,7 @@ int main(int argc, char** argv) {
     if (!in || !out) return 2;
     Handle h;
     h.out = out;
-    h.init(2, 1, 1, 0, false, false);
+    h.init(2, 1, 1, 0, false, false, 0);
     std::string line, cmd;
     while (std::getline(in, line)) {
         std::istringstream ls(line);
@@ -157,11 +158,11 @@ int main(int argc, char** argv) {
         fprintf(out, "> %s\n", line.c_str());
         int rc = PYVB_OK, a = 0, b = 0, c = 0;
         g_err[0] = 0;
-        if (cmd == "init") { int T, N, D, P, dense, big; ls >> T >> N >> D >> P >> dense >> big; h.init(T, N, D, P, dense != 0, big != 0); }
+        if (cmd == "init") { int T, N, D, P, dense, big, Pv = 0; ls >> T >> N >> D >> P >> dense >> big; ls >> Pv; h.init(T, N, D, P, dense != 0, big != 0, Pv); }
         else if (cmd == "sweep") { ls >> a; rc = h.flow().update_sweep(a); }
         else if (cmd == "x") { ls >> a; rc = h.flow().update_x(a); }
         else if (cmd == "cols") { ls >> a >> b >> c; rc = h.flow().update_columns(a, b, c); }
-        else if (cmd == "B") rc = h.flow().update_B();
+        else if (cmd == "B" || cmd == "E") rc = h.flow().update_gain(cmd == "E");
         else if (cmd == "parents") { ls >> a >> b; rc = h.flow().update_parents(a, b); }
         else if (cmd == "Q") rc = h.flow().update_noise(0);
         else if (cmd == "R") rc = h.flow().update_noise(1);
@@ -181,9 +182,9 @@ int main(int argc, char** argv) {
         else if (cmd == "column_cov" || cmd == "column_obs") h.st.columns_changed();
         else if (cmd == "observations") { ls >> a; h.facts.has_missing = a != 0; h.st.outputs_changed(); }
         else if (cmd == "output_state") { if ((rc = h.settled("stage")) == PYVB_OK) h.st.outputs_changed(); }
-        else if (cmd == "inputs") { h.facts.inputs_set = true; h.st.outputs_changed(); }
-        else if (cmd == "input_priors") { h.facts.input_priors_set = true; h.st.parameters_changed(); }
-        else if (cmd == "input_state") h.st.parameters_changed();
+        else if (cmd == "inputs" || cmd == "regressors") { h.facts.known_set[cmd == "regressors"] = true; h.st.outputs_changed(); }
+        else if (cmd == "input_priors" || cmd == "regressor_priors") { h.facts.known_priors_set[cmd == "regressor_priors"] = true; h.st.parameters_changed(); }
+        else if (cmd == "input_state" || cmd == "regressor_state") h.st.parameters_changed();
         else if (cmd == "state") { ls >> a >> b >> c; if ((rc = h.settled("stage")) == PYVB_OK) h.flow().state_given(a != 0, b != 0, c != 0); }
         else if (cmd == "classes") { if ((rc = h.settled("stage")) == PYVB_OK) h.st.classes_set(); }
         else if (cmd == "time_split") h.st.x_changed();

@@ -195,8 +195,8 @@ REACH = {
 def test_cases_reach_what_the_table_says(R, name, geometry):
     T, D, K, P, Pv = _shape(R, name)
     Kt = K + 2 * P + Pv
-    IN_PMAX, RE = _constant("k_inputs.hip", r"#define IN_PMAX (\d+)"), _constant("k_regressors.hip", r"__shared__ double RE\[(\d+)\]")
-    assert (IN_PMAX, RE) == (31, 1024) and _constant("k_inputs.hip", r"__shared__ double WV\[64 \* (\d+)\]") == 65
+    IN_PMAX, RE = _constant("k_known.hip", r"#define IN_PMAX (\d+)"), _constant("k_known.hip", r"__shared__ double RE\[(\d+)\]")
+    assert (IN_PMAX, RE) == (31, 1024) and _constant("k_known.hip", r"__shared__ double WV\[64 \* (\d+)\]") == 65
     assert max(D, Kt) <= 64 and P <= IN_PMAX and K * Pv <= RE            # what a handle accepts (include/pyvb_hip.h)
     # the layout is that of D states and Kt = K + 2 P + Pv output channels (api.hip: lds_geometry(N, T, D, K + 2 P + Pv, noise))
     v = [int(x) for x in geometry(["layout %d %d" % (D, Kt)])[0].split("|")[0].split()]

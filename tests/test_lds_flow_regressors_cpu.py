@@ -1,6 +1,7 @@
 """CPU-only: the update flow of an LDS handle with regressors in the output equation (pyvb_lds_create_regressors) -- the steps of
-k_regressors.hip that pyvb_amd/csrc/lds_flow.h takes through its compile-time detection.  tests/c/lds_flow_regressors_driver.cpp is
-tests/c/lds_flow_driver.cpp with a recorder that has those steps and a handle that carries Pv; it is a stand-alone program, built
+k_known.hip that pyvb_amd/csrc/lds_flow.h takes for side 1, the output equation.  tests/c/lds_flow_driver.cpp is the one driver of
+both flow tests: its recorder prints the steps of the known channels as in_* (side 0) and rg_* (side 1), and `init` takes Pv as a
+seventh number; it is a stand-alone program, built
 here with the address and undefined-behaviour sanitizers (runtimes linked statically), and nothing is loaded into Python.  The model
 is that of tests/test_lds_flow_cpu.py, a version counter per primary quantity, with E among the parameters:
 
@@ -10,8 +11,7 @@ is that of tests/test_lds_flow_cpu.py, a version counter per primary quantity, w
     resR         also from E                     resid 1 then rg_resR; C and R share no launch
 
 It pins the steps of an iteration for P = 0, Pv > 0 and for P > 0, Pv > 0, that update_E drops the gains and the residual of R, the
-errors of a handle that does not have its regressors yet, and holds seeded random call sequences to the model.  The recorder of
-tests/test_lds_flow_cpu.py, which lacks the new steps, still compiles and records what it did: that test is unchanged.
+errors of a handle that does not have its regressors yet, and holds seeded random call sequences to the model.
 """
 import os
 import subprocess
@@ -36,7 +36,7 @@ def driver(tmp_path_factory):
     if subprocess.run(SAN + [str(probe), "-o", str(tmp / "probe")], capture_output=True).returncode != 0:
         pytest.skip("this compiler cannot link the static sanitizer runtimes")
     exe = tmp / "lds_flow_regressors_driver"
-    subprocess.run(SAN + ["-Wall", "-I", CSRC, os.path.join(HERE, "c", "lds_flow_regressors_driver.cpp"), "-o", str(exe)], check=True, capture_output=True)
+    subprocess.run(SAN + ["-Wall", "-I", CSRC, os.path.join(HERE, "c", "lds_flow_driver.cpp"), "-o", str(exe)], check=True, capture_output=True)
 
     def run(commands):
         """commands: lists of a word and integers.  Returns, per command, [the command, its steps, the error or None, the state after it]."""
